@@ -7,9 +7,18 @@ synthetic EnMAP-shape cubes (8x8x200 bands, depth 12 per stack, dim 96, heads 8,
 8 GPUs, weak scaling).  One process per GPU; for N>1 launch with
 ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`` (RCCL over xGMI).
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the
+headline (metric, value, unit, higher_is_better, dtype, ms_per_step, final_loss).  --dump-outputs DIR
+also writes what the last timed step computed (loss, gradients, updated parameters) as DIR/<name>.npy.
+
+--full adds everything else, each part switched off by its --no-* option:
   roofline      the dominant kernel's algorithmic FLOP/s (DESIGN.md "work model") from HIP events
                 recorded around its launches inside the timed steps, vs the dense bf16 MFMA peak
+  kernels       per-kernel HIP-event times; live HBM traffic from two rocprofv3 --pmc child runs
+  box_probe     the MFMA rate, clock and HBM read rate this box sustains, before and after the steps
+  bf16_operand_forward, pipeline_inclusive   two more timed regions (bf16 forward operands; batches
+                fed by SyntheticCubeLoader)
+  parity_note   the committed loss errors of the timed kernels against the reference anchors
   cpu_baseline  the CPU oracle (plain PyTorch fp32 restatement of the reference, oracle/) timed on
                 the host cores of this box on a bounded sample of the same workload (rank 0, N=1)
 """
@@ -93,10 +102,24 @@ def main():
     ap.add_argument("--force-dp", action="store_true",
                     help="single process, but through the data-parallel path: a one-rank RCCL process group, bucket hooks, "
                          "all-reduce calls, mean inside AdamW (MSST_FORCE_DP=1); for traces of the DP wiring on a 1-GPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beyond the headline: kernel profile and roofline, live HBM traffic, "
+                         "box probe, the bf16-operand and pipeline-inclusive regions, parity note, CPU baseline (each --no-* "
+                         "option switches its part off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, gradients, updated parameters) as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all")
     args = ap.parse_args()
     if args.cpu_leg:
         cpu_leg(args)
         return
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        if args.profile_all:
+            ap.error("--profile-all needs --full")
+        # a plain run does only what the headline needs
+        args.no_cpu_baseline = args.no_profile = args.no_pipeline = args.no_traffic = args.no_alt = args.no_probe = True
     if args.force_dp and "RANK" not in os.environ:
         os.environ.update(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MSST_FORCE_DP="1")
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -190,7 +213,8 @@ def main():
 
     # warmup doubles as the survey pass: every kernel is timed there, the timed region then carries event
     # pairs only around the dominant MFMA kernel (the one the roofline object is about)
-    lib.msst_profile_select(ctypes.c_ulonglong(~0 & (2 ** 64 - 1)))
+    if prof:
+        lib.msst_profile_select(ctypes.c_ulonglong(~0 & (2 ** 64 - 1)))
     for w in range(args.warmup):
         if prof and w == args.warmup - 1:
             torch.cuda.synchronize()
@@ -226,13 +250,17 @@ def main():
     t1 = time.perf_counter()
     elapsed = t1 - t0
     kernels = collect() if prof else {}
-    lib.msst_profile_select(ctypes.c_ulonglong(2 ** 64 - 1))
-    lib.msst_profile_sample(1)
+    if prof:
+        lib.msst_profile_select(ctypes.c_ulonglong(2 ** 64 - 1))
+        lib.msst_profile_sample(1)
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = float(loss.item())
+    fwd_half = bool(getattr(model.engine(), "fwd_half", False))   # read before the bf16-operand region below switches it
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss, SEED)
     probe_after = box_probe() if not args.no_probe else None
 
     # the same K steps with the forward's GEMM operands in bf16 (MSST_FWD_HALF=0: round 5's forward; the engine reads the switch per
@@ -306,7 +334,7 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
-            "forward_gemm_operands": ("fp16 (IEEE half, MSST_FWD_HALF; backward bf16)" if getattr(model.engine(), "fwd_half", False) else args.precision),
+            "forward_gemm_operands": ("fp16 (IEEE half, MSST_FWD_HALF; backward bf16)" if fwd_half else args.precision),
             "config": {"workload": f"SimMIM pretrain step (fwd+bwd+AdamW), EnMAP-shape cubes 8x8x{args.bands}, "
                                    f"depth {args.depth}x2, dim 96, heads {args.heads}, mlp 64, mask 0.7/4/tube, dropout {args.dropout}",
                        "global_batch": B * world, "per_gpu_batch": B, "parallelism": f"dp{world}"},
@@ -314,7 +342,8 @@ def main():
             "gflop_per_sample_step": round(3 * fwd_flops / 1e9, 3),
             "final_loss": final_loss,
         }
-        out["parity_note"] = parity_note(args.precision)
+        if args.full:
+            out["parity_note"] = parity_note(args.precision)
         if ranks_seen is not None:
             out["rccl_ranks_seen"] = ranks_seen
         if args.force_dp:
@@ -431,6 +460,32 @@ def main():
         print(json.dumps(out), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(path, model, loss, seed):
+    """What the last timed step handed its caller, as float32 .npy files under `path`:
+      loss.npy    [1]  the step's loss
+      grads.npy        the step's gradients, every parameter that received one, flattened in named_parameters() order
+      params.npy       every parameter after the step's AdamW update, flattened in named_parameters() order
+    The order is that of the module surface, not of the flat buffer's layout, so two builds compare element for element.
+    An array larger than its share of DUMP_BYTES is replaced by a fixed sample: sorted indices drawn by a generator
+    seeded with `seed`, the same for every run of the same configuration."""
+    named = list(model.named_parameters())
+    arrays = {
+        "loss": loss.detach().float().reshape(1).cpu().numpy(),
+        "grads": torch.cat([p.grad.detach().float().reshape(-1) for _, p in named if p.grad is not None]).cpu().numpy(),
+        "params": torch.cat([p.detach().float().reshape(-1) for _, p in named]).cpu().numpy(),
+    }
+    share = (DUMP_BYTES - 4096) // len(arrays)   # 4 KB for the .npy headers
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, share // a.itemsize, replace=False))
+            a = a[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # (pattern in the kernel's symbol, bench.py kernel name): first match wins, the more specific pattern first

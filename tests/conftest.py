@@ -26,14 +26,24 @@ def load_golden(name):
     return d
 
 
+GOLDEN_THREADS = 8   # tools/make_golden.py runs under torch.set_num_threads(8)
+
+
 def fp_np(t):
-    """same fingerprint as tools/make_golden.py:fp"""
+    """same fingerprint as tools/make_golden.py:fp, summed under the same thread count: torch splits a large reduction into one
+    chunk per intra-op thread, so the last bit of a float64 sum depends on the thread count of the process"""
     import torch
     t = t.detach().to(torch.float64).reshape(-1)
     head = np.zeros(8, dtype=np.float64)
     n = min(8, t.numel())
     head[:n] = t[:n].numpy()
-    return np.concatenate([[t.sum().item(), t.abs().sum().item(), float(t.numel())], head])
+    threads = torch.get_num_threads()
+    torch.set_num_threads(GOLDEN_THREADS)
+    try:
+        sums = [t.sum().item(), t.abs().sum().item()]
+    finally:
+        torch.set_num_threads(threads)
+    return np.concatenate([sums, [float(t.numel())], head])
 
 
 def oracle_cfg_from(cfg):

@@ -421,3 +421,35 @@ def test_strict_tier_trips_at_twice_the_baseline():
             assert util.strict_violations(t, r2), (t, r)
             tripped += 1
     assert tripped > 30
+
+
+# ----------------------------------------------------------------------------- bench.py --dump-outputs
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: loss, gradients and parameters as float32 .npy, in named_parameters() order; an array larger than
+    its share of the size cap is replaced by the same seeded sample on every call"""
+    import bench
+    model, _, _ = build_product(dict(bands=30, depth=2, B=2, heads=2))
+    named = list(model.named_parameters())
+    for i, (n, p) in enumerate(named):
+        if not n.startswith("encoder.mlp_head"):   # no gradient in pre-training
+            p.grad = torch.full_like(p, float(i))
+    with_grad = [p for _, p in named if p.grad is not None]
+    assert 0 < len(with_grad) < len(named)
+    bench.dump_outputs(str(tmp_path / "a"), model, torch.tensor(0.25), 5)
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("loss", "grads", "params")}
+    assert sorted(os.listdir(tmp_path / "a")) == ["grads.npy", "loss.npy", "params.npy"]
+    assert all(v.dtype == np.float32 for v in a.values())
+    np.testing.assert_array_equal(a["loss"], np.float32([0.25]))
+    np.testing.assert_array_equal(a["grads"], torch.cat([p.grad.reshape(-1) for p in with_grad]).numpy())
+    np.testing.assert_array_equal(a["params"], torch.cat([p.detach().reshape(-1) for _, p in named]).numpy())
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096 + 3 * 40000)   # 10000 float32 per array
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), model, torch.tensor(0.25), 5)
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= bench.DUMP_BYTES
+    for n in ("grads", "params"):
+        b, c = np.load(tmp_path / "b" / (n + ".npy")), np.load(tmp_path / "c" / (n + ".npy"))
+        idx = np.sort(np.random.default_rng(5).choice(a[n].size, 10000, replace=False))
+        np.testing.assert_array_equal(b, a[n][idx])
+        np.testing.assert_array_equal(b, c)
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "loss.npy"), a["loss"])

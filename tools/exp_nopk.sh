@@ -2,7 +2,7 @@
 # (tools/valu_microbench.hip: one v_pk_*_f32 beside another wave's MFMAs costs ~120 cycles, two scalar ops ~20)
 NOPK="-Xclang -target-feature -Xclang -packed-fp32-ops"
 run() {
-  python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-pipeline --profile-all ${AB_BENCH_ARGS} 2>/dev/null | tail -1 | python3 -c "
+  python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-pipeline --profile-all ${AB_BENCH_ARGS} 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print(d['value'], {k: round(v['avg_us'],1) for k,v in d['kernels'].items()})"
 }

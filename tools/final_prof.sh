@@ -29,17 +29,17 @@ find $OUT -name "*.csv" -size +512k -delete
 # the per-launch HBM traffic table bench.py quotes (roofline.traffic, hbm_bound_kernels) comes from these passes: write it in
 # place BEFORE the bench lines below are taken, so that the committed line and the committed table belong to the same kernels
 python3 tools/make_profiles.py "$TAG" --traffic-only
-rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats -o "$TAG" -- python3 bench.py --no-cpu-baseline --no-traffic > $OUT/bench_under_rocprof.txt 2>&1 || true
+rocprofv3 --kernel-trace --stats -f csv -d $OUT/stats -o "$TAG" -- python3 bench.py --full --no-cpu-baseline --no-traffic > $OUT/bench_under_rocprof.txt 2>&1 || true
 find $OUT/stats -name "*kernel_trace.csv" -delete
-timeout 900 python3 bench.py > $OUT/bench_default.json 2>$OUT/bench_default.err || true
+timeout 900 python3 bench.py --full > $OUT/bench_default.json 2>$OUT/bench_default.err || true
 tail -1 $OUT/bench_default.json | cut -c1-600
-timeout 600 python3 bench.py --no-cpu-baseline --no-traffic --no-alt --profile-all > $OUT/bench_profile_all.json 2>/dev/null || true
+timeout 600 python3 bench.py --full --no-cpu-baseline --no-traffic --no-alt --profile-all > $OUT/bench_profile_all.json 2>/dev/null || true
 # other configurations (parity-test shapes and the batch sweep), one line each
-( python3 bench.py --no-cpu-baseline --no-traffic --dropout 0 | tail -1
-  python3 bench.py --no-cpu-baseline --no-traffic --bands 50 | tail -1
-  python3 bench.py --no-cpu-baseline --no-traffic --batch 64 | tail -1
-  python3 bench.py --no-cpu-baseline --no-traffic --batch 1024 --steps 5 | tail -1
-  python3 bench.py --no-cpu-baseline --no-traffic --precision fp32 --steps 3 --warmup 1 | tail -1 ) > $OUT/bench_other_configs.jsonl 2>/dev/null || true
+( python3 bench.py --full --no-cpu-baseline --no-traffic --dropout 0 | tail -1
+  python3 bench.py --full --no-cpu-baseline --no-traffic --bands 50 | tail -1
+  python3 bench.py --full --no-cpu-baseline --no-traffic --batch 64 | tail -1
+  python3 bench.py --full --no-cpu-baseline --no-traffic --batch 1024 --steps 5 | tail -1
+  python3 bench.py --full --no-cpu-baseline --no-traffic --precision fp32 --steps 3 --warmup 1 | tail -1 ) > $OUT/bench_other_configs.jsonl 2>/dev/null || true
 cut -c1-200 $OUT/bench_other_configs.jsonl
 # CU contention: the step with N occupancy-probe workgroups held on a side stream, default grid and the DP grid
 # static partition (single-GPU default), static partition on grids sized for 32 free CUs (round 3's DP choice; with and without a

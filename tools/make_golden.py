@@ -256,6 +256,41 @@ def run_peaky():
             run_case(f"{tag}_qkv{s}", dict(cfg, qkv_scale=s))
 
 
+def run_f64_anchor(name, cfg):
+    """`loss_f64`, added to an existing fixture: the reference's loss in float64 on the same parameters, input and masks.  The x8
+    fixtures amplify fp32 round-off to ~1e-3 of the loss, and which round-off depends on the CPU (MKL picks its kernels by
+    processor), so their fp32 loss pins the oracle only on a CPU like the one that wrote it; in float64 two evaluations of the
+    same formulas agree to ~1e-12 on any CPU."""
+    path = os.path.join(OUT, f"simmim_{name}.npz")
+    z = np.load(path)
+    out = {k: z[k] for k in z.files}
+    seed_all()
+    model = build(cfg)
+    B, C = cfg["B"], cfg["bands"]
+    x = torch.randn(B, C, cfg.get("image_size", 8), cfg.get("image_size", 8))
+    model.eval()
+    attention_stats(model, x)   # run_case's draws, in run_case's order
+    model.double()
+    if hasattr(model.to_pixels, "dtype"):
+        model.to_pixels.dtype = torch.float64   # the per-block decoder allocates its output in this dtype (vit_simmim_original.py:25-31)
+    dtype = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    try:
+        with torch.no_grad():
+            loss = model(x.double())
+    finally:
+        torch.set_default_dtype(dtype)
+    assert loss.dtype == torch.float64
+    out["loss_f64"] = np.array(loss.item(), dtype=np.float64)
+    np.savez_compressed(path, **out)
+    print(f"{name}: loss_f64={loss.item():.15e} (fp32 capture {float(out['loss']):.9e})")
+
+
+def run_f64_anchors():
+    for tag, cfg in PEAKY:
+        run_f64_anchor(f"{tag}_qkv8", dict(cfg, qkv_scale=8))
+
+
 def run_adamw_traj():
     """BASELINE config 1 plumbing case: depth 2, 32 cubes 8x8x200, AdamW lr 0.008 wd 0.05,
     clamp hook (pretrain.py:71-73), dropout 0 (deterministic), 5 steps."""
@@ -476,6 +511,10 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "peaky":   # depth-12 cases with peaky attention rows (to_qkv.weight x4 / x8)
         run_peaky()
+        run_f64_anchors()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "f64":   # float64 loss anchors of the x8 fixtures, added to the files run_peaky wrote
+        run_f64_anchors()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "shapes":   # other image sizes / sequence packings (padding rows in the 64-row tiles)
         run_case("70b_L1_B3_img4_mps2", dict(bands=70, depth=1, B=3, image_size=4, mask_patch_size=2))
@@ -502,6 +541,7 @@ if __name__ == "__main__":
     run_case("70b_L1_B3_img4_mps2", dict(bands=70, depth=1, B=3, image_size=4, mask_patch_size=2))
     run_case("30b_L1_B2_img6_mps2_h2", dict(bands=30, depth=1, B=2, image_size=6, mask_patch_size=2, heads=2))
     run_peaky()
+    run_f64_anchors()
     run_adamw_traj()
     run_finetune_case("200b_L4_B2", dict(bands=200, depth=4, B=2, n_classes=8, spectral_pos_embed=False))
     run_finetune_case("50b_L2_B2_specpos", dict(bands=50, depth=2, B=2, n_classes=20, spectral_pos_embed=True))
