@@ -48,6 +48,9 @@ def main():
     ap.add_argument("--batch-size", type=int, default=None)
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--val-scenes", type=int, default=0,
+                    help="validate on N held-out synthetic 64 x 64 scenes with predict_scene (0: no validation)")
+    ap.add_argument("--val-every", type=int, default=0, help="validate every K steps (0: no validation)")
     args = ap.parse_args()
     random.seed(SEED); np.random.seed(SEED); torch.manual_seed(SEED)
     if not torch.cuda.is_available():
@@ -78,6 +81,15 @@ def main():
                                  weight_decay=config.weight_decay)   # finetune.py:110-134 (two learning rates)
     criterion = torch.nn.CrossEntropyLoss(ignore_index=config.ignored_label)
     gen = torch.Generator().manual_seed(SEED)
+    val = None
+    if args.val_scenes > 0 and args.val_every > 0:
+        # held-out scenes from a generator of their own: the training draws (and the default output) stay as they are
+        vgen = torch.Generator().manual_seed(SEED + 1)
+        vimg = torch.randn(args.val_scenes, config.n_bands, 64, 64, generator=vgen)
+        if config.dataset == "houston2018":
+            vimg[:, 48:] = 0.0
+        vlab = torch.randint(-1, config.n_classes, (args.val_scenes, 64, 64), generator=vgen)
+        val = (vimg.to(device), vlab.to(device))
     model.train()
     t0 = time.time()
     for step in range(1, args.steps + 1):
@@ -89,6 +101,18 @@ def main():
         if step % config.logging_freq == 0:
             print(f"step {step} loss {loss.item():.4f} acc {float(acc):.3f} {step * config.batch_size / (time.time() - t0):.1f} samples/s",
                   flush=True)
+        if val is not None and step % args.val_every == 0:
+            validate(model, val, step, config.ignored_label)
+
+
+def validate(model, val, step, ignored_label):
+    """validate_downstream (reference src/utils.py:477-605) over whole scenes: one predict_scene pass (windows of image_size,
+    eval forward, the module's mode untouched) and the scene metrics of maskedsst_amd.scene"""
+    from maskedsst_amd.scene import scene_metrics
+    img, label = val
+    classes, logits = model.predict_scene(img, return_logits=True)
+    m = scene_metrics(logits, classes, label, ignore_index=ignored_label)
+    print(f"val step {step} loss {m.loss:.4f} acc {m.acc:.3f} macro_acc {m.macro_acc:.3f} scenes {img.shape[0]}", flush=True)
 
 
 if __name__ == "__main__":

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MSST_VERSION 104
+#define MSST_VERSION 105
 #define MSST_DIM 96
 #define MSST_DIM_HEAD 64
 #define MSST_MLP 64
@@ -128,6 +128,37 @@ int msst_tokenize_fwd(const float* img, const float* pre_g, const float* pre_b, 
                       const float* b_emb, const float* post_g, const float* post_b, const float* pos_a,
                       const float* pos_b, int pos_split, const float* mask_token, const uint8_t* mask,
                       float* out, int B, int S, int N, int P, float emb_dropout_p, uint32_t seed, void* stream);
+
+/* MSST_VERSION 105: scene inference (sliding windows).  Replaces the window loops of the reference's inference_example.ipynb (cell
+ * "for x in range(0, 64, eff_size): for y in range(0, 64, eff_size): ... model(img).argmax(dim=1)") and of validate_downstream
+ * (src/utils.py:497-541): there every window is a .narrow() copy and a model(window) call of its own; here one tokenizer launch reads
+ * any number of windows of many scenes straight out of the scene tensor, the block / head kernels run on all of them as one batch,
+ * and msst_scene_assemble writes the scene-shaped maps.
+ * Windows: window i of a call is window win0 + i, row-major over (scene, window row r, window column q) of the grid
+ * nr = (Hs - window) / stride + 1 rows by nq = (Ws - window) / stride + 1 columns; window (r, q) has its origin at (r stride, q stride)
+ * -- the notebook's origins 0, s, 2s, ... (H outer, W inner), keeping only windows with origin + window <= the scene size.
+ * Where our semantics differ from the reference: overlapping windows (stride < window) are AVERAGED (mean of the logits of every
+ * window covering a pixel; the notebook lets the last window's argmax overwrite); pixels no window covers get class -1 (the configs'
+ * ignored_label) and logit 0 (the notebook leaves 0, a real class); every window with origin + window <= size is kept
+ * (validate_downstream's `x + image_size >= 64` also drops the last window row); scenes of any size (the notebook: 64 x 64).
+ *
+ * msst_tokenize_scene_fwd: msst_tokenize_fwd (no mask, position table(s) added, no embedding dropout) of windows win0 .. win0 + nwin - 1
+ * of scene [Bs][S*P][Hs][Ws] (fp32, contiguous): out [nwin][S*window*window][96], the values msst_tokenize_fwd gives for the copied
+ * windows.  pos_a / pos_b / pos_split as there.  1 <= stride <= window <= Hs, Ws; window * window <= 64 and P <= 16
+ * (MSST_ERR_UNSUPPORTED otherwise; for P != 10 or window != 8 also nwin <= 65535). */
+int msst_tokenize_scene_fwd(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb,
+                            const float* b_emb, const float* post_g, const float* post_b, const float* pos_a,
+                            const float* pos_b, int pos_split, float* out, int Bs, int Hs, int Ws, int window, int stride,
+                            long win0, int nwin, int S, int P, void* stream);
+
+/* msst_scene_assemble: adds the per-window logits win_logits [nwin][n_classes][window*window] (msst_cls_head_fwd of windows
+ * win0 .. win0 + nwin - 1) into the running per-pixel sums logits [Bs][n_classes][Hs][Ws] (fp32).  The calls of one scene batch
+ * must cover windows 0, 1, ... in order (any split into calls); logits needs no initialisation.  finalize != 0 (the last call, after
+ * its own windows): logits = the sums divided by the number of windows covering the pixel (the plain mean), classes [Bs][Hs][Ws]
+ * (int64) = the argmax over classes (ties: lowest index, as torch.argmax); uncovered pixels: logits 0, class -1.  Each pixel sums
+ * its windows in window order (row, then column) without atomics: bitwise reproducible, whatever the split into calls. */
+int msst_scene_assemble(const float* win_logits, long win0, int nwin, float* logits, int64_t* classes, int Bs,
+                        int n_classes, int Hs, int Ws, int window, int stride, int finalize, void* stream);
 
 /* a7-a10: one fused pre-norm transformer block (PreNorm+Attention+FeedForward+residuals,
  * vit_spatial_spectral.py:22-104) over all B*S*N tokens; mode selects the spatial or spectral

@@ -54,6 +54,8 @@ _SIGS = {
     "msst_last_error": (c_char_p, []),
     "msst_prep_weights": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "msst_tokenize_fwd": (c_int, [_P] * 9 + [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_uint32, _P]),
+    "msst_tokenize_scene_fwd": (c_int, [_P] * 9 + [c_int, _P, c_int, c_int, c_int, c_int, c_int, c_long, c_int, c_int, c_int, _P]),
+    "msst_scene_assemble": (c_int, [_P, c_long, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "msst_cls_head_fwd": (c_int, [_P] * 6 + [c_int, c_int, c_int, c_int, _P]),
     "msst_cls_head_bwd": (c_int, [_P] * 11 + [c_int, c_int, c_int, c_int, _P]),
     "msst_block_lse_floats": (c_long, [c_int, c_int, c_int, c_int, c_int]),

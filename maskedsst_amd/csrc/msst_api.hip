@@ -283,6 +283,59 @@ int msst_tokenize_fwd(const float* img, const float* pre_g, const float* pre_b, 
     return fail(launch_tokenize_fwd(a, (hipStream_t)stream), "msst_tokenize_fwd");
 }
 
+// window grid of a scene: false when the shapes are not a valid (scene, window, stride) triple
+static bool scene_grid(int Bs, int Hs, int Ws, int window, int stride, int* nr, int* nq) {
+    if (Bs < 1 || window < 1 || stride < 1 || stride > window || Hs < window || Ws < window) return false;
+    *nr = (Hs - window) / stride + 1;
+    *nq = (Ws - window) / stride + 1;
+    return true;
+}
+
+int msst_tokenize_scene_fwd(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb,
+                            const float* b_emb, const float* post_g, const float* post_b, const float* pos_a,
+                            const float* pos_b, int pos_split, float* out, int Bs, int Hs, int Ws, int window, int stride,
+                            long win0, int nwin, int S, int P, void* stream) {
+    int nr = 0, nq = 0;
+    if (!scene || !out || S < 1 || P < 1 || nwin < 0 || win0 < 0 || !scene_grid(Bs, Hs, Ws, window, stride, &nr, &nq))
+        return fail(MSST_ERR_BADARG, "msst_tokenize_scene_fwd");
+    const long wps = (long)nr * nq;
+    if (wps > 0x7fffffffL || win0 + nwin > (long)Bs * wps) return fail(MSST_ERR_BADARG, "msst_tokenize_scene_fwd (windows out of range)");
+    if (window > 8) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_scene_fwd (more than 64 pixels per window)");
+    TokArgs a;
+    a.drop = make_drop(0.f, 0, 255);
+    a.img = scene; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb;
+    a.post_g = post_g; a.post_b = post_b; a.pos_a = pos_a; a.pos_b = pos_b; a.mask_token = nullptr; a.mask = nullptr;
+    a.out = out; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P; a.pos_split = pos_split;
+    a.win0 = win0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nq = nq; a.wps = (int)wps;
+    return fail(launch_tokenize_scene_fwd(a, (hipStream_t)stream), "msst_tokenize_scene_fwd");
+}
+
+int msst_scene_assemble(const float* win_logits, long win0, int nwin, float* logits, int64_t* classes, int Bs,
+                        int n_classes, int Hs, int Ws, int window, int stride, int finalize, void* stream) {
+    int nr = 0, nq = 0;
+    if (!logits || (finalize && !classes) || (nwin > 0 && !win_logits) || n_classes < 1 || nwin < 0 || win0 < 0 ||
+        !scene_grid(Bs, Hs, Ws, window, stride, &nr, &nq))
+        return fail(MSST_ERR_BADARG, "msst_scene_assemble");
+    const long wps = (long)nr * nq;
+    if (win0 + nwin > (long)Bs * wps) return fail(MSST_ERR_BADARG, "msst_scene_assemble (windows out of range)");
+    SceneArgs a;
+    a.win_logits = win_logits; a.logits = logits; a.classes = classes; a.win0 = win0; a.nwin = nwin;
+    a.Bs = Bs; a.NC = n_classes; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nr = nr; a.nq = nq;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = 0;
+    if (nwin > 0) {
+        // the flattened (scene, pixel row) rows the windows of this call reach: first window's top row .. last window's bottom row
+        const long g0 = win0, g1 = win0 + nwin - 1;
+        const long s0 = g0 / wps, s1 = g1 / wps;
+        const long r0 = (g0 - s0 * wps) / nq, r1 = (g1 - s1 * wps) / nq;
+        a.row0 = s0 * Hs + r0 * stride;
+        const long rows = s1 * Hs + r1 * stride + window - a.row0;
+        rc = launch_scene_accumulate(a, rows * Ws, st);
+    }
+    if (!rc && finalize) rc = launch_scene_finalize(a, st);
+    return fail(rc, "msst_scene_assemble");
+}
+
 long msst_block_lse_floats(int mode, int B, int S, int N, int heads) {
     if (B < 1 || S < 1 || N < 1 || heads < 1 || N > 64 || S > 64) return 0;
     return (long)ntiles_of(make_tilemap(mode, B, S, N)) * heads * 64 + (long)B * S * N;   // [tiles][heads][64] lse | [tokens] rstd of LN1

@@ -21,15 +21,26 @@ namespace msst {
 // ==========================================================================================
 // PC: pixels per patch as a compile-time constant (10 = the reference's spectral patch, configs/config.yaml: band_patch_size)
 // so that the small loops over it unroll and their LDS reads are batched; 0 = run-time value (any P <= 16)
-template <int PC>
-__global__ __launch_bounds__(256) void tokenize_fwd_kernel(TokArgs a) {
+// SCENE: addressing policy of the source pixels.  false: img[b, c P + k, n] of a batch of cubes [B][S*P][N];  true: the same pixel of
+// window b of a scene, scene[s, c P + k, y0 + n / win, x0 + n % win] (TokArgs scene fields; no mask, no dropout).  Nothing else differs.
+template <int PC, bool SCENE>
+__device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
     __shared__ float patch[16][64];
     __shared__ float W[96][17];
     __shared__ float bias[96];
     const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int P = PC ? PC : a.P, N = a.N;
-    const float* src = a.img + ((long)b * a.S + c) * P * N;
-    for (int i = tid; i < P * N; i += 256) patch[i / N][i % N] = src[i];
+    if constexpr (SCENE) {
+        const long plane = (long)a.Hs * a.Ws;
+        const float* src = scene_window_origin(a, b) + (long)c * P * plane;
+        for (int i = tid; i < P * N; i += 256) {
+            const int k = i / N, n = i % N;
+            patch[k][n] = src[k * plane + (long)(n / a.win) * a.Ws + n % a.win];
+        }
+    } else {
+        const float* src = a.img + ((long)b * a.S + c) * P * N;
+        for (int i = tid; i < P * N; i += 256) patch[i / N][i % N] = src[i];
+    }
     for (int i = tid; i < 96 * P; i += 256) W[i / P][i % P] = a.w_emb[(long)c * 96 * P + i];
     if (tid < 96) bias[tid] = a.b_emb[c * 96 + tid];
     __syncthreads();
@@ -70,7 +81,7 @@ __global__ __launch_bounds__(256) void tokenize_fwd_kernel(TokArgs a) {
     v2 += __shfl_xor(v2, 1); v2 += __shfl_xor(v2, 2);
     const float rstd2 = rsqrtf(v2 * (1.f / 96.f) + 1e-5f);
     const int t = c * N + n;
-    const bool masked = a.mask[(long)b * a.T + t] != 0;
+    const bool masked = SCENE ? false : a.mask[(long)b * a.T + t] != 0;
     float* dst = a.out + ((long)b * a.T + t) * 96 + part * 4;
 #pragma unroll
     for (int i = 0; i < 24; ++i) {
@@ -79,15 +90,20 @@ __global__ __launch_bounds__(256) void tokenize_fwd_kernel(TokArgs a) {
         if (a.pos_split) pos = d < a.pos_split ? a.pos_a[n * a.pos_split + d] : a.pos_b[c * (96 - a.pos_split) + d - a.pos_split];
         else pos = a.pos_a[(long)t * 96 + d];
         const float tok = (e[i] - m2) * rstd2 * a.post_g[d] + a.post_b[d];
-        e[i] = (masked ? a.mask_token[d] : tok) + pos;
+        e[i] = (!SCENE && masked ? a.mask_token[d] : tok) + pos;
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
         f32x4 v = {e[4*i], e[4*i+1], e[4*i+2], e[4*i+3]};
-        if (a.drop.thr) v = drop4(a.drop, 0, (unsigned)(((long)b * a.T + t) * 24 + 4 * i + part), v);   // emb dropout (group = feature / 4)
+        if (!SCENE && a.drop.thr) v = drop4(a.drop, 0, (unsigned)(((long)b * a.T + t) * 24 + 4 * i + part), v);   // emb dropout (group = feature / 4)
         *reinterpret_cast<f32x4*>(dst + 16 * i) = v;
     }
 }
+
+template <int PC>
+__global__ __launch_bounds__(256) void tokenize_fwd_kernel(TokArgs a) { tokenize_fwd_body<PC, false>(a); }
+template <int PC>
+__global__ __launch_bounds__(256) void tokenize_scene_fwd_kernel(TokArgs a) { tokenize_fwd_body<PC, true>(a); }
 
 
 // ------------------------------------------------------------------------------------------
@@ -100,12 +116,14 @@ __global__ __launch_bounds__(256) void tokenize_fwd_kernel(TokArgs a) {
 // layout), and the C layout (4 consecutive features of one token per lane) is the 16-byte store of the token row.
 // grid (S, nchunk), 256 threads: wave w <-> tokens 16 w .. + 15 of spectral block c, samples chunk, chunk + nchunk, ...
 // Position rows, bias, both LayerNorms' vectors and the mask token are tile invariant for a wave: registers / LDS.
+// SCENE: the source addressing policy of tokenize_fwd_body (windows of a scene instead of a batch of cubes; no mask, no dropout).
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256, 2) void tokenize_fwd_mfma_kernel(TokArgs a) {
+template <bool SCENE>
+__device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
     constexpr int P = 10, N = 64;
     __shared__ __attribute__((aligned(16))) float vec[3][96];   // post_g | post_b | mask_token
     const int c = blockIdx.x, tid = threadIdx.x, w = tid >> 6, l = tid & 63, g = l >> 4, j = l & 15;
-    if (tid < 96) { vec[0][tid] = a.post_g[tid]; vec[1][tid] = a.post_b[tid]; vec[2][tid] = a.mask_token[tid]; }
+    if (tid < 96) { vec[0][tid] = a.post_g[tid]; vec[1][tid] = a.post_b[tid]; vec[2][tid] = SCENE ? 0.f : a.mask_token[tid]; }
     // A fragments of W_c [96][10]: lane (i = l & 15, kq = l >> 4) holds W[16 mt + i][4 ks + kq] (zero beyond k = 9)
     float wf[6][3];
 #pragma unroll
@@ -141,10 +159,18 @@ __global__ __launch_bounds__(256, 2) void tokenize_fwd_mfma_kernel(TokArgs a) {
     unsigned char mk;
     auto request = [&](int b) {
         const int bc = b < a.B ? b : a.B - 1;
-        const float* src = a.img + ((long)bc * a.S + c) * P * N + n;
+        if constexpr (SCENE) {
+            const long plane = (long)a.Hs * a.Ws;
+            const float* src = scene_window_origin(a, bc) + (long)c * P * plane + (long)(n / a.win) * a.Ws + n % a.win;
 #pragma unroll
-        for (int ks = 0; ks < 3; ++ks) { const int k = 4 * ks + g; px[ks] = src[(k < P ? k : 0) * N]; }
-        mk = a.mask[(long)bc * a.T + t];
+            for (int ks = 0; ks < 3; ++ks) { const int k = 4 * ks + g; px[ks] = src[(k < P ? k : 0) * plane]; }
+            mk = 0;
+        } else {
+            const float* src = a.img + ((long)bc * a.S + c) * P * N + n;
+#pragma unroll
+            for (int ks = 0; ks < 3; ++ks) { const int k = 4 * ks + g; px[ks] = src[(k < P ? k : 0) * N]; }
+            mk = a.mask[(long)bc * a.T + t];
+        }
     };
     request(blockIdx.y);
     for (int b = blockIdx.y; b < a.B; b += nb) {
@@ -189,11 +215,14 @@ __global__ __launch_bounds__(256, 2) void tokenize_fwd_mfma_kernel(TokArgs a) {
             f32x4 v;
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = (masked ? m4[r] : (e[mt][r] - m2) * rstd2 * g4[r] + b4[r]) + pos4[mt][r];
-            if (a.drop.thr) v = drop4(a.drop, 0, (unsigned)(((long)b * a.T + t) * 24 + 4 * mt + g), v);   // emb dropout (group = feature / 4)
+            if (!SCENE && a.drop.thr) v = drop4(a.drop, 0, (unsigned)(((long)b * a.T + t) * 24 + 4 * mt + g), v);   // emb dropout (group = feature / 4)
             *reinterpret_cast<f32x4*>(dst + 16 * mt) = v;
         }
     }
 }
+
+__global__ __launch_bounds__(256, 2) void tokenize_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<false>(a); }
+__global__ __launch_bounds__(256, 2) void tokenize_scene_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<true>(a); }
 
 // ==========================================================================================
 // fused transformer block, forward.  Reference vit_spatial_spectral.py:22-29 (PreNorm),
@@ -862,6 +891,24 @@ int launch_tokenize_fwd(const TokArgs& a, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
+// the same kernel selection as launch_tokenize_fwd, SCENE instances (a.B = windows of the call)
+int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st) {
+    if (a.P > 16 || a.N > 64) return MSST_ERR_UNSUPPORTED;
+    if (a.B < 1) return 0;
+    ProfScope ps(K_TOK_FWD, st);
+    if (a.P == 10 && a.N == 64) {
+        int nchunk = 1024 / (a.S > 0 ? a.S : 1);
+        if (nchunk < 1) nchunk = 1;
+        if (nchunk > a.B) nchunk = a.B;
+        hipLaunchKernelGGL(tokenize_scene_fwd_mfma_kernel, dim3(a.S, nchunk), dim3(256), 0, st, a);
+    } else {
+        if (a.B > 65535) return MSST_ERR_UNSUPPORTED;   // one workgroup row per window (grid y)
+        if (a.P == 10) hipLaunchKernelGGL(tokenize_scene_fwd_kernel<10>, dim3(a.S, a.B), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(tokenize_scene_fwd_kernel<0>, dim3(a.S, a.B), dim3(256), 0, st, a);
+    }
+    return (int)hipGetLastError();
+}
+
 template <class P>
 static int launch_block_fwd_t(const BlockArgs& a, int grid, hipStream_t st) {
     static std::atomic<bool> attr_set{false};
@@ -985,6 +1032,94 @@ __global__ __launch_bounds__(256) void cls_head_fwd_kernel(ClsArgs a) {
 int launch_cls_head_fwd(const ClsArgs& a, hipStream_t st) {
     if (a.N > 64) return MSST_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(cls_head_fwd_kernel, dim3(a.B), dim3(256), 0, st, a);
+    return (int)hipGetLastError();
+}
+
+// ==========================================================================================
+// scene assembly: per-window logits [nwin][NC][win * win] (cls_head_fwd_kernel of windows of a scene) -> scene logit map = mean of
+// the logits of every window covering a pixel, class map = argmax.  Replaces the window loop of the reference's
+// inference_example.ipynb (model(window).argmax(1) written into the class map) and of validate_downstream (src/utils.py:497-541).
+// The windows covering pixel (y, x) are the rectangle of window rows r in [ceil((y - win + 1) / stride), y / stride] and columns
+// likewise, clipped to the grid; each thread owns one pixel and sums them in window order (row, then column): no atomics, a fixed
+// order, so the map is bitwise reproducible and independent of how the windows were split into calls.
+// ==========================================================================================
+__device__ __forceinline__ bool scene_cover(const SceneArgs& a, int y, int x, int& rlo, int& rhi, int& qlo, int& qhi) {
+    rlo = y < a.win ? 0 : (y - a.win) / a.stride + 1;
+    rhi = min(y / a.stride, a.nr - 1);
+    qlo = x < a.win ? 0 : (x - a.win) / a.stride + 1;
+    qhi = min(x / a.stride, a.nq - 1);
+    return rlo <= rhi && qlo <= qhi;
+}
+
+// adds the windows win0 .. win0 + nwin - 1 into the running sums; pixel p of the launch = flattened row row0 + p / Ws, column p % Ws.
+// A pixel whose first covering window is in this call starts from 0 (no memset); one with no window in this call is not touched.
+__global__ __launch_bounds__(256) void scene_accumulate_kernel(SceneArgs a, long pixels) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= pixels) return;
+    const long R = a.row0 + p / a.Ws;
+    const int x = (int)(p % a.Ws);
+    const long s = R / a.Hs;
+    const int y = (int)(R - s * a.Hs);
+    int rlo, rhi, qlo, qhi;
+    if (!scene_cover(a, y, x, rlo, rhi, qlo, qhi)) return;
+    const long wps = (long)a.nr * a.nq, base = s * wps;
+    const long first = base + (long)rlo * a.nq + qlo, last = base + (long)rhi * a.nq + qhi, end = a.win0 + a.nwin;
+    if (last < a.win0 || first >= end) return;
+    const int N = a.win * a.win;
+    const long plane = (long)a.Hs * a.Ws;
+    float* out = a.logits + s * a.NC * plane + (long)y * a.Ws + x;
+    for (int k = 0; k < a.NC; ++k) {
+        float acc = first >= a.win0 ? 0.f : out[k * plane];
+        for (int r = rlo; r <= rhi; ++r) {
+            const long g0 = base + (long)r * a.nq;
+            for (int q = qlo; q <= qhi; ++q) {
+                const long g = g0 + q;
+                if (g < a.win0 || g >= end) continue;
+                acc += a.win_logits[((g - a.win0) * a.NC + k) * N + (y - r * a.stride) * a.win + (x - q * a.stride)];
+            }
+        }
+        out[k * plane] = acc;
+    }
+}
+
+// sums -> means (sum / windows covering the pixel), argmax over classes (first maximum, NaN counts as the maximum: torch.argmax);
+// uncovered pixels: logits 0, class -1
+__global__ __launch_bounds__(256) void scene_finalize_kernel(SceneArgs a) {
+    const long plane = (long)a.Hs * a.Ws;
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (long)a.Bs * plane) return;
+    const long s = p / plane, pix = p - s * plane;
+    const int y = (int)(pix / a.Ws), x = (int)(pix % a.Ws);
+    float* out = a.logits + s * a.NC * plane + pix;
+    int rlo, rhi, qlo, qhi;
+    if (!scene_cover(a, y, x, rlo, rhi, qlo, qhi)) {
+        for (int k = 0; k < a.NC; ++k) out[k * plane] = 0.f;
+        a.classes[p] = -1;
+        return;
+    }
+    const float cnt = (float)((rhi - rlo + 1) * (qhi - qlo + 1));
+    float best = 0.f;
+    int arg = 0;
+    for (int k = 0; k < a.NC; ++k) {
+        const float v = out[k * plane] / cnt;
+        out[k * plane] = v;
+        if (k == 0 || (best == best && (v > best || v != v))) { best = v; arg = k; }
+    }
+    a.classes[p] = arg;
+}
+
+int launch_scene_accumulate(const SceneArgs& a, long pixels, hipStream_t st) {
+    if (pixels < 1) return 0;
+    const long grid = (pixels + 255) / 256;
+    if (grid > 0x7fffffffL) return MSST_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(scene_accumulate_kernel, dim3((unsigned)grid), dim3(256), 0, st, a, pixels);
+    return (int)hipGetLastError();
+}
+
+int launch_scene_finalize(const SceneArgs& a, hipStream_t st) {
+    const long grid = ((long)a.Bs * a.Hs * a.Ws + 255) / 256;
+    if (grid > 0x7fffffffL) return MSST_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(scene_finalize_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 

@@ -78,7 +78,30 @@ struct TokArgs {
     float* out;              // [B][T][96]
     int B, S, N, T, P, pos_split;
     Drop drop;               // embedding dropout on (token + pos) (vit_spatial_spectral.py:530), classification path only
+    // scene windows (msst_tokenize_scene_fwd, the kernels' SCENE = true instances only): img is a scene [Bs][S*P][Hs][Ws] and
+    // sample b is window win0 + b, row-major over (scene, window row, window column), origin (r * stride, q * stride), win x win pixels
+    long win0;
+    int Hs, Ws, win, stride, nq, wps;   // nq: windows per window row, wps: windows per scene
 };
+
+// img pointer of sample b's window origin (scene s, band 0, row r * stride, column q * stride); 64-bit: scenes may be large
+__device__ __forceinline__ const float* scene_window_origin(const TokArgs& a, int b) {
+    const long i = a.win0 + b;
+    const long s = i / a.wps;
+    const int rem = (int)(i - s * a.wps), r = rem / a.nq, q = rem - r * a.nq;
+    return a.img + ((s * a.S * a.P) * a.Hs + (long)r * a.stride) * a.Ws + (long)q * a.stride;
+}
+
+// scene assembly (msst_scene_assemble): per-window logits -> running per-pixel sums (accumulate), then mean / argmax (finalize)
+struct SceneArgs {
+    const float* win_logits;   // [nwin][NC][win * win] of windows win0 .. win0 + nwin - 1
+    float* logits;             // [Bs][NC][Hs][Ws]: the running sums, then the means
+    int64_t* classes;          // [Bs][Hs][Ws]
+    long win0, row0;           // row0: first flattened (scene, pixel row) row the windows of the call touch (accumulate)
+    int nwin, Bs, NC, Hs, Ws, win, stride, nr, nq;
+};
+int launch_scene_accumulate(const SceneArgs& a, long pixels, hipStream_t st);
+int launch_scene_finalize(const SceneArgs& a, hipStream_t st);
 
 struct HeadArgs {
     const float* y;      // [B][T][96] encoder output
@@ -190,6 +213,7 @@ int launch_cls_head_fwd(const ClsArgs& a, hipStream_t st);
 int launch_cls_head_bwd(const ClsBwdArgs& a, hipStream_t st);
 
 int launch_tokenize_fwd(const TokArgs& a, hipStream_t st);
+int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st);   // the same kernels reading windows of a scene (TokArgs scene fields)
 int launch_head_bwd(const HeadBwdArgs& a, int nchunk, hipStream_t st);
 // One reduction segment: dst[(i / row_len) * row_stride + i % row_len] = sum_{k < nslab} src[k * slab_stride + i], i < n
 struct RSeg {

@@ -880,6 +880,60 @@ class Engine:
         out = _ClassifyFn.apply(self, names, drop, emb_drop, img, *params)
         return out.view(img.shape[0], -1, H, W)
 
+    # ------------------------------------------------------------------ scene inference (maskedsst_amd/scene.py, msst_scene_assemble)
+    def scene_forward(self, scene, stride, max_windows):
+        """Eval forward of every window of scene [Bs, C, Hs, Ws] (window = image_size, origins 0, stride, 2 stride, ...): returns
+        (logits [Bs, num_classes, Hs, Ws] = mean over the windows covering a pixel, classes [Bs, Hs, Ws] int64, -1 where uncovered).
+        Windows run in chunks of at most max_windows: one tokenizer launch reads a chunk's windows out of the scene, the blocks
+        run on two token buffers in turn (msst_block_fwd, the kernels and precision flags of blocks_fwd; its one-launch stack
+        variant computes the same bits but keeps every block's output), the head writes per-window logits and msst_scene_assemble
+        adds them into the scene map.  No dropout, nothing saved for a backward."""
+        self._require_cuda(scene)
+        self.ensure()
+        scene = scene.contiguous().float()
+        Bs, _, Hs, Ws = scene.shape
+        enc, fp = self.enc, self.fp
+        S, N, P, H = self.S, self.N, self.P, enc.heads
+        w = enc.num_spatial_patches_sqrt
+        nc = enc.num_classes
+        nr, nq = (Hs - w) // stride + 1, (Ws - w) // stride + 1
+        total = Bs * nr * nq
+        chunk = max(1, min(int(max_windows), total, 65535))   # 65535: the generic tokenizer runs one grid row per window
+        dev = scene.device
+        self.prep_weights()
+        if enc.spectral_pos_embed:
+            split, pos_a, pos_b = enc.pos_embed.shape[-1], fp.ptr("pos_embed"), fp.ptr("channel_embed")
+        else:
+            split, pos_a, pos_b = 0, fp.ptr("pos_embedding"), 0
+        flags = _kernel_flags()
+        prec = self.prec | flags | self._half_flag(flags)
+        layers = self._layers()
+        bufs = [torch.empty(chunk, S * N, D, dtype=torch.float32, device=dev) for _ in range(2)]
+        win_logits = torch.empty(chunk, nc, N, dtype=torch.float32, device=dev)
+        logits = torch.empty(Bs, nc, Hs, Ws, dtype=torch.float32, device=dev)
+        classes = torch.empty(Bs, Hs, Ws, dtype=torch.int64, device=dev)
+        V = ctypes.c_void_p
+        st = _stream()
+        wrote = ctypes.c_int(0)
+        for win0 in range(0, total, chunk):
+            n = min(chunk, total - win0)
+            x, y = bufs[0], bufs[1]
+            _lib.check(self.lib.msst_tokenize_scene_fwd(
+                _p(scene), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
+                V(fp.ptr("post_g")), V(fp.ptr("post_b")), V(pos_a), V(pos_b), split, _p(x), Bs, Hs, Ws, w, stride, win0, n, S, P, st),
+                "msst_tokenize_scene_fwd")
+            for i, (sname, _) in enumerate(layers):
+                mode = MODE_SPATIAL if sname == "spatial" else MODE_SPECTRAL
+                _lib.check(self.lib.msst_block_fwd(ctypes.byref(self._bw[i]), _p(x), _p(y), None, mode, n, S, N, H, prec,
+                                                   self.max_grid, 0.0, 0, i, None, None, ctypes.byref(wrote), st), "msst_block_fwd")
+                x, y = y, x
+            _lib.check(self.lib.msst_cls_head_fwd(
+                _p(x), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")), V(fp.ptr("mlp_head.1.weight")),
+                V(fp.ptr("mlp_head.1.bias")), _p(win_logits), n, S, N, nc, st), "msst_cls_head_fwd")
+            _lib.check(self.lib.msst_scene_assemble(_p(win_logits), win0, n, _p(logits), _p(classes), Bs, nc, Hs, Ws, w, stride,
+                                                    int(win0 + n == total), st), "msst_scene_assemble")
+        return logits, classes
+
     # ------------------------------------------------------------------ staged forward (tests / debugging)
     def simmim_forward_stages(self, img, bool_mask, idx, drop=(0.0, 0)):
         """Forward only, returning the intermediates the golden fixtures pin."""

@@ -294,3 +294,13 @@ class ViTSpatialSpectral(nn.Module):
         """reference :536-564: features -> mean over the spectral axis -> LN -> Linear ->
         [B, num_classes, H, W]."""
         return self.engine().classify(img)
+
+    def predict_scene(self, scene, stride=None, return_logits=False, max_windows=None):
+        """Classify whole scenes [Bs, channels, Hs, Ws] with sliding windows of image_size (the window loop of the reference's
+        inference_example.ipynb, one batched pass): returns the class map [Bs, Hs, Ws] (int64; -1 where no window covers a
+        pixel) and, with return_logits, also the logit map [Bs, num_classes, Hs, Ws] (mean over the windows covering a pixel).
+        stride: window step, 1 .. image_size (None: image_size, non-overlapping tiles).  Eval forward (no dropout) under
+        no_grad whatever the module's mode, which is left unchanged; windows run in chunks of at most max_windows
+        (None: maskedsst_amd.scene.SCENE_MAX_WINDOWS).  Raises ValueError for a scene of the wrong shape."""
+        from .scene import predict_scene, SCENE_MAX_WINDOWS
+        return predict_scene(self, scene, stride, return_logits, SCENE_MAX_WINDOWS if max_windows is None else max_windows)
