@@ -51,6 +51,9 @@ def main():
     ap.add_argument("--val-scenes", type=int, default=0,
                     help="validate on N held-out synthetic 64 x 64 scenes with predict_scene (0: no validation)")
     ap.add_argument("--val-every", type=int, default=0, help="validate every K steps (0: no validation)")
+    ap.add_argument("--spectral-mlp-head", action="store_true",
+                    help="classify from the S spectral tokens of a position concatenated (reference spectral_mlp_head=True); a "
+                         "--checkpoint must come from an encoder built with the same head (pretrain.py --spectral-mlp-head)")
     args = ap.parse_args()
     random.seed(SEED); np.random.seed(SEED); torch.manual_seed(SEED)
     if not torch.cuda.is_available():
@@ -68,7 +71,8 @@ def main():
         dropout=config.transformer_dropout, emb_dropout=config.transformer_emb_dropout, channels=config.n_bands,
         spectral_pos=config.spectral_pos, spectral_pos_embed=config.spectral_pos_embed,
         blockwise_patch_embed=config.blockwise_patch_embed, spectral_only=config.spectral_only,
-        pixelwise=config.pixelwise, pos_embed_len=config.pos_embed_len, precision=args.precision)
+        pixelwise=config.pixelwise, pos_embed_len=config.pos_embed_len, spectral_mlp_head=args.spectral_mlp_head,
+        precision=args.precision)
     if config.checkpoint_path is not None:
         model = load_checkpoint(config, model, "mlp_head", "cpu")
     model.to(device)

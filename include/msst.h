@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MSST_VERSION 105
+#define MSST_VERSION 106
 #define MSST_DIM 96
 #define MSST_DIM_HEAD 64
 #define MSST_MLP 64
@@ -309,6 +309,22 @@ int msst_cls_head_fwd(const float* y, const float* ln_g, const float* ln_b, cons
 int msst_cls_head_bwd(const float* y, const float* dlogits, const float* ln_g, const float* ln_b, const float* w,
                       float* dy, float* slab, float* dln_g, float* dln_b, float* dw, float* db, int B, int S,
                       int N, int n_classes, void* stream);
+
+/* Spectral MLP head of ViTSpatialSpectral(spectral_mlp_head=True) (vit_spatial_spectral.py:440-453, :536-564; MSST_VERSION 106):
+ * 'b (c h w) d -> b h w (c d)' (the S tokens of a position concatenated, feature j = c * 96 + d, NO mean over c) -> LayerNorm(96 S)
+ * -> Linear(96 S -> n_classes).  A row is one position (b, n): R = B * N rows of F = 96 * S features; y [B][S*N][96].
+ * ln_g / ln_b [F], w [n_classes][F], b [n_classes].  logits [B][n_classes][N] (the layout of msst_cls_head_fwd).  fp32 arithmetic,
+ * two-pass LayerNorm statistics, eps 1e-5.  Limits: N <= 64, S <= 64 (F <= 6144), n_classes <= 32 (MSST_ERR_UNSUPPORTED otherwise).
+ * _bwd: dy [B][S*N][96] fully written (each token receives its own slice of d(row), no 1/S factor); dln_g / dln_b [F],
+ * dw [n_classes][F], db [n_classes] are fully written (not accumulated), summed without atomics over a static row partition that
+ * depends on B * N only: bitwise reproducible, independent of the device.  slab: msst_spec_head_bwd_slab(B, S, N, n_classes)
+ * floats of scratch (16-byte aligned). */
+int msst_spec_head_fwd(const float* y, const float* ln_g, const float* ln_b, const float* w, const float* b,
+                       float* logits, int B, int S, int N, int n_classes, void* stream);
+long msst_spec_head_bwd_slab(int B, int S, int N, int n_classes);
+int msst_spec_head_bwd(const float* y, const float* dlogits, const float* ln_g, const float* ln_b, const float* w,
+                       float* dy, float* slab, float* dln_g, float* dln_b, float* dw, float* db, int B, int S,
+                       int N, int n_classes, void* stream);
 
 /* a7: LayerNorm over the last axis as an op of its own (nn.LayerNorm of PreNorm, vit_spatial_spectral.py:25, and of the
  * tokenizer, :194-195: eps 1e-5, affine, biased variance), fp32, rows of D <= 128 contiguous floats (D = 96 vectorised; D = 10 =

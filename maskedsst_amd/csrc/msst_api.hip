@@ -783,6 +783,43 @@ int msst_cls_head_bwd(const float* y, const float* dlogits, const float* ln_g, c
     return fail(launch_reduce_segs(rb.r, st), "msst_cls_head_bwd(reduce)");
 }
 
+int msst_spec_head_fwd(const float* y, const float* ln_g, const float* ln_b, const float* w, const float* b,
+                       float* logits, int B, int S, int N, int n_classes, void* stream) {
+    SpecHeadArgs a = {};
+    a.y = y; a.ln_g = ln_g; a.ln_b = ln_b; a.w = w; a.b = b; a.logits = logits;
+    a.B = B; a.S = S; a.N = N; a.T = S * N; a.NC = n_classes; a.R = B * N;
+    return fail(launch_spec_head_fwd(a, (hipStream_t)stream), "msst_spec_head_fwd");
+}
+
+long msst_spec_head_bwd_slab(int B, int S, int N, int n_classes) {
+    return B < 1 || S < 1 || N < 1 || n_classes < 1 ? 0 : spec_head_bwd_slab_floats(B, S, N, n_classes);
+}
+
+int msst_spec_head_bwd(const float* y, const float* dlogits, const float* ln_g, const float* ln_b, const float* w,
+                       float* dy, float* slab, float* dln_g, float* dln_b, float* dw, float* db, int B, int S,
+                       int N, int n_classes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SpecHeadArgs a = {};
+    a.y = y; a.dlogits = dlogits; a.ln_g = ln_g; a.ln_b = ln_b; a.w = w; a.dy = dy;
+    a.B = B; a.S = S; a.N = N; a.T = S * N; a.NC = n_classes; a.R = B * N;
+    spec_head_chunks(a.R, a.G, a.RC);
+    const long F = 96L * S, stats = (2L * a.R + 3) / 4 * 4;
+    a.stats = slab;
+    a.slab = slab + stats;
+    a.slab_stride = n_classes * F + 32;
+    float* A = a.slab + (long)a.G * a.slab_stride;
+    int rc = launch_spec_head_bwd_rows(a, st);
+    if (!rc) rc = launch_spec_head_wgrad(a, st);
+    if (rc) return fail(rc, "msst_spec_head_bwd");
+    RSegBuilder rb;
+    bool ok = rb.add(a.slab, a.slab_stride, a.G, A, (int)(n_classes * F));
+    ok = ok && rb.add(a.slab + n_classes * F, a.slab_stride, a.G, db, n_classes);
+    if (!ok) return fail(MSST_ERR_UNSUPPORTED, "msst_spec_head_bwd");
+    rc = launch_reduce_segs(rb.r, st);
+    if (!rc) rc = launch_spec_head_wgrad_finish(a, A, db, dw, dln_g, dln_b, st);
+    return fail(rc, "msst_spec_head_bwd(reduce)");
+}
+
 int msst_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, long rows,
                        int D, float eps, void* stream) {
     return fail(launch_layernorm_fwd(x, gamma, beta, y, mean, rstd, rows, D, eps, (hipStream_t)stream), "msst_layernorm_fwd");

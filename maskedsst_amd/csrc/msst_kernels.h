@@ -211,6 +211,21 @@ struct ClsBwdArgs {
 };
 int launch_cls_head_fwd(const ClsArgs& a, hipStream_t st);
 int launch_cls_head_bwd(const ClsBwdArgs& a, hipStream_t st);
+// spectral MLP head (msst_head.hip): rows R = B N of F = 96 S features; G chunks of RC rows in the weight-gradient pass,
+// slab g at slab + g slab_stride, stats [R][2] (mean, rstd) written by the row backward
+struct SpecHeadArgs {
+    const float* y; const float* ln_g; const float* ln_b; const float* w; const float* b; const float* dlogits;
+    float* logits; float* dy; float* stats; float* slab;
+    long slab_stride;
+    int B, S, N, T, NC, R, G, RC;
+};
+void spec_head_chunks(long R, int& G, int& RC);
+long spec_head_bwd_slab_floats(int B, int S, int N, int NC);
+int launch_spec_head_fwd(const SpecHeadArgs& a, hipStream_t st);
+int launch_spec_head_bwd_rows(const SpecHeadArgs& a, hipStream_t st);
+int launch_spec_head_wgrad(const SpecHeadArgs& a, hipStream_t st);
+int launch_spec_head_wgrad_finish(const SpecHeadArgs& a, const float* A, const float* db, float* dw, float* dg, float* dbeta,
+                                  hipStream_t st);
 
 int launch_tokenize_fwd(const TokArgs& a, hipStream_t st);
 int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st);   // the same kernels reading windows of a scene (TokArgs scene fields)

@@ -857,6 +857,44 @@ class Engine:
         self._fire("cls_head")
         return dy
 
+    def spec_head_fwd(self, y):
+        """spectral_mlp_head: the S tokens of a position concatenated -> LN(96 S) -> Linear; logits [B, nc, N] (cls_head_fwd's layout)"""
+        B = y.shape[0]
+        nc = self.enc.num_classes
+        logits = torch.empty(B, nc, self.N, dtype=torch.float32, device=y.device)
+        self._spec_head_fwd_into(y, B, logits, _stream())
+        return logits
+
+    def _spec_head_fwd_into(self, y, B, logits, st):
+        fp = self.fp
+        V = ctypes.c_void_p
+        _lib.check(self.lib.msst_spec_head_fwd(
+            _p(y), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")), V(fp.ptr("mlp_head.1.weight")),
+            V(fp.ptr("mlp_head.1.bias")), _p(logits), B, self.S, self.N, self.enc.num_classes, st), "msst_spec_head_fwd")
+
+    def spec_head_bwd(self, y, dlogits):
+        """-> dy [B, T, 96]; the four head gradients are written (not accumulated) into the flat gradient buffer"""
+        B = y.shape[0]
+        nc = self.enc.num_classes
+        dy = torch.empty_like(y)
+        slab = torch.empty(int(self.lib.msst_spec_head_bwd_slab(B, self.S, self.N, nc)), dtype=torch.float32, device=y.device)
+        fp, g = self.fp, self.fp.grad
+        V = ctypes.c_void_p
+        _lib.check(self.lib.msst_spec_head_bwd(
+            _p(y), _p(dlogits), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")),
+            V(fp.ptr("mlp_head.1.weight")), _p(dy), _p(slab), V(fp.ptr("mlp_head.0.weight", g)),
+            V(fp.ptr("mlp_head.0.bias", g)), V(fp.ptr("mlp_head.1.weight", g)), V(fp.ptr("mlp_head.1.bias", g)),
+            B, self.S, self.N, nc, _stream()), "msst_spec_head_bwd")
+        self._fire("cls_head")
+        return dy
+
+    def head_logits(self, y):
+        """the classifier head the encoder was built with: logits [B, nc, N]"""
+        return self.spec_head_fwd(y) if self.enc.spectral_mlp_head else self.cls_head_fwd(y)
+
+    def head_logits_bwd(self, y, dlogits):
+        return self.spec_head_bwd(y, dlogits) if self.enc.spectral_mlp_head else self.cls_head_bwd(y, dlogits)
+
     def classify(self, img):
         """ViTSpatialSpectral.forward: logits [B, num_classes, H, W] (reference :536-564)."""
         self._require_cuda(img)
@@ -875,7 +913,7 @@ class Engine:
             self.prep_weights()
             x0 = self.tokenize(img, None, emb_drop=emb_drop)
             acts, _ = self.blocks_fwd(x0, save=False, drop=drop)
-            return self.cls_head_fwd(acts[-1]).view(img.shape[0], -1, H, W)
+            return self.head_logits(acts[-1]).view(img.shape[0], -1, H, W)
         names = [n for n, _ in self.trainable()]
         out = _ClassifyFn.apply(self, names, drop, emb_drop, img, *params)
         return out.view(img.shape[0], -1, H, W)
@@ -927,9 +965,12 @@ class Engine:
                 _lib.check(self.lib.msst_block_fwd(ctypes.byref(self._bw[i]), _p(x), _p(y), None, mode, n, S, N, H, prec,
                                                    self.max_grid, 0.0, 0, i, None, None, ctypes.byref(wrote), st), "msst_block_fwd")
                 x, y = y, x
-            _lib.check(self.lib.msst_cls_head_fwd(
-                _p(x), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")), V(fp.ptr("mlp_head.1.weight")),
-                V(fp.ptr("mlp_head.1.bias")), _p(win_logits), n, S, N, nc, st), "msst_cls_head_fwd")
+            if enc.spectral_mlp_head:
+                self._spec_head_fwd_into(x, n, win_logits, st)
+            else:
+                _lib.check(self.lib.msst_cls_head_fwd(
+                    _p(x), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")), V(fp.ptr("mlp_head.1.weight")),
+                    V(fp.ptr("mlp_head.1.bias")), _p(win_logits), n, S, N, nc, st), "msst_cls_head_fwd")
             _lib.check(self.lib.msst_scene_assemble(_p(win_logits), win0, n, _p(logits), _p(classes), Bs, nc, Hs, Ws, w, stride,
                                                     int(win0 + n == total), st), "msst_scene_assemble")
         return logits, classes
@@ -1051,7 +1092,7 @@ class _ClassifyFn(torch.autograd.Function):
         eng.prep_weights()
         x0 = eng.tokenize(img, None, emb_drop=emb_drop)
         acts, x1s = eng.blocks_fwd(x0, save=True, drop=drop)
-        logits = eng.cls_head_fwd(acts[-1])
+        logits = eng.head_logits(acts[-1])
         ctx.eng, ctx.names, ctx.drop, ctx.emb_drop = eng, names, drop, emb_drop
         ctx.stash = (img, acts, x1s)
         return logits
@@ -1066,7 +1107,7 @@ class _ClassifyFn(torch.autograd.Function):
             if p.grad is not None and lo <= p.grad.data_ptr() < hi:
                 raise RuntimeError("call optimizer.zero_grad(set_to_none=True) before the next backward "
                                    "(maskedsst_amd hands autograd views of its flat gradient buffer)")
-        dy = eng.cls_head_bwd(acts[-1], dlogits.contiguous().float())
+        dy = eng.head_logits_bwd(acts[-1], dlogits.contiguous().float())
         dx0 = eng.blocks_bwd(acts, x1s, dy, drop=ctx.drop)
         if eng._zero_mask is None or eng._zero_mask.numel() < img.shape[0] * eng.S * eng.N:
             eng._zero_mask = torch.zeros(img.shape[0] * eng.S * eng.N, dtype=torch.uint8, device=img.device)

@@ -193,10 +193,10 @@ class ViTSpatialSpectral(nn.Module):
             unsupported.append("blockwise_patch_embed=False")
         if spectral_only:
             unsupported.append("spectral_only=True")
-        if spectral_mlp_head:
-            unsupported.append("spectral_mlp_head=True")
         if pixelwise:
-            unsupported.append("pixelwise=True")
+            unsupported.append("pixelwise=True" + (" (also with spectral_mlp_head=True)" if spectral_mlp_head else ""))
+        if spectral_mlp_head and num_classes > 32:
+            unsupported.append(f"spectral_mlp_head=True with num_classes={num_classes} (the spectral head is built for <= 32)")
         if dim != 96 or dim_head != 64 or mlp_dim != 64:
             unsupported.append(f"dim/dim_head/mlp_dim={dim}/{dim_head}/{mlp_dim} (kernels are built for 96/64/64)")
         if self.patch_height != 1 or self.patch_width != 1:
@@ -247,9 +247,11 @@ class ViTSpatialSpectral(nn.Module):
         self.to_latent = nn.Identity()
         self.dim = dim
         num_out_pixels = self.patch_width * self.patch_height
+        # spectral_mlp_head (reference :440-453): the S tokens of a position concatenated (96 S features) instead of averaged
+        head_dim = dim * self.num_spectral_patches if spectral_mlp_head else dim
         self.mlp_head = nn.Sequential(
-            nn.LayerNorm(dim),
-            nn.Linear(dim, num_classes * num_out_pixels),
+            nn.LayerNorm(head_dim),
+            nn.Linear(head_dim, num_classes * num_out_pixels),
             _HeadRearrange(self.patch_height, self.patch_width, num_classes),
             MoveAxis((-1, 1)),
         )
@@ -291,8 +293,8 @@ class ViTSpatialSpectral(nn.Module):
         return self.engine().features(img)
 
     def forward(self, img):
-        """reference :536-564: features -> mean over the spectral axis -> LN -> Linear ->
-        [B, num_classes, H, W]."""
+        """reference :536-564: features -> mean over the spectral axis (spectral_mlp_head: the S tokens of a position
+        concatenated instead) -> LN -> Linear -> [B, num_classes, H, W]."""
         return self.engine().classify(img)
 
     def predict_scene(self, scene, stride=None, return_logits=False, max_windows=None):

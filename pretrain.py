@@ -60,6 +60,9 @@ def main():
     ap.add_argument("--dropout", type=float, default=None, help="override transformer_dropout of the config")
     ap.add_argument("--torch-optim", action="store_true")
     ap.add_argument("--save-dir", default=None)
+    ap.add_argument("--spectral-mlp-head", action="store_true",
+                    help="build the encoder with the spectral MLP head (unused in pre-training; its checkpoint then loads "
+                         "strictly into finetune.py --spectral-mlp-head)")
     args = ap.parse_args()
 
     random.seed(SEED); np.random.seed(SEED); torch.manual_seed(SEED)
@@ -94,7 +97,7 @@ def main():
         emb_dropout=config.transformer_emb_dropout, channels=config.n_bands,
         spectral_pos_embed=config.spectral_pos_embed, spectral_pos=spectral_pos,
         blockwise_patch_embed=config.blockwise_patch_embed, spectral_only=config.spectral_only,
-        precision=args.precision)
+        spectral_mlp_head=args.spectral_mlp_head, precision=args.precision)
     model = SimMIMSpatialSpectral(
         encoder=model, intermediate_losses=config.mim_intermediate_losses,
         masking_ratio=config.mim_masking_ratio, mask_patch_size=config.mim_mask_patch_size,
