@@ -22,9 +22,12 @@ from maskedsst_amd.utils import get_spectral_pos_embedding, load_checkpoint, tra
 SEED = 5
 
 
-def get_finetune_config(path, general_path, seed, device):
-    """reference src/utils.py:337-364 (ViTSpatialSpectral branch; worldcover/dfc spectral positions)"""
+def get_finetune_config(path, general_path, seed, device, pixelwise=None):
+    """reference src/utils.py:337-364 (ViTSpatialSpectral branch; worldcover/dfc spectral positions).  pixelwise: overrides
+    the config's flag before patch_sub is derived from it (None: the config's value)."""
     hp = yaml.safe_load(open(path))
+    if pixelwise is not None:
+        hp["pixelwise"] = bool(pixelwise)
     general = yaml.safe_load(open(general_path))
     hp.update(general["data"][hp["dataset"]])
     hp.update(general["transformer"])
@@ -54,16 +57,24 @@ def main():
     ap.add_argument("--spectral-mlp-head", action="store_true",
                     help="classify from the S spectral tokens of a position concatenated (reference spectral_mlp_head=True); a "
                          "--checkpoint must come from an encoder built with the same head (pretrain.py --spectral-mlp-head)")
+    ap.add_argument("--pixelwise", action="store_true",
+                    help="the centre-pixel classifier (reference pixelwise=True): windows of image_size - 1 (odd), one class "
+                         "per window; --val-scenes then predicts dense per-pixel maps (stride 1)")
     args = ap.parse_args()
     random.seed(SEED); np.random.seed(SEED); torch.manual_seed(SEED)
     if not torch.cuda.is_available():
         raise SystemExit("finetune.py needs an MI355X: maskedsst_amd has no CPU fallback")
     device = torch.device("cuda")
-    config = get_finetune_config(f"configs/finetune_config_{args.dataset}.yaml", "configs/config.yaml", SEED, device)
+    config = get_finetune_config(f"configs/finetune_config_{args.dataset}.yaml", "configs/config.yaml", SEED, device,
+                                 pixelwise=True if args.pixelwise else None)
     if args.batch_size:
         config.batch_size = args.batch_size
     if args.checkpoint:
         config.checkpoint_path = args.checkpoint
+        if config.pixelwise and config.patch_sub and not config.spectral_pos_embed and config.pos_embed_len is None:
+            # the checkpoint's pos_embedding has the image_size x image_size length: the reference's strict load needs
+            # pos_embed_len set to it (the model reads its first S N rows)
+            config.pos_embed_len = config.n_bands // config.band_patch_size * config.image_size ** 2 + 1
     model = ViTSpatialSpectral(
         image_size=config.image_size - config.patch_sub, spatial_patch_size=config.patch_size,
         spectral_patch_size=config.band_patch_size, num_classes=config.n_classes, dim=config.transformer_dim,
@@ -111,7 +122,8 @@ def main():
 
 def validate(model, val, step, ignored_label):
     """validate_downstream (reference src/utils.py:477-605) over whole scenes: one predict_scene pass (windows of image_size,
-    eval forward, the module's mode untouched) and the scene metrics of maskedsst_amd.scene"""
+    eval forward, the module's mode untouched; a pixelwise model: one window per pixel, its centre) and the scene metrics of
+    maskedsst_amd.scene (pixels of class -1 are skipped)"""
     from maskedsst_amd.scene import scene_metrics
     img, label = val
     classes, logits = model.predict_scene(img, return_logits=True)

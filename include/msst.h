@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MSST_VERSION 106
+#define MSST_VERSION 107
 #define MSST_DIM 96
 #define MSST_DIM_HEAD 64
 #define MSST_MLP 64
@@ -325,6 +325,33 @@ long msst_spec_head_bwd_slab(int B, int S, int N, int n_classes);
 int msst_spec_head_bwd(const float* y, const float* dlogits, const float* ln_g, const float* ln_b, const float* w,
                        float* dy, float* slab, float* dln_g, float* dln_b, float* dw, float* db, int B, int S,
                        int N, int n_classes, void* stream);
+
+/* Pixelwise centre-pixel head of ViTSpatialSpectral(pixelwise=True) (vit_spatial_spectral.py:466-478, :536-564; MSST_VERSION 107):
+ * 'b (c h w) d -> b c h w d', mean over c, LayerNorm(96) per position, Flatten (feature n * 96 + d, n = h * W + w) -> Linear(96 N ->
+ * n_classes): one class vector per sample (window), for its centre pixel.  y [B][S*N][96]; ln_g / ln_b [96], w [n_classes][96 N],
+ * b [n_classes]; logits [B][n_classes].  fp32 arithmetic, two-pass LayerNorm statistics, eps 1e-5.  ws: msst_pix_head_fwd_ws(B, N)
+ * floats of scratch (the normalised features; 16-byte aligned).  Limits: S <= 64, N <= 64, n_classes <= 32 (MSST_ERR_UNSUPPORTED);
+ * sizes below 1 or a null pointer: MSST_ERR_BADARG.  Both are checked before anything is enqueued.
+ * _bwd (given dlogits [B][n_classes]): dy [B][S*N][96] fully written (every token of a position receives d(mean) / S); dln_g,
+ * dln_b [96], dw [n_classes][96 N], db [n_classes] fully written (not accumulated), summed without atomics over a static partition
+ * of the samples into groups of 32 (depends on B only): bitwise reproducible, independent of the device.  slab:
+ * msst_pix_head_bwd_slab(B, S, N, n_classes) floats of scratch (16-byte aligned); 0 for a refused shape. */
+long msst_pix_head_fwd_ws(int B, int N);
+int msst_pix_head_fwd(const float* y, const float* ln_g, const float* ln_b, const float* w, const float* b, float* logits,
+                      float* ws, int B, int S, int N, int n_classes, void* stream);
+long msst_pix_head_bwd_slab(int B, int S, int N, int n_classes);
+int msst_pix_head_bwd(const float* y, const float* dlogits, const float* ln_g, const float* ln_b, const float* w, float* dy,
+                      float* slab, float* dln_g, float* dln_b, float* dw, float* db, int B, int S, int N, int n_classes,
+                      void* stream);
+
+/* msst_scene_centre_assemble (MSST_VERSION 107): the scene maps of a pixelwise model.  win_logits [nwin][n_classes]
+ * (msst_pix_head_fwd of windows win0 .. win0 + nwin - 1, numbered as for msst_tokenize_scene_fwd) go to the centre pixel
+ * (r * stride + window / 2, q * stride + window / 2) of their window in logits [Bs][n_classes][Hs][Ws], with the argmax in
+ * classes [Bs][Hs][Ws] (int64; ties: lowest index, as torch.argmax).  A pixel is the centre of at most one window: no sums, no
+ * atomics, any split into calls gives the same bits.  finalize != 0: pixels that are no window's centre get logit 0 and class -1
+ * (msst_scene_assemble's "uncovered" convention).  The calls of one scene batch cover every window once, in any order. */
+int msst_scene_centre_assemble(const float* win_logits, long win0, int nwin, float* logits, int64_t* classes, int Bs,
+                               int n_classes, int Hs, int Ws, int window, int stride, int finalize, void* stream);
 
 /* a7: LayerNorm over the last axis as an op of its own (nn.LayerNorm of PreNorm, vit_spatial_spectral.py:25, and of the
  * tokenizer, :194-195: eps 1e-5, affine, biased variance), fp32, rows of D <= 128 contiguous floats (D = 96 vectorised; D = 10 =

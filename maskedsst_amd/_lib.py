@@ -61,6 +61,11 @@ _SIGS = {
     "msst_spec_head_fwd": (c_int, [_P] * 6 + [c_int, c_int, c_int, c_int, _P]),
     "msst_spec_head_bwd_slab": (c_long, [c_int, c_int, c_int, c_int]),
     "msst_spec_head_bwd": (c_int, [_P] * 11 + [c_int, c_int, c_int, c_int, _P]),
+    "msst_pix_head_fwd_ws": (c_long, [c_int, c_int]),
+    "msst_pix_head_fwd": (c_int, [_P] * 7 + [c_int, c_int, c_int, c_int, _P]),
+    "msst_pix_head_bwd_slab": (c_long, [c_int, c_int, c_int, c_int]),
+    "msst_pix_head_bwd": (c_int, [_P] * 11 + [c_int, c_int, c_int, c_int, _P]),
+    "msst_scene_centre_assemble": (c_int, [_P, c_long, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "msst_block_lse_floats": (c_long, [c_int, c_int, c_int, c_int, c_int]),
     "msst_block_tiles": (c_long, [c_int, c_int, c_int, c_int]),
     "msst_block_fwd": (c_int, [POINTER(MsstBlockWeights), _P, _P, _P, c_int, c_int, c_int, c_int, c_int,

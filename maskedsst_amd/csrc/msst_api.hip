@@ -820,6 +820,73 @@ int msst_spec_head_bwd(const float* y, const float* dlogits, const float* ln_g, 
     return fail(rc, "msst_spec_head_bwd(reduce)");
 }
 
+// shape of the pixelwise head: 0, MSST_ERR_BADARG (a size below 1) or MSST_ERR_UNSUPPORTED (beyond the kernels' limits)
+static int pix_head_shape(int B, int S, int N, int n_classes) {
+    if (B < 1 || S < 1 || N < 1 || n_classes < 1) return MSST_ERR_BADARG;
+    if (S > 64 || N > 64 || n_classes > 32) return MSST_ERR_UNSUPPORTED;
+    return 0;
+}
+
+long msst_pix_head_fwd_ws(int B, int N) { return B < 1 || N < 1 || N > 64 ? 0 : 96L * B * N; }
+
+int msst_pix_head_fwd(const float* y, const float* ln_g, const float* ln_b, const float* w, const float* b, float* logits,
+                      float* ws, int B, int S, int N, int n_classes, void* stream) {
+    int rc = pix_head_shape(B, S, N, n_classes);
+    if (rc) return fail(rc, "msst_pix_head_fwd");
+    if (!y || !ln_g || !ln_b || !w || !b || !logits || !ws) return fail(MSST_ERR_BADARG, "msst_pix_head_fwd");
+    PixHeadArgs a = {};
+    a.y = y; a.ln_g = ln_g; a.ln_b = ln_b; a.w = w; a.b = b; a.logits = logits; a.xn = ws;
+    a.B = B; a.S = S; a.N = N; a.T = S * N; a.NC = n_classes; a.G = pix_head_groups(B);
+    return fail(launch_pix_head_fwd(a, (hipStream_t)stream), "msst_pix_head_fwd");
+}
+
+long msst_pix_head_bwd_slab(int B, int S, int N, int n_classes) {
+    return pix_head_shape(B, S, N, n_classes) ? 0 : pix_head_bwd_slab_floats(B, N, n_classes);
+}
+
+int msst_pix_head_bwd(const float* y, const float* dlogits, const float* ln_g, const float* ln_b, const float* w, float* dy,
+                      float* slab, float* dln_g, float* dln_b, float* dw, float* db, int B, int S, int N, int n_classes,
+                      void* stream) {
+    int rc = pix_head_shape(B, S, N, n_classes);
+    if (rc) return fail(rc, "msst_pix_head_bwd");
+    if (!y || !dlogits || !ln_g || !ln_b || !w || !dy || !slab || !dln_g || !dln_b || !dw || !db)
+        return fail(MSST_ERR_BADARG, "msst_pix_head_bwd");
+    hipStream_t st = (hipStream_t)stream;
+    PixHeadArgs a = {};
+    a.y = y; a.dlogits = dlogits; a.ln_g = ln_g; a.ln_b = ln_b; a.w = w; a.dy = dy; a.slab = slab;
+    a.B = B; a.S = S; a.N = N; a.T = S * N; a.NC = n_classes; a.G = pix_head_groups(B);
+    const long K = 96L * N, G = a.G;
+    const float* p_db = slab + G * n_classes * K;
+    const float* p_dg = p_db + G * 32;
+    const float* p_dbeta = p_dg + G * K;
+    RSegBuilder rb;
+    bool ok = rb.add(slab, n_classes * K, a.G, dw, (int)(n_classes * K));
+    ok = ok && rb.add(p_db, 32, a.G, db, n_classes);
+    ok = ok && rb.add(p_dg, 96, a.G * N, dln_g, 96);
+    ok = ok && rb.add(p_dbeta, 96, a.G * N, dln_b, 96);
+    if (!ok) return fail(MSST_ERR_UNSUPPORTED, "msst_pix_head_bwd");
+    rc = launch_pix_head_bwd(a, st);
+    if (rc) return fail(rc, "msst_pix_head_bwd");
+    return fail(launch_reduce_segs(rb.r, st), "msst_pix_head_bwd(reduce)");
+}
+
+int msst_scene_centre_assemble(const float* win_logits, long win0, int nwin, float* logits, int64_t* classes, int Bs,
+                               int n_classes, int Hs, int Ws, int window, int stride, int finalize, void* stream) {
+    int nr = 0, nq = 0;
+    if (!logits || !classes || (nwin > 0 && !win_logits) || n_classes < 1 || nwin < 0 || win0 < 0 ||
+        !scene_grid(Bs, Hs, Ws, window, stride, &nr, &nq))
+        return fail(MSST_ERR_BADARG, "msst_scene_centre_assemble");
+    const long wps = (long)nr * nq;
+    if (win0 + nwin > (long)Bs * wps) return fail(MSST_ERR_BADARG, "msst_scene_centre_assemble (windows out of range)");
+    SceneArgs a = {};
+    a.win_logits = win_logits; a.logits = logits; a.classes = classes; a.win0 = win0; a.nwin = nwin;
+    a.Bs = Bs; a.NC = n_classes; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nr = nr; a.nq = nq;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = launch_scene_centre_scatter(a, st);
+    if (!rc && finalize) rc = launch_scene_centre_fill(a, st);
+    return fail(rc, "msst_scene_centre_assemble");
+}
+
 int msst_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, long rows,
                        int D, float eps, void* stream) {
     return fail(launch_layernorm_fwd(x, gamma, beta, y, mean, rstd, rows, D, eps, (hipStream_t)stream), "msst_layernorm_fwd");

@@ -226,6 +226,19 @@ int launch_spec_head_bwd_rows(const SpecHeadArgs& a, hipStream_t st);
 int launch_spec_head_wgrad(const SpecHeadArgs& a, hipStream_t st);
 int launch_spec_head_wgrad_finish(const SpecHeadArgs& a, const float* A, const float* db, float* dw, float* dg, float* dbeta,
                                   hipStream_t st);
+// pixelwise centre-pixel head (msst_pixhead.hip): K = 96 N features per sample; G = pix_head_groups(B) groups of 32 samples;
+// xn [B][K] the forward's workspace; slab: pix_head_bwd_slab_floats(B, N, NC) floats of weight-gradient partials
+struct PixHeadArgs {
+    const float* y; const float* ln_g; const float* ln_b; const float* w; const float* b; const float* dlogits;
+    float* logits; float* xn; float* dy; float* slab;
+    int B, S, N, T, NC, G;
+};
+int pix_head_groups(int B);
+long pix_head_bwd_slab_floats(int B, int N, int NC);
+int launch_pix_head_fwd(const PixHeadArgs& a, hipStream_t st);
+int launch_pix_head_bwd(const PixHeadArgs& a, hipStream_t st);
+int launch_scene_centre_scatter(const SceneArgs& a, hipStream_t st);   // SceneArgs.win_logits: [nwin][NC]
+int launch_scene_centre_fill(const SceneArgs& a, hipStream_t st);
 
 int launch_tokenize_fwd(const TokArgs& a, hipStream_t st);
 int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st);   // the same kernels reading windows of a scene (TokArgs scene fields)

@@ -888,19 +888,61 @@ class Engine:
         self._fire("cls_head")
         return dy
 
+    def pix_head_fwd(self, y):
+        """pixelwise: mean over the S tokens -> LN(96) per position -> flatten -> Linear(96 N); logits [B, nc] (centre pixel)"""
+        B = y.shape[0]
+        logits = torch.empty(B, self.enc.num_classes, dtype=torch.float32, device=y.device)
+        self._pix_head_fwd_into(y, B, logits, _stream())
+        return logits
+
+    def _pix_head_fwd_into(self, y, B, logits, st):
+        fp = self.fp
+        V = ctypes.c_void_p
+        ws = torch.empty(int(self.lib.msst_pix_head_fwd_ws(B, self.N)), dtype=torch.float32, device=y.device)
+        _lib.check(self.lib.msst_pix_head_fwd(
+            _p(y), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")), V(fp.ptr("mlp_head.2.weight")),
+            V(fp.ptr("mlp_head.2.bias")), _p(logits), _p(ws), B, self.S, self.N, self.enc.num_classes, st), "msst_pix_head_fwd")
+
+    def pix_head_bwd(self, y, dlogits):
+        """dlogits [B, nc] -> dy [B, T, 96]; the four head gradients are written (not accumulated) into the flat gradient buffer"""
+        B = y.shape[0]
+        nc = self.enc.num_classes
+        dy = torch.empty_like(y)
+        slab = torch.empty(int(self.lib.msst_pix_head_bwd_slab(B, self.S, self.N, nc)), dtype=torch.float32, device=y.device)
+        fp, g = self.fp, self.fp.grad
+        V = ctypes.c_void_p
+        _lib.check(self.lib.msst_pix_head_bwd(
+            _p(y), _p(dlogits), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")),
+            V(fp.ptr("mlp_head.2.weight")), _p(dy), _p(slab), V(fp.ptr("mlp_head.0.weight", g)),
+            V(fp.ptr("mlp_head.0.bias", g)), V(fp.ptr("mlp_head.2.weight", g)), V(fp.ptr("mlp_head.2.bias", g)),
+            B, self.S, self.N, nc, _stream()), "msst_pix_head_bwd")
+        self._fire("cls_head")
+        return dy
+
     def head_logits(self, y):
-        """the classifier head the encoder was built with: logits [B, nc, N]"""
+        """the classifier head the encoder was built with: logits [B, nc, N] ([B, nc] for the pixelwise head)"""
+        if self.enc.pixelwise:
+            return self.pix_head_fwd(y)
         return self.spec_head_fwd(y) if self.enc.spectral_mlp_head else self.cls_head_fwd(y)
 
     def head_logits_bwd(self, y, dlogits):
+        if self.enc.pixelwise:
+            return self.pix_head_bwd(y, dlogits)
         return self.spec_head_bwd(y, dlogits) if self.enc.spectral_mlp_head else self.cls_head_bwd(y, dlogits)
 
+    def _classify_view(self, logits, B):
+        """the reference's output layout: [B, nc, H, W]; pixelwise: [B, nc, 1, 1].squeeze() -- [B, nc], or [nc] when B = 1"""
+        if self.enc.pixelwise:
+            return logits.view(B, -1, 1, 1).squeeze()
+        H = W = self.enc.num_spatial_patches_sqrt
+        return logits.view(B, -1, H, W)
+
     def classify(self, img):
-        """ViTSpatialSpectral.forward: logits [B, num_classes, H, W] (reference :536-564)."""
+        """ViTSpatialSpectral.forward: logits [B, num_classes, H, W] (reference :536-564); pixelwise: [B, num_classes] ([num_classes]
+        for B = 1, the reference's squeeze)."""
         self._require_cuda(img)
         self.ensure()
         img = img.contiguous().float()
-        H = W = self.enc.num_spatial_patches_sqrt
         p = float(self.enc.dropout_p) if self.enc.training else 0.0
         pe = float(self.enc.emb_dropout_p) if self.enc.training else 0.0
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if (p > 0 or pe > 0) else 0
@@ -913,10 +955,10 @@ class Engine:
             self.prep_weights()
             x0 = self.tokenize(img, None, emb_drop=emb_drop)
             acts, _ = self.blocks_fwd(x0, save=False, drop=drop)
-            return self.head_logits(acts[-1]).view(img.shape[0], -1, H, W)
+            return self._classify_view(self.head_logits(acts[-1]), img.shape[0])
         names = [n for n, _ in self.trainable()]
         out = _ClassifyFn.apply(self, names, drop, emb_drop, img, *params)
-        return out.view(img.shape[0], -1, H, W)
+        return self._classify_view(out, img.shape[0])
 
     # ------------------------------------------------------------------ scene inference (maskedsst_amd/scene.py, msst_scene_assemble)
     def scene_forward(self, scene, stride, max_windows):
@@ -925,7 +967,9 @@ class Engine:
         Windows run in chunks of at most max_windows: one tokenizer launch reads a chunk's windows out of the scene, the blocks
         run on two token buffers in turn (msst_block_fwd, the kernels and precision flags of blocks_fwd; its one-launch stack
         variant computes the same bits but keeps every block's output), the head writes per-window logits and msst_scene_assemble
-        adds them into the scene map.  No dropout, nothing saved for a backward."""
+        adds them into the scene map.  A pixelwise model's window logits go to the window's centre pixel instead
+        (msst_scene_centre_assemble): logits 0 and class -1 on every pixel that is no window's centre.  No dropout, nothing saved
+        for a backward."""
         self._require_cuda(scene)
         self.ensure()
         scene = scene.contiguous().float()
@@ -947,7 +991,7 @@ class Engine:
         prec = self.prec | flags | self._half_flag(flags)
         layers = self._layers()
         bufs = [torch.empty(chunk, S * N, D, dtype=torch.float32, device=dev) for _ in range(2)]
-        win_logits = torch.empty(chunk, nc, N, dtype=torch.float32, device=dev)
+        win_logits = torch.empty(chunk, nc, 1 if enc.pixelwise else N, dtype=torch.float32, device=dev)
         logits = torch.empty(Bs, nc, Hs, Ws, dtype=torch.float32, device=dev)
         classes = torch.empty(Bs, Hs, Ws, dtype=torch.int64, device=dev)
         V = ctypes.c_void_p
@@ -965,6 +1009,11 @@ class Engine:
                 _lib.check(self.lib.msst_block_fwd(ctypes.byref(self._bw[i]), _p(x), _p(y), None, mode, n, S, N, H, prec,
                                                    self.max_grid, 0.0, 0, i, None, None, ctypes.byref(wrote), st), "msst_block_fwd")
                 x, y = y, x
+            if enc.pixelwise:
+                self._pix_head_fwd_into(x, n, win_logits, st)
+                _lib.check(self.lib.msst_scene_centre_assemble(_p(win_logits), win0, n, _p(logits), _p(classes), Bs, nc, Hs, Ws, w,
+                                                               stride, int(win0 + n == total), st), "msst_scene_centre_assemble")
+                continue
             if enc.spectral_mlp_head:
                 self._spec_head_fwd_into(x, n, win_logits, st)
             else:

@@ -8,6 +8,10 @@ into scene-shaped maps on the device (``include/msst.h``: ``msst_tokenize_scene_
 
 Where this differs from the notebook: overlapping windows (``stride < image_size``) are averaged (mean of the logits of
 every window covering a pixel), and pixels no window covers get class ``-1`` (the configs' ``ignored_label``) and logit 0.
+
+A pixelwise model (``pixelwise=True``) predicts one class per window, for its centre pixel: its map is the dense per-pixel
+map of DeepHyperX's ``test()`` (default stride 1, one window per pixel; ``msst_scene_centre_assemble``).  The border of
+width ``image_size // 2``, and with a stride above 1 every pixel that is no window's centre, gets class ``-1`` and logit 0.
 """
 from collections import namedtuple
 
@@ -36,7 +40,8 @@ def _check_scene(model, scene, stride, max_windows):
     w = model.num_spatial_patches_sqrt
     if scene.shape[0] < 1 or scene.shape[2] < w or scene.shape[3] < w:
         raise ValueError(f"scene {tuple(scene.shape)} is smaller than one {w} x {w} window")
-    stride = w if stride is None else stride
+    if stride is None:
+        stride = 1 if getattr(model, "pixelwise", False) else w
     if isinstance(stride, bool) or int(stride) != stride or not 1 <= int(stride) <= w:
         raise ValueError(f"stride must be an integer in [1, {w}] (the window size), got {stride!r}")
     if isinstance(max_windows, bool) or int(max_windows) != max_windows or int(max_windows) < 1:

@@ -81,13 +81,18 @@ def load_checkpoint(config, model, classifier_name="mlp_head", device="cpu", che
 
 def train_step(img, label, model, config, device, criterion, optimizer, acc_criterion=None):
     """reference src/utils.py:608-663 for the ViTSpatialSpectral method: optional random crop, forward,
-    CE(ignore_index) loss, pixel accuracy on valid labels, backward, optimizer step."""
+    CE(ignore_index) loss, pixel accuracy on valid labels, backward, optimizer step.  With ``config.pixelwise`` a label
+    map [B, s, s] is reduced to its centre pixel ``label[:, c, c]``, ``c = (image_size - patch_sub) // 2`` (reference
+    :630-636); a label that is already one class per sample ([B]) passes through unchanged."""
     patch_sub = getattr(config, "patch_sub", 0)
     if config.image_size != 64 and img.shape[-1] == 64:
         x, y = torch.randint(0, 64 - config.image_size - patch_sub, size=(2,))
         s = config.image_size - patch_sub
         img = img[:, :, x:x + s, y:y + s]
         label = label[:, x:x + s, y:y + s]
+    if getattr(config, "pixelwise", False) and label.dim() == 3:
+        c = (config.image_size - patch_sub) // 2
+        label = label[:, c, c]
     img = img.to(device)
     label = label.to(device)
     optimizer.zero_grad()

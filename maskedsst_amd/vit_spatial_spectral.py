@@ -156,6 +156,24 @@ class _HeadRearrange(nn.Module):
         return x.reshape(b, h * self.p1, w * self.p2, self.nc)
 
 
+class _PixRearrange(nn.Module):
+    """'b (p1 p2 num_classes) -> b p1 p2 num_classes' of the pixelwise head (reference :472-477)"""
+
+    def __init__(self, p1, p2, num_classes):
+        super().__init__()
+        self.p1, self.p2, self.nc = p1, p2, num_classes
+
+    def forward(self, x):
+        return x.reshape(x.shape[0], self.p1, self.p2, self.nc)
+
+
+class _Squeeze(nn.Module):
+    """reference Squeeze: x.squeeze() -- [B, nc, 1, 1] -> [B, nc], or [nc] for a single sample"""
+
+    def forward(self, x):
+        return x.squeeze()
+
+
 class ViTSpatialSpectral(nn.Module):
     """Same keyword-only constructor as reference :257-301.  Extra keyword ``precision``
     ('bf16' | 'fp32') selects the MFMA operand type of the fused kernels."""
@@ -193,8 +211,13 @@ class ViTSpatialSpectral(nn.Module):
             unsupported.append("blockwise_patch_embed=False")
         if spectral_only:
             unsupported.append("spectral_only=True")
-        if pixelwise:
-            unsupported.append("pixelwise=True" + (" (also with spectral_mlp_head=True)" if spectral_mlp_head else ""))
+        if pixelwise and spectral_mlp_head:
+            unsupported.append("pixelwise=True with spectral_mlp_head=True")
+        elif pixelwise and (image_height != image_width or image_height % 2 == 0):
+            unsupported.append(f"pixelwise=True with image_size={image_size} (no centre pixel exists: the reference builds "
+                               "pixelwise models at odd sizes, image_size - patch_sub)")
+        elif pixelwise and num_classes > 32:
+            unsupported.append(f"pixelwise=True with num_classes={num_classes} (the pixelwise head is built for <= 32)")
         if spectral_mlp_head and num_classes > 32:
             unsupported.append(f"spectral_mlp_head=True with num_classes={num_classes} (the spectral head is built for <= 32)")
         if dim != 96 or dim_head != 64 or mlp_dim != 64:
@@ -249,12 +272,24 @@ class ViTSpatialSpectral(nn.Module):
         num_out_pixels = self.patch_width * self.patch_height
         # spectral_mlp_head (reference :440-453): the S tokens of a position concatenated (96 S features) instead of averaged
         head_dim = dim * self.num_spectral_patches if spectral_mlp_head else dim
-        self.mlp_head = nn.Sequential(
-            nn.LayerNorm(head_dim),
-            nn.Linear(head_dim, num_classes * num_out_pixels),
-            _HeadRearrange(self.patch_height, self.patch_width, num_classes),
-            MoveAxis((-1, 1)),
-        )
+        if pixelwise:
+            # centre-pixel classifier (reference :466-478): per-position LN(96), flatten [h, w, d] (feature n 96 + d,
+            # n = h W + w), one Linear(96 N -> num_classes) per window, squeezed to [B, num_classes]
+            self.mlp_head = nn.Sequential(
+                nn.LayerNorm(dim),
+                nn.Flatten(start_dim=1, end_dim=-1),
+                nn.Linear(dim * self.num_spatial_patches, num_classes),
+                _PixRearrange(self.patch_height, self.patch_width, num_classes),
+                MoveAxis((-1, 1)),
+                _Squeeze(),
+            )
+        else:
+            self.mlp_head = nn.Sequential(
+                nn.LayerNorm(head_dim),
+                nn.Linear(head_dim, num_classes * num_out_pixels),
+                _HeadRearrange(self.patch_height, self.patch_width, num_classes),
+                MoveAxis((-1, 1)),
+            )
         self.num_classes = num_classes
 
         import weakref
@@ -294,14 +329,18 @@ class ViTSpatialSpectral(nn.Module):
 
     def forward(self, img):
         """reference :536-564: features -> mean over the spectral axis (spectral_mlp_head: the S tokens of a position
-        concatenated instead) -> LN -> Linear -> [B, num_classes, H, W]."""
+        concatenated instead) -> LN -> Linear -> [B, num_classes, H, W].  pixelwise: mean over the spectral axis -> LN per
+        position -> flatten -> Linear -> [B, num_classes] for the centre pixel ([num_classes] when B = 1: the reference's
+        squeeze)."""
         return self.engine().classify(img)
 
     def predict_scene(self, scene, stride=None, return_logits=False, max_windows=None):
         """Classify whole scenes [Bs, channels, Hs, Ws] with sliding windows of image_size (the window loop of the reference's
         inference_example.ipynb, one batched pass): returns the class map [Bs, Hs, Ws] (int64; -1 where no window covers a
         pixel) and, with return_logits, also the logit map [Bs, num_classes, Hs, Ws] (mean over the windows covering a pixel).
-        stride: window step, 1 .. image_size (None: image_size, non-overlapping tiles).  Eval forward (no dropout) under
+        stride: window step, 1 .. image_size (None: image_size, non-overlapping tiles).  A pixelwise model classifies the
+        centre pixel of each window instead (None: stride 1, the dense per-pixel map of DeepHyperX's test()); every pixel that is
+        no window's centre, the border of width image_size // 2 included, gets class -1 and logit 0.  Eval forward (no dropout) under
         no_grad whatever the module's mode, which is left unchanged; windows run in chunks of at most max_windows
         (None: maskedsst_amd.scene.SCENE_MAX_WINDOWS).  Raises ValueError for a scene of the wrong shape."""
         from .scene import predict_scene, SCENE_MAX_WINDOWS
