@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MSST_VERSION 107
+#define MSST_VERSION 108
 #define MSST_DIM 96
 #define MSST_DIM_HEAD 64
 #define MSST_MLP 64
@@ -303,7 +303,11 @@ int msst_tokenize_bwd(const float* img, const float* pre_g, const float* pre_b, 
 
 /* a17: classification head of ViTSpatialSpectral.forward (vit_spatial_spectral.py:536-564, :481-493):
  * mean over the spectral axis -> LayerNorm(96) -> Linear(96 -> n_classes); logits [B][n_classes][N].
- * _bwd: dy [B][T][96] fully written; slab B*(n_classes*97 + 192) floats. */
+ * Limits: N <= 64, S <= 64, any n_classes >= 1 (MSST_VERSION 108: the backward used to refuse n_classes > 32).  Both calls check
+ * their arguments before any launch: MSST_ERR_BADARG for B, S, N or n_classes < 1 or a null pointer, MSST_ERR_UNSUPPORTED beyond
+ * the limits.
+ * _bwd: dy [B][T][96] fully written; dln_g / dln_b [96], dw [n_classes][96], db [n_classes] fully written (not accumulated),
+ * bitwise reproducible; slab B*(n_classes*97 + 192) floats. */
 int msst_cls_head_fwd(const float* y, const float* ln_g, const float* ln_b, const float* w, const float* b,
                       float* logits, int B, int S, int N, int n_classes, void* stream);
 int msst_cls_head_bwd(const float* y, const float* dlogits, const float* ln_g, const float* ln_b, const float* w,

@@ -756,8 +756,18 @@ int msst_tokenize_bwd(const float* img, const float* pre_g, const float* pre_b, 
     return fail(rc, "msst_tokenize_bwd(reduce)");
 }
 
+// shape of the default head: 0, MSST_ERR_BADARG (a size below 1) or MSST_ERR_UNSUPPORTED (beyond the kernels' limits; any n_classes)
+static int cls_head_shape(int B, int S, int N, int n_classes) {
+    if (B < 1 || S < 1 || N < 1 || n_classes < 1) return MSST_ERR_BADARG;
+    if (S > 64 || N > 64) return MSST_ERR_UNSUPPORTED;
+    return 0;
+}
+
 int msst_cls_head_fwd(const float* y, const float* ln_g, const float* ln_b, const float* w, const float* b,
                       float* logits, int B, int S, int N, int n_classes, void* stream) {
+    const int rc = cls_head_shape(B, S, N, n_classes);
+    if (rc) return fail(rc, "msst_cls_head_fwd");
+    if (!y || !ln_g || !ln_b || !w || !b || !logits) return fail(MSST_ERR_BADARG, "msst_cls_head_fwd");
     ClsArgs a;
     a.y = y; a.ln_g = ln_g; a.ln_b = ln_b; a.w = w; a.b = b; a.logits = logits;
     a.B = B; a.S = S; a.N = N; a.T = S * N; a.NC = n_classes;
@@ -767,11 +777,15 @@ int msst_cls_head_fwd(const float* y, const float* ln_g, const float* ln_b, cons
 int msst_cls_head_bwd(const float* y, const float* dlogits, const float* ln_g, const float* ln_b, const float* w,
                       float* dy, float* slab, float* dln_g, float* dln_b, float* dw, float* db, int B, int S,
                       int N, int n_classes, void* stream) {
+    int rc = cls_head_shape(B, S, N, n_classes);
+    if (rc) return fail(rc, "msst_cls_head_bwd");
+    if (!y || !dlogits || !ln_g || !ln_b || !w || !dy || !slab || !dln_g || !dln_b || !dw || !db)
+        return fail(MSST_ERR_BADARG, "msst_cls_head_bwd");
     hipStream_t st = (hipStream_t)stream;
     ClsBwdArgs a;
     a.y = y; a.dlogits = dlogits; a.ln_g = ln_g; a.ln_b = ln_b; a.w = w; a.dy = dy; a.slab = slab;
     a.B = B; a.S = S; a.N = N; a.T = S * N; a.NC = n_classes;
-    int rc = launch_cls_head_bwd(a, st);
+    rc = launch_cls_head_bwd(a, st);
     if (rc) return fail(rc, "msst_cls_head_bwd");
     const long ss = (long)n_classes * 96 + n_classes + 192;
     RSegBuilder rb;

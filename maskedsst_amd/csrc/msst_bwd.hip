@@ -1886,7 +1886,8 @@ namespace msst {
 // ==========================================================================================
 // classification head backward (forward: cls_head_fwd_kernel).  grid (B), 256 threads.
 // slab per sample: [dW NC*96 | db NC | dgamma 96 | dbeta 96]; dy [B][T][96] fully written
-// (every spectral block of a position receives d(mean) / S).
+// (every spectral block of a position receives d(mean) / S).  Any NC: dlogits is staged in LDS 32 classes at a time for the
+// dW / db partials (each still a sum over the positions nn = 0, 1, ... in order, whatever NC is).
 // ==========================================================================================
 __global__ __launch_bounds__(256) void cls_head_bwd_kernel(ClsBwdArgs a) {
     __shared__ float xn_s[64][97];
@@ -1922,7 +1923,6 @@ __global__ __launch_bounds__(256) void cls_head_bwd_kernel(ClsBwdArgs a) {
         for (int i = 0; i < 24; ++i) { m[i] = (m[i] - mean) * rstd; dxn[i] = 0.f; }   // m = xhat
         for (int k = 0; k < NC; ++k) {
             const float dl = a.dlogits[((long)b * NC + k) * a.N + n];
-            if (part == 0) dl_s[n][k] = dl;
 #pragma unroll
             for (int i = 0; i < 24; ++i) dxn[i] += dl * a.w[k * 96 + part * 24 + i];
         }
@@ -1951,18 +1951,24 @@ __global__ __launch_bounds__(256) void cls_head_bwd_kernel(ClsBwdArgs a) {
             for (int i = 0; i < 6; ++i) dst[i] = o[i];
         }
     }
-    __syncthreads();
     float* slab = a.slab + (long)b * (NC * 96 + NC + 192);
-    for (int idx = tid; idx < NC * 96; idx += 256) {
-        const int k = idx / 96, d = idx - k * 96;
-        float s = 0.f;
-        for (int nn = 0; nn < a.N; ++nn) s += dl_s[nn][k] * xn_s[nn][d];
-        slab[idx] = s;
-    }
-    if (tid < NC) {
-        float s = 0.f;
-        for (int nn = 0; nn < a.N; ++nn) s += dl_s[nn][tid];
-        slab[NC * 96 + tid] = s;
+    for (int k0 = 0; k0 < NC; k0 += 32) {
+        const int nk = min(32, NC - k0);
+        __syncthreads();   // xn_s written (first chunk) / the previous chunk's dl_s read
+        if (active)
+            for (int k = part; k < nk; k += 4) dl_s[n][k] = a.dlogits[((long)b * NC + k0 + k) * a.N + n];
+        __syncthreads();
+        for (int idx = tid; idx < nk * 96; idx += 256) {
+            const int k = idx / 96, d = idx - k * 96;
+            float s = 0.f;
+            for (int nn = 0; nn < a.N; ++nn) s += dl_s[nn][k] * xn_s[nn][d];
+            slab[k0 * 96 + idx] = s;
+        }
+        if (tid < nk) {
+            float s = 0.f;
+            for (int nn = 0; nn < a.N; ++nn) s += dl_s[nn][tid];
+            slab[NC * 96 + k0 + tid] = s;
+        }
     }
     for (int which = 0; which < 2; ++which) {
         __syncthreads();
@@ -1978,7 +1984,7 @@ __global__ __launch_bounds__(256) void cls_head_bwd_kernel(ClsBwdArgs a) {
 }
 
 int launch_cls_head_bwd(const ClsBwdArgs& a, hipStream_t st) {
-    if (a.N > 64 || a.NC > 32) return MSST_ERR_UNSUPPORTED;
+    if (a.N > 64) return MSST_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(cls_head_bwd_kernel, dim3(a.B), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }

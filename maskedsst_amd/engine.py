@@ -831,10 +831,12 @@ class Engine:
             return self.transformer(x0)
 
     # ------------------------------------------------------------------ classification (row a17 / finetune.py)
-    def cls_head_fwd(self, y):
+    # the head calls take optional output buffers (logits / dy): the kernels write every element of them, whatever they held
+    def cls_head_fwd(self, y, logits=None):
         B = y.shape[0]
         nc = self.enc.num_classes
-        logits = torch.empty(B, nc, self.N, dtype=torch.float32, device=y.device)
+        if logits is None:
+            logits = torch.empty(B, nc, self.N, dtype=torch.float32, device=y.device)
         fp = self.fp
         V = ctypes.c_void_p
         _lib.check(self.lib.msst_cls_head_fwd(
@@ -842,10 +844,11 @@ class Engine:
             V(fp.ptr("mlp_head.1.bias")), _p(logits), B, self.S, self.N, nc, _stream()), "msst_cls_head_fwd")
         return logits
 
-    def cls_head_bwd(self, y, dlogits):
+    def cls_head_bwd(self, y, dlogits, dy=None):
         B = y.shape[0]
         nc = self.enc.num_classes
-        dy = torch.empty_like(y)
+        if dy is None:
+            dy = torch.empty_like(y)
         slab = torch.empty(B * (nc * 97 + 192), dtype=torch.float32, device=y.device)
         fp, g = self.fp, self.fp.grad
         V = ctypes.c_void_p
@@ -857,11 +860,12 @@ class Engine:
         self._fire("cls_head")
         return dy
 
-    def spec_head_fwd(self, y):
+    def spec_head_fwd(self, y, logits=None):
         """spectral_mlp_head: the S tokens of a position concatenated -> LN(96 S) -> Linear; logits [B, nc, N] (cls_head_fwd's layout)"""
         B = y.shape[0]
         nc = self.enc.num_classes
-        logits = torch.empty(B, nc, self.N, dtype=torch.float32, device=y.device)
+        if logits is None:
+            logits = torch.empty(B, nc, self.N, dtype=torch.float32, device=y.device)
         self._spec_head_fwd_into(y, B, logits, _stream())
         return logits
 
@@ -872,11 +876,12 @@ class Engine:
             _p(y), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")), V(fp.ptr("mlp_head.1.weight")),
             V(fp.ptr("mlp_head.1.bias")), _p(logits), B, self.S, self.N, self.enc.num_classes, st), "msst_spec_head_fwd")
 
-    def spec_head_bwd(self, y, dlogits):
+    def spec_head_bwd(self, y, dlogits, dy=None):
         """-> dy [B, T, 96]; the four head gradients are written (not accumulated) into the flat gradient buffer"""
         B = y.shape[0]
         nc = self.enc.num_classes
-        dy = torch.empty_like(y)
+        if dy is None:
+            dy = torch.empty_like(y)
         slab = torch.empty(int(self.lib.msst_spec_head_bwd_slab(B, self.S, self.N, nc)), dtype=torch.float32, device=y.device)
         fp, g = self.fp, self.fp.grad
         V = ctypes.c_void_p
@@ -888,10 +893,11 @@ class Engine:
         self._fire("cls_head")
         return dy
 
-    def pix_head_fwd(self, y):
+    def pix_head_fwd(self, y, logits=None):
         """pixelwise: mean over the S tokens -> LN(96) per position -> flatten -> Linear(96 N); logits [B, nc] (centre pixel)"""
         B = y.shape[0]
-        logits = torch.empty(B, self.enc.num_classes, dtype=torch.float32, device=y.device)
+        if logits is None:
+            logits = torch.empty(B, self.enc.num_classes, dtype=torch.float32, device=y.device)
         self._pix_head_fwd_into(y, B, logits, _stream())
         return logits
 
@@ -903,11 +909,12 @@ class Engine:
             _p(y), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")), V(fp.ptr("mlp_head.2.weight")),
             V(fp.ptr("mlp_head.2.bias")), _p(logits), _p(ws), B, self.S, self.N, self.enc.num_classes, st), "msst_pix_head_fwd")
 
-    def pix_head_bwd(self, y, dlogits):
+    def pix_head_bwd(self, y, dlogits, dy=None):
         """dlogits [B, nc] -> dy [B, T, 96]; the four head gradients are written (not accumulated) into the flat gradient buffer"""
         B = y.shape[0]
         nc = self.enc.num_classes
-        dy = torch.empty_like(y)
+        if dy is None:
+            dy = torch.empty_like(y)
         slab = torch.empty(int(self.lib.msst_pix_head_bwd_slab(B, self.S, self.N, nc)), dtype=torch.float32, device=y.device)
         fp, g = self.fp, self.fp.grad
         V = ctypes.c_void_p

@@ -1,0 +1,222 @@
+"""GPU: spectral patch depths P other than the shipped 10 (config key band_patch_size; the constructor accepts 1 .. 16).  Every P != 10
+runs the run-time-P kernels: tokenize_fwd_kernel<0>, tokenize_bwd_kernel<0>, tokenize_scene_fwd_kernel<0> and the generic SimMIM
+to-pixels head (head_fwd_kernel / head_bwd_kernel).  Against the CPU oracle (OracleConfig(spectral_patch=P)) at the bars of
+tests/test_gpu_forward.py / tests/test_gpu_backward.py / tests/test_gpu_finetune.py, and against the reference captures of
+tools/make_golden.py patch."""
+import json
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from conftest import load_golden, seed_all, fp_np
+from util import build_product, oracle_cfg, relerr, rel_l2, record
+
+pytestmark = pytest.mark.gpu
+
+CASES = [
+    dict(bands=12, depth=1, B=2, heads=2, spectral_patch=1),        # P = 1: the pre-norm LayerNorm sees one pixel
+    dict(bands=50, depth=1, B=2, spectral_patch=5),                 # the shape of patch_P5_50b_L1_B2.npz
+    dict(bands=56, depth=1, B=3, heads=2, image_size=5, mask_patch_size=1, spectral_patch=8),
+    dict(bands=64, depth=1, B=3, heads=2, image_size=6, mask_patch_size=2, spectral_patch=16),   # patch_P16_64b_L1_B3_img6_mps2_h2.npz
+    dict(bands=192, depth=1, B=2, heads=2, image_size=4, mask_patch_size=2, spectral_patch=3),   # S = 64 spectral blocks
+]
+FIXTURES = ["patch_P5_50b_L1_B2.npz", "patch_P16_64b_L1_B3_img6_mps2_h2.npz"]
+
+# the existing bars: fp32 stages / loss (test_forward_stages), fp32 parameter gradients (test_param_grads_fp32), bf16 stages / loss
+# / gradient cosine (test_forward_stages, test_param_grads_bf16), the classifier step (test_finetune_step_fp32), predict_scene
+# against the window loop (tests/test_gpu_scene.py FP32_LOOP_BAR)
+FP32_STAGE, FP32_GRAD, CLS_GRAD, LOOP_BAR = 1e-4, 2e-4, 3e-4, 1e-5
+BF16_STAGE, BF16_LOSS, BF16_COS = 9e-3, 2.5e-4, 0.99958
+STAGES = ["tok_embed", "tok_masked", "after_spatial", "enc_out", "pred"]
+
+
+def grad_errors(named_grads, ref_grad, cfg):
+    """{name: relerr against the oracle}.  P = 1: LayerNorm over one pixel has xhat = 0 exactly, so the pre-norm weight's gradient is
+    exactly 0 (float64 autograd: 6e-21); the fp32 oracle's is round-off (2e-11) and no relative error against it means anything --
+    the product's must be exactly 0 instead"""
+    errs = {}
+    for name, g in named_grads:
+        if cfg["spectral_patch"] == 1 and name.endswith("pre_norm.weight"):
+            assert g is not None and not g.any(), (name, g)
+            continue
+        errs[name] = relerr(g, ref_grad(name))
+    return errs
+
+
+def case_id(c):
+    return "P%d-%db-img%d-B%d" % (c["spectral_patch"], c["bands"], c.get("image_size", 8), c["B"])
+
+
+def simmim_pair(cfg, prec):
+    """the product SimMIM step and the oracle's on the same parameters, input and masks: (model, params, ref, stages, loss)"""
+    from oracle import simmim_forward
+    model, params, x = build_product(cfg, precision=prec, device="cuda")
+    masks = model.draw_masks(cfg["B"])
+    for p in params.values():
+        p.requires_grad_(True)
+    ref = simmim_forward(params, x, oracle_cfg(cfg), masks=masks)
+    ref["loss"].backward()
+    with torch.no_grad():
+        stages = model.engine().simmim_forward_stages(x.cuda(), masks[0], masks[1])
+    loss = model(x.cuda(), masks=masks)
+    loss.backward()
+    torch.cuda.synchronize()
+    return model, params, ref, stages, loss
+
+
+@pytest.mark.parametrize("cfg", CASES, ids=case_id)
+def test_simmim_fp32(cfg):
+    """every forward stage, the loss and every parameter gradient (the tokenizer's and the to-pixels head's included)"""
+    model, params, ref, stages, loss = simmim_pair(cfg, "fp32")
+    errs = {k: relerr(stages[k], ref[k]) for k in STAGES}
+    lr = ref["loss"].item()
+    assert all(e < FP32_STAGE for e in errs.values()), errs
+    assert abs(stages["loss"].item() - lr) <= 1e-4 * abs(lr) + 1e-7, (stages["loss"].item(), lr)
+    assert abs(loss.item() - lr) <= 1e-4 * abs(lr) + 1e-7, (loss.item(), lr)
+    named = []
+    for name, p in model.named_parameters():
+        if params[name].grad is None:
+            assert p.grad is None, name
+        else:
+            assert p.grad is not None, name
+            named.append((name, p.grad))
+    assert any(n.endswith("pre_norm.weight") for n, _ in named) and any(n.startswith("to_pixels") for n, _ in named)
+    gerr = grad_errors(named, lambda n: params[n].grad, cfg)
+    bad = [(k, e) for k, e in gerr.items() if not e < FP32_GRAD]
+    assert not bad, bad
+    worst = max(gerr, key=gerr.get)
+    record("patch_depth_simmim_fp32", cfg=cfg, stage_err=errs, loss_err=abs(loss.item() - lr) / abs(lr), worst_grad=gerr[worst],
+           worst_grad_name=worst)
+
+
+@pytest.mark.parametrize("cfg", CASES, ids=case_id)
+def test_simmim_bf16(cfg):
+    """bf16 block kernels (the tokenizer and the to-pixels head are fp32 in both modes): stages, loss and the whole-gradient cosine"""
+    model, params, ref, stages, loss = simmim_pair(cfg, "bf16")
+    errs = {k: relerr(stages[k], ref[k]) for k in STAGES}
+    lr = ref["loss"].item()
+    assert all(e < BF16_STAGE for e in errs.values()), errs
+    assert abs(loss.item() - lr) <= BF16_LOSS * abs(lr), (loss.item(), lr)
+    ga, gb = [], []
+    for name, p in model.named_parameters():
+        if params[name].grad is not None:
+            ga.append(p.grad.detach().double().cpu().reshape(-1))
+            gb.append(params[name].grad.double().reshape(-1))
+    ga, gb = torch.cat(ga), torch.cat(gb)
+    cos = float((ga * gb).sum() / (ga.norm() * gb.norm()))
+    assert cos > BF16_COS, cos
+    record("patch_depth_simmim_bf16", cfg=cfg, stage_err=errs, loss_err=abs(loss.item() - lr) / abs(lr), cos=cos)
+
+
+def classifier(cfg, n_classes=5, precision="fp32"):
+    """a seeded default-head encoder at the case's spectral patch depth, then x and labels from the same stream (the draw order of
+    tools/make_golden.py run_finetune_case)"""
+    from maskedsst_amd import ViTSpatialSpectral
+    seed_all(5)
+    P, w = cfg["spectral_patch"], cfg.get("image_size", 8)
+    enc = ViTSpatialSpectral(
+        image_size=w, spatial_patch_size=1, spectral_patch_size=P, num_classes=n_classes, dim=96, depth=cfg["depth"],
+        heads=cfg.get("heads", 8), mlp_dim=64, dropout=0.0, emb_dropout=0.0, channels=cfg["bands"], spectral_pos_embed=False,
+        spectral_pos=torch.arange(cfg["bands"] // P), blockwise_patch_embed=True, precision=precision)
+    x = torch.randn(cfg["B"], cfg["bands"], w, w)
+    label = torch.randint(-1, n_classes, (cfg["B"], w, w))
+    return enc, x, label
+
+
+def classify_step(cfg, n_classes):
+    from oracle import classify_forward
+    enc, x, label = classifier(cfg, n_classes)
+    params = {"encoder." + k: v.detach().clone().requires_grad_(True) for k, v in enc.state_dict().items()}
+    ref_logits = classify_forward(params, x, oracle_cfg(dict(cfg, n_classes=n_classes)))
+    ref_loss = F.cross_entropy(ref_logits, label, ignore_index=-1)
+    ref_loss.backward()
+    enc = enc.cuda()
+    logits = enc(x.cuda())
+    assert logits.shape == ref_logits.shape
+    loss = F.cross_entropy(logits, label.cuda(), ignore_index=-1)
+    loss.backward()
+    torch.cuda.synchronize()
+    gerr = grad_errors([(k, p.grad) for k, p in enc.named_parameters()], lambda n: params["encoder." + n].grad, cfg)
+    return enc, x, label, logits, loss, ref_logits, ref_loss, gerr
+
+
+@pytest.mark.parametrize("cfg", CASES, ids=case_id)
+def test_classify_step_fp32(cfg):
+    """the default-head classifier step: logits and every gradient against the oracle"""
+    enc, x, label, logits, loss, ref_logits, ref_loss, gerr = classify_step(cfg, 5)
+    err = relerr(logits, ref_logits)
+    assert err < 1e-4, err
+    assert abs(loss.item() - ref_loss.item()) <= 1e-4 * abs(ref_loss.item())
+    bad = [(k, e) for k, e in gerr.items() if not e < CLS_GRAD]
+    assert not bad, bad
+    record("patch_depth_classify_fp32", cfg=cfg, err=err, worst_grad=max(gerr.values()))
+
+
+@pytest.mark.parametrize("cfg", CASES, ids=case_id)
+def test_predict_scene(cfg):
+    """predict_scene (the scene tokenizer) against the product's own model(window) loop, and against the oracle per window"""
+    from oracle import classify_forward
+    enc, _, _ = classifier(cfg, 4)
+    w = cfg.get("image_size", 8)
+    params = {"encoder." + k: v.detach().clone() for k, v in enc.state_dict().items()}
+    gen = torch.Generator().manual_seed(7)
+    Hs, Ws = 3 * w + 1, 2 * w + 3     # a ragged border no window covers
+    scene = torch.randn(2, cfg["bands"], Hs, Ws, generator=gen)
+    enc = enc.cuda().eval()
+    classes, logits = enc.predict_scene(scene.cuda(), return_logits=True)
+    classes, logits = classes.cpu(), logits.cpu()
+    loop = torch.zeros_like(logits)
+    ref = torch.zeros_like(logits)
+    covered = torch.zeros(2, Hs, Ws, dtype=torch.bool)
+    ocfg = oracle_cfg(dict(cfg, n_classes=4))
+    with torch.no_grad():
+        for y0 in range(0, Hs - w + 1, w):
+            for x0 in range(0, Ws - w + 1, w):
+                win = scene[:, :, y0:y0 + w, x0:x0 + w]
+                loop[:, :, y0:y0 + w, x0:x0 + w] = enc(win.cuda()).cpu()
+                ref[:, :, y0:y0 + w, x0:x0 + w] = classify_forward(params, win, ocfg)
+                covered[:, y0:y0 + w, x0:x0 + w] = True
+    assert torch.equal(classes < 0, ~covered)
+    assert (logits.permute(0, 2, 3, 1)[~covered] == 0).all()
+    lg, lp, rf = (t.permute(0, 2, 3, 1)[covered] for t in (logits, loop, ref))
+    err_loop, err = rel_l2(lg, lp), rel_l2(lg, rf)
+    assert err_loop < LOOP_BAR, err_loop
+    assert err < 1e-4, err
+    record("patch_depth_predict_scene", cfg=cfg, err=err, err_loop=err_loop)
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_reference_captures(name):
+    """the product against the reference's own outputs at P = 5 and P = 16: the SimMIM loss and gradient norm, and the default-head
+    classifier's logits, loss and gradient norm"""
+    g = load_golden(name)
+    cfg = g["cfg"]
+    model, params, x = build_product(cfg, precision="fp32", device="cuda")
+    np.testing.assert_array_equal(fp_np(x), g["x_fp"])
+    masks = model.draw_masks(cfg["B"])   # from the same stream as the reference's
+    np.testing.assert_array_equal(np.packbits(masks[0].numpy().astype(np.uint8), axis=-1), g["bool_mask_bits"])
+    np.testing.assert_array_equal(masks[1].numpy().astype(np.int16), g["masked_indices"])
+    loss = model(x.cuda(), masks=masks)
+    loss.backward()
+    torch.cuda.synchronize()
+    assert abs(loss.item() - float(g["loss"])) <= 1e-4 * abs(float(g["loss"])), (loss.item(), float(g["loss"]))
+    gsq = sum(float((p.grad.double() ** 2).sum()) for p in model.parameters() if p.grad is not None)
+    assert abs(gsq ** 0.5 - float(g["grad_l2"])) <= 1e-3 * float(g["grad_l2"]), (gsq ** 0.5, float(g["grad_l2"]))
+    ft = json.loads(bytes(g["ft/cfg"]).decode())
+    assert ft["spectral_patch"] == cfg["spectral_patch"]
+    enc, x, label = classifier(cfg, ft["n_classes"])
+    np.testing.assert_array_equal(label.numpy().astype(np.int8), g["ft/label"])
+    assert sum(p.numel() for p in enc.parameters()) == int(g["ft/n_params"])
+    enc = enc.cuda()
+    logits = enc(x.cuda())
+    lossc = F.cross_entropy(logits, label.cuda(), ignore_index=-1)
+    lossc.backward()
+    torch.cuda.synchronize()
+    err = relerr(logits, torch.from_numpy(g["ft/logits"]))
+    assert err < 1e-4, err
+    assert abs(lossc.item() - float(g["ft/loss"])) <= 1e-4 * abs(float(g["ft/loss"]))
+    gsq = sum(float((p.grad.double() ** 2).sum()) for p in enc.parameters())
+    assert abs(gsq ** 0.5 - float(g["ft/grad_l2"])) <= 1e-3 * float(g["ft/grad_l2"])
+    record("patch_depth_reference_captures", name=name, err=err, loss_err=abs(loss.item() - float(g["loss"])) / abs(float(g["loss"])))

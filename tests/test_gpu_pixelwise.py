@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import load_golden, oracle_cfg_from, seed_all, ROOT
-from util import relerr, rel_l2
+from util import relerr, rel_l2, pix_head_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -25,15 +25,6 @@ def pixelwise_encoder(cfg, n_classes=None, pixelwise=True, precision="fp32", ima
         num_classes=n_classes or cfg["n_classes"], dim=96, depth=cfg["depth"], heads=cfg.get("heads", 8), mlp_dim=64,
         dropout=0.0, emb_dropout=0.0, channels=cfg["bands"], spectral_pos_embed=cfg.get("spectral_pos_embed", False),
         spectral_pos=torch.arange(cfg["bands"] // 10), blockwise_patch_embed=True, pixelwise=pixelwise, precision=precision)
-
-
-def pix_head_ref(y, ln_g, ln_b, w, b, S, N):
-    """the reference head on tokens y [B, S N, 96] (order c h w): mean over c -> LayerNorm(96) per position -> flatten (n, d) ->
-    Linear -> [B, nc]"""
-    B = y.shape[0]
-    x = y.reshape(B, S, N, 96).mean(dim=1)
-    x = F.layer_norm(x, (96,), ln_g, ln_b, 1e-5)
-    return x.reshape(B, N * 96) @ w.t() + b
 
 
 def classify_ref(params, img, cfg):

@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import load_golden, oracle_cfg_from, seed_all, ROOT
-from util import record, relerr, rel_l2
+from util import record, relerr, rel_l2, spectral_head_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -25,15 +25,6 @@ def spectral_encoder(cfg, n_classes=None, spectral_mlp_head=True, precision="fp3
         dropout=0.0, emb_dropout=0.0, channels=cfg["bands"], spectral_pos_embed=cfg.get("spectral_pos_embed", False),
         spectral_pos=torch.arange(cfg["bands"] // 10), blockwise_patch_embed=True, spectral_mlp_head=spectral_mlp_head,
         precision=precision)
-
-
-def spectral_head_ref(y, ln_g, ln_b, w, b, S, Nsq):
-    """the reference head on tokens y [B, S N, 96] (order c h w): 'b (c h w) d -> b h w (c d)' -> LayerNorm -> Linear ->
-    [B, nc, H, W]"""
-    B = y.shape[0]
-    x = y.reshape(B, S, Nsq, Nsq, 96).permute(0, 2, 3, 1, 4).reshape(B, Nsq, Nsq, S * 96)
-    x = F.layer_norm(x, (S * 96,), ln_g, ln_b, 1e-5)
-    return torch.moveaxis(x @ w.t() + b, -1, 1)
 
 
 def classify_ref(params, img, cfg):

@@ -212,12 +212,12 @@ def test_finetune_config_pixelwise_override():
     assert not c.pixelwise and c.patch_sub == 0
 
 
-def test_c_abi_symbols_and_argument_checks():
-    """msst_pix_head_* and msst_scene_centre_assemble are exported (MSST_VERSION 107) and refuse bad arguments before anything is
-    enqueued"""
+def test_pix_head_c_abi_symbols_and_argument_checks():
+    """msst_pix_head_* and msst_scene_centre_assemble are exported (since MSST_VERSION 107: the loaded library is the revision of
+    include/msst.h, and that is 107 or later) and refuse bad arguments before anything is enqueued"""
     from maskedsst_amd import _lib
     lib = _lib.load()
-    assert lib.msst_version() == 107
+    assert lib.msst_version() == _lib.header_version() >= 107
     unsupported, badarg = -2, -3   # include/msst.h: MSST_ERR_UNSUPPORTED, MSST_ERR_BADARG
     for B, S, N, nc in [(2, 20, 65, 8), (2, 65, 49, 8), (2, 20, 49, 33)]:
         assert lib.msst_pix_head_fwd(*([None] * 7), B, S, N, nc, None) == unsupported, (B, S, N, nc)

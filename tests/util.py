@@ -10,13 +10,15 @@ from conftest import ROOT, seed_all, oracle_cfg_from, apply_qkv_scale
 
 
 def build_product(cfg, precision="fp32", device="cpu"):
+    """cfg key spectral_patch: the spectral patch depth P (default 10, the shipped band_patch_size)"""
     from maskedsst_amd import ViTSpatialSpectral, SimMIMSpatialSpectral
     seed_all(5)
+    P = cfg.get("spectral_patch", 10)
     enc = ViTSpatialSpectral(
-        image_size=cfg.get("image_size", 8), spatial_patch_size=1, spectral_patch_size=10, num_classes=cfg.get("n_classes", 8),
+        image_size=cfg.get("image_size", 8), spatial_patch_size=1, spectral_patch_size=P, num_classes=cfg.get("n_classes", 8),
         dim=96, depth=cfg["depth"], heads=cfg.get("heads", 8), mlp_dim=64, dropout=0.0, emb_dropout=0.0,
         channels=cfg["bands"], spectral_pos_embed=cfg.get("spectral_pos_embed", False),
-        spectral_pos=torch.arange(cfg["bands"] // 10), blockwise_patch_embed=True, spectral_only=False,
+        spectral_pos=torch.arange(cfg["bands"] // P), blockwise_patch_embed=True, spectral_only=False,
         precision=precision)
     model = SimMIMSpatialSpectral(
         encoder=enc, intermediate_losses=False, masking_ratio=cfg.get("masking_ratio", 0.7),
@@ -31,6 +33,36 @@ def build_product(cfg, precision="fp32", device="cpu"):
     if device != "cpu":
         model = model.to(device)
     return model, params, x
+
+
+def oracle_cfg(cfg):
+    """conftest.oracle_cfg_from plus the spectral patch depth (cfg key spectral_patch, default 10)"""
+    import dataclasses
+    return dataclasses.replace(oracle_cfg_from(cfg), spectral_patch=cfg.get("spectral_patch", 10))
+
+
+# ---- the three classifier heads on encoder tokens y [B, S N, 96] (token order c h w), in plain PyTorch: float64 references ----
+def cls_head_ref(y, ln_g, ln_b, w, b, S, N):
+    """default head (reference vit_spatial_spectral.py:481-493, :536-564): mean over c -> LayerNorm(96) -> Linear -> [B, nc, N]"""
+    B = y.shape[0]
+    x = torch.nn.functional.layer_norm(y.reshape(B, S, N, 96).mean(dim=1), (96,), ln_g, ln_b, 1e-5)
+    return torch.moveaxis(x @ w.t() + b, -1, 1)
+
+
+def spectral_head_ref(y, ln_g, ln_b, w, b, S, Nsq):
+    """the spectral MLP head: 'b (c h w) d -> b h w (c d)' -> LayerNorm -> Linear -> [B, nc, H, W]"""
+    B = y.shape[0]
+    x = y.reshape(B, S, Nsq, Nsq, 96).permute(0, 2, 3, 1, 4).reshape(B, Nsq, Nsq, S * 96)
+    x = torch.nn.functional.layer_norm(x, (S * 96,), ln_g, ln_b, 1e-5)
+    return torch.moveaxis(x @ w.t() + b, -1, 1)
+
+
+def pix_head_ref(y, ln_g, ln_b, w, b, S, N):
+    """the pixelwise head: mean over c -> LayerNorm(96) per position -> flatten (n, d) -> Linear -> [B, nc]"""
+    B = y.shape[0]
+    x = y.reshape(B, S, N, 96).mean(dim=1)
+    x = torch.nn.functional.layer_norm(x, (96,), ln_g, ln_b, 1e-5)
+    return x.reshape(B, N * 96) @ w.t() + b
 
 
 def relerr(a, b):

@@ -60,10 +60,11 @@ def fp(t):
 
 
 def build(cfg):
+    P = cfg.get("spectral_patch", 10)
     enc = ViTSpatialSpectral(
         image_size=cfg.get("image_size", 8),
         spatial_patch_size=1,
-        spectral_patch_size=10,
+        spectral_patch_size=P,
         num_classes=cfg.get("n_classes", 8),
         dim=96,
         depth=cfg["depth"],
@@ -73,7 +74,7 @@ def build(cfg):
         emb_dropout=cfg.get("dropout", 0.0),
         channels=cfg["bands"],
         spectral_pos_embed=cfg.get("spectral_pos_embed", False),
-        spectral_pos=torch.arange(cfg["bands"] // 10),
+        spectral_pos=torch.arange(cfg["bands"] // P),
         blockwise_patch_embed=True,
         spectral_only=False,
     )
@@ -174,7 +175,8 @@ def staged_forward(model, x):
     )
 
 
-def run_case(name, cfg, full=False):
+def run_case(name, cfg, full=False, save=True):
+    """save=False: return the capture instead of writing simmim_<name>.npz"""
     seed_all()
     model = build(cfg)
     B, C = cfg["B"], cfg["bands"]
@@ -237,6 +239,8 @@ def run_case(name, cfg, full=False):
                 out["grad/" + k] = g.numpy()
         for k in ["tok_embed", "tok_masked", "after_spatial", "enc_out", "pred", "target"]:
             out["full/" + k] = st[k].numpy()
+    if not save:
+        return out
     np.savez_compressed(os.path.join(OUT, f"simmim_{name}.npz"), **out)
     print(f"{name}: loss={loss.item():.9e} grad_l2={gsq ** 0.5:.6e} n_params={int(out['n_params'])} "
           f"idx[1,:4]={st['masked_indices'][min(1, B - 1), :4].tolist()}")
@@ -320,18 +324,20 @@ def run_adamw_traj():
     print("adamw traj:", losses)
 
 
-def run_finetune_case(name, cfg):
-    """Classification step (finetune.py / src/utils.py:608-663): logits [B,ncls,8,8], CE(ignore -1)."""
+def run_finetune_case(name, cfg, save=True):
+    """Classification step (finetune.py / src/utils.py:608-663): logits [B,ncls,8,8], CE(ignore -1).
+    save=False: return the capture instead of writing finetune_<name>.npz"""
     seed_all()
+    P, w = cfg.get("spectral_patch", 10), cfg.get("image_size", 8)
     enc = ViTSpatialSpectral(
-        image_size=8, spatial_patch_size=1, spectral_patch_size=10, num_classes=cfg["n_classes"],
-        dim=96, depth=cfg["depth"], heads=8, mlp_dim=64, dropout=0.0, emb_dropout=0.0,
+        image_size=w, spatial_patch_size=1, spectral_patch_size=P, num_classes=cfg["n_classes"],
+        dim=96, depth=cfg["depth"], heads=cfg.get("heads", 8), mlp_dim=64, dropout=0.0, emb_dropout=0.0,
         channels=cfg["bands"], spectral_pos_embed=cfg["spectral_pos_embed"],
-        spectral_pos=torch.arange(cfg["bands"] // 10), blockwise_patch_embed=True,
+        spectral_pos=torch.arange(cfg["bands"] // P), blockwise_patch_embed=True,
     )
     B = cfg["B"]
-    x = torch.randn(B, cfg["bands"], 8, 8)
-    label = torch.randint(-1, cfg["n_classes"], (B, 8, 8))
+    x = torch.randn(B, cfg["bands"], w, w)
+    label = torch.randint(-1, cfg["n_classes"], (B, w, w))
     enc.eval()
     logits = enc(x)
     loss = F.cross_entropy(logits, label, ignore_index=-1)
@@ -353,6 +359,8 @@ def run_finetune_case(name, cfg):
         gsq += float((p.grad.double() ** 2).sum())
     out["names"] = np.frombuffer("\n".join(names).encode(), dtype=np.uint8)
     out["grad_l2"] = np.array(gsq ** 0.5, dtype=np.float64)
+    if not save:
+        return out
     np.savez_compressed(os.path.join(OUT, f"finetune_{name}.npz"), **out)
     print(f"finetune {name}: loss={loss.item():.9e} grad_l2={gsq ** 0.5:.6e} n_params={int(out['n_params'])}")
 
@@ -481,6 +489,26 @@ def run_config_kat():
     print("config KAT:", len(pre), "pretrain keys,", len(fin), "finetune keys")
 
 
+# spectral patch depths other than the shipped 10 (configs' band_patch_size): the generic tokenizer and to-pixels head paths.
+# Not named simmim_*: tests/test_oracle_golden.py globs that prefix with a config that has no spectral patch depth.
+PATCH_CASES = [("P5_50b_L1_B2", dict(bands=50, depth=1, B=2, spectral_patch=5), dict(n_classes=8)),
+               ("P16_64b_L1_B3_img6_mps2_h2", dict(bands=64, depth=1, B=3, image_size=6, mask_patch_size=2, heads=2, spectral_patch=16),
+                dict(n_classes=5))]
+
+
+def run_patch_cases():
+    """For each PATCH_CASES shape, one fixture patch_<name>.npz: the SimMIM capture of run_case (same keys) and, under "ft/", the
+    default-head classifier step of run_finetune_case at the same spectral patch depth and image size"""
+    for name, cfg, ft in PATCH_CASES:
+        out = run_case(name, cfg, save=False)
+        ft_cfg = dict(bands=cfg["bands"], depth=cfg["depth"], B=cfg["B"], heads=cfg.get("heads", 8), image_size=cfg.get("image_size", 8),
+                      spectral_patch=cfg["spectral_patch"], spectral_pos_embed=False, **ft)
+        for k, v in run_finetune_case(name, ft_cfg, save=False).items():
+            out["ft/" + k] = v
+        np.savez_compressed(os.path.join(OUT, f"patch_{name}.npz"), **out)
+        print(f"patch {name}: loss={float(out['loss']):.9e} ft loss={float(out['ft/loss']):.9e}")
+
+
 def run_spectral_pos_kat():
     """Houston2018 -> EnMAP spectral-position lookup (reference src/utils.py:415-429 -> vit_spatial_spectral.py:767-800):
     the sensors' band-centre tables (data), the reference's answer for the shipped spectral patch depth (the SURVEY 8c KAT
@@ -520,6 +548,9 @@ if __name__ == "__main__":
         run_case("70b_L1_B3_img4_mps2", dict(bands=70, depth=1, B=3, image_size=4, mask_patch_size=2))
         run_case("30b_L1_B2_img6_mps2_h2", dict(bands=30, depth=1, B=2, image_size=6, mask_patch_size=2, heads=2))
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "patch":   # spectral patch depths 5 and 16 (SimMIM + default-head classifier)
+        run_patch_cases()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "tiny":  # regenerate only the element-wise cases
         run_case("tiny_20b_L1_B2_h2", dict(bands=20, depth=1, B=2, heads=2), full=True)
         run_case("tiny_30b_L1_B3_h2_nontube", dict(bands=30, depth=1, B=3, heads=2, tube_masking=False), full=True)
@@ -545,6 +576,7 @@ if __name__ == "__main__":
     run_adamw_traj()
     run_finetune_case("200b_L4_B2", dict(bands=200, depth=4, B=2, n_classes=8, spectral_pos_embed=False))
     run_finetune_case("50b_L2_B2_specpos", dict(bands=50, depth=2, B=2, n_classes=20, spectral_pos_embed=True))
+    run_patch_cases()
     run_load_checkpoint()
     run_spectral_pos_kat()
     run_config_kat()
