@@ -171,6 +171,14 @@ static Drop make_drop(float p, uint32_t seed, int layer) {
 
 static int ntiles_of(const TileMap& tm) { return (tm.nseq + tm.TS - 1) / tm.TS; }
 
+// shape of a block call, checked before its pointers, its tile map (64 / L) or any launch: 0, MSST_ERR_BADARG (a size below 1 or a
+// mode outside {spatial, spectral}) or MSST_ERR_UNSUPPORTED (a sequence longer than one 64-row tile)
+static int block_shape(int mode, int B, int S, int N, int heads) {
+    if (B < 1 || S < 1 || N < 1 || heads < 1 || (mode != MSST_MODE_SPATIAL && mode != MSST_MODE_SPECTRAL)) return MSST_ERR_BADARG;
+    if (N > 64 || S > 64) return MSST_ERR_UNSUPPORTED;
+    return 0;
+}
+
 static bool bw_ok(const MsstBlockWeights* w) { return w && w->struct_bytes == sizeof(MsstBlockWeights); }
 
 static BlockWeights to_bw(const MsstBlockWeights* w) {
@@ -349,8 +357,8 @@ long msst_block_tiles(int mode, int B, int S, int N) {
 int msst_block_fwd(const MsstBlockWeights* w, const float* x, float* y, float* x1, int mode, int B, int S,
                    int N, int heads, int prec, int max_grid, float dropout_p, uint32_t seed, int layer,
                    void* xn_out, float* lse_out, int* saved, void* stream) {
+    if (int rc = block_shape(mode, B, S, N, heads)) return fail(rc, "msst_block_fwd (B, S, N, heads < 1, mode not 0 / 1, or sequence length > 64)");
     if (!bw_ok(w) || !x || !y || x == y) return fail(MSST_ERR_BADARG, "msst_block_fwd (null argument, or MsstBlockWeights of another header revision)");
-    if (N > 64 || S > 64) return fail(MSST_ERR_UNSUPPORTED, "msst_block_fwd (sequence length > 64)");
     const int dbg = (prec >> 8) & 0xffff;   // MSST_KERNEL_* selection flags ride in the upper bits of `prec`
     prec &= 0xff;
     BlockArgs a;
@@ -391,8 +399,9 @@ int msst_block_fwd(const MsstBlockWeights* w, const float* x, float* y, float* x
 int msst_block_fwd_stack(const MsstBlockWeights* const* w, int nblk, const float* x0, float* const* y, float* const* x1,
                          void* const* xn_out, float* const* lse_out, int mode, int B, int S, int N, int heads, int prec, int max_grid,
                          float dropout_p, uint32_t seed, int layer0, int* saved, void* stream) {
+    if (int rc = block_shape(mode, B, S, N, heads)) return fail(rc, "msst_block_fwd_stack (B, S, N, heads < 1, mode not 0 / 1, or sequence length > 64)");
     if (!w || !x0 || !y || nblk < 1) return fail(MSST_ERR_BADARG, "msst_block_fwd_stack");
-    if (nblk > MSST_MAX_STACK || N > 64 || S > 64) return fail(MSST_ERR_UNSUPPORTED, "msst_block_fwd_stack (more than 16 blocks, or sequence length > 64)");
+    if (nblk > MSST_MAX_STACK) return fail(MSST_ERR_UNSUPPORTED, "msst_block_fwd_stack (more than 16 blocks)");
     const int dbg = (prec >> 8) & 0xffff;
     prec &= 0xff;
     // the role-split bf16 forward only: 8 heads, no kernel selection flags (MSST_X1_BF16 is the one flag it takes)
@@ -583,9 +592,9 @@ static int block_bwd_impl(const MsstBlockWeights* w, const MsstBlockGrads* g, co
                           int nchunk, int mode, int B, int S, int N, int heads, int prec, float dropout_p,
                           uint32_t seed, int layer, const void* xn_saved, const float* lse_saved, void* dab_ws, int chain, int first,
                           int32_t* tile_queue, hipStream_t st) {
+    if (int rc = block_shape(mode, B, S, N, heads)) return fail(rc, "msst_block_bwd (B, S, N, heads < 1, mode not 0 / 1, or sequence length > 64)");
     if (!bw_ok(w) || (w_prev && !bw_ok(w_prev)) || !g || grid_rows < 1 || nchunk < 1)
         return fail(MSST_ERR_BADARG, "msst_block_bwd (null argument, or MsstBlockWeights of another header revision)");
-    if (N > 64 || S > 64) return fail(MSST_ERR_UNSUPPORTED, "msst_block_bwd (sequence length > 64)");
     const int dbg = (prec >> 8) & 0xffff;   // MSST_KERNEL_* selection flags ride in the upper bits of `prec`
     prec &= 0xff;
     const long ntok = (long)B * S * N;
@@ -701,6 +710,7 @@ int msst_block_bwd_chain(const MsstBlockWeights* w, const MsstBlockGrads* g, con
 int msst_block_bwd_reduce(const MsstBlockGrads* g, const MsstBlockGrads* g_prev, float* slab, long slab_stride, long grad_stride,
                           int count, int count_prev, int first, int grid_rows, int nchunk, int mode, int B, int S, int N, int heads,
                           int prec, void* stream) {
+    if (int rc = block_shape(mode, B, S, N, heads)) return fail(rc, "msst_block_bwd_reduce (B, S, N, heads < 1, mode not 0 / 1, or sequence length > 64)");
     if (!g || count < 1 || count_prev < 0 || count_prev > count || (count_prev && !g_prev) || !slab || grid_rows < 1 || nchunk < 1 ||
         (count > 1 && ((slab_stride & 3) || (grad_stride & 3))))
         return fail(MSST_ERR_BADARG, "msst_block_bwd_reduce");

@@ -65,6 +65,37 @@ def pix_head_ref(y, ln_g, ln_b, w, b, S, N):
     return x.reshape(B, N * 96) @ w.t() + b
 
 
+# ---- the role-split forward's saved softmax statistics (include/msst.h: msst_block_fwd, lse_out) and their float64 restatement ----
+def ln1_rows_as_used(x, ln_g, ln_b, x1, half):
+    """LN1 rows [tokens, 96] as the role-split forward multiplied them, and their element type: IEEE half of LN1(x) computed in fp32
+    (MSST_FWD_HALF), else the bf16 rows the forward saved with x1 (x1._msst_xn)"""
+    if half:
+        xn = torch.nn.functional.layer_norm(x.float().reshape(-1, 96), (96,), ln_g, ln_b, 1e-5)
+        return xn.to(torch.float16).float(), torch.float16
+    return x1._msst_xn.float().reshape(-1, 96), torch.bfloat16
+
+
+def lse_restatement(xn, wqkv, heads, low):
+    """xn [sequences, L, 96]: LN1 rows as used (ln1_rows_as_used, in sequence layout); wqkv [3 heads 64, 96] fp32 -> [sequences, heads, L]
+    lse = log2 of every query's softmax denominator in the kernels' exponent domain (s = q k * dim_head^-0.5 * log2 e), q and k
+    rounded to `low` as the forward rounds them, the rest in float64"""
+    wq = wqkv.to(low).float()
+    qkv = (xn @ wq.t()).to(low).double()
+    n, L = xn.shape[0], xn.shape[1]
+    q, k = qkv[..., :heads * 64].reshape(n, L, heads, 64), qkv[..., heads * 64:2 * heads * 64].reshape(n, L, heads, 64)
+    s = torch.einsum("bnhd,bmhd->bhnm", q, k) * (0.125 * 1.4426950408889634)
+    return torch.logsumexp(s * 0.6931471805599453, dim=-1) * 1.4426950408889634
+
+
+def saved_lse_rows(lse, heads, L, nseq):
+    """the statistics buffer [tiles][heads][64] lse | [tokens] rstd of LN1 -> (lse [sequences, heads, L] without the padding rows of
+    each tile (64 // L whole sequences per tile), rstd [tokens])"""
+    TS = 64 // L
+    ntiles = -(-nseq // TS)
+    got = lse[:ntiles * heads * 64].reshape(ntiles, heads, 64)[:, :, :TS * L].reshape(ntiles, heads, TS, L).permute(0, 2, 1, 3)
+    return got.reshape(ntiles * TS, heads, L)[:nseq], lse[ntiles * heads * 64:]
+
+
 def relerr(a, b):
     a = a.detach().double().cpu()
     b = b.detach().double().cpu()
