@@ -44,7 +44,7 @@ def get_finetune_config(path, general_path, seed, device, pixelwise=None):
     return Dotdict(hp)
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("dataset", nargs="?", default="enmap", choices=["enmap", "houston2018"])   # reference finetune.py:42-46
     ap.add_argument("--steps", type=int, default=50)
@@ -60,7 +60,31 @@ def main():
     ap.add_argument("--pixelwise", action="store_true",
                     help="the centre-pixel classifier (reference pixelwise=True): windows of image_size - 1 (odd), one class "
                          "per window; --val-scenes then predicts dense per-pixel maps (stride 1)")
-    args = ap.parse_args()
+    ap.add_argument("--linear-eval", action="store_true", default=None,
+                    help="linear evaluation (reference finetune.py:110-136; overrides the config's linear_eval): everything outside "
+                         "mlp_head is frozen, the optimizer sees the head only, the step runs no block or tokenizer backward")
+    ap.add_argument("--optimizer", default="torch", choices=["torch", "fused"],
+                    help="torch: torch.optim.Adam; fused: maskedsst_amd.optim.FusedAdam (the same update, one launch per step)")
+    return ap
+
+
+def make_optimizer(model, config, kind):
+    """reference finetune.py:110-136: Adam with coupled L2 decay; two learning rates (lr for the body, mlp_head_lr for the head), or
+    under linear_eval the head parameters alone, at lr as there"""
+    head = [p for n, p in model.named_parameters() if "mlp_head" in n]
+    body = [p for n, p in model.named_parameters() if "mlp_head" not in n]
+    if config.linear_eval:
+        groups = head
+    else:
+        groups = [{"params": body}, {"params": head, "lr": config.mlp_head_lr}]
+    if kind == "fused":
+        from maskedsst_amd.optim import FusedAdam
+        return FusedAdam(model, groups, lr=config.lr, weight_decay=config.weight_decay)
+    return torch.optim.Adam(groups, lr=config.lr, weight_decay=config.weight_decay)
+
+
+def main():
+    args = build_parser().parse_args()
     random.seed(SEED); np.random.seed(SEED); torch.manual_seed(SEED)
     if not torch.cuda.is_available():
         raise SystemExit("finetune.py needs an MI355X: maskedsst_amd has no CPU fallback")
@@ -69,6 +93,8 @@ def main():
                                  pixelwise=True if args.pixelwise else None)
     if args.batch_size:
         config.batch_size = args.batch_size
+    if args.linear_eval is not None:
+        config.linear_eval = args.linear_eval
     if args.checkpoint:
         config.checkpoint_path = args.checkpoint
         if config.pixelwise and config.patch_sub and not config.spectral_pos_embed and config.pos_embed_len is None:
@@ -90,10 +116,7 @@ def main():
     if config.linear_eval:
         for n, p in model.named_parameters():
             p.requires_grad_("mlp_head" in n)
-    head = [p for n, p in model.named_parameters() if "mlp_head" in n]
-    body = [p for n, p in model.named_parameters() if "mlp_head" not in n]
-    optimizer = torch.optim.Adam([{"params": body}, {"params": head, "lr": config.mlp_head_lr}], lr=config.lr,
-                                 weight_decay=config.weight_decay)   # finetune.py:110-134 (two learning rates)
+    optimizer = make_optimizer(model, config, args.optimizer)
     criterion = torch.nn.CrossEntropyLoss(ignore_index=config.ignored_label)
     gen = torch.Generator().manual_seed(SEED)
     val = None

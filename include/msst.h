@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MSST_VERSION 108
+#define MSST_VERSION 109
 #define MSST_DIM 96
 #define MSST_DIM_HEAD 64
 #define MSST_MLP 64
@@ -307,7 +307,10 @@ int msst_tokenize_bwd(const float* img, const float* pre_g, const float* pre_b, 
  * their arguments before any launch: MSST_ERR_BADARG for B, S, N or n_classes < 1 or a null pointer, MSST_ERR_UNSUPPORTED beyond
  * the limits.
  * _bwd: dy [B][T][96] fully written; dln_g / dln_b [96], dw [n_classes][96], db [n_classes] fully written (not accumulated),
- * bitwise reproducible; slab B*(n_classes*97 + 192) floats. */
+ * bitwise reproducible; slab B*(n_classes*97 + 192) floats.
+ * dy may be NULL (MSST_VERSION 109; a frozen body: nobody consumes dy): a variant of the kernel compiled without the LayerNorm
+ * backward and without the dy stores runs; the four head gradients are bit-identical to those of the call with a dy buffer (same
+ * partition, same summation order). */
 int msst_cls_head_fwd(const float* y, const float* ln_g, const float* ln_b, const float* w, const float* b,
                       float* logits, int B, int S, int N, int n_classes, void* stream);
 int msst_cls_head_bwd(const float* y, const float* dlogits, const float* ln_g, const float* ln_b, const float* w,
@@ -322,7 +325,10 @@ int msst_cls_head_bwd(const float* y, const float* dlogits, const float* ln_g, c
  * _bwd: dy [B][S*N][96] fully written (each token receives its own slice of d(row), no 1/S factor); dln_g / dln_b [F],
  * dw [n_classes][F], db [n_classes] are fully written (not accumulated), summed without atomics over a static row partition that
  * depends on B * N only: bitwise reproducible, independent of the device.  slab: msst_spec_head_bwd_slab(B, S, N, n_classes)
- * floats of scratch (16-byte aligned). */
+ * floats of scratch (16-byte aligned).  _bwd with a null pointer other than dy: MSST_ERR_BADARG, checked before anything is enqueued.
+ * dy may be NULL (MSST_VERSION 109): the row pass is then a variant compiled without dxn = W^T dl, the LayerNorm backward and the dy
+ * stores (it only leaves the row statistics for the weight-gradient pass); the four head gradients are bit-identical to those of
+ * the call with a dy buffer. */
 int msst_spec_head_fwd(const float* y, const float* ln_g, const float* ln_b, const float* w, const float* b,
                        float* logits, int B, int S, int N, int n_classes, void* stream);
 long msst_spec_head_bwd_slab(int B, int S, int N, int n_classes);
@@ -339,7 +345,9 @@ int msst_spec_head_bwd(const float* y, const float* dlogits, const float* ln_g, 
  * _bwd (given dlogits [B][n_classes]): dy [B][S*N][96] fully written (every token of a position receives d(mean) / S); dln_g,
  * dln_b [96], dw [n_classes][96 N], db [n_classes] fully written (not accumulated), summed without atomics over a static partition
  * of the samples into groups of 32 (depends on B only): bitwise reproducible, independent of the device.  slab:
- * msst_pix_head_bwd_slab(B, S, N, n_classes) floats of scratch (16-byte aligned); 0 for a refused shape. */
+ * msst_pix_head_bwd_slab(B, S, N, n_classes) floats of scratch (16-byte aligned); 0 for a refused shape.
+ * dy may be NULL (MSST_VERSION 109): a variant of the kernel compiled without the LayerNorm backward and the dy stores runs; the
+ * four head gradients are bit-identical to those of the call with a dy buffer. */
 long msst_pix_head_fwd_ws(int B, int N);
 int msst_pix_head_fwd(const float* y, const float* ln_g, const float* ln_b, const float* w, const float* b, float* logits,
                       float* ws, int B, int S, int N, int n_classes, void* stream);
@@ -373,6 +381,32 @@ int msst_layernorm_bwd(const float* x, const float* gamma, const float* dy, floa
  * reference's value clamp of the gradient (pretrain.py:71-73) when clamp > 0. */
 int msst_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                float eps, float weight_decay, int step, float clamp, float gscale, void* stream);
+
+/* Grouped Adam / AdamW (MSST_VERSION 109): ONE launch updates any number of disjoint element ranges of the flat buffers, each with
+ * its own learning rate, weight decay and bias-correction step -- the finetune recipe of the reference (finetune.py:110-136:
+ * torch.optim.Adam with coupled L2 decay, lr / mlp_head_lr, frozen parameters skipped).  Per element of a range, flags == 0:
+ *     g' = g * gscale + wd * p;  m += (1 - b1) (g' - m);  v = b2 v + (1 - b2) g'^2;
+ *     p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+ * = torch.optim.Adam(weight_decay=wd), no amsgrad.  MSST_ADAM_DECOUPLED: g' = g * gscale and p *= 1 - lr * wd before the update
+ * (torch.optim.AdamW).  1 - b1, 1 - b2, the bias corrections and 1 - lr * wd are formed on the host in double, as torch does,
+ * and reach the kernel as floats; that is why the betas are doubles here: the float nearest to 0.999 has a 1 - b2 that is off by
+ * 1.3e-5 of itself, which v would inherit in the first steps.
+ * groups: HOST array of ngroups entries sorted by start, disjoint, end >= start, step >= 1; group_bytes = sizeof(MsstAdamGroup) (a
+ * table of another header revision is refused).  The table travels by value in the kernel arguments: no allocation, no copy, no
+ * synchronisation.  ngroups <= MSST_ADAM_MAX_GROUPS.  Every violation returns MSST_ERR_BADARG before anything is enqueued; an
+ * empty table or only empty ranges: 0, nothing launched.  Elements outside every range are neither read nor written in any of
+ * the four buffers.  Range ends are arbitrary: the 16-byte aligned interior of a range moves as dwordx4, its ragged ends
+ * (at most 3 + 3 elements) as single floats; buffers that are not 16-byte aligned themselves are walked float by float. */
+#define MSST_ADAM_DECOUPLED 1
+#define MSST_ADAM_MAX_GROUPS 64
+typedef struct {
+    long start, end;       /* element range [start, end) of p / g / m / v */
+    float lr, weight_decay;
+    int step;              /* bias-correction step of this range, >= 1 */
+    int flags;             /* MSST_ADAM_DECOUPLED: AdamW decay; 0: coupled L2 (Adam) */
+} MsstAdamGroup;
+int msst_adam_groups(float* p, const float* g, float* m, float* v, const MsstAdamGroup* groups /*host*/, int ngroups,
+                     int group_bytes, double beta1, double beta2, float eps, float gscale, void* stream);
 
 /* Opt-in per-kernel timing: when enabled every kernel launch of the library is bracketed by a pair
  * of HIP events recorded on the launch stream.  msst_profile_collect synchronises on the recorded

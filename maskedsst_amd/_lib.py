@@ -41,7 +41,13 @@ class MsstBlockGrads(Structure):
         "ln1_g", "ln1_b", "wqkv", "wout", "bo", "ln2_g", "ln2_b", "w1", "b1", "w2", "b2")]
 
 
+class MsstAdamGroup(Structure):
+    _fields_ = [("start", c_long), ("end", c_long), ("lr", c_float), ("weight_decay", c_float), ("step", c_int), ("flags", c_int)]
+
+
 _P = c_void_p
+ADAM_DECOUPLED = 1            # include/msst.h: MSST_ADAM_DECOUPLED
+ADAM_MAX_GROUPS = 64          # include/msst.h: MSST_ADAM_MAX_GROUPS
 BWD_DEFER_REDUCE = 512 << 8   # include/msst.h: MSST_BWD_DEFER_REDUCE
 X1_BF16 = 1024 << 8           # include/msst.h: MSST_X1_BF16
 SAVED_XN, SAVED_LSE, SAVED_RSTD = 1, 2, 4    # include/msst.h: MSST_SAVED_*
@@ -100,6 +106,8 @@ _SIGS = {
     "msst_layernorm_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_long, c_int, c_float, _P]),
     "msst_adamw": (c_int, [_P, _P, _P, _P, c_long, c_float, c_float, c_float, c_float, c_float, c_int,
                            c_float, c_float, _P]),
+    "msst_adam_groups": (c_int, [_P, _P, _P, _P, POINTER(MsstAdamGroup), c_int, c_int, ctypes.c_double, ctypes.c_double,
+                                 c_float, c_float, _P]),
 }
 
 _lib = None

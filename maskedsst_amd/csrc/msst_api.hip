@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <math.h>
 #include <atomic>
 #include <mutex>
 #include <vector>
@@ -245,7 +246,7 @@ int msst_profile_kernels(void) { return K_COUNT; }
 const char* msst_profile_name(int id) {
     static const char* names[K_COUNT] = {"prep_weights", "tokenize_fwd", "block_fwd", "head_fwd", "loss_reduce",
                                          "head_bwd", "reduce_slabs", "block_bwd_mlp", "block_bwd_attn",
-                                         "attn_slab_reduce", "block_bwd_ln1", "tokenize_bwd", "pos_split", "adamw", "block_bwd_ln1mlp", "layernorm"};
+                                         "attn_slab_reduce", "block_bwd_ln1", "tokenize_bwd", "pos_split", "adamw", "block_bwd_ln1mlp", "layernorm", "adam_groups"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 
@@ -789,7 +790,7 @@ int msst_cls_head_bwd(const float* y, const float* dlogits, const float* ln_g, c
                       int N, int n_classes, void* stream) {
     int rc = cls_head_shape(B, S, N, n_classes);
     if (rc) return fail(rc, "msst_cls_head_bwd");
-    if (!y || !dlogits || !ln_g || !ln_b || !w || !dy || !slab || !dln_g || !dln_b || !dw || !db)
+    if (!y || !dlogits || !ln_g || !ln_b || !w || !slab || !dln_g || !dln_b || !dw || !db)   // dy may be null: no dy wanted
         return fail(MSST_ERR_BADARG, "msst_cls_head_bwd");
     hipStream_t st = (hipStream_t)stream;
     ClsBwdArgs a;
@@ -822,6 +823,9 @@ long msst_spec_head_bwd_slab(int B, int S, int N, int n_classes) {
 int msst_spec_head_bwd(const float* y, const float* dlogits, const float* ln_g, const float* ln_b, const float* w,
                        float* dy, float* slab, float* dln_g, float* dln_b, float* dw, float* db, int B, int S,
                        int N, int n_classes, void* stream) {
+    if (B < 1 || S < 1 || S > 64 || N < 1 || N > 64 || n_classes < 1 || n_classes > 32) return fail(MSST_ERR_UNSUPPORTED, "msst_spec_head_bwd");
+    if (!y || !dlogits || !ln_g || !ln_b || !w || !slab || !dln_g || !dln_b || !dw || !db)   // dy may be null: no dy wanted
+        return fail(MSST_ERR_BADARG, "msst_spec_head_bwd");
     hipStream_t st = (hipStream_t)stream;
     SpecHeadArgs a = {};
     a.y = y; a.dlogits = dlogits; a.ln_g = ln_g; a.ln_b = ln_b; a.w = w; a.dy = dy;
@@ -873,7 +877,7 @@ int msst_pix_head_bwd(const float* y, const float* dlogits, const float* ln_g, c
                       void* stream) {
     int rc = pix_head_shape(B, S, N, n_classes);
     if (rc) return fail(rc, "msst_pix_head_bwd");
-    if (!y || !dlogits || !ln_g || !ln_b || !w || !dy || !slab || !dln_g || !dln_b || !dw || !db)
+    if (!y || !dlogits || !ln_g || !ln_b || !w || !slab || !dln_g || !dln_b || !dw || !db)   // dy may be null: no dy wanted
         return fail(MSST_ERR_BADARG, "msst_pix_head_bwd");
     hipStream_t st = (hipStream_t)stream;
     PixHeadArgs a = {};
@@ -942,6 +946,52 @@ int msst_adamw(float* p, const float* g, float* m, float* v, long n, float lr, f
                float eps, float weight_decay, int step, float clamp, float gscale, void* stream) {
     return fail(launch_adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, clamp, gscale,
                              (hipStream_t)stream), "msst_adamw");
+}
+
+int msst_adam_groups(float* p, const float* g, float* m, float* v, const MsstAdamGroup* groups, int ngroups, int group_bytes,
+                     double beta1, double beta2, float eps, float gscale, void* stream) {
+    if (group_bytes != (int)sizeof(MsstAdamGroup)) return fail(MSST_ERR_BADARG, "msst_adam_groups (MsstAdamGroup of another header revision)");
+    if (ngroups < 0 || ngroups > MSST_ADAM_MAX_GROUPS) return fail(MSST_ERR_BADARG, "msst_adam_groups (more than MSST_ADAM_MAX_GROUPS ranges)");
+    if (ngroups == 0) return 0;
+    if (!groups) return fail(MSST_ERR_BADARG, "msst_adam_groups (null table)");
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0)) return fail(MSST_ERR_BADARG, "msst_adam_groups (beta outside [0, 1))");
+    // the whole table is validated before anything is enqueued
+    long prev_end = 0;
+    for (int i = 0; i < ngroups; ++i) {
+        const MsstAdamGroup& q = groups[i];
+        if (q.start < 0 || q.end < q.start) return fail(MSST_ERR_BADARG, "msst_adam_groups (range with end < start)");
+        if (q.start < prev_end) return fail(MSST_ERR_BADARG, "msst_adam_groups (ranges overlap or are not sorted by start)");
+        if (q.step < 1) return fail(MSST_ERR_BADARG, "msst_adam_groups (step < 1)");
+        if (q.flags & ~MSST_ADAM_DECOUPLED) return fail(MSST_ERR_BADARG, "msst_adam_groups (unknown flag)");
+        prev_end = q.end;
+    }
+    const bool aligned = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+    AdamTable t;
+    t.nseg = 0; t.nblocks = 0;
+    t.b2 = (float)beta2; t.omb1 = (float)(1.0 - beta1); t.omb2 = (float)(1.0 - beta2); t.eps = eps; t.gscale = gscale;
+    constexpr long QPB = ADAM_QPB;
+    for (int i = 0; i < ngroups; ++i) {
+        const MsstAdamGroup& q = groups[i];
+        if (q.end == q.start) continue;
+        AdamSeg& s = t.s[t.nseg++];
+        s.start = q.start; s.end = q.end;
+        s.a0 = (q.start + 3) & ~3L;
+        s.a1 = q.end & ~3L;
+        if (!aligned || s.a1 <= s.a0) s.a0 = s.a1 = q.end;   // no aligned interior: the range moves float by float
+        const bool dec = (q.flags & MSST_ADAM_DECOUPLED) != 0;
+        s.step_size = (float)((double)q.lr / (1.0 - pow(beta1, (double)q.step)));
+        s.bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)q.step));
+        s.wd = dec ? 0.f : q.weight_decay;
+        s.decay = dec ? (float)(1.0 - (double)q.lr * (double)q.weight_decay) : 1.f;
+        s.blk0 = t.nblocks; s.pad = 0;
+        const long nb = ((s.a1 - s.a0) / 4 + QPB - 1) / QPB;
+        const long total = (long)t.nblocks + (nb < 1 ? 1 : nb);
+        if (total > 0x7fffffffL) return fail(MSST_ERR_UNSUPPORTED, "msst_adam_groups (grid)");
+        t.nblocks = (int)total;
+    }
+    if (!t.nseg) return 0;
+    if (!p || !g || !m || !v) return fail(MSST_ERR_BADARG, "msst_adam_groups (null buffer)");
+    return fail(launch_adam_groups(p, g, m, v, t, (hipStream_t)stream), "msst_adam_groups");
 }
 
 }  // extern "C"

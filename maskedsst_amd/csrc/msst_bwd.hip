@@ -1888,7 +1888,10 @@ namespace msst {
 // slab per sample: [dW NC*96 | db NC | dgamma 96 | dbeta 96]; dy [B][T][96] fully written
 // (every spectral block of a position receives d(mean) / S).  Any NC: dlogits is staged in LDS 32 classes at a time for the
 // dW / db partials (each still a sum over the positions nn = 0, 1, ... in order, whatever NC is).
+// WANT_DY = false (a.dy null: a frozen body, nobody consumes dy): the LayerNorm backward and the dy stores are compiled out; every
+// operation that feeds the four head gradients is the same, in the same order, so they come out bit-identical.
 // ==========================================================================================
+template <bool WANT_DY>
 __global__ __launch_bounds__(256) void cls_head_bwd_kernel(ClsBwdArgs a) {
     __shared__ float xn_s[64][97];
     __shared__ float dl_s[64][33];
@@ -1933,22 +1936,26 @@ __global__ __launch_bounds__(256) void cls_head_bwd_kernel(ClsBwdArgs a) {
             xn_s[n][d] = m[i] * a.ln_g[d] + a.ln_b[d];
             dg[i] = dxn[i] * m[i];
             db[i] = dxn[i];
-            dxn[i] *= a.ln_g[d];
-            g1 += dxn[i];
-            g2 += dxn[i] * m[i];
+            if constexpr (WANT_DY) {
+                dxn[i] *= a.ln_g[d];
+                g1 += dxn[i];
+                g2 += dxn[i] * m[i];
+            }
         }
-        g1 += __shfl_xor(g1, 1); g1 += __shfl_xor(g1, 2);
-        g2 += __shfl_xor(g2, 1); g2 += __shfl_xor(g2, 2);
-        g1 *= (1.f / 96.f); g2 *= (1.f / 96.f);
-        f32x4 o[6];
+        if constexpr (WANT_DY) {
+            g1 += __shfl_xor(g1, 1); g1 += __shfl_xor(g1, 2);
+            g2 += __shfl_xor(g2, 1); g2 += __shfl_xor(g2, 2);
+            g1 *= (1.f / 96.f); g2 *= (1.f / 96.f);
+            f32x4 o[6];
 #pragma unroll
-        for (int i = 0; i < 6; ++i)
+            for (int i = 0; i < 6; ++i)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[i][e] = rstd * (dxn[4*i+e] - g1 - m[4*i+e] * g2) * invS;
-        for (int c = 0; c < a.S; ++c) {
-            f32x4* dst = reinterpret_cast<f32x4*>(a.dy + ((long)b * a.T + c * a.N + n) * 96 + part * 24);
+                for (int e = 0; e < 4; ++e) o[i][e] = rstd * (dxn[4*i+e] - g1 - m[4*i+e] * g2) * invS;
+            for (int c = 0; c < a.S; ++c) {
+                f32x4* dst = reinterpret_cast<f32x4*>(a.dy + ((long)b * a.T + c * a.N + n) * 96 + part * 24);
 #pragma unroll
-            for (int i = 0; i < 6; ++i) dst[i] = o[i];
+                for (int i = 0; i < 6; ++i) dst[i] = o[i];
+            }
         }
     }
     float* slab = a.slab + (long)b * (NC * 96 + NC + 192);
@@ -1985,7 +1992,8 @@ __global__ __launch_bounds__(256) void cls_head_bwd_kernel(ClsBwdArgs a) {
 
 int launch_cls_head_bwd(const ClsBwdArgs& a, hipStream_t st) {
     if (a.N > 64) return MSST_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(cls_head_bwd_kernel, dim3(a.B), dim3(256), 0, st, a);
+    if (a.dy) hipLaunchKernelGGL(cls_head_bwd_kernel<true>, dim3(a.B), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(cls_head_bwd_kernel<false>, dim3(a.B), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 

@@ -11,7 +11,11 @@
 //
 // Backward, three launches plus the shared fixed-order reduction:
 //   spec_head_bwd_rows:  per row, dxn = W^T dl, LayerNorm backward dx = rstd (g - mean(g) - xhat mean(g xhat)), g = gamma dxn,
-//                        scattered back to the S tokens (dy fully written, no 1/S factor); the row's (mean, rstd) are kept.
+//                        scattered back to the S tokens (dy fully written, no 1/S factor); the row's (mean, rstd) are kept
+//                        (store_row_stats: arithmetic pinned with explicit fmaf, the same bits from either variant).
+//                        With a null dy (a frozen body: nobody consumes it) the variant compiled without all of that runs: it
+//                        reads the rows and keeps their (mean, rstd), the only thing the weight-gradient pass takes from here, so
+//                        the four head gradients are bit-identical.
 //   spec_head_wgrad:     A[k][j] = sum_rows dl[k] xhat[j] and sum_rows dl[k], per (token c, row chunk g) workgroup into slab g.
 //                        The row chunks are a static partition of the B N rows (spec_head_chunks: depends on B N only), so
 //                        every partial sums the same rows in the same order on every device.
@@ -79,6 +83,35 @@ __device__ __forceinline__ void load_rows(const SpecHeadArgs& a, int row0, int l
     }
 }
 
+// (mean, rstd) of the RPW rows in v -> stats, as the weight-gradient pass reads them.  Written with explicit fmaf and nothing else
+// that could contract: which products the compiler fuses otherwise depends on what else the calling kernel computes, and the
+// with-dy and the no-dy variant of the row backward must leave the same bits here (their head gradients are compared bit for bit).
+template <int NQ, int RPW>
+__device__ __forceinline__ void store_row_stats(const SpecHeadArgs& a, int row0, int lane, const f32x4 (&v)[RPW][NQ]) {
+    const int F4 = a.S * 24;
+    const float invF = 1.f / (float)(a.S * 96);
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) s += sum4(v[r][i]);
+        const float ws = wave_sum64(s);
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+            if (lane + 64 * i < F4) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float d = __builtin_fmaf(-ws, invF, v[r][i][e]);
+                    q = __builtin_fmaf(d, d, q);
+                }
+            }
+        }
+        const float rstd = rsqrtf(__builtin_fmaf(wave_sum64(q), invF, 1e-5f));
+        if (lane == 0 && row0 + r < a.R) { a.stats[2 * (row0 + r)] = ws * invF; a.stats[2 * (row0 + r) + 1] = rstd; }
+    }
+}
+
 }  // namespace
 
 // grid (ceil(R / (4 RPW))), 256 threads
@@ -137,7 +170,7 @@ __global__ __launch_bounds__(256) void spec_head_fwd_kernel(SpecHeadArgs a) {
 }
 
 // grid (ceil(R / (4 RPW))), 256 threads
-template <int NQ, int RPW>
+template <int NQ, int RPW, bool WANT_DY>
 __global__ __launch_bounds__(256) void spec_head_bwd_rows_kernel(SpecHeadArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row0 = (blockIdx.x * 4 + wave) * RPW;
@@ -147,6 +180,8 @@ __global__ __launch_bounds__(256) void spec_head_bwd_rows_kernel(SpecHeadArgs a)
     f32x4 v[RPW][NQ], d[RPW][NQ];
     float mean[RPW], rstd[RPW];
     load_rows<NQ, RPW>(a, row0, lane, v, mean, rstd);
+    store_row_stats<NQ, RPW>(a, row0, lane, v);
+    if constexpr (!WANT_DY) return;
     int bb[RPW], nn[RPW];
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
@@ -210,7 +245,6 @@ __global__ __launch_bounds__(256) void spec_head_bwd_rows_kernel(SpecHeadArgs a)
             const int q = lane + 64 * i;
             if (q < F4) *reinterpret_cast<f32x4*>(base + piece_off(q, a.N)) = rstd[r] * (d[r][i] - m1 - v[r][i] * m2);
         }
-        if (lane == 0) { a.stats[2 * row] = mean[r]; a.stats[2 * row + 1] = rstd[r]; }
     }
 }
 
@@ -329,7 +363,9 @@ template <int NQ>
 struct BwdLaunch {
     static constexpr int RPW = NQ <= 4 ? 4 : NQ <= 8 ? 2 : 1;
     static int go(const SpecHeadArgs& a, hipStream_t st) {
-        hipLaunchKernelGGL((spec_head_bwd_rows_kernel<NQ, RPW>), dim3((a.R + 4 * RPW - 1) / (4 * RPW)), dim3(256), 0, st, a);
+        const dim3 grid((a.R + 4 * RPW - 1) / (4 * RPW));
+        if (a.dy) hipLaunchKernelGGL((spec_head_bwd_rows_kernel<NQ, RPW, true>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((spec_head_bwd_rows_kernel<NQ, RPW, false>), grid, dim3(256), 0, st, a);
         return (int)hipGetLastError();
     }
 };

@@ -8,6 +8,7 @@
 #define MSST_PREC_BF16 1
 #define MSST_ERR_UNSUPPORTED (-2)
 #define MSST_ERR_BADARG (-3)
+#define MSST_ADAM_MAX_GROUPS 64
 
 namespace msst {
 
@@ -190,7 +191,7 @@ struct TokBwdArgs {
 // ---- opt-in per-kernel timing with HIP events on the launch stream (bench.py roofline leg) ----
 enum KernelId {
     K_PREP = 0, K_TOK_FWD, K_BLOCK_FWD, K_HEAD_FWD, K_LOSS_REDUCE, K_HEAD_BWD, K_REDUCE, K_BWD_MLP, K_BWD_ATTN,
-    K_ATTN_REDUCE, K_BWD_LN1, K_TOK_BWD, K_POS_SPLIT, K_ADAMW, K_BWD_LN1MLP, K_LAYERNORM, K_COUNT
+    K_ATTN_REDUCE, K_BWD_LN1, K_TOK_BWD, K_POS_SPLIT, K_ADAMW, K_BWD_LN1MLP, K_LAYERNORM, K_ADAM_GROUPS, K_COUNT
 };
 void prof_begin(int id, hipStream_t st);
 void prof_end(hipStream_t st);
@@ -287,6 +288,21 @@ int launch_tokenize_bwd(const TokBwdArgs& a, int nchunk, hipStream_t st);
 int launch_pos_split(const float* dpos, int S, int N, int split, float* dpe, float* dce, hipStream_t st);
 int launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                  float wd, int step, float clamp, float gscale, hipStream_t st);
+// grouped Adam (msst_opt.hip): the range table as the kernel receives it -- by value, constants already formed on the host
+struct AdamSeg {
+    long start, end;     // element range
+    long a0, a1;         // its 16-byte aligned interior [a0, a1) (a0 == a1 == end: none; the whole range then moves float by float)
+    float step_size, bc2_sqrt, wd, decay;   // lr / (1 - b1^t), sqrt(1 - b2^t), coupled L2 factor (0 when decoupled), 1 - lr wd (1 when coupled)
+    int blk0, pad;       // first workgroup of the range
+};
+struct AdamTable {
+    AdamSeg s[MSST_ADAM_MAX_GROUPS];
+    float b2, omb1, omb2, eps, gscale;
+    int nseg, nblocks;
+};
+constexpr int ADAM_QPB = 1024;   // float4 pieces of a range's aligned interior per workgroup (256 threads x 4)
+static_assert(sizeof(AdamTable) <= 4096, "AdamTable travels as a kernel argument");
+int launch_adam_groups(float* p, const float* g, float* m, float* v, const AdamTable& t, hipStream_t st);
 int launch_cu_thief(int nblocks, int us, unsigned* sink, hipStream_t st);   // msst_opt.hip (occupancy probe)
 int launch_box_probe(double* out4, void* scratch, long bytes, hipStream_t st);   // msst_opt.hip (MFMA rate / shader clock / HBM read rate of this box)
 int launch_block_fwd_rs(const BlockArgs& a, int grid, hipStream_t st);   // msst_fwd3.hip (bf16, 8 heads; role split: the default)

@@ -63,6 +63,73 @@ int launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr,
     return (int)hipGetLastError();
 }
 
+// ---- grouped Adam / AdamW (msst_adam_groups) ----
+// One launch over a table of disjoint element ranges, each with its own learning rate, decay and bias correction: the finetune
+// recipe (torch.optim.Adam, coupled L2 decay, lr / mlp_head_lr, frozen parameters skipped).  The arithmetic follows torch's
+// single-tensor Adam operation by operation (grad.add(p, alpha=wd); exp_avg.lerp_; exp_avg_sq.mul_().addcmul_(); addcdiv_) with the
+// host-side constants formed in double and rounded once.  A workgroup owns ADAM_QPB float4 pieces of ONE range's 16-byte aligned
+// interior; the first workgroup of a range also walks its ragged ends (at most 3 + 3 floats).  Nothing outside the ranges is touched.
+constexpr int ADAM_U = ADAM_QPB / 256;       // float4 pieces per thread: 16 x 16 bytes in flight per lane over the four buffers
+
+__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamSeg& s, const AdamTable& t) {
+    float gr = g * t.gscale + s.wd * p;      // coupled L2 (wd = 0 when decoupled)
+    float pv = p * s.decay;                  // decoupled decay (decay = 1 when coupled)
+    const float mn = m + t.omb1 * (gr - m);
+    const float vn = v * t.b2 + (t.omb2 * gr) * gr;
+    const float denom = sqrtf(vn) / s.bc2_sqrt + t.eps;
+    pv -= s.step_size * (mn / denom);
+    p = pv; m = mn; v = vn;
+}
+
+__global__ __launch_bounds__(256) void adam_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v, AdamTable t) {
+    int si = 0;
+    while (si + 1 < t.nseg && (int)blockIdx.x >= t.s[si + 1].blk0) ++si;   // (block uniform)
+    const AdamSeg s = t.s[si];
+    const int lb = (int)blockIdx.x - s.blk0;
+    const long q0 = (s.a0 >> 2) + (long)lb * ADAM_QPB + threadIdx.x, qend = s.a1 >> 2;
+    f32x4* p4 = reinterpret_cast<f32x4*>(p);
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+    f32x4* m4 = reinterpret_cast<f32x4*>(m);
+    f32x4* v4 = reinterpret_cast<f32x4*>(v);
+    f32x4 pp[ADAM_U], gg[ADAM_U], mm[ADAM_U], vv[ADAM_U];
+#pragma unroll
+    for (int u = 0; u < ADAM_U; ++u) {
+        const long q = q0 + u * 256;
+        if (q < qend) { pp[u] = p4[q]; gg[u] = g4[q]; mm[u] = m4[q]; vv[u] = v4[q]; }
+    }
+#pragma unroll
+    for (int u = 0; u < ADAM_U; ++u) {
+        const long q = q0 + u * 256;
+        if (q < qend) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float pv = pp[u][e], mv = mm[u][e], vl = vv[u][e];
+                adam_one(pv, gg[u][e], mv, vl, s, t);
+                pp[u][e] = pv; mm[u][e] = mv; vv[u][e] = vl;
+            }
+            p4[q] = pp[u]; m4[q] = mm[u]; v4[q] = vv[u];
+        }
+    }
+    if (lb == 0) {
+        // ragged ends: [start, a0) and [a1, end) -- or the whole range when the buffers themselves are not 16-byte aligned
+        const long nhead = s.a0 - s.start, ntail = s.end - s.a1;
+        for (long k = threadIdx.x; k < nhead + ntail; k += 256) {
+            const long i = k < nhead ? s.start + k : s.a1 + (k - nhead);
+            float pv = p[i], mv = m[i], vl = v[i];
+            adam_one(pv, g[i], mv, vl, s, t);
+            p[i] = pv; m[i] = mv; v[i] = vl;
+        }
+    }
+}
+
+int launch_adam_groups(float* p, const float* g, float* m, float* v, const AdamTable& t, hipStream_t st) {
+    if (t.nseg < 1 || t.nblocks < 1) return 0;
+    ProfScope ps(K_ADAM_GROUPS, st);
+    hipLaunchKernelGGL(adam_groups_kernel, dim3((unsigned)t.nblocks), dim3(256), 0, st, p, g, m, v, t);
+    return (int)hipGetLastError();
+}
+
 // CU-occupancy probe for the data-parallel overlap: `nblocks` workgroups that do nothing but hold a CU each
 // -- they declare all 160 KB of its LDS, so no workgroup that uses LDS (every MFMA kernel here) fits beside one, like a CU
 // lost to a communication kernel's channel workgroup -- until `us` microseconds of the constant-rate device clock have passed.

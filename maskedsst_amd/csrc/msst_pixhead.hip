@@ -14,7 +14,9 @@
 //                     It stages W[:, n 96 .. n 96 + 95] and dl of its samples in LDS, recomputes the row statistics, forms
 //                     dxn = W^T dl for its slice, the LayerNorm backward, and writes dy[b, c, n, :] = dx / S for every c (fully
 //                     written).  Then it writes the partials of its 32 samples: dW[:, n slice] and db (n == 0) into slab g,
-//                     dgamma / dbeta into partial row (g, n).
+//                     dgamma / dbeta into partial row (g, n).  With a null dy (a frozen body: nobody consumes it) the variant compiled
+//                     without the LayerNorm backward and the dy stores runs; everything that feeds the four head gradients is
+//                     the same arithmetic in the same order (bit-identical results).
 //   launch_reduce_segs: the G slabs -> dW, db, and the G N partial rows -> dgamma, dbeta (fixed slab order).
 // No float atomics: the gradients are bitwise reproducible run to run and independent of the CU count.
 //
@@ -144,7 +146,7 @@ __global__ __launch_bounds__(256) void pix_head_logits_kernel(PixHeadArgs a) {
 
 // grid (N, G), 256 threads = 32 rows (samples) x 8 lanes.  Slab layout (floats): [G][NC][96 N] dW partials | [G][32] db partials |
 // [G N][96] dgamma partials | [G N][96] dbeta partials
-template <int NCB>
+template <int NCB, bool WANT_DY>
 __global__ __launch_bounds__(256) void pix_head_bwd_kernel(PixHeadArgs a) {
     __shared__ float w_s[NCB][96];
     __shared__ float dl_s[PIX_GROUP][NCB + 1];
@@ -183,24 +185,28 @@ __global__ __launch_bounds__(256) void pix_head_bwd_kernel(PixHeadArgs a) {
             xn_s[r][d] = m[i] * gam + a.ln_b[d];
             pg_s[r][d] = dxn[i] * m[i];
             pb_s[r][d] = dxn[i];
-            dxn[i] *= gam;
-            g1 += dxn[i];
-            g2 += dxn[i] * m[i];
+            if constexpr (WANT_DY) {
+                dxn[i] *= gam;
+                g1 += dxn[i];
+                g2 += dxn[i] * m[i];
+            }
         }
-        g1 = sum8(g1) * (1.f / 96.f);
-        g2 = sum8(g2) * (1.f / 96.f);
-        const float invS = 1.f / a.S;
-        f32x4 o[3];
+        if constexpr (WANT_DY) {
+            g1 = sum8(g1) * (1.f / 96.f);
+            g2 = sum8(g2) * (1.f / 96.f);
+            const float invS = 1.f / a.S;
+            f32x4 o[3];
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
+            for (int i = 0; i < 3; ++i)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[i][e] = rstd * (dxn[4 * i + e] - g1 - m[4 * i + e] * g2) * invS;
-        float* base = a.dy + ((long)b * a.T + n) * 96 + part * 12;
-        const long cstride = (long)a.N * 96;
-        for (int c = 0; c < a.S; ++c) {
-            f32x4* dst = reinterpret_cast<f32x4*>(base + c * cstride);
+                for (int e = 0; e < 4; ++e) o[i][e] = rstd * (dxn[4 * i + e] - g1 - m[4 * i + e] * g2) * invS;
+            float* base = a.dy + ((long)b * a.T + n) * 96 + part * 12;
+            const long cstride = (long)a.N * 96;
+            for (int c = 0; c < a.S; ++c) {
+                f32x4* dst = reinterpret_cast<f32x4*>(base + c * cstride);
 #pragma unroll
-            for (int i = 0; i < 3; ++i) dst[i] = o[i];
+                for (int i = 0; i < 3; ++i) dst[i] = o[i];
+            }
         }
     } else {
 #pragma unroll
@@ -288,11 +294,17 @@ int launch_pix_head_fwd(const PixHeadArgs& a, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-int launch_pix_head_bwd(const PixHeadArgs& a, hipStream_t st) {
+template <bool WANT_DY>
+static void pix_head_bwd_go(const PixHeadArgs& a, hipStream_t st) {
     const dim3 grid(a.N, a.G);
-    if (a.NC <= 8) hipLaunchKernelGGL(pix_head_bwd_kernel<8>, grid, dim3(256), 0, st, a);
-    else if (a.NC <= 16) hipLaunchKernelGGL(pix_head_bwd_kernel<16>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(pix_head_bwd_kernel<32>, grid, dim3(256), 0, st, a);
+    if (a.NC <= 8) hipLaunchKernelGGL((pix_head_bwd_kernel<8, WANT_DY>), grid, dim3(256), 0, st, a);
+    else if (a.NC <= 16) hipLaunchKernelGGL((pix_head_bwd_kernel<16, WANT_DY>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((pix_head_bwd_kernel<32, WANT_DY>), grid, dim3(256), 0, st, a);
+}
+
+int launch_pix_head_bwd(const PixHeadArgs& a, hipStream_t st) {
+    if (a.dy) pix_head_bwd_go<true>(a, st);
+    else pix_head_bwd_go<false>(a, st);
     return (int)hipGetLastError();
 }
 

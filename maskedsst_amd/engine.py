@@ -376,6 +376,24 @@ class Engine:
             i0 = i1
         return acts, x1s
 
+    def blocks_fwd_pingpong(self, x0, drop=(0.0, 0)):
+        """the 2*depth fused blocks with nothing kept for a backward, on two token buffers in turn (x0 and one more; x0 is
+        overwritten): returns the last block's output.  One msst_block_fwd per block with the kernels, precision flags and dropout
+        arguments of blocks_fwd(save=False) -- the same bits -- but one residual stream of scratch instead of 2*depth."""
+        B = x0.shape[0]
+        S, N, H = self.S, self.N, self.enc.heads
+        flags = _kernel_flags()
+        prec = self.prec | flags | self._half_flag(flags)
+        x, y = x0, torch.empty_like(x0)
+        wrote = ctypes.c_int(0)
+        st = _stream()
+        for i, (sname, _) in enumerate(self._layers()):
+            mode = MODE_SPATIAL if sname == "spatial" else MODE_SPECTRAL
+            _lib.check(self.lib.msst_block_fwd(ctypes.byref(self._bw[i]), _p(x), _p(y), None, mode, B, S, N, H, prec, self.max_grid,
+                                               drop[0], drop[1], i, None, None, ctypes.byref(wrote), st), "msst_block_fwd")
+            x, y = y, x
+        return x
+
     def _tiles_per_workgroup(self, sname, B):
         """64-row tiles the busiest workgroup of a block forward walks (the library's own tiling: msst_block_lse_floats counts tiles x heads x 64)"""
         mode = MODE_SPATIAL if sname == "spatial" else MODE_SPECTRAL
@@ -844,10 +862,11 @@ class Engine:
             V(fp.ptr("mlp_head.1.bias")), _p(logits), B, self.S, self.N, nc, _stream()), "msst_cls_head_fwd")
         return logits
 
-    def cls_head_bwd(self, y, dlogits, dy=None):
+    def cls_head_bwd(self, y, dlogits, dy=None, want_dy=True):
+        """want_dy=False (a frozen body): the kernel variant without dy runs (null dy); the four head gradients are the same bits"""
         B = y.shape[0]
         nc = self.enc.num_classes
-        if dy is None:
+        if dy is None and want_dy:
             dy = torch.empty_like(y)
         slab = torch.empty(B * (nc * 97 + 192), dtype=torch.float32, device=y.device)
         fp, g = self.fp, self.fp.grad
@@ -876,11 +895,11 @@ class Engine:
             _p(y), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")), V(fp.ptr("mlp_head.1.weight")),
             V(fp.ptr("mlp_head.1.bias")), _p(logits), B, self.S, self.N, self.enc.num_classes, st), "msst_spec_head_fwd")
 
-    def spec_head_bwd(self, y, dlogits, dy=None):
-        """-> dy [B, T, 96]; the four head gradients are written (not accumulated) into the flat gradient buffer"""
+    def spec_head_bwd(self, y, dlogits, dy=None, want_dy=True):
+        """-> dy [B, T, 96] (None with want_dy=False); the four head gradients are written (not accumulated) into the flat gradient buffer"""
         B = y.shape[0]
         nc = self.enc.num_classes
-        if dy is None:
+        if dy is None and want_dy:
             dy = torch.empty_like(y)
         slab = torch.empty(int(self.lib.msst_spec_head_bwd_slab(B, self.S, self.N, nc)), dtype=torch.float32, device=y.device)
         fp, g = self.fp, self.fp.grad
@@ -909,11 +928,12 @@ class Engine:
             _p(y), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")), V(fp.ptr("mlp_head.2.weight")),
             V(fp.ptr("mlp_head.2.bias")), _p(logits), _p(ws), B, self.S, self.N, self.enc.num_classes, st), "msst_pix_head_fwd")
 
-    def pix_head_bwd(self, y, dlogits, dy=None):
-        """dlogits [B, nc] -> dy [B, T, 96]; the four head gradients are written (not accumulated) into the flat gradient buffer"""
+    def pix_head_bwd(self, y, dlogits, dy=None, want_dy=True):
+        """dlogits [B, nc] -> dy [B, T, 96] (None with want_dy=False); the four head gradients are written (not accumulated) into the
+        flat gradient buffer"""
         B = y.shape[0]
         nc = self.enc.num_classes
-        if dy is None:
+        if dy is None and want_dy:
             dy = torch.empty_like(y)
         slab = torch.empty(int(self.lib.msst_pix_head_bwd_slab(B, self.S, self.N, nc)), dtype=torch.float32, device=y.device)
         fp, g = self.fp, self.fp.grad
@@ -932,10 +952,11 @@ class Engine:
             return self.pix_head_fwd(y)
         return self.spec_head_fwd(y) if self.enc.spectral_mlp_head else self.cls_head_fwd(y)
 
-    def head_logits_bwd(self, y, dlogits):
+    def head_logits_bwd(self, y, dlogits, want_dy=True):
         if self.enc.pixelwise:
-            return self.pix_head_bwd(y, dlogits)
-        return self.spec_head_bwd(y, dlogits) if self.enc.spectral_mlp_head else self.cls_head_bwd(y, dlogits)
+            return self.pix_head_bwd(y, dlogits, want_dy=want_dy)
+        bwd = self.spec_head_bwd if self.enc.spectral_mlp_head else self.cls_head_bwd
+        return bwd(y, dlogits, want_dy=want_dy)
 
     def _classify_view(self, logits, B):
         """the reference's output layout: [B, nc, H, W]; pixelwise: [B, nc, 1, 1].squeeze() -- [B, nc], or [nc] when B = 1"""
@@ -963,7 +984,17 @@ class Engine:
             x0 = self.tokenize(img, None, emb_drop=emb_drop)
             acts, _ = self.blocks_fwd(x0, save=False, drop=drop)
             return self._classify_view(self.head_logits(acts[-1]), img.shape[0])
-        names = [n for n, _ in self.trainable()]
+        named = self.trainable()
+        if not any(q.requires_grad for n, q in named if not n.startswith("mlp_head.")):
+            # linear evaluation (reference finetune.py:110-136: only mlp_head trains): the body runs as in a no-gradient forward --
+            # module still in training mode, so its dropout stays on -- with nothing saved, and only the head has a backward
+            self.prep_weights()
+            x0 = self.tokenize(img, None, emb_drop=emb_drop)
+            y = self.blocks_fwd_pingpong(x0, drop=drop)
+            head = [(n, q) for n, q in named if n.startswith("mlp_head.")]
+            out = _HeadOnlyFn.apply(self, [n for n, _ in head], y, *[q for _, q in head])
+            return self._classify_view(out, img.shape[0])
+        names = [n for n, _ in named]
         out = _ClassifyFn.apply(self, names, drop, emb_drop, img, *params)
         return self._classify_view(out, img.shape[0])
 
@@ -1170,3 +1201,24 @@ class _ClassifyFn(torch.autograd.Function):
         eng.tokenize_bwd(img, eng._zero_mask, dx0, emb_drop=ctx.emb_drop)
         grads = tuple(eng.fp.view(n, eng.fp.grad) for n in ctx.names)
         return (None,) * 5 + grads
+
+
+class _HeadOnlyFn(torch.autograd.Function):
+    """logits = head(y) over the output y of a frozen body (linear evaluation): the stash is y alone, the backward is the head
+    backward without dy (nobody consumes it) and returns gradients for the head parameters only."""
+
+    @staticmethod
+    def forward(ctx, eng, names, y, *params):
+        ctx.eng, ctx.names = eng, names
+        ctx.stash = (y,)
+        return eng.head_logits(y)
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        eng = ctx.eng
+        (y,) = ctx.stash
+        ctx.stash = None
+        _refuse_accumulation(eng, ctx.names)
+        eng.head_logits_bwd(y, dlogits.contiguous().float(), want_dy=False)
+        grads = tuple(eng.fp.view(n, eng.fp.grad) for n in ctx.names)
+        return (None, None, None) + grads

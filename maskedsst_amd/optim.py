@@ -1,4 +1,4 @@
-"""Fused AdamW + data-parallel gradient reduction for maskedsst_amd models.
+"""Fused AdamW / grouped Adam + data-parallel gradient reduction for maskedsst_amd models.
 
 ``FusedAdamW`` is a ``torch.optim.Optimizer`` (so LR schedulers such as the reference's
 ``ReduceLROnPlateau``, ``src/utils.py:47-50``, drive it unchanged) whose ``step`` is ONE launch of
@@ -8,6 +8,10 @@ gradient are skipped" rule: ``encoder.mlp_head.*`` receives no gradient in pre-t
 outside the updated range.  ``grad_clamp`` applies the reference's per-parameter gradient hook
 ``clamp(grad, -1, 1)`` (``pretrain.py:71-73``) inside the kernel, after the data-parallel mean.
 
+``FusedAdam`` is the finetune optimizer (reference ``finetune.py:110-136``: ``torch.optim.Adam`` with coupled L2 decay, two
+learning rates -- ``lr`` / ``mlp_head_lr`` -- and frozen parameters under ``linear_eval``): its ``step`` turns the parameter groups
+into a table of element ranges of the flat buffer (``adam_ranges``) and updates all of them in ONE launch of ``msst_adam_groups``.
+
 ``BucketReducer`` all-reduces slices of the flat gradient buffer as soon as the backward has
 completed them (buckets are contiguous because the flat layout follows backward order), on the
 process group's own stream (``torch.distributed`` NCCL backend == RCCL on ROCm), overlapping the
@@ -16,6 +20,7 @@ exercise the same code on CPU tensors.
 """
 import ctypes
 import os
+from collections import namedtuple
 
 import torch
 import torch.distributed as dist
@@ -183,6 +188,157 @@ class FusedAdamW(torch.optim.Optimizer):
             raise ValueError(f"fused moments have {fused['m'].numel()} elements, the model needs {m.numel()}")
         super().load_state_dict(state_dict)
         self._step = int(fused["step"])
+        if fused["m"] is not None:
+            m.copy_(fused["m"].to(m.device))
+            v.copy_(fused["v"].to(v.device))
+        else:
+            m.zero_()
+            v.zero_()
+
+
+class AdamRange(namedtuple("AdamRange", "start end group step params")):
+    """one entry of the grouped-Adam table: elements [start, end) of the flat buffers, updated with the hyper-parameters of
+    param_groups[group] at bias-correction step `step`; params: the tensors it covers, in flat order"""
+    __slots__ = ()
+
+    @property
+    def aligned(self):
+        """both ends on a 16-byte boundary (otherwise the kernel moves up to 3 + 3 single floats at the ragged ends)"""
+        return self.start % 4 == 0 and self.end % 4 == 0
+
+
+def adam_ranges(fp, param_groups, step_of=None, max_ranges=64):
+    """The range table of one grouped-Adam step over the flat buffers of ``fp`` (a ``FlatParams``; CPU or GPU).
+
+    Every parameter of ``param_groups`` is located in ``fp.flat`` by its ``data_ptr``; parameters with
+    ``requires_grad=False`` or ``grad is None`` are skipped (torch's rule) and leave a hole; a ``.grad`` that is not the
+    parameter's view of ``fp.grad`` raises.  ``step_of(p)``: updates this tensor has received so far (default: none), its range runs
+    at that plus one.  Neighbouring segments of one group whose step counters are equal merge into one range.  Returns the
+    ``AdamRange`` list sorted by start; more than ``max_ranges`` (the kernel's table size, MSST_ADAM_MAX_GROUPS) raises."""
+    base, gbase = fp.flat.data_ptr(), fp.grad.data_ptr()
+    known = {off: n for off, n, _ in fp.segments.values()}
+    segs = []
+    for gi, group in enumerate(param_groups):
+        for p in group["params"]:
+            if not p.requires_grad or p.grad is None:
+                continue
+            off, rem = divmod(p.data_ptr() - base, 4)
+            if rem or known.get(off) != p.numel():
+                raise RuntimeError("FusedAdam: a parameter of the optimizer is no view of the model's flat parameter buffer "
+                                   "(was the model rebuilt or moved without a forward since?)")
+            if p.grad.data_ptr() != gbase + 4 * off or p.grad.numel() != p.numel() or p.grad.dtype != torch.float32:
+                raise RuntimeError("FusedAdam.step(): a gradient is no view of the flat gradient buffer (gradients must be "
+                                   "the ones the HIP backward hands to autograd)")
+            segs.append((off, off + p.numel(), gi, (step_of(p) if step_of is not None else 0) + 1, p))
+    segs.sort(key=lambda t: t[0])
+    out = []
+    for start, end, gi, step, p in segs:
+        if out and out[-1].end == start and out[-1].group == gi and out[-1].step == step:
+            last = out[-1]
+            out[-1] = last._replace(end=end, params=last.params + [p])
+        else:
+            out.append(AdamRange(start, end, gi, step, [p]))
+    if len(out) > max_ranges:
+        raise ValueError(f"FusedAdam: the frozen / unfrozen pattern of the parameters splits the flat buffer into {len(out)} "
+                         f"ranges, the kernel's table holds {max_ranges}; use torch.optim.Adam for this pattern")
+    return out
+
+
+class FusedAdam(torch.optim.Optimizer):
+    """``torch.optim.Adam`` (``decoupled=True``: ``AdamW``) over a maskedsst_amd model as ONE launch per step.
+
+    ``params``: ``None`` (every parameter of ``model``), a parameter list, or a list of group dicts with their own ``lr`` /
+    ``weight_decay`` -- what ``torch.optim.Adam`` takes; ``param_groups`` look like torch's, so LR schedulers and a manual
+    ``group["lr"] = ...`` drive it.  Parameters that are frozen or received no gradient are skipped, as torch skips them; each tensor
+    counts its own updates for the bias correction (a host integer in ``state[p]["step"]``), so a body unfrozen after some linear-eval
+    steps starts at step 1 with zero moments.  betas and eps are those of the first group (one pair per launch)."""
+
+    def __init__(self, model, params=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False):
+        params = list(model.parameters()) if params is None else list(params)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.model = model
+        self.decoupled = bool(decoupled)
+        self.grad_scale = 1.0
+        self._m = None
+        self._v = None
+        self._flat_id = None
+        self._key = None      # (flat layout version, skip pattern) the cached table was built for
+        self._ranges = None
+        self._table = None
+
+    _state = FusedAdamW._state   # the flat moment buffers (carried over a re-flatten)
+
+    def zero_grad(self, set_to_none=True):
+        # as FusedAdamW: the backward hands autograd views of the flat gradient buffer, a surviving .grad would accumulate onto itself
+        return super().zero_grad(set_to_none=True)
+
+    def _steps_taken(self, p):
+        return int(self.state[p].get("step", 0)) if p in self.state else 0
+
+    def ranges(self, fp):
+        """this step's range table (cached on the flat layout and on which parameters are skipped: between most steps only lr changes)"""
+        from . import _lib
+        pattern = tuple(p.requires_grad and p.grad is not None for g in self.param_groups for p in g["params"])
+        key = (fp.version, pattern)
+        if key != self._key:
+            self._ranges = adam_ranges(fp, self.param_groups, self._steps_taken, _lib.ADAM_MAX_GROUPS)
+            self._table = (_lib.MsstAdamGroup * max(1, len(self._ranges)))()
+            self._key = key
+        else:
+            gbase, base = fp.grad.data_ptr(), fp.flat.data_ptr()
+            for r in self._ranges:
+                for p in r.params:
+                    if p.grad.data_ptr() - gbase != p.data_ptr() - base:
+                        raise RuntimeError("FusedAdam.step(): a gradient is no view of the flat gradient buffer (gradients must "
+                                           "be the ones the HIP backward hands to autograd)")
+        return self._ranges
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        from . import _lib
+        eng = self.model.engine()
+        flat, grad, m, v = self._state(eng)
+        ranges = self.ranges(eng.fp)
+        if not ranges:
+            return None
+        g0 = self.param_groups[0]
+        if any(tuple(g["betas"]) != tuple(g0["betas"]) or g["eps"] != g0["eps"] for g in self.param_groups):
+            raise ValueError("FusedAdam: betas and eps must be the same in every parameter group (one launch, one pair)")
+        flags = _lib.ADAM_DECOUPLED if self.decoupled else 0
+        for t, r in zip(self._table, ranges):
+            g = self.param_groups[r.group]
+            t.start, t.end, t.lr, t.weight_decay, t.step, t.flags = r.start, r.end, float(g["lr"]), float(g["weight_decay"]), r.step, flags
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.check(eng.lib.msst_adam_groups(P(flat), P(grad), P(m), P(v), self._table, len(ranges), ctypes.sizeof(_lib.MsstAdamGroup),
+                                            float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]), float(self.grad_scale),
+                                            stream), "msst_adam_groups")
+        for i, r in enumerate(ranges):
+            for p in r.params:
+                self.state[p]["step"] = r.step
+            ranges[i] = r._replace(step=r.step + 1)
+        return None
+
+    def state_dict(self):
+        d = super().state_dict()   # param_groups and the per-tensor step counters
+        # copies and clones: an in-memory snapshot must not keep changing as training continues (torch hands out its live state)
+        d["state"] = {k: dict(v) for k, v in d["state"].items()}
+        d["fused"] = dict(m=None if self._m is None else self._m.clone(), v=None if self._v is None else self._v.clone())
+        return d
+
+    def load_state_dict(self, state_dict):
+        """Restores lr / betas / ... and the per-tensor step counters through torch, and the flat moments saved by ``state_dict``."""
+        state_dict = dict(state_dict)
+        fused = state_dict.pop("fused", None)
+        # validate everything BEFORE touching any state: a failed load must leave the optimizer as it was
+        if fused is None:
+            raise KeyError("state dict has no 'fused' entry: it was not produced by FusedAdam.state_dict()")
+        eng = self.model.engine()
+        _, _, m, v = self._state(eng)
+        if fused["m"] is not None and (fused["m"].numel() != m.numel() or fused["v"] is None or fused["v"].numel() != v.numel()):
+            raise ValueError(f"fused moments have {fused['m'].numel()} elements, the model needs {m.numel()}")
+        super().load_state_dict(state_dict)
+        self._key = None
         if fused["m"] is not None:
             m.copy_(fused["m"].to(m.device))
             v.copy_(fused["v"].to(v.device))
