@@ -65,7 +65,18 @@ def build_parser():
                          "mlp_head is frozen, the optimizer sees the head only, the step runs no block or tokenizer backward")
     ap.add_argument("--optimizer", default="torch", choices=["torch", "fused"],
                     help="torch: torch.optim.Adam; fused: maskedsst_amd.optim.FusedAdam (the same update, one launch per step)")
+    ap.add_argument("--loss", default="torch", choices=["torch", "fused"],
+                    help="torch: torch.nn.CrossEntropyLoss and eager accuracy; fused: maskedsst_amd.ops.FusedCrossEntropy (loss, gradient, "
+                         "accuracy and macro accuracy from one pass of the HIP loss kernels, one read-back per step; also in validation)")
     return ap
+
+
+def make_criterion(kind, ignored_label):
+    """reference finetune.py:136: CrossEntropyLoss(ignore_index=ignored_label)"""
+    if kind == "fused":
+        from maskedsst_amd.ops import FusedCrossEntropy
+        return FusedCrossEntropy(ignore_index=ignored_label)
+    return torch.nn.CrossEntropyLoss(ignore_index=ignored_label)
 
 
 def make_optimizer(model, config, kind):
@@ -117,7 +128,8 @@ def main():
         for n, p in model.named_parameters():
             p.requires_grad_("mlp_head" in n)
     optimizer = make_optimizer(model, config, args.optimizer)
-    criterion = torch.nn.CrossEntropyLoss(ignore_index=config.ignored_label)
+    criterion = make_criterion(args.loss, config.ignored_label)
+    fused = args.loss == "fused"
     gen = torch.Generator().manual_seed(SEED)
     val = None
     if args.val_scenes > 0 and args.val_every > 0:
@@ -135,22 +147,23 @@ def main():
         if config.dataset == "houston2018":
             img[:, 48:] = 0.0   # 48 real bands zero padded to 50 (reference src/data_houston2018.py:268-269)
         label = torch.randint(-1, config.n_classes, (config.batch_size, 64, 64), generator=gen)
-        loss, acc, _ = train_step(img, label, model, config, device, criterion, optimizer)
+        loss, acc, macro_acc = train_step(img, label, model, config, device, criterion, optimizer)
         if step % config.logging_freq == 0:
-            print(f"step {step} loss {loss.item():.4f} acc {float(acc):.3f} {step * config.batch_size / (time.time() - t0):.1f} samples/s",
+            macro = f" macro_acc {float(macro_acc):.3f}" if fused else ""   # (the eager path has no macro accuracy: it repeats acc)
+            print(f"step {step} loss {loss.item():.4f} acc {float(acc):.3f}{macro} {step * config.batch_size / (time.time() - t0):.1f} samples/s",
                   flush=True)
         if val is not None and step % args.val_every == 0:
-            validate(model, val, step, config.ignored_label)
+            validate(model, val, step, config.ignored_label, fused=fused)
 
 
-def validate(model, val, step, ignored_label):
+def validate(model, val, step, ignored_label, fused=False):
     """validate_downstream (reference src/utils.py:477-605) over whole scenes: one predict_scene pass (windows of image_size,
     eval forward, the module's mode untouched; a pixelwise model: one window per pixel, its centre) and the scene metrics of
     maskedsst_amd.scene (pixels of class -1 are skipped)"""
     from maskedsst_amd.scene import scene_metrics
     img, label = val
     classes, logits = model.predict_scene(img, return_logits=True)
-    m = scene_metrics(logits, classes, label, ignore_index=ignored_label)
+    m = scene_metrics(logits, classes, label, ignore_index=ignored_label, fused=fused)
     print(f"val step {step} loss {m.loss:.4f} acc {m.acc:.3f} macro_acc {m.macro_acc:.3f} scenes {img.shape[0]}", flush=True)
 
 

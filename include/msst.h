@@ -377,6 +377,41 @@ long msst_layernorm_bwd_slab(long rows, int D);
 int msst_layernorm_bwd(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta,
                        float* slab, long rows, int D, float eps, void* stream);
 
+/* Softmax cross entropy with ignore_index, its gradient and the counts of the finetune loops in one pass (reference src/utils.py:645-658:
+ * CrossEntropyLoss(ignore_index) forward / backward, pixel accuracy on valid labels, NaN check; finetune.py:144-146: macro accuracy;
+ * src/utils.py:531-541 in validation).  Added under MSST_VERSION 109 (additive: no struct, no existing signature changes).
+ * logits [R0][n_classes][M] fp32 contiguous ([B, nc, H, W]: R0 = B, M = H W; [B, nc]: M = 1); labels [R0][M] int64.  A row is one
+ * (sample, pixel).  A row COUNTS when its label is not ignore_index, its label lies in [0, n_classes) and, if skip (optional, int64
+ * [R0][M]) is given, skip[row] >= 0 (the class map of msst_scene_assemble: -1 = no window covers the pixel).  A row that is neither
+ * ignored nor skipped and whose label lies outside [0, n_classes) does not count and is tallied in bad_labels.
+ * msst_ce_stats_fwd writes
+ *   loss [1]: the mean over the counting rows of log sum_c exp(x_c) - x_label (row maximum subtracted first); NaN when no row counts;
+ *   d (optional) [R0][n_classes][M]: softmax - onehot for a counting row, zeros for every other row;
+ *   record [MSST_CE_RECORD_SLOTS(n_classes)], 8-byte slots: MSST_CE_LOSS_SUM (a DOUBLE: the sum of the rows' fp32 losses, one fp32
+ *     partial per 256 rows, the partials added in double, both in a fixed order), then int64: MSST_CE_N_VALID (counting rows),
+ *     MSST_CE_N_CORRECT (counting rows whose argmax -- ties: lowest index, a NaN is the maximum, as torch.argmax -- is the label),
+ *     MSST_CE_BAD_LABELS, MSST_CE_NONFINITE (counting rows whose loss is NaN or +-inf), from MSST_CE_SUPPORT on support[n_classes]
+ *     (counting rows by label) and correct[n_classes] (the correct ones by label).
+ * Every word of loss, d and record is written (nothing needs zeroing); no float atomics: two calls give the same bits.
+ * scratch: msst_ce_scratch_bytes(R0, n_classes, M) bytes (4-byte aligned; 0 for a refused shape).  Two launches.
+ * msst_ce_bwd: dlogits = (d / n_valid) * gout, n_valid = record[MSST_CE_N_VALID] and gout (optional device scalar, null: 1) read on
+ * the device; n_valid == 0: zeros.  dlogits may be d itself.  One launch.
+ * Both check their arguments before any launch: MSST_ERR_BADARG for R0, n_classes or M < 1 or a null required pointer,
+ * MSST_ERR_UNSUPPORTED when R0 * M or R0 * n_classes * M is 2^31 or more.  Any n_classes >= 1. */
+#define MSST_CE_LOSS_SUM 0
+#define MSST_CE_N_VALID 1
+#define MSST_CE_N_CORRECT 2
+#define MSST_CE_BAD_LABELS 3
+#define MSST_CE_NONFINITE 4
+#define MSST_CE_SUPPORT 5
+#define MSST_CE_RECORD_SLOTS(n_classes) (5 + 2 * (n_classes))
+long msst_ce_scratch_bytes(int R0, int n_classes, int M);
+int msst_ce_stats_fwd(const float* logits, const int64_t* labels, const int64_t* skip /*optional*/, long ignore_index,
+                      float* d /*optional*/, float* loss, int64_t* record, void* scratch, int R0, int n_classes, int M,
+                      void* stream);
+int msst_ce_bwd(const float* d, const int64_t* record, const float* gout /*optional*/, float* dlogits, int R0, int n_classes,
+                int M, void* stream);
+
 /* Fused AdamW over a flat fp32 buffer (torch.optim.AdamW semantics, src/utils.py:36-45), with the
  * reference's value clamp of the gradient (pretrain.py:71-73) when clamp > 0. */
 int msst_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,

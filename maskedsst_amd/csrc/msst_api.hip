@@ -246,7 +246,7 @@ int msst_profile_kernels(void) { return K_COUNT; }
 const char* msst_profile_name(int id) {
     static const char* names[K_COUNT] = {"prep_weights", "tokenize_fwd", "block_fwd", "head_fwd", "loss_reduce",
                                          "head_bwd", "reduce_slabs", "block_bwd_mlp", "block_bwd_attn",
-                                         "attn_slab_reduce", "block_bwd_ln1", "tokenize_bwd", "pos_split", "adamw", "block_bwd_ln1mlp", "layernorm", "adam_groups"};
+                                         "attn_slab_reduce", "block_bwd_ln1", "tokenize_bwd", "pos_split", "adamw", "block_bwd_ln1mlp", "layernorm", "adam_groups", "cross_entropy"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 
@@ -940,6 +940,41 @@ int msst_layernorm_bwd(const float* x, const float* gamma, const float* dy, floa
     ok = ok && rb.add(slab + D, 2L * D, grid, dbeta, D);
     if (!ok) return fail(MSST_ERR_UNSUPPORTED, "msst_layernorm_bwd");
     return fail(launch_reduce_segs(rb.r, st), "msst_layernorm_bwd(reduce)");
+}
+
+// shape of a cross-entropy call: 0, MSST_ERR_BADARG (a size below 1) or MSST_ERR_UNSUPPORTED (2^31 rows or logits and beyond)
+static int ce_shape(int R0, int n_classes, int M) {
+    if (R0 < 1 || n_classes < 1 || M < 1) return MSST_ERR_BADARG;
+    if ((long)R0 * M > 0x7fffffffL || (long)R0 * M > 0x7fffffffL / n_classes) return MSST_ERR_UNSUPPORTED;
+    return 0;
+}
+
+long msst_ce_scratch_bytes(int R0, int n_classes, int M) {
+    if (ce_shape(R0, n_classes, M)) return 0;
+    return (long)ce_workgroups((long)R0 * M) * (5 + 2L * n_classes) * 4;
+}
+
+int msst_ce_stats_fwd(const float* logits, const int64_t* labels, const int64_t* skip, long ignore_index, float* d, float* loss,
+                      int64_t* record, void* scratch, int R0, int n_classes, int M, void* stream) {
+    int rc = ce_shape(R0, n_classes, M);
+    if (rc) return fail(rc, "msst_ce_stats_fwd");
+    if (!logits || !labels || !loss || !record || !scratch) return fail(MSST_ERR_BADARG, "msst_ce_stats_fwd");   // skip and d are optional
+    CeArgs a = {};
+    a.logits = logits; a.labels = labels; a.skip = skip; a.d = d; a.loss = loss; a.record = record;
+    a.rows = (long)R0 * M; a.ignore_index = ignore_index; a.NC = n_classes; a.M = M;
+    a.partial = (float*)scratch;
+    a.slab = (int*)scratch + ce_workgroups(a.rows);
+    hipStream_t st = (hipStream_t)stream;
+    rc = launch_ce_fwd(a, st);
+    if (rc) return fail(rc, "msst_ce_stats_fwd");
+    return fail(launch_ce_finish(a, st), "msst_ce_stats_fwd(finish)");
+}
+
+int msst_ce_bwd(const float* d, const int64_t* record, const float* gout, float* dlogits, int R0, int n_classes, int M, void* stream) {
+    const int rc = ce_shape(R0, n_classes, M);
+    if (rc) return fail(rc, "msst_ce_bwd");
+    if (!d || !record || !dlogits) return fail(MSST_ERR_BADARG, "msst_ce_bwd");   // gout is optional (1)
+    return fail(launch_ce_bwd(d, record, gout, dlogits, (long)R0 * n_classes * M, (hipStream_t)stream), "msst_ce_bwd");
 }
 
 int msst_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,

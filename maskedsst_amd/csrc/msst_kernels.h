@@ -191,7 +191,7 @@ struct TokBwdArgs {
 // ---- opt-in per-kernel timing with HIP events on the launch stream (bench.py roofline leg) ----
 enum KernelId {
     K_PREP = 0, K_TOK_FWD, K_BLOCK_FWD, K_HEAD_FWD, K_LOSS_REDUCE, K_HEAD_BWD, K_REDUCE, K_BWD_MLP, K_BWD_ATTN,
-    K_ATTN_REDUCE, K_BWD_LN1, K_TOK_BWD, K_POS_SPLIT, K_ADAMW, K_BWD_LN1MLP, K_LAYERNORM, K_ADAM_GROUPS, K_COUNT
+    K_ATTN_REDUCE, K_BWD_LN1, K_TOK_BWD, K_POS_SPLIT, K_ADAMW, K_BWD_LN1MLP, K_LAYERNORM, K_ADAM_GROUPS, K_CE, K_COUNT
 };
 void prof_begin(int id, hipStream_t st);
 void prof_end(hipStream_t st);
@@ -318,5 +318,20 @@ int launch_layernorm_fwd(const float* x, const float* g, const float* b, float* 
 int layernorm_bwd_grid(long rows, int D);   // workgroups (= slab rows of 2 D floats) the backward launch uses
 int launch_layernorm_bwd(const float* x, const float* g, const float* dy, float* dx, float* slab, int grid, long rows, int D,
                          float eps, hipStream_t st);
+// msst_loss.hip: softmax cross entropy with ignore_index over class-major logits [R0][NC][M], rows = R0 M (one lane per row)
+struct CeArgs {
+    const float* logits; const int64_t* labels; const int64_t* skip;   // skip: optional [rows], entries < 0 do not count
+    float* d;            // optional [R0][NC][M]: softmax - onehot (zeros for rows that do not count)
+    float* loss;         // the mean over the rows that count (NaN over none)
+    int64_t* record;     // [5 + 2 NC]: loss sum (a double) | n_valid | n_correct | bad_labels | nonfinite | support[NC] | correct[NC]
+    float* partial;      // [workgroups] loss partials
+    int* slab;           // [workgroups][4 + 2 NC] count partials
+    long rows, ignore_index;
+    int NC, M;
+};
+int ce_workgroups(long rows);   // workgroups of the forward launch = rows of its two partial arrays
+int launch_ce_fwd(const CeArgs& a, hipStream_t st);
+int launch_ce_finish(const CeArgs& a, hipStream_t st);
+int launch_ce_bwd(const float* d, const int64_t* record, const float* gout, float* dlogits, long n, hipStream_t st);
 
 }  // namespace msst

@@ -57,7 +57,7 @@ def predict_scene(model, scene, stride=None, return_logits=False, max_windows=SC
     return (classes, logits) if return_logits else classes
 
 
-def scene_metrics(logits, classes, labels, ignore_index=-1):
+def scene_metrics(logits, classes, labels, ignore_index=-1, fused=False):
     """Validation numbers of a predicted scene batch (what validate_downstream logs, src/utils.py:531-541, over whole scenes).
 
     logits [Bs, nc, Hs, Ws], classes [Bs, Hs, Ws] (-1: no window covers the pixel), labels [Bs, Hs, Ws].  Pixels count when
@@ -65,7 +65,16 @@ def scene_metrics(logits, classes, labels, ignore_index=-1):
       loss      cross entropy of the logits over those pixels (mean),
       acc       pixel accuracy over those pixels,
       macro_acc mean per-class recall over the classes present among those pixels' labels (torchmetrics' macro accuracy).
-    All three are nan when no pixel counts."""
+    All three are nan when no pixel counts.
+    fused=True: one pass of ``maskedsst_amd.ops.cross_entropy_stats`` over the logit map as it lies, with ``skip=classes``, and one
+    read-back of its record (the same integer counts; the loss summed in the kernels' fixed order) instead of the boolean
+    indexing and the per-class loop below."""
+    if fused:
+        from .ops import cross_entropy_stats
+        with torch.no_grad():
+            _, stats = cross_entropy_stats(logits, labels, ignore_index, skip=classes)
+        h = stats.host()
+        return SceneMetrics(h.loss, h.acc, h.macro_acc)
     labels = labels.to(classes.device).long()
     valid = (classes != -1) & (labels != ignore_index)
     n = int(valid.sum())

@@ -83,7 +83,10 @@ def train_step(img, label, model, config, device, criterion, optimizer, acc_crit
     """reference src/utils.py:608-663 for the ViTSpatialSpectral method: optional random crop, forward,
     CE(ignore_index) loss, pixel accuracy on valid labels, backward, optimizer step.  With ``config.pixelwise`` a label
     map [B, s, s] is reduced to its centre pixel ``label[:, c, c]``, ``c = (image_size - patch_sub) // 2`` (reference
-    :630-636); a label that is already one class per sample ([B]) passes through unchanged."""
+    :630-636); a label that is already one class per sample ([B]) passes through unchanged.
+    ``criterion`` a ``maskedsst_amd.ops.FusedCrossEntropy``: loss, gradient and counts come from one pass of the HIP loss kernels,
+    ``macro_acc`` is the true macro accuracy (mean per-class recall) and the step reads the device back once (``_fused_tail``).  Any
+    other criterion: the eager path below, unchanged."""
     patch_sub = getattr(config, "patch_sub", 0)
     if config.image_size != 64 and img.shape[-1] == 64:
         x, y = torch.randint(0, 64 - config.image_size - patch_sub, size=(2,))
@@ -97,6 +100,8 @@ def train_step(img, label, model, config, device, criterion, optimizer, acc_crit
     label = label.to(device)
     optimizer.zero_grad()
     output = model(img)
+    if getattr(criterion, "fused_stats", False):
+        return _fused_tail(output, label, criterion, optimizer)
     loss = criterion(output, label)
     if torch.isnan(loss):
         raise ValueError("Loss is NaN")
@@ -107,3 +112,19 @@ def train_step(img, label, model, config, device, criterion, optimizer, acc_crit
     loss.backward()
     optimizer.step()
     return loss, acc, macro_acc
+
+
+def _fused_tail(output, label, criterion, optimizer):
+    """train_step from the loss on, for a FusedCrossEntropy: loss + record (two launches), ONE read-back of the record, the
+    reference's NaN check on it (before the backward, as there), backward (one launch up to the head's), optimizer step.
+    -> (loss: 0-d device tensor, acc, macro_acc: floats; acc = 0 and macro_acc = acc when no label is valid, as on the eager path)"""
+    loss, stats = criterion(output, label, return_stats=True)
+    h = stats.host()
+    if h.loss != h.loss:
+        raise ValueError("Loss is NaN" + (f" ({h.nonfinite} non-finite rows)" if h.nonfinite else " (no valid label)" if not h.n_valid else ""))
+    if h.bad_labels:
+        raise ValueError(f"{h.bad_labels} labels outside [0, {stats.n_classes}) that are not the ignored label")
+    loss.backward(criterion.unit_gradient(loss.device))
+    optimizer.step()
+    acc = h.n_correct / max(h.n_valid, 1)
+    return loss, acc, (h.macro_acc if h.n_valid else acc)

@@ -11,7 +11,14 @@ alternately in one process with HIP events around each step; a repetition report
 repetitions and their spread.  Legs whose pieces a revision lacks (no ``FusedAdam``) are left out, so the tool also runs on an
 older tree: that is where a baseline comes from.
 
+``--loss torch | fused | both``: a step is then ``maskedsst_amd.utils.train_step`` as finetune.py runs it -- the loss, the accuracy
+numbers and the NaN check with their host synchronisations, not the bare ``F.cross_entropy`` of the default -- with
+``torch.nn.CrossEntropyLoss`` or ``maskedsst_amd.ops.FusedCrossEntropy`` (finetune.py --loss); ``both`` gives every leg twice
+(``...+loss_torch`` / ``...+loss_fused``), alternated step by step in the one process.  ``--legs`` keeps the legs whose name contains
+one of the given words.
+
 Prints ONE JSON line.  Run:  python tools/finetune_time.py [--steps 20] [--reps 3] [--warmup 5] [--precision bf16] [--batch 256]
+                                                           [--loss both] [--legs linear_eval+fused full+torch]
 """
 import argparse
 import ctypes
@@ -28,6 +35,7 @@ sys.path.insert(0, ROOT)
 
 import finetune  # noqa: E402
 from maskedsst_amd import ViTSpatialSpectral  # noqa: E402
+from maskedsst_amd.utils import train_step  # noqa: E402
 
 
 def build(precision, device, linear_eval):
@@ -60,6 +68,16 @@ def optimizer(model, config, kind):
     return torch.optim.Adam([{"params": body}, {"params": head, "lr": config.mlp_head_lr}], lr=config.lr, weight_decay=config.weight_decay)
 
 
+def criterion(loss, config):
+    """finetune.py's criterion for --loss; None: the bare F.cross_entropy step.  ImportError: the revision has no fused loss"""
+    if loss is None:
+        return None
+    if loss == "fused":
+        from maskedsst_amd.ops import FusedCrossEntropy
+        return FusedCrossEntropy(ignore_index=config.ignored_label)
+    return torch.nn.CrossEntropyLoss(ignore_index=config.ignored_label)
+
+
 def box_probe(model):
     """shader clock (MHz) and MFMA rate this box holds right now (msst_debug_box_probe); {} when the library has no probe"""
     lib = model.engine().lib
@@ -79,25 +97,39 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--loss", default=None, choices=["torch", "fused", "both"],
+                    help="time utils.train_step with this criterion (default: the bare F.cross_entropy step)")
+    ap.add_argument("--legs", nargs="*", default=None, help="keep the legs whose name contains one of these words")
     args = ap.parse_args()
     dev = torch.device("cuda")
     legs = {}
+    losses = [None] if args.loss is None else ["torch", "fused"] if args.loss == "both" else [args.loss]
     for mode, linear_eval in (("full", False), ("linear_eval", True)):
         for kind in ("torch", "fused"):
-            config, model = build(args.precision, dev, linear_eval)
-            try:
-                opt = optimizer(model, config, kind)
-            except ImportError:
-                opt = None
-            if opt is not None:
-                legs[f"{mode}+{kind}"] = (model, opt)
+            for loss in losses:
+                name = f"{mode}+{kind}" + (f"+loss_{loss}" if loss else "")
+                if args.legs and not any(w in name for w in args.legs):
+                    continue
+                config, model = build(args.precision, dev, linear_eval)
+                try:
+                    opt = optimizer(model, config, kind)
+                    crit = criterion(loss, config)
+                except ImportError:
+                    opt = None
+                if opt is not None:
+                    legs[name] = (model, opt, crit, config)
+    if not legs:
+        raise SystemExit("no leg left: this revision lacks the pieces, or --legs matches nothing")
     gen = torch.Generator().manual_seed(finetune.SEED)
     size = config.image_size - config.patch_sub
     x = torch.randn(args.batch, config.n_bands, size, size, generator=gen).to(dev)
     label = torch.randint(-1, config.n_classes, (args.batch, size, size), generator=gen).to(dev)
 
     def step(name):
-        model, opt = legs[name]
+        model, opt, crit, cfg = legs[name]
+        if crit is not None:
+            train_step(x, label, model, cfg, dev, crit, opt)
+            return
         opt.zero_grad()
         F.cross_entropy(model(x), label, ignore_index=-1).backward()
         opt.step()
@@ -129,7 +161,7 @@ def main():
             reps[name].append(round(statistics.median(t[name]), 4))
     res = dict(tool="finetune_time", shape=dict(B=args.batch, bands=config.n_bands, depth=config.transformer_depth,
                                                 n_classes=config.n_classes, image_size=size),
-               precision=args.precision, steps=args.steps, warmup=args.warmup, box_probe=probe,
+               precision=args.precision, loss=args.loss, steps=args.steps, warmup=args.warmup, box_probe=probe,
                step_ms={name: round(statistics.median(v), 4) for name, v in reps.items()},
                step_ms_reps=reps, step_ms_spread={name: round(max(v) - min(v), 4) for name, v in reps.items()},
                peak_step_bytes=peak)
