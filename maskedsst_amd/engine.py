@@ -4,6 +4,7 @@ launch sequence of the HIP kernels (through the C-ABI in ``libmsst.so``) for one
 PyTorch is used for device memory (``torch.empty``), streams and autograd bookkeeping only; all
 arithmetic of the hot path runs in the kernels under ``maskedsst_amd/csrc``.
 """
+import collections
 import ctypes
 import os
 
@@ -19,6 +20,24 @@ D = 96
 DH = 64
 STACK_MAX_TILES = 12   # msst_block_fwd_stack is used for a stack whose workgroups hold at most this many tiles (crossover measured near 14; batch 256 at the EnMAP shape: 20 / 22)
 MLP = 64
+_MODE = {"spatial": MODE_SPATIAL, "spectral": MODE_SPECTRAL}   # stack name (Engine._layers) -> block mode
+
+# The three classifier heads.  linear: index of the Linear in mlp_head (the LayerNorm is 0); shape(B, nc, N): the logits; fwd_ws /
+# bwd_slab(lib, B, S, N, nc): floats of the forward workspace (None: the kernel takes none) and of the backward slab; assemble: the
+# scene assembler that consumes this head's per-window logits.
+_Head = collections.namedtuple("_Head", "fwd bwd linear shape fwd_ws bwd_slab assemble")
+_HEADS = {
+    # default: mean over the S tokens of a position -> LN(96) -> Linear; logits [B, nc, N]
+    "cls": _Head("msst_cls_head_fwd", "msst_cls_head_bwd", 1, lambda B, nc, N: (B, nc, N), None,
+                 lambda lib, B, S, N, nc: B * (nc * 97 + 192), "msst_scene_assemble"),
+    # spectral_mlp_head: the S tokens of a position concatenated -> LN(96 S) -> Linear; logits [B, nc, N]
+    "spec": _Head("msst_spec_head_fwd", "msst_spec_head_bwd", 1, lambda B, nc, N: (B, nc, N), None,
+                  lambda lib, B, S, N, nc: lib.msst_spec_head_bwd_slab(B, S, N, nc), "msst_scene_assemble"),
+    # pixelwise: mean over the S tokens -> LN(96) per position -> flatten -> Linear(96 N); logits [B, nc] (centre pixel)
+    "pix": _Head("msst_pix_head_fwd", "msst_pix_head_bwd", 2, lambda B, nc, N: (B, nc),
+                 lambda lib, B, S, N, nc: lib.msst_pix_head_fwd_ws(B, N),
+                 lambda lib, B, S, N, nc: lib.msst_pix_head_bwd_slab(B, S, N, nc), "msst_scene_centre_assemble"),
+}
 
 
 def _prec_of(name):
@@ -241,24 +260,15 @@ class Engine:
             |LayerNorm row| <= max |gamma| * sqrt(96) + max |beta| -- q / k / v (and the attention output, a convex combination of v
             rows) from Wqkv and LN1, the hidden pre-activation (>= |GELU output|) from W1, b1 and LN2."""
         if getattr(self, "_ln1_idx_key", None) is not self._jobs:
-            layers = self._layers()
+            blocks = [f"{s_}.{l}" for s_, l in self._layers()]
             names = ["ln1_g", "ln1_b", "wqkv", "ln2_g", "ln2_b", "w1", "b1"]
-            seg = self.fp.segments
-            base = [seg[f"{layers[0][0]}.{layers[0][1]}.{n}"][0] for n in names]
-            starts = [min(seg[f"{s_}.{l}.{n}"][0] for n in names) for s_, l in layers]
-            lo = min(starts)
-            stride = None
-            order = sorted(range(len(layers)), key=lambda i: starts[i])
-            affine = True
-            for a_, b_ in zip(order, order[1:]):
-                d = starts[b_] - starts[a_]
-                stride = d if stride is None else stride
-                affine = affine and d == stride
-            rel = [o - starts[0] for o in base]
-            for i, (s_, l) in enumerate(layers):
-                affine = affine and all(seg[f"{s_}.{l}.{n}"][0] - starts[i] == r for n, r in zip(names, rel))
-            span = max(seg[f"{layers[0][0]}.{layers[0][1]}.{n}"][0] + seg[f"{layers[0][0]}.{layers[0][1]}.{n}"][1] for n in names) - starts[0]
-            self._guard_view = (lo, stride if len(layers) > 1 else span, len(layers), dict(zip(names, rel)), span) if affine and (stride or 0) >= span else None
+            seg0 = [self.fp.segments[f"{blocks[0]}.{n}"] for n in names]
+            start = min(s[0] for s in seg0)
+            span = max(s[0] + s[1] for s in seg0) - start
+            d = self.fp.block_stride(blocks, names)   # block 0 -> block 1 of the forward order: negative in FlatParams' own layout
+            # rows of the view: the blocks in memory order, from the lowest; they must not overlap (a single block has no stride: no view)
+            self._guard_view = (min(start, start + d * (len(blocks) - 1)), abs(d), len(blocks),
+                                {n: s[0] - start for n, s in zip(names, seg0)}, span) if d is not None and abs(d) >= span else None
             self._ln1_idx_key = self._jobs
             self._ln1_host = torch.empty(2, dtype=torch.float32, pin_memory=True)
             self._ln1_ev = None
@@ -307,6 +317,20 @@ class Engine:
         return b is not None and b <= self.HALF_MAX_BOUND
 
     # ------------------------------------------------------------------ forward pieces
+    def _pos_tables(self, buf=None):
+        """(split, a, b): the position tables the tokenizer kernels read, or with buf = the gradient buffer write -- spectral_pos_embed:
+        pos_embed | channel_embed, split after pos_embed's width; else the one pos_embedding table (split 0, no b)"""
+        fp = self.fp
+        if self.enc.spectral_pos_embed:
+            return self.enc.pos_embed.shape[-1], fp.ptr("pos_embed", buf), fp.ptr("channel_embed", buf)
+        return 0, fp.ptr("pos_embedding", buf), 0
+
+    def _zero_mask_for(self, n, device):
+        """an all-zero token mask of at least n bytes on `device` (nothing masked), grown or moved when needed"""
+        if self._zero_mask is None or self._zero_mask.numel() < n or self._zero_mask.device != torch.device(device):
+            self._zero_mask = torch.zeros(n, dtype=torch.uint8, device=device)
+        return self._zero_mask
+
     def tokenize(self, img, mask_u8=None, with_pos=True, emb_drop=(0.0, 0)):
         """img [B, C, H, W] fp32 cuda -> tokens [B, T, 96] (pos added, mask token substituted)"""
         self._require_cuda(img)
@@ -317,20 +341,14 @@ class Engine:
         img = img.contiguous().float()
         out = torch.empty(B, T, D, dtype=torch.float32, device=img.device)
         if mask_u8 is None:
-            if self._zero_mask is None or self._zero_mask.numel() < B * T:
-                self._zero_mask = torch.zeros(B * T, dtype=torch.uint8, device=img.device)
-            mask_u8 = self._zero_mask
+            mask_u8 = self._zero_mask_for(B * T, img.device)
         fp = self.fp
         if not with_pos:
             if getattr(self, "_zero_pos", None) is None or self._zero_pos.numel() < T * D:
                 self._zero_pos = torch.zeros(T * D, dtype=torch.float32, device=img.device)
-            pos_a, pos_b, split = self._zero_pos.data_ptr(), 0, 0
-        elif self.enc.spectral_pos_embed:
-            split = self.enc.pos_embed.shape[-1]
-            pos_a, pos_b = fp.ptr("pos_embed"), fp.ptr("channel_embed")
+            split, pos_a, pos_b = 0, self._zero_pos.data_ptr(), 0
         else:
-            split = 0
-            pos_a, pos_b = fp.ptr("pos_embedding"), 0
+            split, pos_a, pos_b = self._pos_tables()
         mt = fp.ptr("mask_token") if self.mim is not None else fp.ptr("post_b")
         V = ctypes.c_void_p
         _lib.check(self.lib.msst_tokenize_fwd(
@@ -341,14 +359,14 @@ class Engine:
 
     def blocks_fwd(self, x0, save=True, drop=(0.0, 0)):
         """run the 2*depth fused blocks; returns (list of activations [x0 .. x_2L], list of x1)"""
-        H = self.enc.heads
         acts = [x0]
         x1s = []
         flags = _kernel_flags()
-        # bf16 x1 rows (MSST_X1_BF16): only the role-split forward writes them -- bf16, 8 heads, no kernel-selection flags;
-        # MSST_X1_BF16=0 keeps fp32 rows.  The x1 tensor's dtype tells the backward which kind it holds.
-        x1_bf16 = (save and self.prec == PREC_BF16 and H == 8 and flags == 0 and os.environ.get("MSST_X1_BF16", "1") != "0")
-        want_lse = save and self.prec == PREC_BF16 and H == 8 and flags == 0 and os.environ.get("MSST_LSE", "1") != "0"
+        role_split = self._role_split(flags)
+        # bf16 x1 rows (MSST_X1_BF16): only the role-split forward writes them; MSST_X1_BF16=0 keeps fp32 rows.  The x1 tensor's
+        # dtype tells the backward which kind it holds.
+        x1_bf16 = save and role_split and os.environ.get("MSST_X1_BF16", "1") != "0"
+        want_lse = save and role_split and os.environ.get("MSST_LSE", "1") != "0"
         # MSST_FWD_HALF (round 6): the role-split forward multiplies IEEE-half operands (11 significant bits, same MFMA rate) instead of
         # bf16 ones -- the bf16 forward's loss error against the fp32 reference is owned by the rounding of the weights
         # (tools/bf16_error_table.py: 2.7e-4 -> 7e-6 on the Houston-shape anchor).  MSST_FWD_HALF=0: bf16 operands.
@@ -359,7 +377,7 @@ class Engine:
         # Measured (tools/fwd_ab.py): ahead when a workgroup holds few tiles (batch 64: -5.5 % forward time, Houston shape: -7.3 %),
         # behind when it holds many (batch 256, EnMAP shape: +1.3 %) -- MSST_FWD_STACK=1 / 0 force it on / off, otherwise by tiles per workgroup.
         want_stack = os.environ.get("MSST_FWD_STACK", "auto")
-        stacked = self.prec == PREC_BF16 and H == 8 and flags == 0 and want_stack != "0"
+        stacked = role_split and want_stack != "0"
         i0 = 0
         self.fwd_launch_blocks = []   # blocks carried by each block-forward launch of this call (bench.py normalises per-launch numbers with it)
         while i0 < len(layers):
@@ -376,27 +394,27 @@ class Engine:
             i0 = i1
         return acts, x1s
 
-    def blocks_fwd_pingpong(self, x0, drop=(0.0, 0)):
-        """the 2*depth fused blocks with nothing kept for a backward, on two token buffers in turn (x0 and one more; x0 is
-        overwritten): returns the last block's output.  One msst_block_fwd per block with the kernels, precision flags and dropout
-        arguments of blocks_fwd(save=False) -- the same bits -- but one residual stream of scratch instead of 2*depth."""
-        B = x0.shape[0]
+    def blocks_fwd_pingpong(self, x0, drop=(0.0, 0), other=None, n=None, stream=None):
+        """the 2*depth fused blocks with nothing kept for a backward, on two token buffers in turn (x0 and `other`, one more of its
+        shape; x0 is overwritten): returns the last block's output.  One msst_block_fwd per block with the kernels, precision flags and
+        dropout arguments of blocks_fwd(save=False) -- the same bits -- but one residual stream of scratch instead of 2*depth.
+        n: the batch, when the buffers hold more rows than are in use (scene_forward's last chunk)."""
+        B = x0.shape[0] if n is None else n
         S, N, H = self.S, self.N, self.enc.heads
         flags = _kernel_flags()
         prec = self.prec | flags | self._half_flag(flags)
-        x, y = x0, torch.empty_like(x0)
+        x, y = x0, torch.empty_like(x0) if other is None else other
         wrote = ctypes.c_int(0)
-        st = _stream()
+        st = _stream() if stream is None else stream
         for i, (sname, _) in enumerate(self._layers()):
-            mode = MODE_SPATIAL if sname == "spatial" else MODE_SPECTRAL
-            _lib.check(self.lib.msst_block_fwd(ctypes.byref(self._bw[i]), _p(x), _p(y), None, mode, B, S, N, H, prec, self.max_grid,
+            _lib.check(self.lib.msst_block_fwd(ctypes.byref(self._bw[i]), _p(x), _p(y), None, _MODE[sname], B, S, N, H, prec, self.max_grid,
                                                drop[0], drop[1], i, None, None, ctypes.byref(wrote), st), "msst_block_fwd")
             x, y = y, x
         return x
 
     def _tiles_per_workgroup(self, sname, B):
         """64-row tiles the busiest workgroup of a block forward walks (the library's own tiling: msst_block_lse_floats counts tiles x heads x 64)"""
-        mode = MODE_SPATIAL if sname == "spatial" else MODE_SPECTRAL
+        mode = _MODE[sname]
         key = (mode, B)
         hit = self._tpw.get(key)
         if hit is None:
@@ -405,11 +423,24 @@ class Engine:
             hit = self._tpw[key] = -(-tiles // grid)
         return hit
 
+    def _role_split(self, flags):
+        """may the role-split forward run?  bf16, 8 heads, no kernel-selection flags -- the one kernel that writes bf16 x1 rows and
+        softmax statistics, takes IEEE-half operands and has the one-launch stack form"""
+        return self.prec == PREC_BF16 and self.enc.heads == 8 and flags == 0
+
     def _half_flag(self, flags):
-        """MSST_FWD_HALF for a forward launch: the role-split kernel (bf16 mode, 8 heads, no kernel selection flags), unless MSST_FWD_HALF=0"""
-        self.fwd_half = (self.prec == PREC_BF16 and self.enc.heads == 8 and flags == 0 and os.environ.get("MSST_FWD_HALF", "1") != "0"
-                         and self.half_ok())
+        """MSST_FWD_HALF for a forward launch: the role-split kernel, unless MSST_FWD_HALF=0"""
+        self.fwd_half = self._role_split(flags) and os.environ.get("MSST_FWD_HALF", "1") != "0" and self.half_ok()
         return _lib.FWD_HALF if self.fwd_half else 0
+
+    def _attach_saved(self, x1, wrote, xn, lse):
+        """what a block forward saved beside x1 (its `saved` word) rides on the x1 tensor object, so that every caller keeps its
+        (acts, x1s) pair: the LN1 rows, the softmax statistics, whether LN1's rstd is in their tail, whether they are those of
+        half-operand scores (the backward then renormalises: MSST_LSE_RENORM)"""
+        x1._msst_xn = xn if (wrote & _lib.SAVED_XN) else None
+        x1._msst_lse = lse if (lse is not None and (wrote & _lib.SAVED_LSE)) else None
+        x1._msst_rstd = bool(wrote & _lib.SAVED_RSTD) and x1._msst_lse is not None
+        x1._msst_half = bool(self.fwd_half)
 
     def _fwd_block(self, acts, x1s, i, save, drop, x1_bf16, want_lse, flags):
         """block i as its own launch (msst_block_fwd): appends its output to acts, its saved mid residual to x1s"""
@@ -420,9 +451,9 @@ class Engine:
         y = torch.empty_like(x)
         x1 = (torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if x1_bf16 else torch.empty_like(x)) if save else None
         # bf16: the block also saves LN1(x) as it used it (bf16 rows), if the selected kernel can; the attention backward
-        # then skips its own LN1.  The buffer rides on the x1 tensor object so that every caller keeps its (acts, x1s) pair.
+        # then skips its own LN1.
         xn = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if (save and self.prec != PREC_F32) else None
-        mode = MODE_SPATIAL if sname == "spatial" else MODE_SPECTRAL
+        mode = _MODE[sname]
         # ... and (role-split kernel) the softmax statistics of every (tile, head, row): MSST_LSE=0 keeps the backward's own softmax
         lse = None
         if xn is not None and want_lse:
@@ -433,10 +464,7 @@ class Engine:
                                            ctypes.byref(wrote), _stream()),
                    "msst_block_fwd")
         if x1 is not None:
-            x1._msst_xn = xn if (wrote.value & _lib.SAVED_XN) else None
-            x1._msst_lse = lse if (wrote.value & _lib.SAVED_LSE) else None
-            x1._msst_rstd = bool(wrote.value & _lib.SAVED_RSTD) and x1._msst_lse is not None   # rstd of LN1 rides in the tail of the statistics buffer
-            x1._msst_half = bool(self.fwd_half)   # the statistics are those of half-operand scores: the backward renormalises (MSST_LSE_RENORM)
+            self._attach_saved(x1, wrote.value, xn, lse)
         acts.append(y)
         x1s.append(x1)
 
@@ -449,7 +477,7 @@ class Engine:
         S, N, H = self.S, self.N, self.enc.heads
         dev = x0.device
         n = i1 - i0
-        mode = MODE_SPATIAL if self._layers()[i0][0] == "spatial" else MODE_SPECTRAL
+        mode = _MODE[self._layers()[i0][0]]
         # one allocation per kind, block j its j-th slice: the kernel addresses block j's operands as block 0's + j x a byte stride
         # (the weight copies and the flat parameters are laid out that way by _build_weight_storage / FlatParams)
         def slices(dtype, shape=None):
@@ -474,10 +502,7 @@ class Engine:
         for j in range(n):
             acts.append(ys[j])
             if save:
-                x1[j]._msst_xn = xn[j] if (wrote.value & _lib.SAVED_XN) else None
-                x1[j]._msst_lse = lse[j] if (lse is not None and (wrote.value & _lib.SAVED_LSE)) else None
-                x1[j]._msst_rstd = bool(wrote.value & _lib.SAVED_RSTD) and x1[j]._msst_lse is not None
-                x1[j]._msst_half = bool(self.fwd_half)
+                self._attach_saved(x1[j], wrote.value, xn[j], lse[j] if lse is not None else None)
                 x1s.append(x1[j])
             else:
                 x1s.append(None)
@@ -529,114 +554,109 @@ class Engine:
     def _grad_stride(self, nlayers):
         """floats between the gradient tensors of consecutive backward calls (block i -> block i - 1), or None when the blocks'
         gradients are not laid out a constant, 16-byte-aligned stride apart (msst_block_bwd_reduce needs that)"""
-        if nlayers < 2:
-            return None
-        fields = [n for n, _ in MsstBlockGrads._fields_]
-        d0 = None
-        for i in range(nlayers - 1, 0, -1):
-            for f in fields:
-                a, b = getattr(self._bg[i], f), getattr(self._bg[i - 1], f)
-                if a is None or b is None:
-                    return None
-                d = b - a
-                if d0 is None:
-                    d0 = d
-                if d != d0:
-                    return None
-        if d0 is None or d0 <= 0 or d0 % 16:
-            return None
-        return d0 // 4
+        blocks = [f"{sname}.{l}" for sname, l in self._layers()[:nlayers]]
+        d = self.fp.block_stride(blocks, [n for n, _ in MsstBlockGrads._fields_])   # forward order: the backward walks it in reverse
+        return -d if d is not None and d < 0 and d % 4 == 0 else None
+
+    def _bwd_workspace(self, B, device):
+        """(dx1, part, slab, dab): the scratch of one block backward at batch B, shared by every block of a backward pass"""
+        H = self.enc.heads
+        ntok = B * self.S * self.N
+        esz = 4 if self.prec == PREC_F32 else 2
+        dx1 = torch.empty(ntok * 96, dtype=torch.float32, device=device)
+        part = torch.empty(H * ntok * 96 * esz, dtype=torch.uint8, device=device)
+        # the bf16 MLP backward runs two workgroups per CU: up to 2 * grid_rows MLP slabs (msst_block_bwd lays the parts out);
+        # the chained form adds one MLP slab per workgroup of the fused LN1 + MLP launch
+        slab = torch.empty(self.grid_rows * (3 * MLP_SLAB + LN1_SLAB) + self.attn_chunks * H * ATTN_SLAB, dtype=torch.float32, device=device)
+        dab = torch.empty(ntok * 96, dtype=torch.bfloat16, device=device) if self.prec != PREC_F32 else None
+        return dx1, part, slab, dab
 
     def blocks_bwd(self, acts, x1s, dy, drop=(0.0, 0)):
         """backward through the 2*depth blocks (reverse order); returns dx0"""
-        B = dy.shape[0]
-        S, N, H = self.S, self.N, self.enc.heads
-        dev = dy.device
-        ntok = B * S * N
-        esz = 4 if self.prec == PREC_F32 else 2
-        dx1 = torch.empty(ntok * 96, dtype=torch.float32, device=dev)
-        part = torch.empty(H * ntok * 96 * esz, dtype=torch.uint8, device=dev)
-        dab = torch.empty(ntok * 96, dtype=torch.bfloat16, device=dev) if self.prec != PREC_F32 else None
-        # the bf16 MLP backward runs two workgroups per CU: up to 2 * grid_rows MLP slabs (msst_block_bwd lays the parts out);
-        # the chained form adds one MLP slab per workgroup of the fused LN1 + MLP launch
-        nslab = self.grid_rows * (3 * MLP_SLAB + LN1_SLAB) + self.attn_chunks * H * ATTN_SLAB
-        slab = torch.empty(nslab, dtype=torch.float32, device=dev)
-        layers = self._layers()
-        flags = _kernel_flags()
-        xns = [getattr(t, "_msst_xn", None) for t in x1s]
-        lses = [getattr(t, "_msst_lse", None) for t in x1s]
+        H = self.enc.heads
+        ntok = dy.shape[0] * self.S * self.N
+        ws = self._bwd_workspace(dy.shape[0], dy.device)
         x1_bf16 = len(x1s) > 0 and all(t.dtype == torch.bfloat16 for t in x1s)
         if not x1_bf16 and any(t.dtype != torch.float32 for t in x1s):
             raise ValueError("saved x1 rows of mixed dtypes")
-        x1flag = _lib.X1_BF16 if x1_bf16 else 0
         # Chained backward (msst_block_bwd_chain): the LN1 backward of block i and the MLP-half backward of block i - 1 are
         # one launch, dx of block i stays on chip.  bf16 tuned kernels with saved LN1 rows only; at most four d(LN1 out)
         # partials (one per head pair for an even head count, else one per head).
         nparts = H // 2 if H % 2 == 0 else H
-        chain = (self.prec == PREC_BF16 and flags == 0 and dab is not None and all(t is not None for t in xns)
-                 and nparts <= 4 and os.environ.get("MSST_BWD_CHAIN", "1") != "0" and len(layers) > 0
+        chain = (self.prec == PREC_BF16 and _kernel_flags() == 0 and all(getattr(t, "_msst_xn", None) is not None for t in x1s)
+                 and nparts <= 4 and os.environ.get("MSST_BWD_CHAIN", "1") != "0" and self.enc.depth > 0
                  and ntok * 384 < 2 ** 31 - 16 and nparts * ntok * 192 < 2 ** 31 - 16)   # 32-bit buffer offsets in the fused launch
         # MSST_LN1_FROM_XN (round 6): the fused LN1 + MLP launch rebuilds xhat of LN1 from the saved bf16 LN1 rows and the saved rstd
         # instead of re-reading the fp32 block input (192 of 2304 bytes per token less) -- when the forward saved both for every block,
         # and the LN1 parameters allow the division by gamma (ln1_xn_ok: max |beta / gamma| <= 12, checked on the device a step behind)
-        xnflag = 0
-        if (chain and x1_bf16 and os.environ.get("MSST_LN1_XN", "1") != "0" and all(getattr(t, "_msst_rstd", False) for t in x1s)
-                and self.ln1_xn_ok()):
-            xnflag = _lib.LN1_FROM_XN
-        self.last_bwd_ln1_from_xn = bool(xnflag)
+        ln1_from_xn = (chain and x1_bf16 and os.environ.get("MSST_LN1_XN", "1") != "0"
+                       and all(getattr(t, "_msst_rstd", False) for t in x1s) and self.ln1_xn_ok())
+        self.last_bwd_ln1_from_xn = bool(ln1_from_xn)
         if chain:
-            # dynamic tile queues (attach_data_parallel sets self.tile_queue; MSST_TILE_QUEUE=1 forces them): see include/msst.h
-            queue = None
-            if self.tile_queue or os.environ.get("MSST_TILE_QUEUE", "0") == "1":
-                if getattr(self, "_queue_ws", None) is None or self._queue_ws.device != dev:
-                    self._queue_ws = torch.zeros(64, dtype=torch.int32, device=dev)
-                queue = self._queue_ws
-            last = len(layers) - 1
-            dx0 = torch.empty_like(dy)
-            null_w = ctypes.POINTER(MsstBlockWeights)()
-            null_g = ctypes.POINTER(MsstBlockGrads)()
-            # Deferred slab reduction (msst_block_bwd_reduce, opt-in with MSST_BWD_DEFER=1): every call of a run of same-mode blocks
-            # keeps its own slab set and ONE launch reduces the run -- 2 block reductions per step instead of 2 * depth.  Bit-identical
-            # gradients; measured (LABNOTES round 4): the reductions drop from 566 to 400 us per EnMAP step, but the producers pay it
-            # back -- their slab epilogues now write 1.5 GB of cold memory per step instead of the same 62 MB that the reduction just
-            # read (attention backward +6 us per launch) -- so the per-call reduction stays the default.
-            gstride = self._grad_stride(len(layers))
-            defer = gstride is not None and os.environ.get("MSST_BWD_DEFER", "0") == "1"
-            nslab_r = (nslab + 3) // 4 * 4
-            if defer:
-                slab = torch.empty(nslab_r * len(layers), dtype=torch.float32, device=dev)
-            run_start = last
-            for i in reversed(range(len(layers))):
-                sname, l = layers[i]
-                mode = MODE_SPATIAL if sname == "spatial" else MODE_SPECTRAL
-                prev = i > 0
-                y = last - i
-                slab_i = slab[y * nslab_r:] if defer else slab
-                _lib.check(self.lib.msst_block_bwd_chain(
-                    ctypes.byref(self._bw[i]), ctypes.byref(self._bg[i]),
-                    ctypes.byref(self._bw[i - 1]) if prev else null_w, ctypes.byref(self._bg[i - 1]) if prev else null_g,
-                    _p(acts[i]), _p(x1s[i]), _p(x1s[i - 1]) if prev else _p(None), _p(dy) if i == last else _p(None),
-                    _p(None) if prev else _p(dx0), _p(dx1), _p(part), _p(slab_i), self.grid_rows, self.attn_chunks, mode,
-                    B, S, N, H, self.prec | x1flag | xnflag | (_lib.LSE_RENORM if getattr(x1s[i], "_msst_half", False) else 0) |
-                    (_lib.BWD_DEFER_REDUCE if defer else 0), drop[0], drop[1], i, _p(xns[i]), _p(lses[i]), _p(dab),
-                    1 if i == last else 0, _p(queue), _stream()),
-                    "msst_block_bwd_chain")
-                if not defer:
-                    self._fire(f"{sname}.{l}")
-                elif i == 0 or layers[i - 1][0] != sname:   # the run of this stack ends here: reduce it, then announce its blocks
-                    count = run_start - i + 1
-                    _lib.check(self.lib.msst_block_bwd_reduce(
-                        ctypes.byref(self._bg[run_start]), ctypes.byref(self._bg[run_start - 1]) if run_start > 0 else null_g,
-                        _p(slab[(last - run_start) * nslab_r:]), nslab_r, gstride, count, count if i > 0 else count - 1,
-                        1 if run_start == last else 0, self.grid_rows, self.attn_chunks, mode, B, S, N, H, self.prec, _stream()),
-                        "msst_block_bwd_reduce")
-                    for j in range(run_start, i - 1, -1):
-                        self._fire(f"{layers[j][0]}.{layers[j][1]}")
-                    run_start = i - 1
-            return dx0
-        g = dy
-        other = torch.empty_like(dy)
-        ws = (dx1, part, slab, dab)
+            return self._blocks_bwd_chained(acts, x1s, dy, drop, ws,
+                                            (_lib.X1_BF16 if x1_bf16 else 0) | (_lib.LN1_FROM_XN if ln1_from_xn else 0))
+        return self._blocks_bwd_unchained(acts, x1s, dy, drop, ws)
+
+    def _blocks_bwd_chained(self, acts, x1s, dy, drop, ws, x1flags):
+        """blocks_bwd through msst_block_bwd_chain, one call per block; x1flags: MSST_X1_BF16 / MSST_LN1_FROM_XN as blocks_bwd decided"""
+        B = dy.shape[0]
+        S, N, H = self.S, self.N, self.enc.heads
+        dev = dy.device
+        dx1, part, slab, dab = ws
+        layers = self._layers()
+        # dynamic tile queues (attach_data_parallel sets self.tile_queue; MSST_TILE_QUEUE=1 forces them): see include/msst.h
+        queue = None
+        if self.tile_queue or os.environ.get("MSST_TILE_QUEUE", "0") == "1":
+            if getattr(self, "_queue_ws", None) is None or self._queue_ws.device != dev:
+                self._queue_ws = torch.zeros(64, dtype=torch.int32, device=dev)
+            queue = self._queue_ws
+        last = len(layers) - 1
+        dx0 = torch.empty_like(dy)
+        null_w = ctypes.POINTER(MsstBlockWeights)()
+        null_g = ctypes.POINTER(MsstBlockGrads)()
+        # Deferred slab reduction (msst_block_bwd_reduce, opt-in with MSST_BWD_DEFER=1): every call of a run of same-mode blocks
+        # keeps its own slab set and ONE launch reduces the run -- 2 block reductions per step instead of 2 * depth.  Bit-identical
+        # gradients; measured (LABNOTES round 4): the reductions drop from 566 to 400 us per EnMAP step, but the producers pay it
+        # back -- their slab epilogues now write 1.5 GB of cold memory per step instead of the same 62 MB that the reduction just
+        # read (attention backward +6 us per launch) -- so the per-call reduction stays the default.
+        gstride = self._grad_stride(len(layers))
+        defer = gstride is not None and os.environ.get("MSST_BWD_DEFER", "0") == "1"
+        nslab_r = (slab.numel() + 3) // 4 * 4
+        if defer:
+            slab = torch.empty(nslab_r * len(layers), dtype=torch.float32, device=dev)
+        run_start = last
+        for i in reversed(range(len(layers))):
+            sname, l = layers[i]
+            prev = i > 0
+            x1 = x1s[i]
+            slab_i = slab[(last - i) * nslab_r:] if defer else slab
+            _lib.check(self.lib.msst_block_bwd_chain(
+                ctypes.byref(self._bw[i]), ctypes.byref(self._bg[i]),
+                ctypes.byref(self._bw[i - 1]) if prev else null_w, ctypes.byref(self._bg[i - 1]) if prev else null_g,
+                _p(acts[i]), _p(x1), _p(x1s[i - 1]) if prev else _p(None), _p(dy) if i == last else _p(None),
+                _p(None) if prev else _p(dx0), _p(dx1), _p(part), _p(slab_i), self.grid_rows, self.attn_chunks, _MODE[sname],
+                B, S, N, H, self.prec | x1flags | (_lib.LSE_RENORM if getattr(x1, "_msst_half", False) else 0) |
+                (_lib.BWD_DEFER_REDUCE if defer else 0), drop[0], drop[1], i, _p(x1._msst_xn), _p(getattr(x1, "_msst_lse", None)), _p(dab),
+                1 if i == last else 0, _p(queue), _stream()),
+                "msst_block_bwd_chain")
+            if not defer:
+                self._fire(f"{sname}.{l}")
+            elif i == 0 or layers[i - 1][0] != sname:   # the run of this stack ends here: reduce it, then announce its blocks
+                count = run_start - i + 1
+                _lib.check(self.lib.msst_block_bwd_reduce(
+                    ctypes.byref(self._bg[run_start]), ctypes.byref(self._bg[run_start - 1]) if run_start > 0 else null_g,
+                    _p(slab[(last - run_start) * nslab_r:]), nslab_r, gstride, count, count if i > 0 else count - 1,
+                    1 if run_start == last else 0, self.grid_rows, self.attn_chunks, _MODE[sname], B, S, N, H, self.prec, _stream()),
+                    "msst_block_bwd_reduce")
+                for j in range(run_start, i - 1, -1):
+                    self._fire(f"{layers[j][0]}.{layers[j][1]}")
+                run_start = i - 1
+        return dx0
+
+    def _blocks_bwd_unchained(self, acts, x1s, dy, drop, ws):
+        """blocks_bwd block by block (block_bwd_single) on two gradient buffers in turn: dy and one more"""
+        layers = self._layers()
+        g, other = dy, torch.empty_like(dy)
         for i in reversed(range(len(layers))):
             self.block_bwd_single(i, acts[i], x1s[i], g, other, drop=drop, ws=ws)
             g, other = other, g
@@ -648,26 +668,15 @@ class Engine:
         x1 = its saved mid residual (with the LN1 rows / statistics its forward attached), dy = the gradient at its output -> dx;
         the block's parameter gradients land in the flat gradient buffer.  The unchained loop of blocks_bwd runs on it; the parity tests
         call it block by block with the ORACLE's activations and gradients (no error carried from block to block)."""
-        B = dy.shape[0]
-        S, N, H = self.S, self.N, self.enc.heads
-        dev = dy.device
-        ntok = B * S * N
-        if ws is None:
-            esz = 4 if self.prec == PREC_F32 else 2
-            ws = (torch.empty(ntok * 96, dtype=torch.float32, device=dev), torch.empty(H * ntok * 96 * esz, dtype=torch.uint8, device=dev),
-                  torch.empty(self.grid_rows * (3 * MLP_SLAB + LN1_SLAB) + self.attn_chunks * H * ATTN_SLAB, dtype=torch.float32, device=dev),
-                  torch.empty(ntok * 96, dtype=torch.bfloat16, device=dev) if self.prec != PREC_F32 else None)
-        dx1, part, slab, dab = ws
+        dx1, part, slab, dab = ws if ws is not None else self._bwd_workspace(dy.shape[0], dy.device)
         if dx is None:
             dx = torch.empty_like(dy)
-        sname, l = self._layers()[i]
-        mode = MODE_SPATIAL if sname == "spatial" else MODE_SPECTRAL
         if x1.dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("saved x1 rows must be fp32 or bf16")
         x1flag = _lib.X1_BF16 if x1.dtype == torch.bfloat16 else 0
         _lib.check(self.lib.msst_block_bwd(
             ctypes.byref(self._bw[i]), ctypes.byref(self._bg[i]), _p(x), _p(x1), _p(dy), _p(dx),
-            _p(dx1), _p(part), _p(slab), self.grid_rows, self.attn_chunks, mode, B, S, N, H,
+            _p(dx1), _p(part), _p(slab), self.grid_rows, self.attn_chunks, _MODE[self._layers()[i][0]], dy.shape[0], self.S, self.N, self.enc.heads,
             self.prec | _kernel_flags() | x1flag | (_lib.LSE_RENORM if getattr(x1, "_msst_half", False) else 0),
             drop[0], drop[1], i, _p(getattr(x1, "_msst_xn", None)), _p(getattr(x1, "_msst_lse", None)), _p(dab), _stream()), "msst_block_bwd")
         return dx
@@ -683,14 +692,7 @@ class Engine:
         slab = torch.empty(S * nchunk * ss + S * N * 96, dtype=torch.float32, device=dev)
         fp, g = self.fp, self.fp.grad
         V = ctypes.c_void_p
-        if not with_pos:
-            split, dpa, dpb = 0, 0, 0
-        elif self.enc.spectral_pos_embed:
-            split = self.enc.pos_embed.shape[-1]
-            dpa, dpb = fp.ptr("pos_embed", g), fp.ptr("channel_embed", g)
-        else:
-            split = 0
-            dpa, dpb = fp.ptr("pos_embedding", g), 0
+        split, dpa, dpb = self._pos_tables(g) if with_pos else (0, 0, 0)
         dmt = fp.ptr("mask_token", g) if (self.mim is not None and with_pos) else 0
         _lib.check(self.lib.msst_tokenize_bwd(
             _p(img), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
@@ -849,118 +851,72 @@ class Engine:
             return self.transformer(x0)
 
     # ------------------------------------------------------------------ classification (row a17 / finetune.py)
-    # the head calls take optional output buffers (logits / dy): the kernels write every element of them, whatever they held
-    def cls_head_fwd(self, y, logits=None):
-        B = y.shape[0]
+    def _head_kind(self):
+        """key into _HEADS of the classifier head the encoder was built with"""
+        return "pix" if self.enc.pixelwise else "spec" if self.enc.spectral_mlp_head else "cls"
+
+    def _head_params(self, head, buf=None):
+        """the head's LayerNorm weight, bias and Linear weight, bias in the flat buffer (or in buf: the gradient buffer)"""
+        return [ctypes.c_void_p(self.fp.ptr(f"mlp_head.{i}.{wb}", buf)) for i in (0, head.linear) for wb in ("weight", "bias")]
+
+    def _head_fwd(self, kind, y, B=None, logits=None, stream=None):
+        """logits of head `kind` over tokens y [>= B, T, 96]; the kernel writes every element of `logits` (head.shape(B, nc, N)),
+        whatever it held.  B: the batch, when y and logits hold more rows than are in use (scene_forward's last chunk)."""
+        head = _HEADS[kind]
+        B = y.shape[0] if B is None else B
         nc = self.enc.num_classes
         if logits is None:
-            logits = torch.empty(B, nc, self.N, dtype=torch.float32, device=y.device)
-        fp = self.fp
-        V = ctypes.c_void_p
-        _lib.check(self.lib.msst_cls_head_fwd(
-            _p(y), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")), V(fp.ptr("mlp_head.1.weight")),
-            V(fp.ptr("mlp_head.1.bias")), _p(logits), B, self.S, self.N, nc, _stream()), "msst_cls_head_fwd")
+            logits = torch.empty(head.shape(B, nc, self.N), dtype=torch.float32, device=y.device)
+        ws = None if head.fwd_ws is None else torch.empty(int(head.fwd_ws(self.lib, B, self.S, self.N, nc)), dtype=torch.float32, device=y.device)
+        _lib.check(getattr(self.lib, head.fwd)(
+            _p(y), *self._head_params(head), _p(logits), *([] if ws is None else [_p(ws)]), B, self.S, self.N, nc,
+            _stream() if stream is None else stream), head.fwd)
         return logits
+
+    def _head_bwd(self, kind, y, dlogits, dy=None, want_dy=True):
+        """-> dy [B, T, 96], written whole (None with want_dy=False, a frozen body: the kernel variant without dy runs, null dy); the
+        four head gradients are written (not accumulated) into the flat gradient buffer, the same bits either way"""
+        head = _HEADS[kind]
+        B = y.shape[0]
+        nc = self.enc.num_classes
+        if dy is None and want_dy:
+            dy = torch.empty_like(y)
+        slab = torch.empty(int(head.bwd_slab(self.lib, B, self.S, self.N, nc)), dtype=torch.float32, device=y.device)
+        g = self._head_params(head, self.fp.grad)
+        _lib.check(getattr(self.lib, head.bwd)(
+            _p(y), _p(dlogits), *self._head_params(head)[:3], _p(dy), _p(slab), *g, B, self.S, self.N, nc, _stream()), head.bwd)
+        self._fire("cls_head")
+        return dy
+
+    # the six public names run their own head's kernels on this model's mlp_head parameters, whatever head the encoder has
+    def cls_head_fwd(self, y, logits=None):
+        return self._head_fwd("cls", y, logits=logits)
 
     def cls_head_bwd(self, y, dlogits, dy=None, want_dy=True):
-        """want_dy=False (a frozen body): the kernel variant without dy runs (null dy); the four head gradients are the same bits"""
-        B = y.shape[0]
-        nc = self.enc.num_classes
-        if dy is None and want_dy:
-            dy = torch.empty_like(y)
-        slab = torch.empty(B * (nc * 97 + 192), dtype=torch.float32, device=y.device)
-        fp, g = self.fp, self.fp.grad
-        V = ctypes.c_void_p
-        _lib.check(self.lib.msst_cls_head_bwd(
-            _p(y), _p(dlogits), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")),
-            V(fp.ptr("mlp_head.1.weight")), _p(dy), _p(slab), V(fp.ptr("mlp_head.0.weight", g)),
-            V(fp.ptr("mlp_head.0.bias", g)), V(fp.ptr("mlp_head.1.weight", g)), V(fp.ptr("mlp_head.1.bias", g)),
-            B, self.S, self.N, nc, _stream()), "msst_cls_head_bwd")
-        self._fire("cls_head")
-        return dy
+        return self._head_bwd("cls", y, dlogits, dy, want_dy)
 
     def spec_head_fwd(self, y, logits=None):
-        """spectral_mlp_head: the S tokens of a position concatenated -> LN(96 S) -> Linear; logits [B, nc, N] (cls_head_fwd's layout)"""
-        B = y.shape[0]
-        nc = self.enc.num_classes
-        if logits is None:
-            logits = torch.empty(B, nc, self.N, dtype=torch.float32, device=y.device)
-        self._spec_head_fwd_into(y, B, logits, _stream())
-        return logits
-
-    def _spec_head_fwd_into(self, y, B, logits, st):
-        fp = self.fp
-        V = ctypes.c_void_p
-        _lib.check(self.lib.msst_spec_head_fwd(
-            _p(y), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")), V(fp.ptr("mlp_head.1.weight")),
-            V(fp.ptr("mlp_head.1.bias")), _p(logits), B, self.S, self.N, self.enc.num_classes, st), "msst_spec_head_fwd")
+        return self._head_fwd("spec", y, logits=logits)
 
     def spec_head_bwd(self, y, dlogits, dy=None, want_dy=True):
-        """-> dy [B, T, 96] (None with want_dy=False); the four head gradients are written (not accumulated) into the flat gradient buffer"""
-        B = y.shape[0]
-        nc = self.enc.num_classes
-        if dy is None and want_dy:
-            dy = torch.empty_like(y)
-        slab = torch.empty(int(self.lib.msst_spec_head_bwd_slab(B, self.S, self.N, nc)), dtype=torch.float32, device=y.device)
-        fp, g = self.fp, self.fp.grad
-        V = ctypes.c_void_p
-        _lib.check(self.lib.msst_spec_head_bwd(
-            _p(y), _p(dlogits), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")),
-            V(fp.ptr("mlp_head.1.weight")), _p(dy), _p(slab), V(fp.ptr("mlp_head.0.weight", g)),
-            V(fp.ptr("mlp_head.0.bias", g)), V(fp.ptr("mlp_head.1.weight", g)), V(fp.ptr("mlp_head.1.bias", g)),
-            B, self.S, self.N, nc, _stream()), "msst_spec_head_bwd")
-        self._fire("cls_head")
-        return dy
+        return self._head_bwd("spec", y, dlogits, dy, want_dy)
 
     def pix_head_fwd(self, y, logits=None):
-        """pixelwise: mean over the S tokens -> LN(96) per position -> flatten -> Linear(96 N); logits [B, nc] (centre pixel)"""
-        B = y.shape[0]
-        if logits is None:
-            logits = torch.empty(B, self.enc.num_classes, dtype=torch.float32, device=y.device)
-        self._pix_head_fwd_into(y, B, logits, _stream())
-        return logits
-
-    def _pix_head_fwd_into(self, y, B, logits, st):
-        fp = self.fp
-        V = ctypes.c_void_p
-        ws = torch.empty(int(self.lib.msst_pix_head_fwd_ws(B, self.N)), dtype=torch.float32, device=y.device)
-        _lib.check(self.lib.msst_pix_head_fwd(
-            _p(y), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")), V(fp.ptr("mlp_head.2.weight")),
-            V(fp.ptr("mlp_head.2.bias")), _p(logits), _p(ws), B, self.S, self.N, self.enc.num_classes, st), "msst_pix_head_fwd")
+        return self._head_fwd("pix", y, logits=logits)
 
     def pix_head_bwd(self, y, dlogits, dy=None, want_dy=True):
-        """dlogits [B, nc] -> dy [B, T, 96] (None with want_dy=False); the four head gradients are written (not accumulated) into the
-        flat gradient buffer"""
-        B = y.shape[0]
-        nc = self.enc.num_classes
-        if dy is None and want_dy:
-            dy = torch.empty_like(y)
-        slab = torch.empty(int(self.lib.msst_pix_head_bwd_slab(B, self.S, self.N, nc)), dtype=torch.float32, device=y.device)
-        fp, g = self.fp, self.fp.grad
-        V = ctypes.c_void_p
-        _lib.check(self.lib.msst_pix_head_bwd(
-            _p(y), _p(dlogits), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")),
-            V(fp.ptr("mlp_head.2.weight")), _p(dy), _p(slab), V(fp.ptr("mlp_head.0.weight", g)),
-            V(fp.ptr("mlp_head.0.bias", g)), V(fp.ptr("mlp_head.2.weight", g)), V(fp.ptr("mlp_head.2.bias", g)),
-            B, self.S, self.N, nc, _stream()), "msst_pix_head_bwd")
-        self._fire("cls_head")
-        return dy
+        return self._head_bwd("pix", y, dlogits, dy, want_dy)
 
     def head_logits(self, y):
         """the classifier head the encoder was built with: logits [B, nc, N] ([B, nc] for the pixelwise head)"""
-        if self.enc.pixelwise:
-            return self.pix_head_fwd(y)
-        return self.spec_head_fwd(y) if self.enc.spectral_mlp_head else self.cls_head_fwd(y)
+        return self._head_fwd(self._head_kind(), y)
 
     def head_logits_bwd(self, y, dlogits, want_dy=True):
-        if self.enc.pixelwise:
-            return self.pix_head_bwd(y, dlogits, want_dy=want_dy)
-        bwd = self.spec_head_bwd if self.enc.spectral_mlp_head else self.cls_head_bwd
-        return bwd(y, dlogits, want_dy=want_dy)
+        return self._head_bwd(self._head_kind(), y, dlogits, want_dy=want_dy)
 
     def _classify_view(self, logits, B):
         """the reference's output layout: [B, nc, H, W]; pixelwise: [B, nc, 1, 1].squeeze() -- [B, nc], or [nc] when B = 1"""
-        if self.enc.pixelwise:
+        if self._head_kind() == "pix":
             return logits.view(B, -1, 1, 1).squeeze()
         H = W = self.enc.num_spatial_patches_sqrt
         return logits.view(B, -1, H, W)
@@ -1013,7 +969,7 @@ class Engine:
         scene = scene.contiguous().float()
         Bs, _, Hs, Ws = scene.shape
         enc, fp = self.enc, self.fp
-        S, N, P, H = self.S, self.N, self.P, enc.heads
+        S, N, P = self.S, self.N, self.P
         w = enc.num_spatial_patches_sqrt
         nc = enc.num_classes
         nr, nq = (Hs - w) // stride + 1, (Ws - w) // stride + 1
@@ -1021,45 +977,25 @@ class Engine:
         chunk = max(1, min(int(max_windows), total, 65535))   # 65535: the generic tokenizer runs one grid row per window
         dev = scene.device
         self.prep_weights()
-        if enc.spectral_pos_embed:
-            split, pos_a, pos_b = enc.pos_embed.shape[-1], fp.ptr("pos_embed"), fp.ptr("channel_embed")
-        else:
-            split, pos_a, pos_b = 0, fp.ptr("pos_embedding"), 0
-        flags = _kernel_flags()
-        prec = self.prec | flags | self._half_flag(flags)
-        layers = self._layers()
+        split, pos_a, pos_b = self._pos_tables()
+        kind = self._head_kind()
+        head = _HEADS[kind]
         bufs = [torch.empty(chunk, S * N, D, dtype=torch.float32, device=dev) for _ in range(2)]
-        win_logits = torch.empty(chunk, nc, 1 if enc.pixelwise else N, dtype=torch.float32, device=dev)
+        win_logits = torch.empty(head.shape(chunk, nc, N), dtype=torch.float32, device=dev)
         logits = torch.empty(Bs, nc, Hs, Ws, dtype=torch.float32, device=dev)
         classes = torch.empty(Bs, Hs, Ws, dtype=torch.int64, device=dev)
         V = ctypes.c_void_p
         st = _stream()
-        wrote = ctypes.c_int(0)
         for win0 in range(0, total, chunk):
             n = min(chunk, total - win0)
-            x, y = bufs[0], bufs[1]
             _lib.check(self.lib.msst_tokenize_scene_fwd(
                 _p(scene), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
-                V(fp.ptr("post_g")), V(fp.ptr("post_b")), V(pos_a), V(pos_b), split, _p(x), Bs, Hs, Ws, w, stride, win0, n, S, P, st),
+                V(fp.ptr("post_g")), V(fp.ptr("post_b")), V(pos_a), V(pos_b), split, _p(bufs[0]), Bs, Hs, Ws, w, stride, win0, n, S, P, st),
                 "msst_tokenize_scene_fwd")
-            for i, (sname, _) in enumerate(layers):
-                mode = MODE_SPATIAL if sname == "spatial" else MODE_SPECTRAL
-                _lib.check(self.lib.msst_block_fwd(ctypes.byref(self._bw[i]), _p(x), _p(y), None, mode, n, S, N, H, prec,
-                                                   self.max_grid, 0.0, 0, i, None, None, ctypes.byref(wrote), st), "msst_block_fwd")
-                x, y = y, x
-            if enc.pixelwise:
-                self._pix_head_fwd_into(x, n, win_logits, st)
-                _lib.check(self.lib.msst_scene_centre_assemble(_p(win_logits), win0, n, _p(logits), _p(classes), Bs, nc, Hs, Ws, w,
-                                                               stride, int(win0 + n == total), st), "msst_scene_centre_assemble")
-                continue
-            if enc.spectral_mlp_head:
-                self._spec_head_fwd_into(x, n, win_logits, st)
-            else:
-                _lib.check(self.lib.msst_cls_head_fwd(
-                    _p(x), V(fp.ptr("mlp_head.0.weight")), V(fp.ptr("mlp_head.0.bias")), V(fp.ptr("mlp_head.1.weight")),
-                    V(fp.ptr("mlp_head.1.bias")), _p(win_logits), n, S, N, nc, st), "msst_cls_head_fwd")
-            _lib.check(self.lib.msst_scene_assemble(_p(win_logits), win0, n, _p(logits), _p(classes), Bs, nc, Hs, Ws, w, stride,
-                                                    int(win0 + n == total), st), "msst_scene_assemble")
+            x = self.blocks_fwd_pingpong(bufs[0], other=bufs[1], n=n, stream=st)
+            self._head_fwd(kind, x, n, win_logits, st)
+            _lib.check(getattr(self.lib, head.assemble)(_p(win_logits), win0, n, _p(logits), _p(classes), Bs, nc, Hs, Ws, w, stride,
+                                                        int(win0 + n == total), st), head.assemble)
         return logits, classes
 
     # ------------------------------------------------------------------ staged forward (tests / debugging)
@@ -1101,29 +1037,31 @@ class _SimMIMLossFn(torch.autograd.Function):
         eng = ctx.eng
         img, mask_u8, csr_ptr, csr_pos, acts, x1s, dpred = ctx.stash
         ctx.stash = None
-        lo, hi = eng.fp.grad.data_ptr(), eng.fp.grad.data_ptr() + 4 * eng.fp.grad.numel()
-        for _, p in eng.trainable():
-            if p.grad is not None and lo <= p.grad.data_ptr() < hi:
-                raise RuntimeError(
-                    "maskedsst_amd hands autograd views of its flat gradient buffer: drop the previous gradients "
-                    "with optimizer.zero_grad(set_to_none=True) (the torch default) before the next backward; "
-                    "in-place gradient accumulation across backward calls is not supported")
+        _refuse_accumulation(eng, ctx.names)
         gout = gout.contiguous().float()
         dy = eng.head_bwd(acts[-1], dpred, csr_ptr, csr_pos, gout)
         dx0 = eng.blocks_bwd(acts, x1s, dy, drop=ctx.drop)
         eng.tokenize_bwd(img, mask_u8, dx0)
-        grads = tuple(eng.fp.view(n, eng.fp.grad) for n in ctx.names)
-        return (None,) * 8 + grads
+        return (None,) * 8 + _grad_views(eng, ctx.names)
 
 
 def _refuse_accumulation(eng, names):
+    """called by every backward before it writes gradients: none of the parameters it returns gradients for (flat names) may
+    still hold the view of the flat gradient buffer that an earlier backward handed out"""
     by_name = dict(eng.trainable())
     lo, hi = eng.fp.grad.data_ptr(), eng.fp.grad.data_ptr() + 4 * eng.fp.grad.numel()
     for n in names:
         p = by_name[n]
         if p.grad is not None and lo <= p.grad.data_ptr() < hi:
-            raise RuntimeError("call optimizer.zero_grad(set_to_none=True) before the next backward "
-                               "(maskedsst_amd hands autograd views of its flat gradient buffer)")
+            raise RuntimeError(
+                "maskedsst_amd hands autograd views of its flat gradient buffer: drop the previous gradients "
+                "with optimizer.zero_grad(set_to_none=True) (the torch default) before the next backward; "
+                "in-place gradient accumulation across backward calls is not supported")
+
+
+def _grad_views(eng, names):
+    """the gradients a backward returns to autograd: views of the flat gradient buffer the kernels have just written"""
+    return tuple(eng.fp.view(n, eng.fp.grad) for n in names)
 
 
 class _TransformerFn(torch.autograd.Function):
@@ -1144,8 +1082,7 @@ class _TransformerFn(torch.autograd.Function):
         ctx.stash = None
         _refuse_accumulation(eng, ctx.names)
         dx0 = eng.blocks_bwd(acts, x1s, dy.contiguous().float().clone(), drop=ctx.drop)
-        grads = tuple(eng.fp.view(n, eng.fp.grad) for n in ctx.names)
-        return (None, None, None, dx0) + grads
+        return (None, None, None, dx0) + _grad_views(eng, ctx.names)
 
 
 class _EmbedFn(torch.autograd.Function):
@@ -1163,12 +1100,9 @@ class _EmbedFn(torch.autograd.Function):
         (img,) = ctx.stash
         ctx.stash = None
         _refuse_accumulation(eng, ctx.names)
-        n = img.shape[0] * eng.S * eng.N
-        if eng._zero_mask is None or eng._zero_mask.numel() < n:
-            eng._zero_mask = torch.zeros(n, dtype=torch.uint8, device=img.device)
-        eng.tokenize_bwd(img, eng._zero_mask, dtok.contiguous().float(), with_pos=False)
-        grads = tuple(eng.fp.view(n_, eng.fp.grad) for n_ in ctx.names)
-        return (None, None, None) + grads
+        zero_mask = eng._zero_mask_for(img.shape[0] * eng.S * eng.N, img.device)
+        eng.tokenize_bwd(img, zero_mask, dtok.contiguous().float(), with_pos=False)
+        return (None, None, None) + _grad_views(eng, ctx.names)
 
 
 class _ClassifyFn(torch.autograd.Function):
@@ -1189,18 +1123,12 @@ class _ClassifyFn(torch.autograd.Function):
         eng = ctx.eng
         img, acts, x1s = ctx.stash
         ctx.stash = None
-        lo, hi = eng.fp.grad.data_ptr(), eng.fp.grad.data_ptr() + 4 * eng.fp.grad.numel()
-        for _, p in eng.trainable():
-            if p.grad is not None and lo <= p.grad.data_ptr() < hi:
-                raise RuntimeError("call optimizer.zero_grad(set_to_none=True) before the next backward "
-                                   "(maskedsst_amd hands autograd views of its flat gradient buffer)")
+        _refuse_accumulation(eng, ctx.names)
         dy = eng.head_logits_bwd(acts[-1], dlogits.contiguous().float())
         dx0 = eng.blocks_bwd(acts, x1s, dy, drop=ctx.drop)
-        if eng._zero_mask is None or eng._zero_mask.numel() < img.shape[0] * eng.S * eng.N:
-            eng._zero_mask = torch.zeros(img.shape[0] * eng.S * eng.N, dtype=torch.uint8, device=img.device)
-        eng.tokenize_bwd(img, eng._zero_mask, dx0, emb_drop=ctx.emb_drop)
-        grads = tuple(eng.fp.view(n, eng.fp.grad) for n in ctx.names)
-        return (None,) * 5 + grads
+        zero_mask = eng._zero_mask_for(img.shape[0] * eng.S * eng.N, img.device)
+        eng.tokenize_bwd(img, zero_mask, dx0, emb_drop=ctx.emb_drop)
+        return (None,) * 5 + _grad_views(eng, ctx.names)
 
 
 class _HeadOnlyFn(torch.autograd.Function):
@@ -1220,5 +1148,4 @@ class _HeadOnlyFn(torch.autograd.Function):
         ctx.stash = None
         _refuse_accumulation(eng, ctx.names)
         eng.head_logits_bwd(y, dlogits.contiguous().float(), want_dy=False)
-        grads = tuple(eng.fp.view(n, eng.fp.grad) for n in ctx.names)
-        return (None, None, None) + grads
+        return (None, None, None) + _grad_views(eng, ctx.names)

@@ -128,6 +128,14 @@ class FlatParams:
         base = self.flat if buf is None else buf
         return base.data_ptr() + 4 * off
 
+    def block_stride(self, blocks, names):
+        """Signed number of floats from block i to block i + 1 of ``blocks`` (prefixes in forward order: "spatial.0", ...) when that is
+        one number for every i and every per-block name in ``names``; None otherwise, and for fewer than two blocks.  Offsets are the
+        same in the parameter and in the gradient buffer."""
+        offs = [[self.segments[f"{b}.{n}"][0] for n in names] for b in blocks]
+        steps = {q - p for a, b in zip(offs, offs[1:]) for p, q in zip(a, b)}
+        return steps.pop() if len(steps) == 1 else None
+
     def grad_views(self, params):
         """gradient views (into ``self.grad``) matching a list of (name) keys"""
         return [self.view(n, self.grad) for n in params]

@@ -149,6 +149,32 @@ def test_load_state_dict_roundtrip_into_flat():
     assert torch.equal(fp.view("mask_token"), new["mask_token"])
 
 
+def test_block_stride_of_the_flat_layout():
+    """FlatParams.block_stride: one signed step between consecutive blocks of the forward order (the layout runs in backward
+    completion order, so it is negative), None when the names do not share one or there are fewer than two blocks"""
+    model, _, _ = build_product(dict(bands=30, depth=2, B=2, heads=2))
+    eng = model.engine()
+    fp = eng.fp.flatten()
+    blocks = [f"{s}.{l}" for s, l in eng._layers()]
+    per_block = sum(fp.segments[f"spatial.0.{n}"][1] for n in ("ln1_g", "ln1_b", "wqkv", "wout", "bo", "ln2_g", "ln2_b", "w1", "b1", "w2", "b2"))
+    assert fp.block_stride(blocks, ["ln1_g", "w2"]) == -per_block
+    assert fp.block_stride(blocks[::-1], ["wqkv"]) == per_block
+    assert fp.block_stride(blocks[:1], ["ln1_g"]) is None and fp.block_stride([], ["ln1_g"]) is None
+    assert fp.block_stride([blocks[0], blocks[1], blocks[3]], ["ln1_g"]) is None
+
+
+def test_zero_mask_follows_size_and_device():
+    model, _, _ = build_product(dict(bands=20, depth=1, B=2, heads=2))
+    eng = model.engine()
+    m = eng._zero_mask_for(100, "cpu")
+    assert m.device.type == "cpu" and m.numel() >= 100 and m.dtype == torch.uint8 and not m.any()
+    assert eng._zero_mask_for(60, torch.device("cpu")) is m          # large enough, same device: kept
+    assert eng._zero_mask_for(200, "cpu").numel() >= 200             # grown
+    moved = eng._zero_mask_for(10, "meta")                           # the model's tensors are elsewhere now: a mask there
+    assert moved.device.type == "meta" and eng._zero_mask_for(10, "meta") is moved
+    assert eng._zero_mask_for(10, "cpu").device.type == "cpu"
+
+
 def test_unsupported_configurations_fail_loudly():
     from maskedsst_amd import ViTSpatialSpectral, SimMIMSpatialSpectral
     base = dict(image_size=8, spatial_patch_size=1, spectral_patch_size=10, num_classes=8, dim=96, depth=1, heads=8,

@@ -168,21 +168,12 @@ def dump_stages(eng, cfg, x, masks):
         # run the backward down to block i so that dab / everything for block i is what the kernel saw
         os.environ["MSST_DBG"] = str(8 | (hsel << 8))
         acts, x1s = out["acts"], out["x1s"]
-        ntok = B * S * N
-        dx1 = torch.empty(ntok * 96, dtype=torch.float32, device="cuda")
-        part = torch.empty(H * ntok * 96 * 2, dtype=torch.uint8, device="cuda")
-        dab = torch.empty(ntok * 96, dtype=torch.bfloat16, device="cuda")
-        from maskedsst_amd._lib import MLP_SLAB, ATTN_SLAB, LN1_SLAB
-        slab = torch.empty(eng.grid_rows * (2 * MLP_SLAB + LN1_SLAB) + eng.attn_chunks * H * ATTN_SLAB, dtype=torch.float32, device="cuda")
         other = torch.empty_like(dy)
-        from maskedsst_amd.engine import _p, _stream, _kernel_flags
-        from maskedsst_amd import _lib
         g_in = dy.clone()
         buf.zero_()
-        _lib.check(eng.lib.msst_block_bwd(
-            ctypes.byref(eng._bw[i]), ctypes.byref(eng._bg[i]), _p(acts[i]), _p(x1s[i]), _p(g_in), _p(other),
-            _p(dx1), _p(part), _p(slab), eng.grid_rows, eng.attn_chunks, mode, B, S, N, H,
-            eng.prec | _kernel_flags() | (_lib.X1_BF16 if x1s[i].dtype == torch.bfloat16 else 0), 0.0, 0, i, _p(getattr(x1s[i], "_msst_xn", None)), _p(getattr(x1s[i], "_msst_lse", None)), _p(dab), _stream()), "msst_block_bwd")
+        ws = eng._bwd_workspace(B, dy.device)
+        dab = ws[3]
+        eng.block_bwd_single(i, acts[i], x1s[i], g_in, other, ws=ws)
         torch.cuda.synchronize()
         os.environ["MSST_DBG"] = "0"
         img = buf.cpu().numpy().view(np.uint8)
