@@ -5,7 +5,12 @@ MI355X-native kernels: build the encoder, optionally initialise it from a SimMIM
 
 The labelled GeoTIFF readers are out of scope: ``--synthetic`` (default) draws standardised random tiles and
 random labels in {-1 .. n_classes-1}, which exercises the identical compute path (BASELINE config 5 checks the
-logits / loss / gradients of that path against the CPU reference in tests/test_gpu_finetune.py)."""
+logits / loss / gradients of that path against the CPU reference in tests/test_gpu_finetune.py).
+
+``shifting_window: True`` in the config, or ``--shifting-window``: a step trains on every non-overlapping window of its 64 x 64
+tiles (64 windows of 8 x 8 per tile; 81 of 7 x 7 with ``--pixelwise``) instead of one random crop per tile, as the reference's
+``train_step`` does; the windows are read out of the tiles on the device (``ViTSpatialSpectral.forward_windows``), and the
+samples/s printed count windows."""
 import argparse
 import random
 import sys
@@ -16,18 +21,20 @@ import torch
 import yaml
 
 from maskedsst_amd import ViTSpatialSpectral
-from maskedsst_amd.config import Dotdict
+from maskedsst_amd.config import Dotdict, parse_flag
 from maskedsst_amd.utils import get_spectral_pos_embedding, load_checkpoint, train_step
 
 SEED = 5
 
 
-def get_finetune_config(path, general_path, seed, device, pixelwise=None):
+def get_finetune_config(path, general_path, seed, device, pixelwise=None, shifting_window=None):
     """reference src/utils.py:337-364 (ViTSpatialSpectral branch; worldcover/dfc spectral positions).  pixelwise: overrides
-    the config's flag before patch_sub is derived from it (None: the config's value)."""
+    the config's flag before patch_sub is derived from it (None: the config's value).  shifting_window: overrides the config's
+    flag (None: the config's value, read as the reference reads it, src/utils.py:254-257)."""
     hp = yaml.safe_load(open(path))
     if pixelwise is not None:
         hp["pixelwise"] = bool(pixelwise)
+    hp["shifting_window"] = parse_flag(hp.get("shifting_window", False)) if shifting_window is None else bool(shifting_window)
     general = yaml.safe_load(open(general_path))
     hp.update(general["data"][hp["dataset"]])
     hp.update(general["transformer"])
@@ -60,6 +67,9 @@ def build_parser():
     ap.add_argument("--pixelwise", action="store_true",
                     help="the centre-pixel classifier (reference pixelwise=True): windows of image_size - 1 (odd), one class "
                          "per window; --val-scenes then predicts dense per-pixel maps (stride 1)")
+    ap.add_argument("--shifting-window", action="store_true", default=None,
+                    help="train on every non-overlapping window of each 64 x 64 tile at once (reference shifting_window=True; overrides "
+                         "the config's shifting_window) instead of one random crop per tile")
     ap.add_argument("--linear-eval", action="store_true", default=None,
                     help="linear evaluation (reference finetune.py:110-136; overrides the config's linear_eval): everything outside "
                          "mlp_head is frozen, the optimizer sees the head only, the step runs no block or tokenizer backward")
@@ -101,7 +111,7 @@ def main():
         raise SystemExit("finetune.py needs an MI355X: maskedsst_amd has no CPU fallback")
     device = torch.device("cuda")
     config = get_finetune_config(f"configs/finetune_config_{args.dataset}.yaml", "configs/config.yaml", SEED, device,
-                                 pixelwise=True if args.pixelwise else None)
+                                 pixelwise=True if args.pixelwise else None, shifting_window=args.shifting_window)
     if args.batch_size:
         config.batch_size = args.batch_size
     if args.linear_eval is not None:
@@ -140,6 +150,9 @@ def main():
             vimg[:, 48:] = 0.0
         vlab = torch.randint(-1, config.n_classes, (args.val_scenes, 64, 64), generator=vgen)
         val = (vimg.to(device), vlab.to(device))
+    # samples of a step: the tiles, or under shifting_window the windows they are cut into (train_step's condition)
+    s = config.image_size - config.patch_sub
+    per_step = config.batch_size * ((64 // s) ** 2 if config.shifting_window and config.image_size != 64 else 1)
     model.train()
     t0 = time.time()
     for step in range(1, args.steps + 1):
@@ -150,7 +163,7 @@ def main():
         loss, acc, macro_acc = train_step(img, label, model, config, device, criterion, optimizer)
         if step % config.logging_freq == 0:
             macro = f" macro_acc {float(macro_acc):.3f}" if fused else ""   # (the eager path has no macro accuracy: it repeats acc)
-            print(f"step {step} loss {loss.item():.4f} acc {float(acc):.3f}{macro} {step * config.batch_size / (time.time() - t0):.1f} samples/s",
+            print(f"step {step} loss {loss.item():.4f} acc {float(acc):.3f}{macro} {step * per_step / (time.time() - t0):.1f} samples/s",
                   flush=True)
         if val is not None and step % args.val_every == 0:
             validate(model, val, step, config.ignored_label, fused=fused)

@@ -151,6 +151,31 @@ int msst_tokenize_scene_fwd(const float* scene, const float* pre_g, const float*
                             const float* pos_b, int pos_split, float* out, int Bs, int Hs, int Ws, int window, int stride,
                             long win0, int nwin, int S, int P, void* stream);
 
+/* Training on the windows of a tile (the reference's shifting_window finetuning: train_step, src/utils.py:608-613, stacks the
+ * non-overlapping s x s windows of every tile along the batch axis with stack_image_batch, :451-474, and trains on all of them).
+ * Additive under MSST_VERSION 109.  The stacked batch is never built: the windows, numbered as above -- stack_image_batch's
+ * '(b h w)' order is that numbering with stride = window -- are read out of the resident tiles.
+ *
+ * msst_tokenize_scene_fwd_train: msst_tokenize_scene_fwd with the embedding dropout of msst_tokenize_fwd.  A dropout element is
+ * addressed by its place in out (window i of the call is sample i of the stacked batch): for every (emb_dropout_p, seed) out is
+ * bit-identical to msst_tokenize_fwd on the copied windows.
+ * msst_tokenize_scene_bwd: msst_tokenize_bwd of those windows (B = nwin), dx0 [nwin][S*window*window][96]; no mask and no mask-token
+ * gradient (the classification path masks nothing).  slab, nchunk, the gradient outputs, pos_split and the dropout regeneration as
+ * there; for equal nchunk every gradient is bit-identical to msst_tokenize_bwd on the copied windows (same kernels, same summation
+ * order, only the pixel addresses differ).  nwin >= 1.
+ * Both check their arguments before anything is enqueued: MSST_ERR_BADARG for a size below 1 (nwin = 0 is an empty forward call), a
+ * null required pointer (dpos_a may be null as in msst_tokenize_bwd) or windows beyond win0 + nwin <= Bs nr nq; MSST_ERR_UNSUPPORTED
+ * outside 1 <= stride <= window <= Hs, Ws, window * window <= 64, P <= 16 (forward, for P != 10 or window != 8: also nwin <= 65535). */
+int msst_tokenize_scene_fwd_train(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb,
+                                  const float* b_emb, const float* post_g, const float* post_b, const float* pos_a,
+                                  const float* pos_b, int pos_split, float* out, int Bs, int Hs, int Ws, int window, int stride,
+                                  long win0, int nwin, int S, int P, float emb_dropout_p, uint32_t seed, void* stream);
+int msst_tokenize_scene_bwd(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb,
+                            const float* b_emb, const float* post_g, const float* post_b, const float* dx0, float* slab,
+                            int nchunk, float* dpre_g, float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g,
+                            float* dpost_b, float* dpos_a, float* dpos_b, int pos_split, int Bs, int Hs, int Ws, int window,
+                            int stride, long win0, int nwin, int S, int P, float emb_dropout_p, uint32_t seed, void* stream);
+
 /* msst_scene_assemble: adds the per-window logits win_logits [nwin][n_classes][window*window] (msst_cls_head_fwd of windows
  * win0 .. win0 + nwin - 1) into the running per-pixel sums logits [Bs][n_classes][Hs][Ws] (fp32).  The calls of one scene batch
  * must cover windows 0, 1, ... in order (any split into calls); logits needs no initialisation.  finalize != 0 (the last call, after

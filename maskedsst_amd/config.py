@@ -12,6 +12,12 @@ class Dotdict(object):
         return f"Dotdict({self.__dict__})"
 
 
+def parse_flag(value):
+    """a boolean switch of the reference's YAMLs as the reference reads it (src/utils.py:254-257, shifting_window): False, "false"
+    and "False" are off, anything else is on"""
+    return value not in (False, "false", "False")
+
+
 def get_pretrain_config(pretrain_config_path, general_config_path, seed, device):
     with open(pretrain_config_path, "r") as f:
         hp = yaml.safe_load(f)

@@ -319,6 +319,38 @@ int msst_tokenize_scene_fwd(const float* scene, const float* pre_g, const float*
     return fail(launch_tokenize_scene_fwd(a, (hipStream_t)stream), "msst_tokenize_scene_fwd");
 }
 
+// the shared argument check of msst_tokenize_scene_fwd_train / msst_tokenize_scene_bwd, in this order: sizes below 1 (BADARG), shapes
+// outside the kernels' limits (UNSUPPORTED), a null required pointer (BADARG), windows beyond the scenes' grids (BADARG).  min_nwin: 0 or 1
+static int scene_train_args(bool pointers, int Bs, int Hs, int Ws, int window, int stride, long win0, int nwin, int min_nwin, int S,
+                            int P, int pos_split, int* nq, long* wps) {
+    if (Bs < 1 || Hs < 1 || Ws < 1 || window < 1 || stride < 1 || S < 1 || P < 1 || nwin < min_nwin || win0 < 0) return MSST_ERR_BADARG;
+    if (stride > window || window > Hs || window > Ws || window > 8 || P > 16) return MSST_ERR_UNSUPPORTED;   // 8: at most 64 pixels per window
+    if (!pointers || pos_split < 0 || pos_split >= 96) return MSST_ERR_BADARG;
+    int nr = 0;
+    scene_grid(Bs, Hs, Ws, window, stride, &nr, nq);
+    *wps = (long)nr * *nq;
+    if (*wps > 0x7fffffffL || win0 + nwin > (long)Bs * *wps) return MSST_ERR_BADARG;
+    return 0;
+}
+
+int msst_tokenize_scene_fwd_train(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb,
+                                  const float* b_emb, const float* post_g, const float* post_b, const float* pos_a,
+                                  const float* pos_b, int pos_split, float* out, int Bs, int Hs, int Ws, int window, int stride,
+                                  long win0, int nwin, int S, int P, float emb_dropout_p, uint32_t seed, void* stream) {
+    int nq = 0;
+    long wps = 0;
+    const bool pointers = scene && pre_g && pre_b && w_emb && b_emb && post_g && post_b && pos_a && (pos_b || !pos_split) && out;
+    if (int rc = scene_train_args(pointers, Bs, Hs, Ws, window, stride, win0, nwin, 0, S, P, pos_split, &nq, &wps))
+        return fail(rc, "msst_tokenize_scene_fwd_train");
+    TokArgs a;
+    a.drop = make_drop(emb_dropout_p, seed, 255);
+    a.img = scene; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb;
+    a.post_g = post_g; a.post_b = post_b; a.pos_a = pos_a; a.pos_b = pos_b; a.mask_token = nullptr; a.mask = nullptr;
+    a.out = out; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P; a.pos_split = pos_split;
+    a.win0 = win0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nq = nq; a.wps = (int)wps;
+    return fail(launch_tokenize_scene_fwd(a, (hipStream_t)stream), "msst_tokenize_scene_fwd_train");
+}
+
 int msst_scene_assemble(const float* win_logits, long win0, int nwin, float* logits, int64_t* classes, int Bs,
                         int n_classes, int Hs, int Ws, int window, int stride, int finalize, void* stream) {
     int nr = 0, nq = 0;
@@ -723,20 +755,12 @@ int msst_block_bwd_reduce(const MsstBlockGrads* g, const MsstBlockGrads* g_prev,
                                    slab_stride, grad_stride, (hipStream_t)stream), "msst_block_bwd_reduce");
 }
 
-int msst_tokenize_bwd(const float* img, const float* pre_g, const float* pre_b, const float* w_emb,
-                      const float* b_emb, const float* post_g, const float* post_b, const uint8_t* mask,
-                      const float* dx0, float* slab, int nchunk, float* dpre_g, float* dpre_b,
-                      float* dw_emb, float* db_emb, float* dpost_g, float* dpost_b, float* dpos_a,
-                      float* dpos_b, int pos_split, float* dmask_token, int B, int S, int N, int P,
-                      float emb_dropout_p, uint32_t seed, void* stream) {
-    if (nchunk < 1) return fail(MSST_ERR_BADARG, "msst_tokenize_bwd");
-    hipStream_t st = (hipStream_t)stream;
-    TokBwdArgs a;
-    a.drop = make_drop(emb_dropout_p, seed, 255);
-    a.img = img; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb; a.post_g = post_g;
-    a.post_b = post_b; a.mask = mask; a.dx0 = dx0; a.slab = slab; a.B = B; a.S = S; a.N = N; a.T = S * N; a.P = P;
-    int rc = launch_tokenize_bwd(a, nchunk, st);
-    if (rc) return fail(rc, "msst_tokenize_bwd");
+// the tokenizer backward's second half: the slabs its kernel wrote, summed into the gradients (msst_tokenize_bwd and
+// msst_tokenize_scene_bwd: one table, one summation order)
+static int tokenize_bwd_reduce(float* slab, int nchunk, float* dpre_g, float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g,
+                               float* dpost_b, float* dpos_a, float* dpos_b, int pos_split, float* dmask_token, int S, int N, int P,
+                               hipStream_t st) {
+    int rc = 0;
     const long ss = (long)N * 96 + 96 * P + 96 * 4 + 32;
     const long bs = (long)nchunk * ss;
     float* stage = slab + (long)S * nchunk * ss;  // [S][N][96] position-gradient staging
@@ -765,6 +789,47 @@ int msst_tokenize_bwd(const float* img, const float* pre_g, const float* pre_b, 
     rc = launch_reduce_segs(rb.r, st);
     if (!rc && pos_split && dpos_a) rc = launch_pos_split(stage, S, N, pos_split, dpos_a, dpos_b, st);
     return fail(rc, "msst_tokenize_bwd(reduce)");
+}
+
+int msst_tokenize_bwd(const float* img, const float* pre_g, const float* pre_b, const float* w_emb,
+                      const float* b_emb, const float* post_g, const float* post_b, const uint8_t* mask,
+                      const float* dx0, float* slab, int nchunk, float* dpre_g, float* dpre_b,
+                      float* dw_emb, float* db_emb, float* dpost_g, float* dpost_b, float* dpos_a,
+                      float* dpos_b, int pos_split, float* dmask_token, int B, int S, int N, int P,
+                      float emb_dropout_p, uint32_t seed, void* stream) {
+    if (nchunk < 1) return fail(MSST_ERR_BADARG, "msst_tokenize_bwd");
+    hipStream_t st = (hipStream_t)stream;
+    TokBwdArgs a;
+    a.drop = make_drop(emb_dropout_p, seed, 255);
+    a.img = img; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb; a.post_g = post_g;
+    a.post_b = post_b; a.mask = mask; a.dx0 = dx0; a.slab = slab; a.B = B; a.S = S; a.N = N; a.T = S * N; a.P = P;
+    int rc = launch_tokenize_bwd(a, nchunk, st);
+    if (rc) return fail(rc, "msst_tokenize_bwd");
+    return tokenize_bwd_reduce(slab, nchunk, dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, dmask_token,
+                               S, N, P, st);
+}
+
+int msst_tokenize_scene_bwd(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb,
+                            const float* b_emb, const float* post_g, const float* post_b, const float* dx0, float* slab,
+                            int nchunk, float* dpre_g, float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g,
+                            float* dpost_b, float* dpos_a, float* dpos_b, int pos_split, int Bs, int Hs, int Ws, int window,
+                            int stride, long win0, int nwin, int S, int P, float emb_dropout_p, uint32_t seed, void* stream) {
+    int nq = 0;
+    long wps = 0;
+    const bool pointers = scene && pre_g && pre_b && w_emb && b_emb && post_g && post_b && dx0 && slab && dpre_g && dpre_b && dw_emb &&
+                          db_emb && dpost_g && dpost_b && (dpos_b || !pos_split || !dpos_a);
+    if (int rc = scene_train_args(pointers, Bs, Hs, Ws, window, stride, win0, nwin, 1, S, P, pos_split, &nq, &wps))
+        return fail(rc, "msst_tokenize_scene_bwd");
+    if (nchunk < 1) return fail(MSST_ERR_BADARG, "msst_tokenize_scene_bwd");
+    hipStream_t st = (hipStream_t)stream;
+    TokSceneBwdArgs a;
+    a.drop = make_drop(emb_dropout_p, seed, 255);
+    a.img = scene; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb; a.post_g = post_g;
+    a.post_b = post_b; a.mask = nullptr; a.dx0 = dx0; a.slab = slab; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P;
+    a.win0 = win0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nq = nq; a.wps = (int)wps;
+    if (int rc = launch_tokenize_scene_bwd(a, nchunk, st)) return fail(rc, "msst_tokenize_scene_bwd");
+    return tokenize_bwd_reduce(slab, nchunk, dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, nullptr,
+                               S, a.N, P, st);
 }
 
 // shape of the default head: 0, MSST_ERR_BADARG (a size below 1) or MSST_ERR_UNSUPPORTED (beyond the kernels' limits; any n_classes)

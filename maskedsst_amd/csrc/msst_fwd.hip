@@ -22,7 +22,8 @@ namespace msst {
 // PC: pixels per patch as a compile-time constant (10 = the reference's spectral patch, configs/config.yaml: band_patch_size)
 // so that the small loops over it unroll and their LDS reads are batched; 0 = run-time value (any P <= 16)
 // SCENE: addressing policy of the source pixels.  false: img[b, c P + k, n] of a batch of cubes [B][S*P][N];  true: the same pixel of
-// window b of a scene, scene[s, c P + k, y0 + n / win, x0 + n % win] (TokArgs scene fields; no mask, no dropout).  Nothing else differs.
+// window b of a scene, scene[s, c P + k, y0 + n / win, x0 + n % win] (TokArgs scene fields; no mask).  Nothing else differs: the
+// embedding dropout addresses an element by its place in `out` in both (msst_tokenize_scene_fwd passes p = 0).
 template <int PC, bool SCENE>
 __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
     __shared__ float patch[16][64];
@@ -95,7 +96,7 @@ __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
         f32x4 v = {e[4*i], e[4*i+1], e[4*i+2], e[4*i+3]};
-        if (!SCENE && a.drop.thr) v = drop4(a.drop, 0, (unsigned)(((long)b * a.T + t) * 24 + 4 * i + part), v);   // emb dropout (group = feature / 4)
+        if (a.drop.thr) v = drop4(a.drop, 0, (unsigned)(((long)b * a.T + t) * 24 + 4 * i + part), v);   // emb dropout (group = feature / 4)
         *reinterpret_cast<f32x4*>(dst + 16 * i) = v;
     }
 }
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void tokenize_scene_fwd_kernel(TokArgs a) { to
 // layout), and the C layout (4 consecutive features of one token per lane) is the 16-byte store of the token row.
 // grid (S, nchunk), 256 threads: wave w <-> tokens 16 w .. + 15 of spectral block c, samples chunk, chunk + nchunk, ...
 // Position rows, bias, both LayerNorms' vectors and the mask token are tile invariant for a wave: registers / LDS.
-// SCENE: the source addressing policy of tokenize_fwd_body (windows of a scene instead of a batch of cubes; no mask, no dropout).
+// SCENE: the source addressing policy of tokenize_fwd_body (windows of a scene instead of a batch of cubes; no mask).
 // ------------------------------------------------------------------------------------------
 template <bool SCENE>
 __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
@@ -215,7 +216,7 @@ __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
             f32x4 v;
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = (masked ? m4[r] : (e[mt][r] - m2) * rstd2 * g4[r] + b4[r]) + pos4[mt][r];
-            if (!SCENE && a.drop.thr) v = drop4(a.drop, 0, (unsigned)(((long)b * a.T + t) * 24 + 4 * mt + g), v);   // emb dropout (group = feature / 4)
+            if (a.drop.thr) v = drop4(a.drop, 0, (unsigned)(((long)b * a.T + t) * 24 + 4 * mt + g), v);   // emb dropout (group = feature / 4)
             *reinterpret_cast<f32x4*>(dst + 16 * mt) = v;
         }
     }

@@ -79,14 +79,16 @@ struct TokArgs {
     float* out;              // [B][T][96]
     int B, S, N, T, P, pos_split;
     Drop drop;               // embedding dropout on (token + pos) (vit_spatial_spectral.py:530), classification path only
-    // scene windows (msst_tokenize_scene_fwd, the kernels' SCENE = true instances only): img is a scene [Bs][S*P][Hs][Ws] and
+    // scene windows (msst_tokenize_scene_fwd / _fwd_train, the kernels' SCENE = true instances only): img is a scene [Bs][S*P][Hs][Ws] and
     // sample b is window win0 + b, row-major over (scene, window row, window column), origin (r * stride, q * stride), win x win pixels
     long win0;
     int Hs, Ws, win, stride, nq, wps;   // nq: windows per window row, wps: windows per scene
 };
 
 // img pointer of sample b's window origin (scene s, band 0, row r * stride, column q * stride); 64-bit: scenes may be large
-__device__ __forceinline__ const float* scene_window_origin(const TokArgs& a, int b) {
+// (Args: TokArgs or TokSceneBwdArgs, the same scene fields)
+template <class Args>
+__device__ __forceinline__ const float* scene_window_origin(const Args& a, int b) {
     const long i = a.win0 + b;
     const long s = i / a.wps;
     const int rem = (int)(i - s * a.wps), r = rem / a.nq, q = rem - r * a.nq;
@@ -187,6 +189,11 @@ struct TokBwdArgs {
     int B, S, N, T, P;
     Drop drop;
 };
+// msst_tokenize_scene_bwd (the kernels' SCENE = true instances): img is a scene, sample b its window win0 + b -- the scene fields of TokArgs
+struct TokSceneBwdArgs : TokBwdArgs {
+    long win0;
+    int Hs, Ws, win, stride, nq, wps;
+};
 
 // ---- opt-in per-kernel timing with HIP events on the launch stream (bench.py roofline leg) ----
 enum KernelId {
@@ -285,6 +292,7 @@ int launch_block_bwd_attn_r4(const AttnBwdArgs& a, int nchunk, hipStream_t st); 
 int launch_block_bwd_ln1(const Ln1BwdArgs& a, int grid, int prec, hipStream_t st);
 int launch_block_bwd_ln1mlp(const LnMlpArgs& a, int grid, hipStream_t st);   // msst_bwd5.hip (bf16: LN1 backward of block i + MLP backward of block i - 1)
 int launch_tokenize_bwd(const TokBwdArgs& a, int nchunk, hipStream_t st);
+int launch_tokenize_scene_bwd(const TokSceneBwdArgs& a, int nchunk, hipStream_t st);   // the same kernels reading windows of a scene (no mask)
 int launch_pos_split(const float* dpos, int S, int N, int split, float* dpe, float* dce, hipStream_t st);
 int launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                  float wd, int step, float clamp, float gscale, hipStream_t st);

@@ -357,6 +357,43 @@ class Engine:
             B, S, N, P, emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_fwd")
         return out
 
+    # the generic tokenizer kernels run one grid row per window; the fp32-MFMA ones (P = 10, 8 x 8 windows) walk any number
+    TILE_WINDOWS_PER_LAUNCH = 65535
+
+    def tile_grid(self, tiles):
+        """(s, nr, nq): the window side and the window grid of one tile of tiles [B, C, Ht, Wt] -- the reference's stack_image_batch
+        (src/utils.py:451-474): non-overlapping s x s windows, s = the model's image size, trailing Ht % s rows / Wt % s columns dropped"""
+        s = self.enc.num_spatial_patches_sqrt
+        return s, tiles.shape[-2] // s, tiles.shape[-1] // s
+
+    def tokenize_windows(self, img, emb_drop=(0.0, 0), tiles=False):
+        """the classification path's tokens (nothing masked, position added, embedding dropout): of a window batch img [B, C, s, s]
+        (tokenize), or with tiles=True of every window of tiles [B, C, Ht, Wt] in stack_image_batch's order, read straight out of
+        the tiles (msst_tokenize_scene_fwd_train) -> [B nr nq, T, 96], bit for bit what tokenize gives for the stacked copy"""
+        if not tiles:
+            return self.tokenize(img, None, emb_drop=emb_drop)
+        self._require_cuda(img)
+        self.ensure()
+        B, _, Ht, Wt = img.shape
+        S, N, P = self.S, self.N, self.P
+        s, nr, nq = self.tile_grid(img)
+        total = B * nr * nq
+        out = torch.empty(total, S * N, D, dtype=torch.float32, device=img.device)
+        chunk = total if (P == 10 and s == 8) else min(total, self.TILE_WINDOWS_PER_LAUNCH)
+        if chunk < total and emb_drop[0] > 0:
+            # a dropout element is addressed by its place in one launch's output: launches in turn would repeat the first one's masks
+            raise NotImplementedError(f"embedding dropout over {total} windows in one step needs more than one launch of the generic "
+                                      f"tokenizer ({self.TILE_WINDOWS_PER_LAUNCH} windows each): use fewer tiles per step")
+        fp = self.fp
+        split, pos_a, pos_b = self._pos_tables()
+        V = ctypes.c_void_p
+        for win0 in range(0, total, chunk):
+            _lib.check(self.lib.msst_tokenize_scene_fwd_train(
+                _p(img), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
+                V(fp.ptr("post_g")), V(fp.ptr("post_b")), V(pos_a), V(pos_b), split, _p(out[win0:]), B, Ht, Wt, s, s, win0,
+                min(chunk, total - win0), S, P, emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_scene_fwd_train")
+        return out
+
     def blocks_fwd(self, x0, save=True, drop=(0.0, 0)):
         """run the 2*depth fused blocks; returns (list of activations [x0 .. x_2L], list of x1)"""
         acts = [x0]
@@ -703,6 +740,30 @@ class Engine:
         if with_pos:
             self._fire("tokenizer")
 
+    def tokenize_windows_bwd(self, img, dx0, emb_drop=(0.0, 0), tiles=False):
+        """backward of tokenize_windows: dx0 [windows, T, 96] -> the tokenizer's gradients in the flat buffer.  Tiles: one
+        msst_tokenize_scene_bwd over all windows, with the nchunk tokenize_bwd takes for as many samples -- the same bits."""
+        if not tiles:
+            zero_mask = self._zero_mask_for(img.shape[0] * self.S * self.N, img.device)
+            return self.tokenize_bwd(img, zero_mask, dx0, emb_drop=emb_drop)
+        B, _, Ht, Wt = img.shape
+        S, N, P = self.S, self.N, self.P
+        s, nr, nq = self.tile_grid(img)
+        total = B * nr * nq
+        nchunk = max(1, min(total, self.tok_chunks))
+        ss = N * 96 + 96 * P + 96 * 4 + 32
+        slab = torch.empty(S * nchunk * ss + S * N * 96, dtype=torch.float32, device=img.device)
+        fp, g = self.fp, self.fp.grad
+        V = ctypes.c_void_p
+        split, dpa, dpb = self._pos_tables(g)
+        _lib.check(self.lib.msst_tokenize_scene_bwd(
+            _p(img), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
+            V(fp.ptr("post_g")), V(fp.ptr("post_b")), _p(dx0), _p(slab), nchunk,
+            V(fp.ptr("pre_g", g)), V(fp.ptr("pre_b", g)), V(fp.ptr("embed.w.0", g)), V(fp.ptr("embed.b.0", g)),
+            V(fp.ptr("post_g", g)), V(fp.ptr("post_b", g)), V(dpa), V(dpb), split, B, Ht, Wt, s, s, 0, total, S, P,
+            emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_scene_bwd")
+        self._fire("tokenizer")
+
     # ------------------------------------------------------------------ autograd entry (SimMIM loss)
     def trainable(self):
         """[(flat name, parameter)] of everything that receives a gradient in pre-training"""
@@ -926,7 +987,27 @@ class Engine:
         for B = 1, the reference's squeeze)."""
         self._require_cuda(img)
         self.ensure()
-        img = img.contiguous().float()
+        return self._classify(img.contiguous().float(), img.shape[0], False)
+
+    def classify_tiles(self, tiles):
+        """classify(stack_image_batch(tiles)) without the stacked copy: logits of every non-overlapping s x s window of tiles
+        [B, C, Ht, Wt] (s = the model's image size; trailing Ht % s rows and Wt % s columns dropped), windows numbered (tile, window
+        row, window column) -- the reference's shifting_window training batch (src/utils.py:608-613, :451-474).  [B nr nq, num_classes,
+        s, s]; pixelwise: [B nr nq, num_classes].  The three regimes of classify, the same seeds drawn in the same order (equal
+        torch.manual_seed: equal bits), and what is kept for the backward is the tiles.
+        Limit: windows other than 8 x 8 of 10-band patches (a pixelwise model's 7 x 7) run the generic tokenizer, 65535 windows per
+        launch; more windows than that in one call are tokenized in several launches, but with embedding dropout on the call raises
+        NotImplementedError (a dropout element is addressed by its place in one launch's output)."""
+        self._require_cuda(tiles)
+        self.ensure()
+        tiles = tiles.contiguous().float()
+        s, nr, nq = self.tile_grid(tiles)
+        if nr < 1 or nq < 1:
+            raise ValueError(f"tiles of {tuple(tiles.shape[-2:])} hold no {s} x {s} window")
+        return self._classify(tiles, tiles.shape[0] * nr * nq, True)
+
+    def _classify(self, img, B, tiles):
+        """classify / classify_tiles: img a batch of B windows, or (tiles) the tiles that hold B windows"""
         p = float(self.enc.dropout_p) if self.enc.training else 0.0
         pe = float(self.enc.emb_dropout_p) if self.enc.training else 0.0
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if (p > 0 or pe > 0) else 0
@@ -937,22 +1018,22 @@ class Engine:
                 raise NotImplementedError("train the classifier through a bare ViTSpatialSpectral (as finetune.py "
                                           "does), not through an encoder wrapped in SimMIMSpatialSpectral")
             self.prep_weights()
-            x0 = self.tokenize(img, None, emb_drop=emb_drop)
+            x0 = self.tokenize_windows(img, emb_drop, tiles)
             acts, _ = self.blocks_fwd(x0, save=False, drop=drop)
-            return self._classify_view(self.head_logits(acts[-1]), img.shape[0])
+            return self._classify_view(self.head_logits(acts[-1]), B)
         named = self.trainable()
         if not any(q.requires_grad for n, q in named if not n.startswith("mlp_head.")):
             # linear evaluation (reference finetune.py:110-136: only mlp_head trains): the body runs as in a no-gradient forward --
             # module still in training mode, so its dropout stays on -- with nothing saved, and only the head has a backward
             self.prep_weights()
-            x0 = self.tokenize(img, None, emb_drop=emb_drop)
+            x0 = self.tokenize_windows(img, emb_drop, tiles)
             y = self.blocks_fwd_pingpong(x0, drop=drop)
             head = [(n, q) for n, q in named if n.startswith("mlp_head.")]
             out = _HeadOnlyFn.apply(self, [n for n, _ in head], y, *[q for _, q in head])
-            return self._classify_view(out, img.shape[0])
+            return self._classify_view(out, B)
         names = [n for n, _ in named]
-        out = _ClassifyFn.apply(self, names, drop, emb_drop, img, *params)
-        return self._classify_view(out, img.shape[0])
+        out = _ClassifyFn.apply(self, names, drop, emb_drop, tiles, img, *params)
+        return self._classify_view(out, B)
 
     # ------------------------------------------------------------------ scene inference (maskedsst_amd/scene.py, msst_scene_assemble)
     def scene_forward(self, scene, stride, max_windows):
@@ -1106,15 +1187,16 @@ class _EmbedFn(torch.autograd.Function):
 
 
 class _ClassifyFn(torch.autograd.Function):
-    """logits = encoder(img) for the classification path; backward through the same HIP kernels."""
+    """logits = encoder(img) for the classification path; backward through the same HIP kernels.  img: a window batch, or (tiles) tiles
+    whose windows both tokenizer passes read in place (Engine.tokenize_windows) -- the stash holds img as it came."""
 
     @staticmethod
-    def forward(ctx, eng, names, drop, emb_drop, img, *params):
+    def forward(ctx, eng, names, drop, emb_drop, tiles, img, *params):
         eng.prep_weights()
-        x0 = eng.tokenize(img, None, emb_drop=emb_drop)
+        x0 = eng.tokenize_windows(img, emb_drop, tiles)
         acts, x1s = eng.blocks_fwd(x0, save=True, drop=drop)
         logits = eng.head_logits(acts[-1])
-        ctx.eng, ctx.names, ctx.drop, ctx.emb_drop = eng, names, drop, emb_drop
+        ctx.eng, ctx.names, ctx.drop, ctx.emb_drop, ctx.tiles = eng, names, drop, emb_drop, tiles
         ctx.stash = (img, acts, x1s)
         return logits
 
@@ -1126,9 +1208,8 @@ class _ClassifyFn(torch.autograd.Function):
         _refuse_accumulation(eng, ctx.names)
         dy = eng.head_logits_bwd(acts[-1], dlogits.contiguous().float())
         dx0 = eng.blocks_bwd(acts, x1s, dy, drop=ctx.drop)
-        zero_mask = eng._zero_mask_for(img.shape[0] * eng.S * eng.N, img.device)
-        eng.tokenize_bwd(img, zero_mask, dx0, emb_drop=ctx.emb_drop)
-        return (None,) * 5 + _grad_views(eng, ctx.names)
+        eng.tokenize_windows_bwd(img, dx0, emb_drop=ctx.emb_drop, tiles=ctx.tiles)
+        return (None,) * 6 + _grad_views(eng, ctx.names)
 
 
 class _HeadOnlyFn(torch.autograd.Function):

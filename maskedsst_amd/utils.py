@@ -79,6 +79,28 @@ def load_checkpoint(config, model, classifier_name="mlp_head", device="cpu", che
     return model
 
 
+def stack_image_batch(config, img, label):
+    """reference src/utils.py:451-474: cut img [B, C, H, W] and label [B, H, W] into their non-overlapping s x s windows,
+    s = image_size - patch_sub, stacked along the batch axis in (tile, window row, window column) order -- the numbering of
+    maskedsst_amd.scene.scene_windows(H, W, s, s) per tile; the trailing H % s rows and W % s columns are dropped (the reference
+    asserts that both remainders are equal).  Plain torch: train_step stacks the labels with its label half (stack_windows), the images stay where they are
+    (ViTSpatialSpectral.forward_windows reads the windows out of the tiles)."""
+    s = config.image_size - getattr(config, "patch_sub", 0)
+    cutoff_h, cutoff_w = img.shape[2] % s, img.shape[3] % s
+    assert cutoff_h == cutoff_w
+    return stack_windows(img, s), stack_windows(label, s)
+
+
+def stack_windows(t, s):
+    """one tensor's half of stack_image_batch: t [B, C, H, W] -> [B nr nq, C, s, s], or a label map [B, H, W] -> [B nr nq, s, s]"""
+    nr, nq = t.shape[-2] // s, t.shape[-1] // s
+    lead = t.shape[:-2]   # (B, C) or (B,)
+    t = t[..., :nr * s, :nq * s].reshape(*lead, nr, s, nq, s)
+    if len(lead) == 2:
+        return t.permute(0, 2, 4, 1, 3, 5).reshape(lead[0] * nr * nq, lead[1], s, s)
+    return t.permute(0, 1, 3, 2, 4).reshape(lead[0] * nr * nq, s, s)
+
+
 def train_step(img, label, model, config, device, criterion, optimizer, acc_criterion=None):
     """reference src/utils.py:608-663 for the ViTSpatialSpectral method: optional random crop, forward,
     CE(ignore_index) loss, pixel accuracy on valid labels, backward, optimizer step.  With ``config.pixelwise`` a label
@@ -86,9 +108,16 @@ def train_step(img, label, model, config, device, criterion, optimizer, acc_crit
     :630-636); a label that is already one class per sample ([B]) passes through unchanged.
     ``criterion`` a ``maskedsst_amd.ops.FusedCrossEntropy``: loss, gradient and counts come from one pass of the HIP loss kernels,
     ``macro_acc`` is the true macro accuracy (mean per-class recall) and the step reads the device back once (``_fused_tail``).  Any
-    other criterion: the eager path below, unchanged."""
+    other criterion: the eager path below, unchanged.
+    ``config.shifting_window`` (reference :608-613) on 64 x 64 tiles: no crop -- the step trains on every non-overlapping window of
+    the tiles at once (``stack_image_batch`` order; 64 windows of 8 x 8 per tile, 81 of 7 x 7 for a pixelwise model), the labels are
+    stacked, the images are not: ``model.forward_windows`` reads the windows out of the tiles on the device."""
     patch_sub = getattr(config, "patch_sub", 0)
-    if config.image_size != 64 and img.shape[-1] == 64:
+    windows = bool(getattr(config, "shifting_window", False)) and config.image_size != 64 and img.shape[-1] == 64
+    if windows:
+        assert img.shape[2] % (config.image_size - patch_sub) == img.shape[3] % (config.image_size - patch_sub)   # stack_image_batch's
+        label = stack_windows(label, config.image_size - patch_sub)   # the labels alone: the tiles go to the device as they are
+    elif config.image_size != 64 and img.shape[-1] == 64:
         x, y = torch.randint(0, 64 - config.image_size - patch_sub, size=(2,))
         s = config.image_size - patch_sub
         img = img[:, :, x:x + s, y:y + s]
@@ -99,7 +128,7 @@ def train_step(img, label, model, config, device, criterion, optimizer, acc_crit
     img = img.to(device)
     label = label.to(device)
     optimizer.zero_grad()
-    output = model(img)
+    output = model.forward_windows(img) if windows else model(img)
     if getattr(criterion, "fused_stats", False):
         return _fused_tail(output, label, criterion, optimizer)
     loss = criterion(output, label)

@@ -334,6 +334,24 @@ class ViTSpatialSpectral(nn.Module):
         squeeze)."""
         return self.engine().classify(img)
 
+    def forward_windows(self, tiles):
+        """forward(stack_image_batch(tiles)) without the stacked copy (the reference's shifting_window training batch, src/utils.py
+        :608-613, :451-474): logits of every non-overlapping image_size x image_size window of tiles [B, channels, Ht, Wt], windows
+        ordered (tile, window row, window column), trailing Ht % image_size rows and Wt % image_size columns dropped ->
+        [B nr nq, num_classes, image_size, image_size]; pixelwise: [B nr nq, num_classes].  Differentiable exactly as forward is, the
+        same bits.  Raises ValueError for tiles of the wrong rank or band count, or smaller than one window; NotImplementedError in
+        training mode with embedding dropout for more than 65535 windows per call of a model whose windows are not 8 x 8 with
+        10-band patches (Engine.classify_tiles)."""
+        s = self.num_spatial_patches_sqrt
+        if tiles.dim() != 4:
+            raise ValueError(f"tiles must be [B, channels, Ht, Wt], got {tuple(tiles.shape)}")
+        bands = self.num_spectral_patches * self.patch_depth
+        if tiles.shape[1] != bands:
+            raise ValueError(f"tiles have {tiles.shape[1]} bands, the model expects {bands}")
+        if tiles.shape[2] < s or tiles.shape[3] < s:
+            raise ValueError(f"tiles of {tuple(tiles.shape[2:])} are smaller than one {s} x {s} window")
+        return self.engine().classify_tiles(tiles)
+
     def predict_scene(self, scene, stride=None, return_logits=False, max_windows=None):
         """Classify whole scenes [Bs, channels, Hs, Ws] with sliding windows of image_size (the window loop of the reference's
         inference_example.ipynb, one batched pass): returns the class map [Bs, Hs, Ws] (int64; -1 where no window covers a

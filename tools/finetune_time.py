@@ -17,6 +17,11 @@ numbers and the NaN check with their host synchronisations, not the bare ``F.cro
 (``...+loss_torch`` / ``...+loss_fused``), alternated step by step in the one process.  ``--legs`` keeps the legs whose name contains
 one of the given words.
 
+``--shifting-window``: the shifting_window step instead -- ``--tiles`` 64 x 64 tiles per step (4: 256 windows), full finetune with
+torch.optim.Adam, the bare ``F.cross_entropy`` step; two legs on ONE model, alternated step by step: ``tiles`` =
+``model.forward_windows(tiles)`` (the windows read out of the resident tiles), ``stacked`` = ``model(stack_windows(tiles, 8))`` -- stack_image_batch's image half --
+(the stacked copy made inside the timed step, as a caller without forward_windows has to).
+
 Prints ONE JSON line.  Run:  python tools/finetune_time.py [--steps 20] [--reps 3] [--warmup 5] [--precision bf16] [--batch 256]
                                                            [--loss both] [--legs linear_eval+fused full+torch]
 """
@@ -90,6 +95,52 @@ def box_probe(model):
     return {} if rc else dict(mfma_tflops=round(out[0], 1), shader_mhz=round(out[1], 1))
 
 
+def shifting_window(args, dev):
+    from maskedsst_amd.utils import stack_windows
+    config, model = build(args.precision, dev, False)
+    opt = optimizer(model, config, "torch")
+    gen = torch.Generator().manual_seed(finetune.SEED)
+    tiles = torch.randn(args.tiles, config.n_bands, 64, 64, generator=gen).to(dev)
+    label = torch.randint(-1, config.n_classes, (args.tiles, 64, 64), generator=gen).to(dev)
+    size = config.image_size - config.patch_sub
+    slabel = stack_windows(label, size).contiguous()
+
+    def step(name):
+        opt.zero_grad()
+        if name == "tiles":
+            out = model.forward_windows(tiles)
+        else:
+            out = model(stack_windows(tiles, size).contiguous())   # the image alone: the labels are stacked once, outside
+        F.cross_entropy(out, slabel, ignore_index=-1).backward()
+        opt.step()
+
+    legs = ("tiles", "stacked")
+    for _ in range(args.warmup):
+        for name in legs:
+            step(name)
+    probe = box_probe(model)
+    reps = {name: [] for name in legs}
+    for _ in range(args.reps):
+        t = {name: [] for name in legs}
+        for _ in range(args.steps):
+            for name in legs:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                step(name)
+                e1.record()
+                e1.synchronize()
+                t[name].append(e0.elapsed_time(e1))
+        for name in legs:
+            reps[name].append(round(statistics.median(t[name]), 4))
+    res = dict(tool="finetune_time", mode="shifting_window",
+               shape=dict(tiles=args.tiles, windows=int(slabel.shape[0]), bands=config.n_bands, depth=config.transformer_depth,
+                          n_classes=config.n_classes, image_size=config.image_size),
+               precision=args.precision, steps=args.steps, warmup=args.warmup, box_probe=probe,
+               step_ms={name: round(statistics.median(v), 4) for name, v in reps.items()}, step_ms_reps=reps,
+               step_ms_spread={name: round(max(v) - min(v), 4) for name, v in reps.items()})
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -100,8 +151,12 @@ def main():
     ap.add_argument("--loss", default=None, choices=["torch", "fused", "both"],
                     help="time utils.train_step with this criterion (default: the bare F.cross_entropy step)")
     ap.add_argument("--legs", nargs="*", default=None, help="keep the legs whose name contains one of these words")
+    ap.add_argument("--shifting-window", action="store_true", help="time the tile path against the stacked copy (see above)")
+    ap.add_argument("--tiles", type=int, default=4, help="--shifting-window: 64 x 64 tiles per step")
     args = ap.parse_args()
     dev = torch.device("cuda")
+    if args.shifting_window:
+        return shifting_window(args, dev)
     legs = {}
     losses = [None] if args.loss is None else ["torch", "fused"] if args.loss == "both" else [args.loss]
     for mode, linear_eval in (("full", False), ("linear_eval", True)):
