@@ -78,15 +78,39 @@ def build_parser():
     ap.add_argument("--loss", default="torch", choices=["torch", "fused"],
                     help="torch: torch.nn.CrossEntropyLoss and eager accuracy; fused: maskedsst_amd.ops.FusedCrossEntropy (loss, gradient, "
                          "accuracy and macro accuracy from one pass of the HIP loss kernels, one read-back per step; also in validation)")
+    ap.add_argument("--class-weights", default="none", choices=["none", "inverse"],
+                    help="inverse: weight every class by 1 / its frequency among the first step's non-ignored labels, normalised to "
+                         "mean 1 over the classes present there, 0 for an absent class (CrossEntropyLoss(weight=), both --loss kinds)")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, metavar="EPS", help="CrossEntropyLoss(label_smoothing=EPS), in [0, 1)")
+    ap.add_argument("--val-report", action="store_true",
+                    help="one more line per validation: overall and average accuracy, Cohen's kappa and mean IoU from the confusion "
+                         "matrix of the same pass of the HIP loss kernels (maskedsst_amd.scene.scene_report)")
     return ap
 
 
-def make_criterion(kind, ignored_label):
-    """reference finetune.py:136: CrossEntropyLoss(ignore_index=ignored_label)"""
+def inverse_frequency_weights(label, n_classes, ignored_label):
+    """--class-weights inverse: 1 / frequency of each class among the labels of `label` that are not ignored (and lie in
+    [0, n_classes)), normalised to mean 1 over the classes present, 0 for a class that is absent.  -> float32 [n_classes] (CPU)"""
+    lab = label.reshape(-1)
+    lab = lab[(lab != ignored_label) & (lab >= 0) & (lab < n_classes)]
+    count = torch.bincount(lab, minlength=n_classes).double()
+    present = count > 0
+    w = torch.zeros(n_classes, dtype=torch.float64)
+    if present.any():
+        w[present] = count.sum() / count[present]
+        w /= w[present].mean()
+    return w.float()
+
+
+def make_criterion(kind, ignored_label, weight=None, label_smoothing=0.0):
+    """reference finetune.py:136: CrossEntropyLoss(ignore_index=ignored_label); weight / label_smoothing: the DeepHyperX protocol's
+    CrossEntropyLoss(weight=...) (reference DeepHyperX/models.py:37-72) and torch's label smoothing, on either kind"""
     if kind == "fused":
         from maskedsst_amd.ops import FusedCrossEntropy
-        return FusedCrossEntropy(ignore_index=ignored_label)
-    return torch.nn.CrossEntropyLoss(ignore_index=ignored_label)
+        return FusedCrossEntropy(ignore_index=ignored_label, weight=weight, label_smoothing=label_smoothing)
+    if weight is None and not label_smoothing:
+        return torch.nn.CrossEntropyLoss(ignore_index=ignored_label)
+    return torch.nn.CrossEntropyLoss(weight=weight, ignore_index=ignored_label, label_smoothing=label_smoothing)
 
 
 def make_optimizer(model, config, kind):
@@ -138,7 +162,10 @@ def main():
         for n, p in model.named_parameters():
             p.requires_grad_("mlp_head" in n)
     optimizer = make_optimizer(model, config, args.optimizer)
-    criterion = make_criterion(args.loss, config.ignored_label)
+    if not 0.0 <= args.label_smoothing < 1.0:
+        raise SystemExit("--label-smoothing must lie in [0, 1)")
+    # --class-weights inverse: the weights come from the first step's labels, so the criterion is made there
+    criterion = make_criterion(args.loss, config.ignored_label, None, args.label_smoothing) if args.class_weights == "none" else None
     fused = args.loss == "fused"
     gen = torch.Generator().manual_seed(SEED)
     val = None
@@ -160,24 +187,34 @@ def main():
         if config.dataset == "houston2018":
             img[:, 48:] = 0.0   # 48 real bands zero padded to 50 (reference src/data_houston2018.py:268-269)
         label = torch.randint(-1, config.n_classes, (config.batch_size, 64, 64), generator=gen)
+        if criterion is None:
+            weight = inverse_frequency_weights(label, config.n_classes, config.ignored_label)
+            print("class weights " + " ".join(f"{v:.4f}" for v in weight.tolist()), flush=True)
+            criterion = make_criterion(args.loss, config.ignored_label, weight, args.label_smoothing).to(device)
         loss, acc, macro_acc = train_step(img, label, model, config, device, criterion, optimizer)
         if step % config.logging_freq == 0:
             macro = f" macro_acc {float(macro_acc):.3f}" if fused else ""   # (the eager path has no macro accuracy: it repeats acc)
             print(f"step {step} loss {loss.item():.4f} acc {float(acc):.3f}{macro} {step * per_step / (time.time() - t0):.1f} samples/s",
                   flush=True)
         if val is not None and step % args.val_every == 0:
-            validate(model, val, step, config.ignored_label, fused=fused)
+            validate(model, val, step, config.ignored_label, fused=fused, report=args.val_report)
 
 
-def validate(model, val, step, ignored_label, fused=False):
+def validate(model, val, step, ignored_label, fused=False, report=False):
     """validate_downstream (reference src/utils.py:477-605) over whole scenes: one predict_scene pass (windows of image_size,
     eval forward, the module's mode untouched; a pixelwise model: one window per pixel, its centre) and the scene metrics of
-    maskedsst_amd.scene (pixels of class -1 are skipped)"""
-    from maskedsst_amd.scene import scene_metrics
+    maskedsst_amd.scene (pixels of class -1 are skipped).  report: a second line from the confusion matrix of scene_report (with
+    the fused loss the same pass gives both lines)"""
+    from maskedsst_amd.scene import scene_metrics, scene_report
     img, label = val
     classes, logits = model.predict_scene(img, return_logits=True)
-    m = scene_metrics(logits, classes, label, ignore_index=ignored_label, fused=fused)
+    full = scene_report(logits, classes, label, ignore_index=ignored_label) if report else None
+    m = full if (fused and report) else scene_metrics(logits, classes, label, ignore_index=ignored_label, fused=fused)
     print(f"val step {step} loss {m.loss:.4f} acc {m.acc:.3f} macro_acc {m.macro_acc:.3f} scenes {img.shape[0]}", flush=True)
+    if report:
+        r = full.report
+        print(f"val step {step} report OA {r.oa:.4f} AA {r.aa:.4f} kappa {r.kappa:.4f} mIoU {r.mean_iou:.4f} mF1 {r.mean_f1:.4f} "
+              f"pixels {r.total}", flush=True)
 
 
 if __name__ == "__main__":

@@ -437,6 +437,43 @@ int msst_ce_stats_fwd(const float* logits, const int64_t* labels, const int64_t*
 int msst_ce_bwd(const float* d, const int64_t* record, const float* gout /*optional*/, float* dlogits, int R0, int n_classes,
                 int M, void* stream);
 
+/* The same loss with class weights, label smoothing and a confusion matrix: torch.nn.CrossEntropyLoss(weight, ignore_index,
+ * label_smoothing) with reduction "mean", as the DeepHyperX protocol trains (reference DeepHyperX/models.py:37-72), and the matrix its
+ * metrics are computed from (DeepHyperX/utils.py:331-385).  Added under MSST_VERSION 109 (additive: no struct, no existing signature
+ * changes; the three calls above and their results are untouched).  Layout, the rule for a row that COUNTS, bad_labels and the record
+ * are those of msst_ce_stats_fwd.  With class_weight w [n_classes] fp32 (optional; null: all ones), W = sum_k w_k, label_smoothing
+ * eps in [0, 1), y a counting row's label and p its softmax:
+ *   row loss  l = -(1 - eps) w_y log p_y - (eps / n_classes) sum_k w_k log p_k
+ *   loss [1]  sum of l / sum of w_y over the counting rows; NaN unless that weight sum is > 0 (no row counts, or only rows of weight 0)
+ *   d (optional)  p_c ((1 - eps) w_y + (eps / n_classes) W) - (1 - eps) w_y [c == y] - (eps / n_classes) w_c; zeros for other rows
+ *   record    as msst_ce_stats_fwd (MSST_CE_LOSS_SUM: the sum of l; the counts do not depend on w or eps: a row of weight 0 counts)
+ *   sums [2]  DOUBLES: MSST_CE_EXT_LOSS_SUM (the same value as record slot 0) and MSST_CE_EXT_WEIGHT_SUM (sum of w_y; one fp32
+ *             partial per 256 rows, the partials added in double, in the order of the loss sum; without weights it equals n_valid)
+ *   confusion (optional) int64 [n_classes][n_classes]: confusion[y][argmax] over the counting rows, argmax as for MSST_CE_N_CORRECT,
+ *             so its diagonal is correct[] and its row sums are support[] of the same call.  n_classes <=
+ *             MSST_CE_CONFUSION_MAX_CLASSES when it is asked for (beyond: MSST_ERR_UNSUPPORTED); without it any n_classes >= 1.
+ * Every word of loss, d, record, sums and confusion is written; no float atomics: two calls give the same bits.  With a null
+ * class_weight and eps = 0 the loss, the record and d are bit for bit those of msst_ce_stats_fwd.
+ * scratch: msst_ce_ext_scratch_bytes(R0, n_classes, M, confusion != 0) bytes (4-byte aligned; 0 for a refused shape): two fp32
+ * partials and an int32 row [4 + 2 n_classes] per 256 rows, and with a confusion matrix an int32 [n_classes][n_classes] per 256 rows.
+ * Two launches.
+ * msst_ce_ext_bwd: dlogits = (d / sums[MSST_CE_EXT_WEIGHT_SUM]) * gout, read on the device; zeros unless the weight sum is > 0.
+ * dlogits may be d itself.  One launch.
+ * Checked before any launch, in this order: MSST_ERR_BADARG for R0, n_classes or M < 1; MSST_ERR_UNSUPPORTED when R0 * M or
+ * R0 * n_classes * M is 2^31 or more; MSST_ERR_BADARG for a label_smoothing outside [0, 1) (a NaN included); MSST_ERR_UNSUPPORTED
+ * for a confusion matrix with n_classes > MSST_CE_CONFUSION_MAX_CLASSES or one whose scratch has 2^31 words or more;
+ * MSST_ERR_BADARG for a null required pointer. */
+#define MSST_CE_EXT_LOSS_SUM 0
+#define MSST_CE_EXT_WEIGHT_SUM 1
+#define MSST_CE_CONFUSION_MAX_CLASSES 128
+long msst_ce_ext_scratch_bytes(int R0, int n_classes, int M, int confusion);
+int msst_ce_ext_fwd(const float* logits, const int64_t* labels, const int64_t* skip /*optional*/, long ignore_index,
+                    const float* class_weight /*optional*/, float label_smoothing, float* d /*optional*/, float* loss,
+                    int64_t* record, double* sums, int64_t* confusion /*optional*/, void* scratch, int R0, int n_classes, int M,
+                    void* stream);
+int msst_ce_ext_bwd(const float* d, const double* sums, const float* gout /*optional*/, float* dlogits, int R0, int n_classes,
+                    int M, void* stream);
+
 /* Fused AdamW over a flat fp32 buffer (torch.optim.AdamW semantics, src/utils.py:36-45), with the
  * reference's value clamp of the gradient (pretrain.py:71-73) when clamp > 0. */
 int msst_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,

@@ -56,6 +56,8 @@ FWD_HALF = 4096 << 8          # include/msst.h: MSST_FWD_HALF
 LSE_RENORM = 8192 << 8        # include/msst.h: MSST_LSE_RENORM
 PREP_HALF = 256               # include/msst.h: MSST_PREP_HALF
 CE_LOSS_SUM, CE_N_VALID, CE_N_CORRECT, CE_BAD_LABELS, CE_NONFINITE, CE_SUPPORT = range(6)   # include/msst.h: MSST_CE_* record slots
+CE_EXT_LOSS_SUM, CE_EXT_WEIGHT_SUM = range(2)   # include/msst.h: MSST_CE_EXT_* slots of the double sums of msst_ce_ext_fwd
+CE_CONFUSION_MAX_CLASSES = 128                  # include/msst.h: MSST_CE_CONFUSION_MAX_CLASSES
 _SIGS = {
     "msst_version": (c_int, []),
     "msst_last_error": (c_char_p, []),
@@ -111,6 +113,9 @@ _SIGS = {
     "msst_ce_scratch_bytes": (c_long, [c_int, c_int, c_int]),
     "msst_ce_stats_fwd": (c_int, [_P, _P, _P, c_long, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "msst_ce_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "msst_ce_ext_scratch_bytes": (c_long, [c_int, c_int, c_int, c_int]),
+    "msst_ce_ext_fwd": (c_int, [_P, _P, _P, c_long, _P, c_float, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "msst_ce_ext_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "msst_adamw": (c_int, [_P, _P, _P, _P, c_long, c_float, c_float, c_float, c_float, c_float, c_int,
                            c_float, c_float, _P]),
     "msst_adam_groups": (c_int, [_P, _P, _P, _P, POINTER(MsstAdamGroup), c_int, c_int, ctypes.c_double, ctypes.c_double,

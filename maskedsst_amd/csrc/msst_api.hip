@@ -1042,6 +1042,57 @@ int msst_ce_bwd(const float* d, const int64_t* record, const float* gout, float*
     return fail(launch_ce_bwd(d, record, gout, dlogits, (long)R0 * n_classes * M, (hipStream_t)stream), "msst_ce_bwd");
 }
 
+static_assert(CE_CONF_MAX_CLASSES == MSST_CE_CONFUSION_MAX_CLASSES, "the kernels' confusion limit is the header's");
+
+// shape of a call of the extended family, in the header's order: ce_shape, then the confusion matrix's class and scratch limits
+static int ce_ext_shape(int R0, int n_classes, int M, bool confusion) {
+    const int rc = ce_shape(R0, n_classes, M);
+    if (rc) return rc;
+    if (confusion && (n_classes > MSST_CE_CONFUSION_MAX_CLASSES ||
+                      (long)ce_workgroups((long)R0 * M) * n_classes * n_classes > 0x7fffffffL))
+        return MSST_ERR_UNSUPPORTED;
+    return 0;
+}
+
+long msst_ce_ext_scratch_bytes(int R0, int n_classes, int M, int confusion) {
+    if (ce_ext_shape(R0, n_classes, M, confusion != 0)) return 0;
+    const long G = ce_workgroups((long)R0 * M);
+    return G * (6 + 2L * n_classes + (confusion ? (long)n_classes * n_classes : 0)) * 4;
+}
+
+int msst_ce_ext_fwd(const float* logits, const int64_t* labels, const int64_t* skip, long ignore_index, const float* class_weight,
+                    float label_smoothing, float* d, float* loss, int64_t* record, double* sums, int64_t* confusion, void* scratch,
+                    int R0, int n_classes, int M, void* stream) {
+    int rc = ce_shape(R0, n_classes, M);
+    if (rc) return fail(rc, "msst_ce_ext_fwd");
+    if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return fail(MSST_ERR_BADARG, "msst_ce_ext_fwd (label_smoothing outside [0, 1))");
+    rc = ce_ext_shape(R0, n_classes, M, confusion != nullptr);
+    if (rc) return fail(rc, "msst_ce_ext_fwd (confusion matrix: more than MSST_CE_CONFUSION_MAX_CLASSES classes, or 2^31 scratch words)");
+    if (!logits || !labels || !loss || !record || !sums || !scratch)   // skip, class_weight, d and confusion are optional
+        return fail(MSST_ERR_BADARG, "msst_ce_ext_fwd");
+    CeExtArgs e = {};
+    CeArgs& a = e.c;
+    a.logits = logits; a.labels = labels; a.skip = skip; a.d = d; a.loss = loss; a.record = record;
+    a.rows = (long)R0 * M; a.ignore_index = ignore_index; a.NC = n_classes; a.M = M;
+    const int G = ce_workgroups(a.rows);
+    a.partial = (float*)scratch;
+    e.wpartial = a.partial + G;
+    a.slab = (int*)scratch + 2L * G;
+    e.cslab = confusion ? a.slab + (long)G * (4 + 2L * n_classes) : nullptr;
+    e.w = class_weight; e.eps = label_smoothing; e.confusion = confusion; e.sums = sums;
+    hipStream_t st = (hipStream_t)stream;
+    rc = launch_ce_ext_fwd(e, st);
+    if (rc) return fail(rc, "msst_ce_ext_fwd");
+    return fail(launch_ce_ext_finish(e, st), "msst_ce_ext_fwd(finish)");
+}
+
+int msst_ce_ext_bwd(const float* d, const double* sums, const float* gout, float* dlogits, int R0, int n_classes, int M, void* stream) {
+    const int rc = ce_shape(R0, n_classes, M);
+    if (rc) return fail(rc, "msst_ce_ext_bwd");
+    if (!d || !sums || !dlogits) return fail(MSST_ERR_BADARG, "msst_ce_ext_bwd");   // gout is optional (1)
+    return fail(launch_ce_ext_bwd(d, sums, gout, dlogits, (long)R0 * n_classes * M, (hipStream_t)stream), "msst_ce_ext_bwd");
+}
+
 int msst_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                float eps, float weight_decay, int step, float clamp, float gscale, void* stream) {
     return fail(launch_adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, clamp, gscale,

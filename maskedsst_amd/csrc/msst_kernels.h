@@ -341,5 +341,19 @@ int ce_workgroups(long rows);   // workgroups of the forward launch = rows of it
 int launch_ce_fwd(const CeArgs& a, hipStream_t st);
 int launch_ce_finish(const CeArgs& a, hipStream_t st);
 int launch_ce_bwd(const float* d, const int64_t* record, const float* gout, float* dlogits, long n, hipStream_t st);
+// ... with class weights, label smoothing and a confusion matrix (the second forward family of msst_loss.hip)
+constexpr int CE_CONF_MAX_CLASSES = 128;   // include/msst.h: MSST_CE_CONFUSION_MAX_CLASSES (msst_api.hip asserts they agree)
+struct CeExtArgs {
+    CeArgs c;             // as for ce_fwd: c.partial [workgroups], c.slab [workgroups][4 + 2 NC]
+    const float* w;       // optional [NC] class weights (null: ones)
+    float eps;            // label smoothing, in [0, 1)
+    float* wpartial;      // [workgroups] partials of the counting rows' w[label]
+    int* cslab;           // [workgroups][NC][NC] confusion partials, null when no confusion matrix is wanted
+    int64_t* confusion;   // [NC][NC] (label, argmax) over the counting rows; null with cslab
+    double* sums;         // [2]: the loss sum (= record slot 0) | the sum of w[label] the mean divides by
+};
+int launch_ce_ext_fwd(const CeExtArgs& e, hipStream_t st);
+int launch_ce_ext_finish(const CeExtArgs& e, hipStream_t st);
+int launch_ce_ext_bwd(const float* d, const double* sums, const float* gout, float* dlogits, long n, hipStream_t st);
 
 }  // namespace msst

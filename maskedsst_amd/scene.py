@@ -23,6 +23,7 @@ import torch.nn.functional as F
 SCENE_MAX_WINDOWS = 2048
 
 SceneMetrics = namedtuple("SceneMetrics", ["loss", "acc", "macro_acc"])
+SceneReport = namedtuple("SceneReport", ["loss", "acc", "macro_acc", "report"])
 
 
 def scene_windows(Hs, Ws, window, stride):
@@ -89,3 +90,18 @@ def scene_metrics(logits, classes, labels, ignore_index=-1, fused=False):
     present = torch.unique(lab)
     recall = torch.stack([hit[lab == c].double().mean() for c in present])
     return SceneMetrics(float(loss), float(acc), float(recall.mean()))
+
+
+def scene_report(logits, classes, labels, ignore_index=-1):
+    """``scene_metrics(..., fused=True)`` and the evaluation protocol of DeepHyperX (confusion matrix, overall and average accuracy,
+    per-class precision / recall / F1 / IoU, Cohen's kappa) from ONE pass of ``maskedsst_amd.ops.cross_entropy_stats`` over the logit
+    map as it lies, with ``skip=classes`` and ``confusion=True``: no boolean indexing, no ``bincount``, two read-backs (the record,
+    the matrix).  The same pixels count as in ``scene_metrics``.  Returns SceneReport(loss, acc, macro_acc, report): the three
+    numbers of ``scene_metrics`` (the same bits as its fused path) and ``report``, the ``maskedsst_amd.ops.ConfusionReport`` of the
+    matrix (``report.total`` pixels; every rate nan when none counts).  The matrix itself: ``cross_entropy_stats(...,
+    confusion=True)[1].confusion``.  At most 128 classes."""
+    from .ops import confusion_report, cross_entropy_stats
+    with torch.no_grad():
+        _, stats = cross_entropy_stats(logits, labels, ignore_index, skip=classes, confusion=True)
+    h = stats.host()
+    return SceneReport(h.loss, h.acc, h.macro_acc, confusion_report(h.confusion))
