@@ -238,6 +238,24 @@ int msst_head_fwd(const float* y, const float* img, const int32_t* idx, const fl
                   const float* b_pix, int per_block, float* dpred, float* pred, float* partial,
                   float* loss, int B, int S, int N, int P, int K, void* stream);
 
+/* SimMIM reconstruction: BlockwiseToPixels / to_pixels (vit_simmim_original.py:9-40, :328-332) over EVERY token instead of the
+ * gathered ones, stored transposed into the cube layout, with the per-band error over the masked pixels from the same pass.
+ * Added under MSST_VERSION 109 (additive: no struct, no existing signature changes).
+ *   y [B][T][96] encoder output (T = S N, token c N + n; 16-byte aligned), img [B][S P][N] the input cube, mask [B][T] as
+ *   msst_tokenize_fwd (1 = masked), w_pix / b_pix / per_block as msst_head_fwd.
+ *   recon [B][S P][N]:  recon[b][c P + k][n] = b_c[k] + sum_d W_c[k][d] y[b][c N + n][d]  (c -> 0 in both tables when
+ *     per_block == 0); fp32, one fmaf chain per element: the bias, then d = 0 .. 95.  blend != 0: a token whose mask byte is 0
+ *     gets img's P values instead, bit for bit.  Every element is written.
+ *   band_err [B][S P] DOUBLES: sum over the MASKED n of |pred - img| (the difference formed in double, the N terms of a band added
+ *     in one fixed order by one wave); band_cnt [B][S P] int32: the number of masked n -- both whatever blend is.  Both null:
+ *     no statistics (recon has the same bits); one null and one not: MSST_ERR_BADARG.
+ * No atomics, nothing to zero: two calls give the same bits.  One launch.  N <= 64, S <= 64, P <= 16 (the constructor's limits).
+ * Checked before anything is enqueued, in this order: MSST_ERR_BADARG for B, S, N or P < 1; MSST_ERR_UNSUPPORTED beyond the limits;
+ * MSST_ERR_BADARG for a null required pointer, one statistics pointer without the other, or a y that is not 16-byte aligned. */
+int msst_recon_fwd(const float* y, const float* img, const uint8_t* mask, const float* w_pix, const float* b_pix, int per_block,
+                   int blend, float* recon, double* band_err /*optional*/, int32_t* band_cnt /*optional*/, int B, int S, int N,
+                   int P, void* stream);
+
 /* ---- backward (a15: what autograd does for the reference at pretrain.py:116) ---- */
 
 /* d(loss)/d(encoder output) through the gather + to_pixels, and the to_pixels grads.

@@ -116,6 +116,7 @@ _SIGS = {
     "msst_ce_ext_scratch_bytes": (c_long, [c_int, c_int, c_int, c_int]),
     "msst_ce_ext_fwd": (c_int, [_P, _P, _P, c_long, _P, c_float, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "msst_ce_ext_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "msst_recon_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "msst_adamw": (c_int, [_P, _P, _P, _P, c_long, c_float, c_float, c_float, c_float, c_float, c_int,
                            c_float, c_float, _P]),
     "msst_adam_groups": (c_int, [_P, _P, _P, _P, POINTER(MsstAdamGroup), c_int, c_int, ctypes.c_double, ctypes.c_double,

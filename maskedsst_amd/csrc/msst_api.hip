@@ -246,7 +246,7 @@ int msst_profile_kernels(void) { return K_COUNT; }
 const char* msst_profile_name(int id) {
     static const char* names[K_COUNT] = {"prep_weights", "tokenize_fwd", "block_fwd", "head_fwd", "loss_reduce",
                                          "head_bwd", "reduce_slabs", "block_bwd_mlp", "block_bwd_attn",
-                                         "attn_slab_reduce", "block_bwd_ln1", "tokenize_bwd", "pos_split", "adamw", "block_bwd_ln1mlp", "layernorm", "adam_groups", "cross_entropy"};
+                                         "attn_slab_reduce", "block_bwd_ln1", "tokenize_bwd", "pos_split", "adamw", "block_bwd_ln1mlp", "layernorm", "adam_groups", "cross_entropy", "recon_fwd"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 
@@ -1091,6 +1091,19 @@ int msst_ce_ext_bwd(const float* d, const double* sums, const float* gout, float
     if (rc) return fail(rc, "msst_ce_ext_bwd");
     if (!d || !sums || !dlogits) return fail(MSST_ERR_BADARG, "msst_ce_ext_bwd");   // gout is optional (1)
     return fail(launch_ce_ext_bwd(d, sums, gout, dlogits, (long)R0 * n_classes * M, (hipStream_t)stream), "msst_ce_ext_bwd");
+}
+
+int msst_recon_fwd(const float* y, const float* img, const uint8_t* mask, const float* w_pix, const float* b_pix, int per_block,
+                   int blend, float* recon, double* band_err, int32_t* band_cnt, int B, int S, int N, int P, void* stream) {
+    if (B < 1 || S < 1 || N < 1 || P < 1) return fail(MSST_ERR_BADARG, "msst_recon_fwd");
+    if (N > 64 || S > 64 || P > 16) return fail(MSST_ERR_UNSUPPORTED, "msst_recon_fwd (N <= 64, S <= 64, P <= 16)");
+    if (!y || !img || !mask || !w_pix || !b_pix || !recon || (band_err == nullptr) != (band_cnt == nullptr))
+        return fail(MSST_ERR_BADARG, "msst_recon_fwd (null argument, or one of band_err / band_cnt without the other)");
+    if ((uintptr_t)y & 15) return fail(MSST_ERR_BADARG, "msst_recon_fwd (y not 16-byte aligned)");
+    ReconArgs a;
+    a.y = y; a.img = img; a.mask = mask; a.w_pix = w_pix; a.b_pix = b_pix; a.recon = recon; a.band_err = band_err; a.band_cnt = band_cnt;
+    a.B = B; a.S = S; a.N = N; a.P = P; a.per_block = per_block ? 1 : 0; a.blend = blend ? 1 : 0;
+    return fail(launch_recon_fwd(a, (hipStream_t)stream), "msst_recon_fwd");
 }
 
 int msst_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,

@@ -198,7 +198,7 @@ struct TokSceneBwdArgs : TokBwdArgs {
 // ---- opt-in per-kernel timing with HIP events on the launch stream (bench.py roofline leg) ----
 enum KernelId {
     K_PREP = 0, K_TOK_FWD, K_BLOCK_FWD, K_HEAD_FWD, K_LOSS_REDUCE, K_HEAD_BWD, K_REDUCE, K_BWD_MLP, K_BWD_ATTN,
-    K_ATTN_REDUCE, K_BWD_LN1, K_TOK_BWD, K_POS_SPLIT, K_ADAMW, K_BWD_LN1MLP, K_LAYERNORM, K_ADAM_GROUPS, K_CE, K_COUNT
+    K_ATTN_REDUCE, K_BWD_LN1, K_TOK_BWD, K_POS_SPLIT, K_ADAMW, K_BWD_LN1MLP, K_LAYERNORM, K_ADAM_GROUPS, K_CE, K_RECON, K_COUNT
 };
 void prof_begin(int id, hipStream_t st);
 void prof_end(hipStream_t st);
@@ -355,5 +355,18 @@ struct CeExtArgs {
 int launch_ce_ext_fwd(const CeExtArgs& e, hipStream_t st);
 int launch_ce_ext_finish(const CeExtArgs& e, hipStream_t st);
 int launch_ce_ext_bwd(const float* d, const double* sums, const float* gout, float* dlogits, long n, hipStream_t st);
+// msst_recon.hip: to_pixels over every token into the cube layout, with the per-band |pred - img| sums over the masked pixels
+struct ReconArgs {
+    const float* y;        // [B][T][96] encoder output (16-byte aligned)
+    const float* img;      // [B][S*P][N]
+    const uint8_t* mask;   // [B][T] (1 = masked)
+    const float* w_pix;    // [S or 1][P][96]
+    const float* b_pix;    // [S or 1][P]
+    float* recon;          // [B][S*P][N]
+    double* band_err;      // optional [B][S*P] (with band_cnt)
+    int32_t* band_cnt;     // optional [B][S*P]
+    int B, S, N, P, per_block, blend;
+};
+int launch_recon_fwd(const ReconArgs& a, hipStream_t st);
 
 }  // namespace msst

@@ -70,6 +70,38 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def recon_fwd(y, img, mask_u8, w_pix, b_pix, per_block, blend, S, N, P, stats=True, lib=None):
+    """msst_recon_fwd (include/msst.h) on tensors: y [B, S N, 96] fp32, img with B S P N elements in the cube layout [B, S P, N]
+    (a [B, C, H, W] cube as it lies), mask_u8 [B, S N] uint8, w_pix / b_pix the to_pixels tables ([S or 1, P, 96] / [S or 1, P]
+    tensors, or device pointers) -> (recon [B, S P, N], band_err [B, S P] float64, band_cnt [B, S P] int32); stats=False: null
+    statistics pointers, (recon, None, None).  The current stream."""
+    lib = lib or _lib.load()
+    for t in (y, img, mask_u8):
+        if not t.is_cuda:
+            raise RuntimeError("maskedsst_amd runs on an MI355X only (tensor is on %s); there is no CPU fallback" % t.device)
+    B = y.shape[0]
+    if (y.dtype, img.dtype, mask_u8.dtype) != (torch.float32, torch.float32, torch.uint8):
+        raise ValueError("recon_fwd takes fp32 y and img and a uint8 mask")
+    if tuple(y.shape) != (B, S * N, D) or img.numel() != B * S * P * N or mask_u8.numel() != B * S * N:
+        raise ValueError(f"recon_fwd: y {tuple(y.shape)}, img {tuple(img.shape)}, mask {tuple(mask_u8.shape)} do not fit "
+                         f"B = {B}, S = {S}, N = {N}, P = {P}")
+    y, img, mask_u8 = y.contiguous(), img.contiguous(), mask_u8.contiguous()
+    tables = []
+    for t, n in ((w_pix, P * D), (b_pix, P)):
+        if torch.is_tensor(t):
+            if not t.is_cuda or t.dtype != torch.float32 or t.numel() != (S if per_block else 1) * n:
+                raise ValueError("recon_fwd: to_pixels tables must be fp32 cuda tensors [S or 1, P, 96] and [S or 1, P]")
+            t = t.contiguous()
+        tables.append(t)
+    recon = torch.empty(B, S * P, N, dtype=torch.float32, device=y.device)
+    err = torch.empty(B, S * P, dtype=torch.float64, device=y.device) if stats else None
+    cnt = torch.empty(B, S * P, dtype=torch.int32, device=y.device) if stats else None
+    wp, bp = (_p(t) if torch.is_tensor(t) else t for t in tables)
+    _lib.check(lib.msst_recon_fwd(_p(y), _p(img), _p(mask_u8), wp, bp, int(bool(per_block)), int(bool(blend)), _p(recon), _p(err),
+                                  _p(cnt), B, S, N, P, _stream()), "msst_recon_fwd")
+    return recon, err, cnt
+
+
 class Engine:
     def __init__(self, encoder, mim):
         self.enc = encoder
@@ -560,6 +592,29 @@ class Engine:
             _p(y), _p(img), _p(idx32), V(self.fp.ptr("to_pixels.w.0")), V(self.fp.ptr("to_pixels.b.0")), per_block,
             _p(dpred), _p(pred), _p(partial), _p(loss), B, S, N, P, K, _stream()), "msst_head_fwd")
         return loss, dpred, pred
+
+    def recon_fwd(self, y, img, mask_u8, blend=True, stats=True):
+        """to_pixels over every token of y [B, T, 96] -> (recon [B, S P, N], band_err [B, S P] float64, band_cnt [B, S P] int32; the
+        last two None without stats): module-level recon_fwd on this model's to_pixels tables"""
+        per_block = 1 if hasattr(self.mim.to_pixels, "layers") else 0
+        V = ctypes.c_void_p
+        return recon_fwd(y, img, mask_u8, V(self.fp.ptr("to_pixels.w.0")), V(self.fp.ptr("to_pixels.b.0")), per_block, blend,
+                         self.S, self.N, self.P, stats=stats, lib=self.lib)
+
+    def reconstruct(self, img, mask_u8, blend=True):
+        """Eval forward of the SimMIM model down to pixels: img [B, C, H, W] fp32 cuda, mask_u8 [B, T] uint8 cuda (1 = masked) ->
+        (recon [B, S P, N] fp32, band_err [B, S P] float64, band_cnt [B, S P] int32).  The encoder path of simmim_loss in eval
+        mode (prep_weights, tokenize with the mask token, the blocks with nothing saved and no dropout, at the model's
+        precision), then msst_recon_fwd instead of the gather head.  No autograd; the current stream."""
+        self._require_cuda(img)
+        if self.mim is None:
+            raise RuntimeError("reconstruct needs the SimMIM wrapper's mask token and to_pixels (a bare encoder has neither)")
+        img = img.contiguous().float()
+        with torch.no_grad():
+            self.prep_weights()
+            x0 = self.tokenize(img, mask_u8)
+            acts, _ = self.blocks_fwd(x0, save=False)
+            return self.recon_fwd(acts[-1], img, mask_u8, blend)
 
     # ------------------------------------------------------------------ backward pieces
     def _fire(self, bucket):

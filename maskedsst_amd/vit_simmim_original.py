@@ -6,6 +6,7 @@ forward/backward arithmetic runs in the HIP kernels of ``libmsst.so``; mask gene
 host and is bit-exact with the reference (``maskedsst_amd/masking.py``).
 """
 import weakref
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -13,6 +14,11 @@ from torch import nn
 
 from .masking import MaskGenerator, topk_masks, inverse_csr
 from .vit_spatial_spectral import ViTSpatialSpectral
+
+
+# what SimMIMSpatialSpectral.reconstruct returns: cube [B, C, H, W] fp32, mask [B, C, H, W] bool (the token mask over the P bands of
+# each token), band_err [B, C] float64 (sum of |prediction - input| over the band's masked pixels), band_cnt [B, C] int32 (how many)
+Reconstruction = namedtuple("Reconstruction", ["cube", "mask", "band_err", "band_cnt"])
 
 
 class BlockwiseToPixels(nn.Module):
@@ -100,3 +106,41 @@ class SimMIMSpatialSpectral(nn.Module):
             masks = self.draw_masks(img.shape[0])
         self.last_masks = masks
         return eng.simmim_loss(img, masks[0], masks[1])
+
+    def _token_mask(self, masks, B):
+        """the bool [B, T] token mask of `masks`: the (bool_mask, idx) pair forward takes, or the bool mask alone"""
+        T = self.encoder.num_patches
+        bm = masks[0] if isinstance(masks, (tuple, list)) else masks
+        bm = bm if torch.is_tensor(bm) else torch.from_numpy(np.asarray(bm))
+        if bm.dtype != torch.bool or tuple(bm.shape) != (B, T):
+            raise ValueError(f"mask must be a bool [{B}, {T}] tensor (batch, tokens), got {bm.dtype} {tuple(bm.shape)}")
+        return bm
+
+    def reconstruct(self, img, masks=None, blend=True):
+        """What the model reconstructs: img [B, bands, H, W] -> Reconstruction(cube, mask, band_err, band_cnt).
+
+        The tokens of `masks` are replaced by the mask token, the encoder runs as in ``forward`` in eval mode and ``to_pixels``
+        is applied to EVERY token (one HIP pass, ``msst_recon_fwd``): ``cube`` holds the predicted pixels, with ``blend`` (default) the
+        input's own pixels where nothing was masked -- the filled-in cube.  ``band_err / band_cnt`` is the mean absolute error of a
+        band over its masked pixels, whatever ``blend`` is (``maskedsst_amd.recon_report`` sums it up).
+        masks: None draws them as ``forward`` does (and sets ``last_masks``); or the (bool_mask, idx) pair ``forward`` takes; or a bare
+        bool [B, T] tensor.  Always an eval forward under no_grad (no dropout), whatever the module's mode, which is left as it is."""
+        enc = self.encoder
+        s = enc.num_spatial_patches_sqrt
+        C = enc.num_spectral_patches * enc.patch_depth
+        if not torch.is_tensor(img) or img.dim() != 4:
+            raise ValueError(f"img must be a 4-D tensor [batch, bands, H, W], got {getattr(img, 'shape', type(img))}")
+        if img.shape[0] < 1 or tuple(img.shape[1:]) != (C, s, s):
+            raise ValueError(f"img {tuple(img.shape)} is not [batch, {C}, {s}, {s}] (the model's bands and image size)")
+        B = img.shape[0]
+        if masks is None:
+            masks = self.draw_masks(B)
+            self.last_masks = masks
+        bm = self._token_mask(masks, B)
+        eng = self.engine()
+        eng._require_cuda(img)
+        S, N, P = enc.num_spectral_patches, enc.num_spatial_patches, enc.pixels_per_patch
+        mask_u8 = bm.to(device=img.device, dtype=torch.uint8).contiguous()
+        recon, err, cnt = eng.reconstruct(img, mask_u8, blend)   # passes no dropout and saves nothing, whatever self.training
+        mask = mask_u8.bool().view(B, S, 1, s, s).expand(B, S, P, s, s).reshape(B, C, s, s)
+        return Reconstruction(recon.view(B, C, s, s), mask, err, cnt)

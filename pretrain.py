@@ -44,7 +44,7 @@ def save_checkpoint(save_dir, epoch, model, optimizer, config, losses, img):
     return path
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="configs/pretrain_config.yaml")
     ap.add_argument("--general-config", default="configs/config.yaml")
@@ -63,7 +63,22 @@ def main():
     ap.add_argument("--spectral-mlp-head", action="store_true",
                     help="build the encoder with the spectral MLP head (unused in pre-training; its checkpoint then loads "
                          "strictly into finetune.py --spectral-mlp-head)")
-    args = ap.parse_args()
+    ap.add_argument("--recon-report", action="store_true",
+                    help="after every validation pass print one more line: the masked mean absolute error of model.reconstruct on "
+                         "the first window of the validation tiles, and its three worst bands")
+    return ap
+
+
+def recon_line(model, window, epoch):
+    """the --recon-report line: model.reconstruct on one validation window batch -> overall masked MAE and the three worst bands"""
+    from maskedsst_amd import recon_report
+    rep = recon_report(model.reconstruct(window), model.pixel_values_per_patch)
+    worst = " ".join(f"{b}:{float(rep.band_mae[b]):.4e}" for b in rep.worst_bands[:3])
+    return f"epoch {epoch} recon masked_mae {rep.mae:.6e} over {rep.masked} pixels, worst bands {worst}"
+
+
+def main():
+    args = build_parser().parse_args()
 
     random.seed(SEED); np.random.seed(SEED); torch.manual_seed(SEED)
     if not torch.cuda.is_available():
@@ -177,6 +192,10 @@ def main():
                     for y0 in range(0, 64, s_):
                         val_losses.append(model(val_tiles[:, :, x0:x0 + s_, y0:y0 + s_].contiguous()))
             val_loss = torch.stack(val_losses).mean()
+            if args.recon_report:   # on every rank: drawing the masks advances the generators the ranks share
+                line = recon_line(model, val_tiles[:, :, :s_, :s_].contiguous(), epoch)
+                if rank == 0:
+                    print(line, flush=True)
             # every rank validates on its own shard: the plateau scheduler must see the SAME number everywhere, or the
             # ranks cut the learning rate at different epochs and the replicas drift apart
             if config.scheduler == "ReduceLROnPlateau":
