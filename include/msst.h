@@ -185,6 +185,46 @@ int msst_tokenize_scene_bwd(const float* scene, const float* pre_g, const float*
 int msst_scene_assemble(const float* win_logits, long win0, int nwin, float* logits, int64_t* classes, int Bs,
                         int n_classes, int Hs, int Ws, int window, int stride, int finalize, void* stream);
 
+/* Whole-scene SimMIM reconstruction (SimMIMSpatialSpectral.reconstruct_scene).  Additive under MSST_VERSION 109: no struct and no
+ * existing signature changes.  The windows of a scene, numbered as for msst_tokenize_scene_fwd, are tokenized WITH a mask given in
+ * scene coordinates, run through msst_block_fwd and msst_recon_fwd (blend = 0, null statistics) as one batch, and
+ * msst_scene_recon_assemble writes the scene-shaped cube: overlapping windows averaged, as msst_scene_assemble does for logits.
+ *
+ * msst_tokenize_scene_fwd_masked: msst_tokenize_scene_fwd plus mask_token [96] and scene_mask [Bs][S][Hs][Ws] (uint8, non-zero =
+ * masked: one byte per spectral block and pixel, i.e. per token).  Token (c, n) of the window with origin (y0, x0) is masked iff
+ * scene_mask[s][c][y0 + n / window][x0 + n % window] != 0; its embedding is replaced by the mask token before the position add, as
+ * msst_tokenize_fwd does.  out is bit-identical to msst_tokenize_fwd on the copied windows with the copied per-window [nwin][T]
+ * masks, and with an all-zero mask to msst_tokenize_scene_fwd (tested properties; both tokenizer paths).  The limits and argument
+ * checks of msst_tokenize_scene_fwd, plus MSST_ERR_BADARG for a null mask_token or scene_mask. */
+int msst_tokenize_scene_fwd_masked(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb,
+                                   const float* b_emb, const float* post_g, const float* post_b, const float* pos_a,
+                                   const float* pos_b, int pos_split, const float* mask_token, const uint8_t* scene_mask, float* out,
+                                   int Bs, int Hs, int Ws, int window, int stride, long win0, int nwin, int S, int P, void* stream);
+
+/* msst_scene_recon_assemble: the counterpart of msst_scene_assemble for pixels.  Adds the per-window predictions
+ * win_recon [nwin][S P][window*window] (msst_recon_fwd with blend = 0 of windows win0 .. win0 + nwin - 1: the layout
+ * msst_scene_assemble takes for logits) into the running fp32 sums cube [Bs][S P][Hs][Ws].  The calls of one scene batch must cover
+ * windows 0, 1, ... in order (any split into calls); cube needs no initialisation.  Each pixel adds its windows in window order
+ * (row, then column) without atomics.  finalize != 0 (the last call, after its own windows), with scene [Bs][S P][Hs][Ws] the input
+ * cube and scene_mask [Bs][S][Hs][Ws] as above:
+ *   a pixel covered by k >= 1 windows holds the prediction sum / k;
+ *   blend != 0: every element whose token is not masked, and every pixel no window covers, gets scene's bits;
+ *   blend == 0: covered pixels hold the prediction, uncovered pixels NaN (an absent value is never a made-up number);
+ *   band_err [Bs][S P] DOUBLES: sum of |prediction - scene| over the band's pixels that are masked AND covered (whatever blend is),
+ *     the difference formed in double; the plane's terms are added in one fixed order (thread t of 256 takes pixels t, t + 256, ...
+ *     in turn, then a butterfly over each wave, then the four waves in order);  band_cnt [Bs][S P] int32: how many such pixels;
+ *     both may be null (no statistics), one without the other is MSST_ERR_BADARG;
+ *   cover [Bs][Hs][Ws] int32: k, the number of windows covering the pixel (0: uncovered).
+ * band_err, band_cnt and cover are written by the finalizing call only.  No atomics, nothing to zero: two runs give the same bits in
+ * every output, whatever the split into calls.
+ * Checked before anything is enqueued, in this order: MSST_ERR_BADARG for a size below 1 (nwin = 0 is allowed); MSST_ERR_UNSUPPORTED
+ * outside 1 <= stride <= window <= Hs, Ws, window * window <= 64, S <= 64, P <= 16; MSST_ERR_BADARG for a null required pointer
+ * (win_recon when nwin > 0, scene, scene_mask, cube, cover), one statistics pointer without the other, or windows beyond
+ * win0 + nwin <= Bs nr nq. */
+int msst_scene_recon_assemble(const float* win_recon, long win0, int nwin, const float* scene, const uint8_t* scene_mask, float* cube,
+                              double* band_err /*optional*/, int32_t* band_cnt /*optional*/, int32_t* cover, int Bs, int S, int P,
+                              int Hs, int Ws, int window, int stride, int finalize, int blend, void* stream);
+
 /* a7-a10: one fused pre-norm transformer block (PreNorm+Attention+FeedForward+residuals,
  * vit_spatial_spectral.py:22-104) over all B*S*N tokens; mode selects the spatial or spectral
  * sequence grouping of vit_spatial_spectral.py:410-431 (no transposes are materialised).

@@ -8,9 +8,9 @@ Compute runs in hand-written HIP kernels (``maskedsst_amd/csrc``) behind the C-A
 ``include/msst.h`` (``libmsst.so``, loaded with ctypes).  There is no CPU or eager fallback.
 """
 from .vit_spatial_spectral import ViTSpatialSpectral  # noqa: F401
-from .vit_simmim_original import SimMIMSpatialSpectral, BlockwiseToPixels, Reconstruction  # noqa: F401
-from .recon import recon_report, ReconReport  # noqa: F401
+from .vit_simmim_original import SimMIMSpatialSpectral, BlockwiseToPixels, Reconstruction, SceneReconstruction  # noqa: F401
+from .recon import recon_report, ReconReport, window_masks_to_scene, scene_mask_to_windows  # noqa: F401
 from .masking import MaskGenerator  # noqa: F401
 
 __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "MaskGenerator", "Reconstruction", "recon_report",
-           "ReconReport"]
+           "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows"]

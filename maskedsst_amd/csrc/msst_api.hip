@@ -319,6 +319,26 @@ int msst_tokenize_scene_fwd(const float* scene, const float* pre_g, const float*
     return fail(launch_tokenize_scene_fwd(a, (hipStream_t)stream), "msst_tokenize_scene_fwd");
 }
 
+int msst_tokenize_scene_fwd_masked(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb,
+                                   const float* b_emb, const float* post_g, const float* post_b, const float* pos_a,
+                                   const float* pos_b, int pos_split, const float* mask_token, const uint8_t* scene_mask, float* out,
+                                   int Bs, int Hs, int Ws, int window, int stride, long win0, int nwin, int S, int P, void* stream) {
+    int nr = 0, nq = 0;
+    if (!scene || !out || !mask_token || !scene_mask || S < 1 || P < 1 || nwin < 0 || win0 < 0 ||
+        !scene_grid(Bs, Hs, Ws, window, stride, &nr, &nq))
+        return fail(MSST_ERR_BADARG, "msst_tokenize_scene_fwd_masked");
+    const long wps = (long)nr * nq;
+    if (wps > 0x7fffffffL || win0 + nwin > (long)Bs * wps) return fail(MSST_ERR_BADARG, "msst_tokenize_scene_fwd_masked (windows out of range)");
+    if (window > 8) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_scene_fwd_masked (more than 64 pixels per window)");
+    TokArgs a;
+    a.drop = make_drop(0.f, 0, 255);
+    a.img = scene; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb;
+    a.post_g = post_g; a.post_b = post_b; a.pos_a = pos_a; a.pos_b = pos_b; a.mask_token = mask_token; a.mask = scene_mask;
+    a.out = out; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P; a.pos_split = pos_split;
+    a.win0 = win0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nq = nq; a.wps = (int)wps;
+    return fail(launch_tokenize_scene_fwd_masked(a, (hipStream_t)stream), "msst_tokenize_scene_fwd_masked");
+}
+
 // the shared argument check of msst_tokenize_scene_fwd_train / msst_tokenize_scene_bwd, in this order: sizes below 1 (BADARG), shapes
 // outside the kernels' limits (UNSUPPORTED), a null required pointer (BADARG), windows beyond the scenes' grids (BADARG).  min_nwin: 0 or 1
 static int scene_train_args(bool pointers, int Bs, int Hs, int Ws, int window, int stride, long win0, int nwin, int min_nwin, int S,
@@ -375,6 +395,40 @@ int msst_scene_assemble(const float* win_logits, long win0, int nwin, float* log
     }
     if (!rc && finalize) rc = launch_scene_finalize(a, st);
     return fail(rc, "msst_scene_assemble");
+}
+
+int msst_scene_recon_assemble(const float* win_recon, long win0, int nwin, const float* scene, const uint8_t* scene_mask, float* cube,
+                              double* band_err, int32_t* band_cnt, int32_t* cover, int Bs, int S, int P, int Hs, int Ws, int window,
+                              int stride, int finalize, int blend, void* stream) {
+    if (Bs < 1 || S < 1 || P < 1 || Hs < 1 || Ws < 1 || window < 1 || stride < 1 || nwin < 0 || win0 < 0)
+        return fail(MSST_ERR_BADARG, "msst_scene_recon_assemble");
+    if (stride > window || window > Hs || window > Ws || window * window > 64 || S > 64 || P > 16)
+        return fail(MSST_ERR_UNSUPPORTED, "msst_scene_recon_assemble (1 <= stride <= window <= Hs, Ws; window * window <= 64, S <= 64, P <= 16)");
+    if ((nwin > 0 && !win_recon) || !scene || !scene_mask || !cube || !cover || (band_err == nullptr) != (band_cnt == nullptr))
+        return fail(MSST_ERR_BADARG, "msst_scene_recon_assemble (null argument, or one of band_err / band_cnt without the other)");
+    int nr = 0, nq = 0;
+    scene_grid(Bs, Hs, Ws, window, stride, &nr, &nq);
+    const long wps = (long)nr * nq;
+    if (win0 + nwin > (long)Bs * wps) return fail(MSST_ERR_BADARG, "msst_scene_recon_assemble (windows out of range)");
+    // both launches' grids fit (so nothing is refused after the first one is enqueued)
+    if (((long)Bs * Hs * Ws + 255) / 256 > 0x7fffffffL || (long)Bs * S * P > 0x7fffffffL) return fail(MSST_ERR_UNSUPPORTED, "msst_scene_recon_assemble (scene batch too large)");
+    SceneReconArgs a;
+    a.win_recon = win_recon; a.scene = scene; a.scene_mask = scene_mask; a.cube = cube; a.band_err = band_err; a.band_cnt = band_cnt;
+    a.cover = cover; a.win0 = win0; a.row0 = 0; a.nwin = nwin; a.Bs = Bs; a.S = S; a.P = P; a.Hs = Hs; a.Ws = Ws; a.win = window;
+    a.stride = stride; a.nr = nr; a.nq = nq; a.blend = blend != 0;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = 0;
+    if (nwin > 0) {
+        // the flattened (scene, pixel row) rows the windows of this call reach, as in msst_scene_assemble
+        const long g0 = win0, g1 = win0 + nwin - 1;
+        const long s0 = g0 / wps, s1 = g1 / wps;
+        const long r0 = (g0 - s0 * wps) / nq, r1 = (g1 - s1 * wps) / nq;
+        a.row0 = s0 * Hs + r0 * stride;
+        const long rows = s1 * Hs + r1 * stride + window - a.row0;
+        rc = launch_scene_recon_accumulate(a, rows * Ws, st);
+    }
+    if (!rc && finalize) rc = launch_scene_recon_finalize(a, st);
+    return fail(rc, "msst_scene_recon_assemble");
 }
 
 long msst_block_lse_floats(int mode, int B, int S, int N, int heads) {

@@ -21,11 +21,15 @@ namespace msst {
 // ==========================================================================================
 // PC: pixels per patch as a compile-time constant (10 = the reference's spectral patch, configs/config.yaml: band_patch_size)
 // so that the small loops over it unroll and their LDS reads are batched; 0 = run-time value (any P <= 16)
-// SCENE: addressing policy of the source pixels.  false: img[b, c P + k, n] of a batch of cubes [B][S*P][N];  true: the same pixel of
-// window b of a scene, scene[s, c P + k, y0 + n / win, x0 + n % win] (TokArgs scene fields; no mask).  Nothing else differs: the
-// embedding dropout addresses an element by its place in `out` in both (msst_tokenize_scene_fwd passes p = 0).
-template <int PC, bool SCENE>
+// SRC: addressing policy of the source pixels and of the token mask.  TOK_BATCH: img[b, c P + k, n] of a batch of cubes [B][S*P][N],
+// mask [B][T];  TOK_SCENE: the same pixel of window b of a scene, scene[s, c P + k, y0 + n / win, x0 + n % win] (TokArgs scene fields;
+// no mask);  TOK_SCENE_MASKED: those pixels, and token (c, n) is masked where the scene mask [Bs][S][Hs][Ws] (a.mask) is non-zero at
+// (s, c, y0 + n / win, x0 + n % win) (msst_tokenize_scene_fwd_masked).  Nothing else differs: the embedding dropout addresses an
+// element by its place in `out` in all three (msst_tokenize_scene_fwd / _fwd_masked pass p = 0).
+enum { TOK_BATCH = 0, TOK_SCENE = 1, TOK_SCENE_MASKED = 2 };
+template <int PC, int SRC>
 __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
+    constexpr bool SCENE = SRC != TOK_BATCH;
     __shared__ float patch[16][64];
     __shared__ float W[96][17];
     __shared__ float bias[96];
@@ -82,7 +86,10 @@ __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
     v2 += __shfl_xor(v2, 1); v2 += __shfl_xor(v2, 2);
     const float rstd2 = rsqrtf(v2 * (1.f / 96.f) + 1e-5f);
     const int t = c * N + n;
-    const bool masked = SCENE ? false : a.mask[(long)b * a.T + t] != 0;
+    bool masked;
+    if constexpr (SRC == TOK_SCENE) masked = false;
+    else if constexpr (SRC == TOK_SCENE_MASKED) masked = scene_window_mask(a, b, c)[(long)(n / a.win) * a.Ws + n % a.win] != 0;
+    else masked = a.mask[(long)b * a.T + t] != 0;
     float* dst = a.out + ((long)b * a.T + t) * 96 + part * 4;
 #pragma unroll
     for (int i = 0; i < 24; ++i) {
@@ -91,7 +98,7 @@ __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
         if (a.pos_split) pos = d < a.pos_split ? a.pos_a[n * a.pos_split + d] : a.pos_b[c * (96 - a.pos_split) + d - a.pos_split];
         else pos = a.pos_a[(long)t * 96 + d];
         const float tok = (e[i] - m2) * rstd2 * a.post_g[d] + a.post_b[d];
-        e[i] = (!SCENE && masked ? a.mask_token[d] : tok) + pos;
+        e[i] = (SRC != TOK_SCENE && masked ? a.mask_token[d] : tok) + pos;
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -102,9 +109,11 @@ __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
 }
 
 template <int PC>
-__global__ __launch_bounds__(256) void tokenize_fwd_kernel(TokArgs a) { tokenize_fwd_body<PC, false>(a); }
+__global__ __launch_bounds__(256) void tokenize_fwd_kernel(TokArgs a) { tokenize_fwd_body<PC, TOK_BATCH>(a); }
 template <int PC>
-__global__ __launch_bounds__(256) void tokenize_scene_fwd_kernel(TokArgs a) { tokenize_fwd_body<PC, true>(a); }
+__global__ __launch_bounds__(256) void tokenize_scene_fwd_kernel(TokArgs a) { tokenize_fwd_body<PC, TOK_SCENE>(a); }
+template <int PC>
+__global__ __launch_bounds__(256) void tokenize_scene_fwd_masked_kernel(TokArgs a) { tokenize_fwd_body<PC, TOK_SCENE_MASKED>(a); }
 
 
 // ------------------------------------------------------------------------------------------
@@ -117,14 +126,16 @@ __global__ __launch_bounds__(256) void tokenize_scene_fwd_kernel(TokArgs a) { to
 // layout), and the C layout (4 consecutive features of one token per lane) is the 16-byte store of the token row.
 // grid (S, nchunk), 256 threads: wave w <-> tokens 16 w .. + 15 of spectral block c, samples chunk, chunk + nchunk, ...
 // Position rows, bias, both LayerNorms' vectors and the mask token are tile invariant for a wave: registers / LDS.
-// SCENE: the source addressing policy of tokenize_fwd_body (windows of a scene instead of a batch of cubes; no mask).
+// SRC: the source addressing policy of tokenize_fwd_body (TOK_SCENE: windows of a scene instead of a batch of cubes, no mask;
+// TOK_SCENE_MASKED: with the scene mask).
 // ------------------------------------------------------------------------------------------
-template <bool SCENE>
+template <int SRC>
 __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
+    constexpr bool SCENE = SRC != TOK_BATCH;
     constexpr int P = 10, N = 64;
     __shared__ __attribute__((aligned(16))) float vec[3][96];   // post_g | post_b | mask_token
     const int c = blockIdx.x, tid = threadIdx.x, w = tid >> 6, l = tid & 63, g = l >> 4, j = l & 15;
-    if (tid < 96) { vec[0][tid] = a.post_g[tid]; vec[1][tid] = a.post_b[tid]; vec[2][tid] = SCENE ? 0.f : a.mask_token[tid]; }
+    if (tid < 96) { vec[0][tid] = a.post_g[tid]; vec[1][tid] = a.post_b[tid]; vec[2][tid] = SRC == TOK_SCENE ? 0.f : a.mask_token[tid]; }
     // A fragments of W_c [96][10]: lane (i = l & 15, kq = l >> 4) holds W[16 mt + i][4 ks + kq] (zero beyond k = 9)
     float wf[6][3];
 #pragma unroll
@@ -165,7 +176,8 @@ __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
             const float* src = scene_window_origin(a, bc) + (long)c * P * plane + (long)(n / a.win) * a.Ws + n % a.win;
 #pragma unroll
             for (int ks = 0; ks < 3; ++ks) { const int k = 4 * ks + g; px[ks] = src[(k < P ? k : 0) * plane]; }
-            mk = 0;
+            if constexpr (SRC == TOK_SCENE_MASKED) mk = scene_window_mask(a, bc, c)[(long)(n / a.win) * a.Ws + n % a.win];
+            else mk = 0;
         } else {
             const float* src = a.img + ((long)bc * a.S + c) * P * N + n;
 #pragma unroll
@@ -222,8 +234,9 @@ __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
     }
 }
 
-__global__ __launch_bounds__(256, 2) void tokenize_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<false>(a); }
-__global__ __launch_bounds__(256, 2) void tokenize_scene_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<true>(a); }
+__global__ __launch_bounds__(256, 2) void tokenize_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<TOK_BATCH>(a); }
+__global__ __launch_bounds__(256, 2) void tokenize_scene_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<TOK_SCENE>(a); }
+__global__ __launch_bounds__(256, 2) void tokenize_scene_fwd_masked_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<TOK_SCENE_MASKED>(a); }
 
 // ==========================================================================================
 // fused transformer block, forward.  Reference vit_spatial_spectral.py:22-29 (PreNorm),
@@ -910,6 +923,24 @@ int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
+// the same selection once more, TOK_SCENE_MASKED instances (a.mask: the scene mask, a.mask_token set)
+int launch_tokenize_scene_fwd_masked(const TokArgs& a, hipStream_t st) {
+    if (a.P > 16 || a.N > 64) return MSST_ERR_UNSUPPORTED;
+    if (a.B < 1) return 0;
+    ProfScope ps(K_TOK_FWD, st);
+    if (a.P == 10 && a.N == 64) {
+        int nchunk = 1024 / (a.S > 0 ? a.S : 1);
+        if (nchunk < 1) nchunk = 1;
+        if (nchunk > a.B) nchunk = a.B;
+        hipLaunchKernelGGL(tokenize_scene_fwd_masked_mfma_kernel, dim3(a.S, nchunk), dim3(256), 0, st, a);
+    } else {
+        if (a.B > 65535) return MSST_ERR_UNSUPPORTED;   // one workgroup row per window (grid y)
+        if (a.P == 10) hipLaunchKernelGGL(tokenize_scene_fwd_masked_kernel<10>, dim3(a.S, a.B), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(tokenize_scene_fwd_masked_kernel<0>, dim3(a.S, a.B), dim3(256), 0, st, a);
+    }
+    return (int)hipGetLastError();
+}
+
 template <class P>
 static int launch_block_fwd_t(const BlockArgs& a, int grid, hipStream_t st) {
     static std::atomic<bool> attr_set{false};
@@ -1042,16 +1073,9 @@ int launch_cls_head_fwd(const ClsArgs& a, hipStream_t st) {
 // inference_example.ipynb (model(window).argmax(1) written into the class map) and of validate_downstream (src/utils.py:497-541).
 // The windows covering pixel (y, x) are the rectangle of window rows r in [ceil((y - win + 1) / stride), y / stride] and columns
 // likewise, clipped to the grid; each thread owns one pixel and sums them in window order (row, then column): no atomics, a fixed
-// order, so the map is bitwise reproducible and independent of how the windows were split into calls.
+// order, so the map is bitwise reproducible and independent of how the windows were split into calls.  (scene_cover: msst_kernels.h,
+// shared with msst_scene_recon.hip.)
 // ==========================================================================================
-__device__ __forceinline__ bool scene_cover(const SceneArgs& a, int y, int x, int& rlo, int& rhi, int& qlo, int& qhi) {
-    rlo = y < a.win ? 0 : (y - a.win) / a.stride + 1;
-    rhi = min(y / a.stride, a.nr - 1);
-    qlo = x < a.win ? 0 : (x - a.win) / a.stride + 1;
-    qhi = min(x / a.stride, a.nq - 1);
-    return rlo <= rhi && qlo <= qhi;
-}
-
 // adds the windows win0 .. win0 + nwin - 1 into the running sums; pixel p of the launch = flattened row row0 + p / Ws, column p % Ws.
 // A pixel whose first covering window is in this call starts from 0 (no memset); one with no window in this call is not touched.
 __global__ __launch_bounds__(256) void scene_accumulate_kernel(SceneArgs a, long pixels) {

@@ -75,11 +75,11 @@ struct TokArgs {
     const float* pos_a;      // pos_split == 0: learned table [T][96]; else spatial table [N][pos_split]
     const float* pos_b;      // pos_split != 0: spectral table [S][96 - pos_split]
     const float* mask_token; // [96]
-    const uint8_t* mask;     // [B][T] (1 = masked); all-zero for the classification path
+    const uint8_t* mask;     // [B][T] (1 = masked); all-zero for the classification path.  TOK_SCENE_MASKED: the scene mask [Bs][S][Hs][Ws]
     float* out;              // [B][T][96]
     int B, S, N, T, P, pos_split;
     Drop drop;               // embedding dropout on (token + pos) (vit_spatial_spectral.py:530), classification path only
-    // scene windows (msst_tokenize_scene_fwd / _fwd_train, the kernels' SCENE = true instances only): img is a scene [Bs][S*P][Hs][Ws] and
+    // scene windows (msst_tokenize_scene_fwd / _fwd_train / _fwd_masked, the kernels' TOK_SCENE* instances only): img is a scene [Bs][S*P][Hs][Ws] and
     // sample b is window win0 + b, row-major over (scene, window row, window column), origin (r * stride, q * stride), win x win pixels
     long win0;
     int Hs, Ws, win, stride, nq, wps;   // nq: windows per window row, wps: windows per scene
@@ -93,6 +93,26 @@ __device__ __forceinline__ const float* scene_window_origin(const Args& a, int b
     const long s = i / a.wps;
     const int rem = (int)(i - s * a.wps), r = rem / a.nq, q = rem - r * a.nq;
     return a.img + ((s * a.S * a.P) * a.Hs + (long)r * a.stride) * a.Ws + (long)q * a.stride;
+}
+
+// mask byte of token (c, n = 0) of sample b's window in a scene mask [Bs][S][Hs][Ws] (TOK_SCENE_MASKED: TokArgs.mask): one byte per
+// spectral block and pixel; token (c, n) is (n / win) * Ws + n % win further
+__device__ __forceinline__ const uint8_t* scene_window_mask(const TokArgs& a, int b, int c) {
+    const long i = a.win0 + b;
+    const long s = i / a.wps;
+    const int rem = (int)(i - s * a.wps), r = rem / a.nq, q = rem - r * a.nq;
+    return a.mask + (((s * a.S + c) * a.Hs) + (long)r * a.stride) * a.Ws + (long)q * a.stride;
+}
+
+// the windows covering pixel (y, x) of a scene: window rows rlo .. rhi and columns qlo .. qhi of the grid (Args: win, stride, nr, nq);
+// false when no window covers it
+template <class Args>
+__device__ __forceinline__ bool scene_cover(const Args& a, int y, int x, int& rlo, int& rhi, int& qlo, int& qhi) {
+    rlo = y < a.win ? 0 : (y - a.win) / a.stride + 1;
+    rhi = min(y / a.stride, a.nr - 1);
+    qlo = x < a.win ? 0 : (x - a.win) / a.stride + 1;
+    qhi = min(x / a.stride, a.nq - 1);
+    return rlo <= rhi && qlo <= qhi;
 }
 
 // scene assembly (msst_scene_assemble): per-window logits -> running per-pixel sums (accumulate), then mean / argmax (finalize)
@@ -250,6 +270,7 @@ int launch_scene_centre_fill(const SceneArgs& a, hipStream_t st);
 
 int launch_tokenize_fwd(const TokArgs& a, hipStream_t st);
 int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st);   // the same kernels reading windows of a scene (TokArgs scene fields)
+int launch_tokenize_scene_fwd_masked(const TokArgs& a, hipStream_t st);   // ... with a scene mask (a.mask [Bs][S][Hs][Ws]) and the mask token
 int launch_head_bwd(const HeadBwdArgs& a, int nchunk, hipStream_t st);
 // One reduction segment: dst[(i / row_len) * row_stride + i % row_len] = sum_{k < nslab} src[k * slab_stride + i], i < n
 struct RSeg {
@@ -368,5 +389,21 @@ struct ReconArgs {
     int B, S, N, P, per_block, blend;
 };
 int launch_recon_fwd(const ReconArgs& a, hipStream_t st);
+
+// msst_scene_recon.hip (msst_scene_recon_assemble): per-window pixel predictions -> running per-pixel sums (accumulate), then the mean, the
+// blend with the scene, the per-band masked |pred - scene| sums and the cover map (finalize)
+struct SceneReconArgs {
+    const float* win_recon;      // [nwin][S*P][win * win] of windows win0 .. win0 + nwin - 1 (msst_recon_fwd, blend = 0)
+    const float* scene;          // [Bs][S*P][Hs][Ws]
+    const uint8_t* scene_mask;   // [Bs][S][Hs][Ws] (non-zero = masked)
+    float* cube;                 // [Bs][S*P][Hs][Ws]: the running sums, then the result
+    double* band_err;            // optional [Bs][S*P] (with band_cnt)
+    int32_t* band_cnt;           // optional [Bs][S*P]
+    int32_t* cover;              // [Bs][Hs][Ws]: windows covering the pixel
+    long win0, row0;             // row0: first flattened (scene, pixel row) row the windows of the call touch (accumulate)
+    int nwin, Bs, S, P, Hs, Ws, win, stride, nr, nq, blend;
+};
+int launch_scene_recon_accumulate(const SceneReconArgs& a, long pixels, hipStream_t st);
+int launch_scene_recon_finalize(const SceneReconArgs& a, hipStream_t st);
 
 }  // namespace msst

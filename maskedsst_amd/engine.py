@@ -616,6 +616,79 @@ class Engine:
             acts, _ = self.blocks_fwd(x0, save=False)
             return self.recon_fwd(acts[-1], img, mask_u8, blend)
 
+    def tokenize_scene_masked(self, scene, scene_mask_u8, stride, win0, nwin, out=None):
+        """msst_tokenize_scene_fwd_masked: the tokens of windows win0 .. win0 + nwin - 1 of scene [Bs, C, Hs, Ws] (fp32 cuda, contiguous)
+        with the tokens that scene_mask_u8 [Bs, S, Hs, Ws] (uint8, non-zero = masked) marks replaced by the mask token -> out
+        [>= nwin, T, 96]; bit for bit what tokenize gives for the copied windows and their copied masks"""
+        self._require_cuda(scene)
+        self._require_cuda(scene_mask_u8)
+        if self.mim is None:
+            raise RuntimeError("tokenize_scene_masked needs the SimMIM wrapper's mask token (a bare encoder has none)")
+        self.ensure()
+        Bs, _, Hs, Ws = scene.shape
+        S, N, P = self.S, self.N, self.P
+        w = self.enc.num_spatial_patches_sqrt
+        if scene.dtype != torch.float32 or not scene.is_contiguous() or scene_mask_u8.dtype != torch.uint8 or \
+                not scene_mask_u8.is_contiguous() or tuple(scene_mask_u8.shape) != (Bs, S, Hs, Ws):
+            raise ValueError(f"tokenize_scene_masked takes a contiguous fp32 scene and a contiguous uint8 mask [{Bs}, {S}, {Hs}, {Ws}]")
+        if out is None:
+            out = torch.empty(nwin, S * N, D, dtype=torch.float32, device=scene.device)
+        fp = self.fp
+        split, pos_a, pos_b = self._pos_tables()
+        V = ctypes.c_void_p
+        _lib.check(self.lib.msst_tokenize_scene_fwd_masked(
+            _p(scene), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
+            V(fp.ptr("post_g")), V(fp.ptr("post_b")), V(pos_a), V(pos_b), split, V(fp.ptr("mask_token")), _p(scene_mask_u8), _p(out),
+            Bs, Hs, Ws, w, stride, win0, nwin, S, P, _stream()), "msst_tokenize_scene_fwd_masked")
+        return out
+
+    def reconstruct_scene(self, scene, scene_mask_u8, stride, blend=True, max_windows=2048):
+        """Eval forward of the SimMIM model down to pixels over every window of scene [Bs, C, Hs, Ws] (window = image_size, origins 0,
+        stride, 2 stride, ...) with scene_mask_u8 [Bs, S, Hs, Ws] (uint8 cuda, non-zero = masked) -> (cube [Bs, C, Hs, Ws] fp32,
+        band_err [Bs, C] float64, band_cnt [Bs, C] int32, cover [Bs, Hs, Ws] int32).  The loop of scene_forward: chunks of at most
+        max_windows windows; the masked scene tokenizer reads a chunk's windows out of the scene, the blocks run on two token buffers
+        in turn, msst_recon_fwd (no blend, no statistics) writes per-window predictions and msst_scene_recon_assemble adds them into
+        the cube, finalizing on the last chunk (mean over the covering windows, blend, per-band masked error, cover).  No dropout,
+        nothing saved, no autograd; the current stream; the model's precision."""
+        self._require_cuda(scene)
+        self._require_cuda(scene_mask_u8)
+        if self.mim is None:
+            raise RuntimeError("reconstruct_scene needs the SimMIM wrapper's mask token and to_pixels (a bare encoder has neither)")
+        with torch.no_grad():
+            scene = scene.contiguous().float()
+            scene_mask_u8 = scene_mask_u8.contiguous()
+            Bs, C, Hs, Ws = scene.shape
+            S, N, P = self.S, self.N, self.P
+            w = self.enc.num_spatial_patches_sqrt
+            nr, nq = (Hs - w) // stride + 1, (Ws - w) // stride + 1
+            total = Bs * nr * nq
+            chunk = max(1, min(int(max_windows), total, 65535))   # 65535: the generic tokenizer runs one grid row per window
+            dev = scene.device
+            self.prep_weights()
+            bufs = [torch.empty(chunk, S * N, D, dtype=torch.float32, device=dev) for _ in range(2)]
+            # msst_recon_fwd reads a cube and a token mask whatever blend is: with blend = 0 and no statistics neither reaches its output
+            no_img = torch.zeros(chunk, S * P, N, dtype=torch.float32, device=dev)
+            no_mask = self._zero_mask_for(chunk * S * N, dev)
+            win_recon = torch.empty(chunk, S * P, N, dtype=torch.float32, device=dev)
+            cube = torch.empty(Bs, C, Hs, Ws, dtype=torch.float32, device=dev)
+            err = torch.empty(Bs, C, dtype=torch.float64, device=dev)
+            cnt = torch.empty(Bs, C, dtype=torch.int32, device=dev)
+            cover = torch.empty(Bs, Hs, Ws, dtype=torch.int32, device=dev)
+            per_block = 1 if hasattr(self.mim.to_pixels, "layers") else 0
+            V = ctypes.c_void_p
+            st = _stream()
+            for win0 in range(0, total, chunk):
+                n = min(chunk, total - win0)
+                self.tokenize_scene_masked(scene, scene_mask_u8, stride, win0, n, out=bufs[0])
+                y = self.blocks_fwd_pingpong(bufs[0], other=bufs[1], n=n, stream=st)
+                _lib.check(self.lib.msst_recon_fwd(_p(y), _p(no_img), _p(no_mask), V(self.fp.ptr("to_pixels.w.0")),
+                                                   V(self.fp.ptr("to_pixels.b.0")), per_block, 0, _p(win_recon), None, None, n, S, N, P, st),
+                           "msst_recon_fwd")
+                _lib.check(self.lib.msst_scene_recon_assemble(_p(win_recon), win0, n, _p(scene), _p(scene_mask_u8), _p(cube), _p(err),
+                                                              _p(cnt), _p(cover), Bs, S, P, Hs, Ws, w, stride, int(win0 + n == total),
+                                                              int(bool(blend)), st), "msst_scene_recon_assemble")
+            return cube, err, cnt, cover
+
     # ------------------------------------------------------------------ backward pieces
     def _fire(self, bucket):
         if self.bucket_hook is not None:

@@ -19,6 +19,10 @@ from .vit_spatial_spectral import ViTSpatialSpectral
 # what SimMIMSpatialSpectral.reconstruct returns: cube [B, C, H, W] fp32, mask [B, C, H, W] bool (the token mask over the P bands of
 # each token), band_err [B, C] float64 (sum of |prediction - input| over the band's masked pixels), band_cnt [B, C] int32 (how many)
 Reconstruction = namedtuple("Reconstruction", ["cube", "mask", "band_err", "band_cnt"])
+# what SimMIMSpatialSpectral.reconstruct_scene returns: the same four over a whole scene [Bs, C, Hs, Ws] -- mask: the scene mask over
+# the P bands of each spectral block AND covered by a window (exactly the pixels band_cnt counts) -- and cover [Bs, Hs, Ws] int32, the
+# number of windows covering a pixel
+SceneReconstruction = namedtuple("SceneReconstruction", ["cube", "mask", "band_err", "band_cnt", "cover"])
 
 
 class BlockwiseToPixels(nn.Module):
@@ -144,3 +148,41 @@ class SimMIMSpatialSpectral(nn.Module):
         recon, err, cnt = eng.reconstruct(img, mask_u8, blend)   # passes no dropout and saves nothing, whatever self.training
         mask = mask_u8.bool().view(B, S, 1, s, s).expand(B, S, P, s, s).reshape(B, C, s, s)
         return Reconstruction(recon.view(B, C, s, s), mask, err, cnt)
+
+    def reconstruct_scene(self, scene, mask=None, stride=None, blend=True, max_windows=None):
+        """``reconstruct`` for whole scenes: scene [Bs, bands, Hs, Ws] (any Hs, Ws >= image_size) with a mask in scene coordinates ->
+        SceneReconstruction(cube, mask, band_err, band_cnt, cover).
+
+        Every ``image_size`` window with origin 0, stride, 2 stride, ... is read straight out of the scene (tokens under the mask
+        replaced by the mask token), all windows run as one batch (in chunks of ``max_windows``), and the per-window predictions are
+        assembled on the device; overlapping windows (``stride < image_size``) are averaged.  With ``blend`` (default) every element
+        whose token is not masked, and every pixel no window covers, is the input's own; without it covered pixels hold the
+        prediction and uncovered pixels NaN.  ``band_err / band_cnt`` is the mean absolute error of a band over its masked, covered
+        pixels (``maskedsst_amd.recon_report`` sums it up); ``cover`` the number of windows covering a pixel.
+        mask: a bool [Bs, S, Hs, Ws] tensor (S spectral blocks; any device): dead detector columns, invalid bands, clouds.  None draws
+        window masks as ``reconstruct`` does for Bs nr nq windows (sets ``last_masks``) and places them in scene coordinates
+        (``maskedsst_amd.window_masks_to_scene``); that needs ``stride == image_size``, the default stride.
+        Always an eval forward under no_grad (no dropout), whatever the module's mode, which is left as it is."""
+        from .recon import window_masks_to_scene
+        from .scene import _check_scene, SCENE_MAX_WINDOWS
+        enc = self.encoder
+        stride, max_windows = _check_scene(enc, scene, stride, SCENE_MAX_WINDOWS if max_windows is None else max_windows)
+        Bs, C, Hs, Ws = scene.shape
+        S, P, w = enc.num_spectral_patches, enc.pixels_per_patch, enc.num_spatial_patches_sqrt
+        if mask is None:
+            if stride != w:
+                raise ValueError(f"mask=None draws one random mask per window, which needs non-overlapping windows: stride must be "
+                                 f"{w} (the window size), got {stride}")
+            nr, nq = (Hs - w) // w + 1, (Ws - w) // w + 1
+            masks = self.draw_masks(Bs * nr * nq)
+            self.last_masks = masks
+            mask = window_masks_to_scene(self._token_mask(masks, Bs * nr * nq), Bs, S, Hs, Ws, w)
+        elif not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (Bs, S, Hs, Ws):
+            raise ValueError(f"mask must be a bool [{Bs}, {S}, {Hs}, {Ws}] tensor (scenes, spectral blocks, H, W), got "
+                             f"{getattr(mask, 'dtype', type(mask))} {tuple(getattr(mask, 'shape', ()))}")
+        eng = self.engine()
+        eng._require_cuda(scene)
+        mask_u8 = mask.to(device=scene.device, dtype=torch.uint8).contiguous()
+        cube, err, cnt, cover = eng.reconstruct_scene(scene, mask_u8, stride, blend, max_windows)
+        counted = (mask_u8.bool() & (cover > 0)[:, None]).view(Bs, S, 1, Hs, Ws).expand(Bs, S, P, Hs, Ws).reshape(Bs, C, Hs, Ws)
+        return SceneReconstruction(cube, counted, err, cnt, cover)

@@ -66,7 +66,19 @@ def build_parser():
     ap.add_argument("--recon-report", action="store_true",
                     help="after every validation pass print one more line: the masked mean absolute error of model.reconstruct on "
                          "the first window of the validation tiles, and its three worst bands")
+    ap.add_argument("--recon-tiles", action="store_true",
+                    help="after every validation pass print one more line: the masked mean absolute error of model.reconstruct_scene "
+                         "over the whole validation tiles (every window), and its three worst bands")
     return ap
+
+
+def recon_tiles_line(model, tiles, epoch):
+    """the --recon-tiles line: model.reconstruct_scene on the whole validation tiles (every non-overlapping window, one random mask
+    per window) -> overall masked MAE and the three worst bands"""
+    from maskedsst_amd import recon_report
+    rep = recon_report(model.reconstruct_scene(tiles), model.pixel_values_per_patch)
+    worst = " ".join(f"{b}:{float(rep.band_mae[b]):.4e}" for b in rep.worst_bands[:3])
+    return f"epoch {epoch} recon tiles masked_mae {rep.mae:.6e} over {rep.masked} pixels, worst bands {worst}"
 
 
 def recon_line(model, window, epoch):
@@ -194,6 +206,10 @@ def main():
             val_loss = torch.stack(val_losses).mean()
             if args.recon_report:   # on every rank: drawing the masks advances the generators the ranks share
                 line = recon_line(model, val_tiles[:, :, :s_, :s_].contiguous(), epoch)
+                if rank == 0:
+                    print(line, flush=True)
+            if args.recon_tiles:    # on every rank, for the same reason
+                line = recon_tiles_line(model, val_tiles, epoch)
                 if rank == 0:
                     print(line, flush=True)
             # every rank validates on its own shard: the plateau scheduler must see the SAME number everywhere, or the

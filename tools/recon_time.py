@@ -14,6 +14,13 @@ then comes out of the 256 MB memory-side cache, as it does right after the last 
 every time and the largest difference between the two results.
 
 Run:  python tools/recon_time.py [--steps 20] [--warmup 3] [--precision bf16] [--batch 256] [--bands 200] [--depth 12]
+
+--scene: whole-tile reconstruction instead.  SimMIMSpatialSpectral.reconstruct_scene on --tiles tiles of --tile-size x --tile-size
+(default 4 of 64 x 64; non-overlapping 8 x 8 windows, one random mask per window placed in tile coordinates) against the path
+there was before it: the windows stacked into a batch (a copy), reconstruct on it, the cube re-tiled and the per-window tables summed
+per tile in PyTorch.  Alternated in one process, median of --steps per repetition, --reps repetitions; msst_scene_recon_assemble and
+the masked scene tokenizer also on their own between device events.  ONE JSON line (tool = "recon_scene_time"); --append FILE also
+appends it to FILE.
 """
 import argparse
 import json
@@ -85,6 +92,87 @@ def event_ms(fn, n=10):
     return a.elapsed_time(b) / n
 
 
+def scene_main(args, device):
+    import ctypes
+    from maskedsst_amd import window_masks_to_scene
+    from maskedsst_amd.engine import _p, _stream
+    model = build(args, device)
+    eng = model.engine()
+    enc = model.encoder
+    S, P, C, B, ts, w = enc.num_spectral_patches, enc.pixels_per_patch, args.bands, args.tiles, args.tile_size, 8
+    nr = nq = ts // w
+    nwin = B * nr * nq
+    gen = torch.Generator().manual_seed(SEED)
+    tiles = torch.randn(B, C, ts, ts, generator=gen).to(device)
+    bm = model.draw_masks(nwin)[0]
+    scene_mask = window_masks_to_scene(bm, B, S, ts, ts, w).to(device)
+
+    def fast():
+        return model.reconstruct_scene(tiles, scene_mask)
+
+    def slow():
+        stacked = tiles[:, :, :nr * w, :nq * w].reshape(B, C, nr, w, nq, w).permute(0, 2, 4, 1, 3, 5).reshape(nwin, C, w, w).contiguous()
+        rec = model.reconstruct(stacked, bm)
+        cube = tiles.clone()   # trailing rows / columns no window covers keep the input
+        cube[:, :, :nr * w, :nq * w] = rec.cube.view(B, nr, nq, C, w, w).permute(0, 3, 1, 4, 2, 5).reshape(B, C, nr * w, nq * w)
+        return cube, rec.band_err.view(B, nr * nq, C).sum(1), rec.band_cnt.view(B, nr * nq, C).sum(1, dtype=torch.int32)
+
+    for _ in range(max(1, args.warmup)):
+        fast()
+        slow()
+    reps = []
+    for _ in range(args.reps):
+        tf, ts_ = [], []
+        for _ in range(args.steps):
+            t, rec = timed(fast)
+            tf.append(t)
+            t, (cube, err, cnt) = timed(slow)
+            ts_.append(t)
+        reps.append((statistics.median(tf), statistics.median(ts_), min(tf), min(ts_)))
+    # the two new kernels on their own: the assembler (accumulate + finalize) on the per-window predictions, the masked tokenizer
+    stacked = tiles[:, :, :nr * w, :nq * w].reshape(B, C, nr, w, nq, w).permute(0, 2, 4, 1, 3, 5).reshape(nwin, C, w, w).contiguous()
+    win_recon = model.reconstruct(stacked, bm, blend=False).cube.contiguous()
+    mask_u8 = scene_mask.to(torch.uint8).contiguous()
+    out = torch.empty(B, C, ts, ts, device=device)
+    e2, c2 = torch.empty(B, C, dtype=torch.float64, device=device), torch.empty(B, C, dtype=torch.int32, device=device)
+    cov = torch.empty(B, ts, ts, dtype=torch.int32, device=device)
+    tok = torch.empty(nwin, S * w * w, 96, device=device)
+
+    def assemble():
+        rc = eng.lib.msst_scene_recon_assemble(_p(win_recon), 0, nwin, _p(tiles), _p(mask_u8), _p(out), _p(e2), _p(c2), _p(cov), B, S, P,
+                                               ts, ts, w, w, 1, 1, _stream())
+        assert rc == 0, rc
+
+    def tokenize():
+        eng.tokenize_scene_masked(tiles, mask_u8, w, 0, nwin, out=tok)
+
+    ta, tt = [], []
+    for _ in range(max(1, args.warmup)):
+        assemble()
+        tokenize()
+    for _ in range(args.steps):
+        ta.append(event_ms(assemble))
+        tt.append(event_ms(tokenize))
+    torch.cuda.synchronize()
+    moved = 4 * (win_recon.numel() + 3 * out.numel() + tiles.numel()) + mask_u8.numel() * P   # accumulate: read + write; finalize: cube r/w, scene, mask per band
+    row = dict(
+        tool="recon_scene_time", precision=args.precision, bands=args.bands, depth=args.depth, tiles=B, tile_size=ts, windows=nwin,
+        steps=args.steps, reps=args.reps,
+        reconstruct_scene_ms=[round(1e3 * r[0], 3) for r in reps], stacked_ms=[round(1e3 * r[1], 3) for r in reps],
+        reconstruct_scene_ms_min=[round(1e3 * r[2], 3) for r in reps], stacked_ms_min=[round(1e3 * r[3], 3) for r in reps],
+        assemble_kernels_ms=round(statistics.median(ta), 4), assemble_kernels_ms_min=round(min(ta), 4), assemble_bytes=moved,
+        masked_tokenizer_ms=round(statistics.median(tt), 4), masked_tokenizer_ms_min=round(min(tt), 4),
+        cube_equal=bool(torch.equal(rec.cube, cube)), assembled_equal=bool(torch.equal(out, cube)),
+        max_rel_band_err_diff=float(((rec.band_err - err).abs() / err.abs().clamp(min=1e-30)).max()),
+        band_cnt_equal=bool(torch.equal(rec.band_cnt, cnt)))
+    line = json.dumps(row)
+    print(line, flush=True)
+    if args.append:
+        os.makedirs(os.path.dirname(os.path.abspath(args.append)), exist_ok=True)
+        with open(args.append, "a") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -94,10 +182,17 @@ def main():
     ap.add_argument("--bands", type=int, default=200)
     ap.add_argument("--depth", type=int, default=12)
     ap.add_argument("--heads", type=int, default=8)
+    ap.add_argument("--scene", action="store_true", help="time reconstruct_scene on whole tiles against the stacked-window path")
+    ap.add_argument("--tiles", type=int, default=4)
+    ap.add_argument("--tile-size", type=int, default=64)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--append", default=None, help="--scene: also append the JSON line to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/recon_time.py needs an MI355X: maskedsst_amd has no CPU fallback")
     device = torch.device("cuda")
+    if args.scene:
+        return scene_main(args, device)
     model = build(args, device)
     eng = model.engine()
     gen = torch.Generator().manual_seed(SEED)
