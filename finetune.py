@@ -85,6 +85,9 @@ def build_parser():
     ap.add_argument("--val-report", action="store_true",
                     help="one more line per validation: overall and average accuracy, Cohen's kappa and mean IoU from the confusion "
                          "matrix of the same pass of the HIP loss kernels (maskedsst_amd.scene.scene_report)")
+    ap.add_argument("--val-embed", action="store_true",
+                    help="one more line per validation: nearest-class-mean accuracy on the frozen per-pixel features of "
+                         "encode_scene(normalize=True); class means from the first half of the --val-scenes, scored on the second half")
     return ap
 
 
@@ -198,6 +201,8 @@ def main():
                   flush=True)
         if val is not None and step % args.val_every == 0:
             validate(model, val, step, config.ignored_label, fused=fused, report=args.val_report)
+            if args.val_embed:
+                validate_embedding(model, val, step, config.n_classes, config.ignored_label)
 
 
 def validate(model, val, step, ignored_label, fused=False, report=False):
@@ -215,6 +220,31 @@ def validate(model, val, step, ignored_label, fused=False, report=False):
         r = full.report
         print(f"val step {step} report OA {r.oa:.4f} AA {r.aa:.4f} kappa {r.kappa:.4f} mIoU {r.mean_iou:.4f} mF1 {r.mean_f1:.4f} "
               f"pixels {r.total}", flush=True)
+
+
+def validate_embedding(model, val, step, n_classes, ignored_label):
+    """--val-embed: how separable the classes are in the encoder's own representation, without the head.  One encode_scene pass
+    (windows of image_size, eval forward, the module's mode untouched, unit-length 96-vectors per pixel); the class means of the
+    labelled covered pixels of the first half of the scenes classify those of the second half by the nearest mean (plain torch on
+    the returned map).  nan when either half has no such pixel (fewer than two scenes)."""
+    img, label = val
+    emb = model.encode_scene(img, normalize=True)
+    f = emb.features.permute(0, 2, 3, 1)                      # [Bs, Hs, Ws, 96]
+    ok = (emb.cover > 0) & (label != ignored_label)
+    half = img.shape[0] // 2
+    ftr, ltr = f[:half][ok[:half]], label[:half][ok[:half]]
+    fte, lte = f[half:][ok[half:]], label[half:][ok[half:]]
+    acc, present = float("nan"), 0
+    if half > 0 and len(ltr) and len(lte):
+        sums = torch.zeros(n_classes, f.shape[-1], device=f.device).index_add_(0, ltr, ftr)
+        count = torch.bincount(ltr, minlength=n_classes)
+        means = sums / count.clamp(min=1).unsqueeze(1)
+        dist = torch.cdist(fte, means)
+        dist[:, count == 0] = float("inf")                   # a class the first half never shows cannot be predicted
+        acc = float((dist.argmin(dim=1) == lte).double().mean())
+        present = int((count > 0).sum())
+    print(f"val-embed step {step} ncm_acc {acc:.3f} classes {present} train_pixels {len(ltr)} test_pixels {len(lte)} "
+          f"scenes {img.shape[0]}", flush=True)
 
 
 if __name__ == "__main__":

@@ -225,6 +225,36 @@ int msst_scene_recon_assemble(const float* win_recon, long win0, int nwin, const
                               double* band_err /*optional*/, int32_t* band_cnt /*optional*/, int32_t* cover, int Bs, int S, int P,
                               int Hs, int Ws, int window, int stride, int finalize, int blend, void* stream);
 
+/* Whole-scene embedding maps (ViTSpatialSpectral.encode_scene).  Additive under MSST_VERSION 109: no struct and no existing signature
+ * changes.  The windows of a scene, numbered as for msst_tokenize_scene_fwd, run through msst_tokenize_scene_fwd and msst_block_fwd as
+ * one batch; msst_pool_spectral_fwd turns the encoder output into per-window features and msst_scene_embed_assemble writes the
+ * scene-shaped feature map: overlapping windows averaged, as msst_scene_assemble does for logits.  No head runs.
+ *
+ * msst_pool_spectral_fwd: y [B][S N][96] (token c N + n) -> out [B][96][N],
+ *   out[b][d][n] = (sum over c = 0 .. S - 1, in that order, of y[b][c N + n][d]) / (float)S
+ * -- the mean over the spectral axis that the default and the pixelwise head normalise, in the window layout msst_scene_assemble and
+ * msst_scene_embed_assemble take (96 in the place of n_classes).  y is read once with 16-byte loads (it must be 16-byte aligned), the
+ * transpose goes through LDS, the stores are runs of N consecutive floats.  Two calls give the same bits.
+ * Checked before anything is enqueued, in this order: MSST_ERR_BADARG for a size below 1; MSST_ERR_UNSUPPORTED for N > 64 or S > 64;
+ * MSST_ERR_BADARG for a null or misaligned pointer. */
+int msst_pool_spectral_fwd(const float* y, float* out, int B, int S, int N, void* stream);
+
+/* msst_scene_embed_assemble: adds the per-window features win_feat [nwin][D][window*window] (windows win0 .. win0 + nwin - 1) into the
+ * running fp32 sums feat [Bs][D][Hs][Ws].  The calls of one scene batch must cover windows 0, 1, ... in order (any split into calls);
+ * feat needs no initialisation: a pixel starts from 0 in the call that holds its first window.  Each pixel adds its windows in window
+ * order (row, then column) without atomics.  finalize != 0 (the last call, after its own windows):
+ *   a pixel covered by k >= 1 windows holds sum / k in every channel; with l2norm != 0 that vector f is then divided by
+ *     max(||f||_2, 1e-12) (torch.nn.functional.normalize), the squares added in the order d = 0 .. D - 1 in fp32: an all-zero pixel
+ *     stays zero;
+ *   a pixel no window covers holds NaN in every channel (an absent value is never a made-up number);
+ *   cover [Bs][Hs][Ws] int32: k, the number of windows covering the pixel (0: uncovered).
+ * cover is written by the finalizing call only.  No atomics, nothing to zero: two runs give the same bits, whatever the split.
+ * Checked before anything is enqueued, in this order: MSST_ERR_BADARG for a size below 1 (nwin = 0 is allowed); MSST_ERR_UNSUPPORTED
+ * outside stride <= window <= Hs, Ws, window * window <= 64, D <= 128; MSST_ERR_BADARG for a null required pointer (win_feat when
+ * nwin > 0, feat, cover when finalize != 0) or windows beyond win0 + nwin <= Bs nr nq. */
+int msst_scene_embed_assemble(const float* win_feat, long win0, int nwin, float* feat, int32_t* cover, int Bs, int D, int Hs, int Ws,
+                              int window, int stride, int finalize, int l2norm, void* stream);
+
 /* a7-a10: one fused pre-norm transformer block (PreNorm+Attention+FeedForward+residuals,
  * vit_spatial_spectral.py:22-104) over all B*S*N tokens; mode selects the spatial or spectral
  * sequence grouping of vit_spatial_spectral.py:410-431 (no transposes are materialised).

@@ -11,6 +11,7 @@ from .vit_spatial_spectral import ViTSpatialSpectral  # noqa: F401
 from .vit_simmim_original import SimMIMSpatialSpectral, BlockwiseToPixels, Reconstruction, SceneReconstruction  # noqa: F401
 from .recon import recon_report, ReconReport, window_masks_to_scene, scene_mask_to_windows  # noqa: F401
 from .masking import MaskGenerator  # noqa: F401
+from .scene import SceneEmbedding  # noqa: F401
 
 __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "MaskGenerator", "Reconstruction", "recon_report",
-           "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows"]
+           "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows", "SceneEmbedding"]

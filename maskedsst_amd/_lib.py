@@ -69,6 +69,8 @@ _SIGS = {
     "msst_tokenize_scene_bwd": (c_int, [_P] * 9 + [c_int] + [_P] * 8 + [c_int] * 6 + [c_long, c_int, c_int, c_int, c_float, c_uint32, _P]),
     "msst_tokenize_scene_fwd_masked": (c_int, [_P] * 9 + [c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_long, c_int, c_int, c_int, _P]),
     "msst_scene_recon_assemble": (c_int, [_P, c_long, c_int, _P, _P, _P, _P, _P, _P] + [c_int] * 9 + [_P]),
+    "msst_pool_spectral_fwd": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "msst_scene_embed_assemble": (c_int, [_P, c_long, c_int, _P, _P] + [c_int] * 8 + [_P]),
     "msst_scene_assemble": (c_int, [_P, c_long, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "msst_cls_head_fwd": (c_int, [_P] * 6 + [c_int, c_int, c_int, c_int, _P]),
     "msst_cls_head_bwd": (c_int, [_P] * 11 + [c_int, c_int, c_int, c_int, _P]),

@@ -431,6 +431,44 @@ int msst_scene_recon_assemble(const float* win_recon, long win0, int nwin, const
     return fail(rc, "msst_scene_recon_assemble");
 }
 
+int msst_pool_spectral_fwd(const float* y, float* out, int B, int S, int N, void* stream) {
+    if (B < 1 || S < 1 || N < 1) return fail(MSST_ERR_BADARG, "msst_pool_spectral_fwd");
+    if (N > 64 || S > 64) return fail(MSST_ERR_UNSUPPORTED, "msst_pool_spectral_fwd (N <= 64, S <= 64)");
+    if (!y || !out || ((uintptr_t)y & 15)) return fail(MSST_ERR_BADARG, "msst_pool_spectral_fwd (null argument, or y not 16-byte aligned)");
+    return fail(launch_pool_spectral(y, out, B, S, N, (hipStream_t)stream), "msst_pool_spectral_fwd");
+}
+
+int msst_scene_embed_assemble(const float* win_feat, long win0, int nwin, float* feat, int32_t* cover, int Bs, int D, int Hs, int Ws,
+                              int window, int stride, int finalize, int l2norm, void* stream) {
+    if (Bs < 1 || D < 1 || Hs < 1 || Ws < 1 || window < 1 || stride < 1 || nwin < 0 || win0 < 0)
+        return fail(MSST_ERR_BADARG, "msst_scene_embed_assemble");
+    if (stride > window || window > Hs || window > Ws || window * window > 64 || D > 128)
+        return fail(MSST_ERR_UNSUPPORTED, "msst_scene_embed_assemble (1 <= stride <= window <= Hs, Ws; window * window <= 64, D <= 128)");
+    if ((nwin > 0 && !win_feat) || !feat || (finalize && !cover)) return fail(MSST_ERR_BADARG, "msst_scene_embed_assemble (null argument)");
+    int nr = 0, nq = 0;
+    scene_grid(Bs, Hs, Ws, window, stride, &nr, &nq);
+    const long wps = (long)nr * nq;
+    if (win0 + nwin > (long)Bs * wps) return fail(MSST_ERR_BADARG, "msst_scene_embed_assemble (windows out of range)");
+    // both launches' grids fit (so nothing is refused after the first one is enqueued)
+    if (((long)Bs * Hs * Ws + 255) / 256 > 0x7fffffffL) return fail(MSST_ERR_UNSUPPORTED, "msst_scene_embed_assemble (scene batch too large)");
+    SceneEmbedArgs a;
+    a.win_feat = win_feat; a.feat = feat; a.cover = cover; a.win0 = win0; a.row0 = 0; a.nwin = nwin; a.Bs = Bs; a.D = D; a.Hs = Hs;
+    a.Ws = Ws; a.win = window; a.stride = stride; a.nr = nr; a.nq = nq; a.l2norm = l2norm != 0;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = 0;
+    if (nwin > 0) {
+        // the flattened (scene, pixel row) rows the windows of this call reach, as in msst_scene_assemble
+        const long g0 = win0, g1 = win0 + nwin - 1;
+        const long s0 = g0 / wps, s1 = g1 / wps;
+        const long r0 = (g0 - s0 * wps) / nq, r1 = (g1 - s1 * wps) / nq;
+        a.row0 = s0 * Hs + r0 * stride;
+        const long rows = s1 * Hs + r1 * stride + window - a.row0;
+        rc = launch_scene_embed_accumulate(a, rows * Ws, st);
+    }
+    if (!rc && finalize) rc = launch_scene_embed_finalize(a, st);
+    return fail(rc, "msst_scene_embed_assemble");
+}
+
 long msst_block_lse_floats(int mode, int B, int S, int N, int heads) {
     if (B < 1 || S < 1 || N < 1 || heads < 1 || N > 64 || S > 64) return 0;
     return (long)ntiles_of(make_tilemap(mode, B, S, N)) * heads * 64 + (long)B * S * N;   // [tiles][heads][64] lse | [tokens] rstd of LN1

@@ -406,4 +406,18 @@ struct SceneReconArgs {
 int launch_scene_recon_accumulate(const SceneReconArgs& a, long pixels, hipStream_t st);
 int launch_scene_recon_finalize(const SceneReconArgs& a, hipStream_t st);
 
+// msst_scene_embed.hip (msst_pool_spectral_fwd, msst_scene_embed_assemble): encoder output -> per-window features (mean over the
+// spectral tokens of a position) -> running per-pixel sums (accumulate), then the mean, the optional L2 normalisation, NaN where no
+// window covers a pixel and the cover map (finalize)
+struct SceneEmbedArgs {
+    const float* win_feat;       // [nwin][D][win * win] of windows win0 .. win0 + nwin - 1 (msst_pool_spectral_fwd)
+    float* feat;                 // [Bs][D][Hs][Ws]: the running sums, then the result
+    int32_t* cover;              // [Bs][Hs][Ws]: windows covering the pixel
+    long win0, row0;             // row0: first flattened (scene, pixel row) row the windows of the call touch (accumulate)
+    int nwin, Bs, D, Hs, Ws, win, stride, nr, nq, l2norm;
+};
+int launch_pool_spectral(const float* y, float* out, int B, int S, int N, hipStream_t st);   // y [B][S N][96] -> out [B][96][N]
+int launch_scene_embed_accumulate(const SceneEmbedArgs& a, long pixels, hipStream_t st);
+int launch_scene_embed_finalize(const SceneEmbedArgs& a, hipStream_t st);
+
 }  // namespace msst

@@ -1174,38 +1174,78 @@ class Engine:
         (msst_scene_centre_assemble): logits 0 and class -1 on every pixel that is no window's centre.  No dropout, nothing saved
         for a backward."""
         self._require_cuda(scene)
-        self.ensure()
         scene = scene.contiguous().float()
         Bs, _, Hs, Ws = scene.shape
-        enc, fp = self.enc, self.fp
-        S, N, P = self.S, self.N, self.P
-        w = enc.num_spatial_patches_sqrt
-        nc = enc.num_classes
-        nr, nq = (Hs - w) // stride + 1, (Ws - w) // stride + 1
-        total = Bs * nr * nq
-        chunk = max(1, min(int(max_windows), total, 65535))   # 65535: the generic tokenizer runs one grid row per window
+        w, nc, N = self.enc.num_spatial_patches_sqrt, self.enc.num_classes, self.N
+        total, chunk = self._scene_chunking(scene, stride, max_windows)
         dev = scene.device
-        self.prep_weights()
-        split, pos_a, pos_b = self._pos_tables()
         kind = self._head_kind()
         head = _HEADS[kind]
-        bufs = [torch.empty(chunk, S * N, D, dtype=torch.float32, device=dev) for _ in range(2)]
         win_logits = torch.empty(head.shape(chunk, nc, N), dtype=torch.float32, device=dev)
         logits = torch.empty(Bs, nc, Hs, Ws, dtype=torch.float32, device=dev)
         classes = torch.empty(Bs, Hs, Ws, dtype=torch.int64, device=dev)
-        V = ctypes.c_void_p
         st = _stream()
+        for win0, n, x in self._scene_encoder_chunks(scene, stride, total, chunk, st):
+            self._head_fwd(kind, x, n, win_logits, st)
+            _lib.check(getattr(self.lib, head.assemble)(_p(win_logits), win0, n, _p(logits), _p(classes), Bs, nc, Hs, Ws, w, stride,
+                                                        int(win0 + n == total), st), head.assemble)
+        return logits, classes
+
+    def _scene_chunking(self, scene, stride, max_windows):
+        """(total, chunk): the windows of scene [Bs, C, Hs, Ws] at this stride and how many of them run at a time"""
+        Bs, _, Hs, Ws = scene.shape
+        w = self.enc.num_spatial_patches_sqrt
+        nr, nq = (Hs - w) // stride + 1, (Ws - w) // stride + 1
+        total = Bs * nr * nq
+        return total, max(1, min(int(max_windows), total, 65535))   # 65535: the generic tokenizer runs one grid row per window
+
+    def _scene_encoder_chunks(self, scene, stride, total, chunk, st):
+        """the front of scene_forward and encode_scene: for every chunk of windows of scene (contiguous fp32) yields (win0, n, y), y the
+        encoder output [>= n, T, 96] of windows win0 .. win0 + n - 1 -- one msst_tokenize_scene_fwd launch reads them out of the scene,
+        the blocks run on two token buffers in turn.  y is one of the two buffers: the next chunk overwrites it."""
+        self.ensure()
+        Bs, _, Hs, Ws = scene.shape
+        fp = self.fp
+        S, N, P = self.S, self.N, self.P
+        w = self.enc.num_spatial_patches_sqrt
+        self.prep_weights()
+        split, pos_a, pos_b = self._pos_tables()
+        bufs = [torch.empty(chunk, S * N, D, dtype=torch.float32, device=scene.device) for _ in range(2)]
+        V = ctypes.c_void_p
         for win0 in range(0, total, chunk):
             n = min(chunk, total - win0)
             _lib.check(self.lib.msst_tokenize_scene_fwd(
                 _p(scene), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
                 V(fp.ptr("post_g")), V(fp.ptr("post_b")), V(pos_a), V(pos_b), split, _p(bufs[0]), Bs, Hs, Ws, w, stride, win0, n, S, P, st),
                 "msst_tokenize_scene_fwd")
-            x = self.blocks_fwd_pingpong(bufs[0], other=bufs[1], n=n, stream=st)
-            self._head_fwd(kind, x, n, win_logits, st)
-            _lib.check(getattr(self.lib, head.assemble)(_p(win_logits), win0, n, _p(logits), _p(classes), Bs, nc, Hs, Ws, w, stride,
-                                                        int(win0 + n == total), st), head.assemble)
-        return logits, classes
+            yield win0, n, self.blocks_fwd_pingpong(bufs[0], other=bufs[1], n=n, stream=st)
+
+    # ------------------------------------------------------------------ scene embedding maps (msst_scene_embed.hip)
+    def encode_scene(self, scene, stride, normalize=False, max_windows=2048):
+        """Eval forward of the encoder over every window of scene [Bs, C, Hs, Ws] (window = image_size, origins 0, stride, 2 stride, ...)
+        -> (features [Bs, 96, Hs, Ws] fp32, cover [Bs, Hs, Ws] int32).  The chunk loop of scene_forward with another tail: no head;
+        msst_pool_spectral_fwd averages a window's encoder output over the spectral axis into [n, 96, N] and msst_scene_embed_assemble
+        adds that into the map, finalizing on the last chunk (mean over the covering windows, with normalize the division by the
+        pixel's L2 norm, NaN where no window covers a pixel, cover).  No dropout, nothing saved, no autograd; the current stream; the
+        model's precision."""
+        self._require_cuda(scene)
+        with torch.no_grad():
+            scene = scene.contiguous().float()
+            Bs, _, Hs, Ws = scene.shape
+            S, N = self.S, self.N
+            w = self.enc.num_spatial_patches_sqrt
+            total, chunk = self._scene_chunking(scene, stride, max_windows)
+            dev = scene.device
+            win_feat = torch.empty(chunk, D, N, dtype=torch.float32, device=dev)
+            feat = torch.empty(Bs, D, Hs, Ws, dtype=torch.float32, device=dev)
+            cover = torch.empty(Bs, Hs, Ws, dtype=torch.int32, device=dev)
+            st = _stream()
+            for win0, n, y in self._scene_encoder_chunks(scene, stride, total, chunk, st):
+                _lib.check(self.lib.msst_pool_spectral_fwd(_p(y), _p(win_feat), n, S, N, st), "msst_pool_spectral_fwd")
+                _lib.check(self.lib.msst_scene_embed_assemble(_p(win_feat), win0, n, _p(feat), _p(cover), Bs, D, Hs, Ws, w, stride,
+                                                              int(win0 + n == total), int(bool(normalize)), st),
+                           "msst_scene_embed_assemble")
+            return feat, cover
 
     # ------------------------------------------------------------------ staged forward (tests / debugging)
     def simmim_forward_stages(self, img, bool_mask, idx, drop=(0.0, 0)):

@@ -12,6 +12,9 @@ every window covering a pixel), and pixels no window covers get class ``-1`` (th
 A pixelwise model (``pixelwise=True``) predicts one class per window, for its centre pixel: its map is the dense per-pixel
 map of DeepHyperX's ``test()`` (default stride 1, one window per pixel; ``msst_scene_centre_assemble``).  The border of
 width ``image_size // 2``, and with a stride above 1 every pixel that is no window's centre, gets class ``-1`` and logit 0.
+
+``ViTSpatialSpectral.encode_scene`` runs the same windows through the same encoder and stops before the head: per-pixel embedding
+maps ``[Bs, 96, Hs, Ws]`` (``msst_pool_spectral_fwd``, ``msst_scene_embed_assemble``), NaN where no window covers a pixel.
 """
 from collections import namedtuple
 
@@ -24,6 +27,8 @@ SCENE_MAX_WINDOWS = 2048
 
 SceneMetrics = namedtuple("SceneMetrics", ["loss", "acc", "macro_acc"])
 SceneReport = namedtuple("SceneReport", ["loss", "acc", "macro_acc", "report"])
+# what ViTSpatialSpectral.encode_scene returns: features [Bs, 96, Hs, Ws] fp32 (NaN where cover == 0), cover [Bs, Hs, Ws] int32
+SceneEmbedding = namedtuple("SceneEmbedding", ["features", "cover"])
 
 
 def scene_windows(Hs, Ws, window, stride):
@@ -56,6 +61,15 @@ def predict_scene(model, scene, stride=None, return_logits=False, max_windows=SC
     with torch.no_grad():
         logits, classes = model.engine().scene_forward(scene, stride, max_windows)
     return (classes, logits) if return_logits else classes
+
+
+def encode_scene(model, scene, stride=None, normalize=False, max_windows=SCENE_MAX_WINDOWS):
+    """See ViTSpatialSpectral.encode_scene."""
+    if stride is None:   # features are per position whatever the head: a pixelwise model's windows tile the scene too
+        stride = model.num_spatial_patches_sqrt
+    stride, max_windows = _check_scene(model, scene, stride, max_windows)
+    features, cover = model.engine().encode_scene(scene, stride, bool(normalize), max_windows)
+    return SceneEmbedding(features, cover)
 
 
 def scene_metrics(logits, classes, labels, ignore_index=-1, fused=False):

@@ -363,3 +363,20 @@ class ViTSpatialSpectral(nn.Module):
         (None: maskedsst_amd.scene.SCENE_MAX_WINDOWS).  Raises ValueError for a scene of the wrong shape."""
         from .scene import predict_scene, SCENE_MAX_WINDOWS
         return predict_scene(self, scene, stride, return_logits, SCENE_MAX_WINDOWS if max_windows is None else max_windows)
+
+    def encode_scene(self, scene, stride=None, normalize=False, max_windows=None):
+        """Per-pixel embedding maps of whole scenes [Bs, channels, Hs, Ws] (fp32, on the device): the encoder's representation for
+        k-NN / SVM on frozen features, clustering, change detection, retrieval.  Sliding windows of image_size, numbered and chunked as
+        for predict_scene; no head runs, so every head kind, a bare encoder and an encoder inside a SimMIMSpatialSpectral all work.
+        Returns SceneEmbedding(features, cover):
+          features [Bs, 96, Hs, Ws] fp32: a window's feature at a position is the mean over the spectral tokens of the encoder output
+            there (what the default head normalises); a pixel's feature is the plain mean of that over the windows covering it.  A
+            pixel no window covers is NaN in all 96 channels (the convention of reconstruct_scene without blend).
+          cover [Bs, Hs, Ws] int32: how many windows cover the pixel.
+        stride: window step, 1 .. image_size (None: image_size, also for a pixelwise model).  normalize=True divides every covered
+        pixel's 96-vector by max(||f||_2, 1e-12) (torch.nn.functional.normalize) after the averaging.  Eval forward (no dropout, no mask
+        token) under no_grad at the model's precision on the current stream, whatever the module's mode, which is left unchanged;
+        windows run in chunks of at most max_windows (None: maskedsst_amd.scene.SCENE_MAX_WINDOWS).  Raises ValueError for a scene of
+        the wrong rank or band count, one smaller than a window, or a stride outside its range; a CPU tensor raises as everywhere."""
+        from .scene import encode_scene, SCENE_MAX_WINDOWS
+        return encode_scene(self, scene, stride, normalize, SCENE_MAX_WINDOWS if max_windows is None else max_windows)
