@@ -88,6 +88,9 @@ def build_parser():
     ap.add_argument("--val-embed", action="store_true",
                     help="one more line per validation: nearest-class-mean accuracy on the frozen per-pixel features of "
                          "encode_scene(normalize=True); class means from the first half of the --val-scenes, scored on the second half")
+    ap.add_argument("--val-saliency", action="store_true",
+                    help="one more line per validation: the five bands with the largest mean |gradient x input| attribution "
+                         "(maskedsst_amd.band_importance, argmax class) over the windows of the --val-scenes")
     return ap
 
 
@@ -203,6 +206,8 @@ def main():
             validate(model, val, step, config.ignored_label, fused=fused, report=args.val_report)
             if args.val_embed:
                 validate_embedding(model, val, step, config.n_classes, config.ignored_label)
+            if args.val_saliency:
+                validate_saliency(model, val, step)
 
 
 def validate(model, val, step, ignored_label, fused=False, report=False):
@@ -245,6 +250,31 @@ def validate_embedding(model, val, step, n_classes, ignored_label):
         present = int((count > 0).sum())
     print(f"val-embed step {step} ncm_acc {acc:.3f} classes {present} train_pixels {len(ltr)} test_pixels {len(lte)} "
           f"scenes {img.shape[0]}", flush=True)
+
+
+def validate_saliency(model, val, step, batch=256, top=5):
+    """--val-saliency: which bands drive the decisions.  The validation scenes are cut into their non-overlapping image_size
+    windows (a torch reshape); band_importance (gradient x input of the argmax class's logit, through the HIP backward down to
+    the input) runs on them in eval mode, `batch` windows at a time, and the bands are ranked by the mean |attribution| over all
+    windows.  The module's mode is put back as found."""
+    from maskedsst_amd import band_importance
+    img, _ = val
+    s = model.num_spatial_patches_sqrt
+    V, C, H, W = img.shape
+    nr, nq = H // s, W // s
+    win = img[:, :, :nr * s, :nq * s].reshape(V, C, nr, s, nq, s).permute(0, 2, 4, 1, 3, 5).reshape(V * nr * nq, C, s, s).contiguous()
+    was_training = model.training
+    model.eval()
+    try:
+        total = torch.zeros(C, dtype=torch.float64, device=img.device)
+        for i in range(0, win.shape[0], batch):
+            total += band_importance(model, win[i:i + batch]).abs().sum(dim=0).double()
+    finally:
+        model.train(was_training)
+    mean = (total / win.shape[0]).cpu()
+    order = torch.argsort(mean, descending=True)[:top].tolist()
+    print(f"val-saliency step {step} top bands " + " ".join(f"{b}:{float(mean[b]):.3e}" for b in order) + f" windows {win.shape[0]}",
+          flush=True)
 
 
 if __name__ == "__main__":

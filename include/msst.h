@@ -414,6 +414,40 @@ int msst_tokenize_bwd(const float* img, const float* pre_g, const float* pre_b, 
                       float* dpos_b, int pos_split, float* dmask_token, int B, int S, int N, int P,
                       float emb_dropout_p, uint32_t seed, void* stream);
 
+/* Input gradient (additive under MSST_VERSION 109): d(loss)/d(img) through the tokenizer, what torch autograd gives the reference when
+ * img.requires_grad.  Separate launches that only read what the parameter backward reads; they run when somebody asks for img.grad.
+ *
+ * msst_tokenize_bwd_input: per (sample, spectral block) the recompute of msst_tokenize_fwd (pre-norm LN over the P pixels, W_c xn + b_c,
+ * post-norm LN over 96), the embedding dropout undone on dx0 [B][T][96] with the (p, seed) element addressing of msst_tokenize_bwd (the
+ * two regenerate identical masks), zero for the tokens mask [B][T] marks (optional; a masked token's output does not depend on its
+ * pixels), post-norm LN backward, dxn = W_c^T de, pre-norm LN backward.  dimg [B][S*P][N] is written whole (not accumulated), with
+ * dtarget [B][S*P][N] (optional) added before the one store.  fp32, no atomics: bitwise reproducible.  The position tables and the
+ * mask token play no part.  MSST_ERR_BADARG for B, S, N or P < 1 or a null required pointer, MSST_ERR_UNSUPPORTED outside N <= 64,
+ * S <= 64, P <= 16; checked before anything is enqueued.
+ *
+ * msst_head_bwd_target: the SimMIM L1 loss's direct dependence on the input (its target is the raw pixels of the masked patches):
+ * dtarget[b][c P + p][n] = -g sum_{k : idx[b][k] = c N + n} dpred[b][k][p], g = 1 / (B K P) / K (the normalisation of msst_head_fwd)
+ * times gout[0] when gout is given; 0 for tokens no index names.  A gather through the inverse CSR of msst_head_bwd, the sum in CSR
+ * order (a row may name a token more than once): bitwise reproducible.  dtarget [B][S*P][N] is written whole.  Argument checks as above
+ * (and K < 1).
+ *
+ * msst_tokenize_scene_bwd_input: msst_tokenize_bwd_input (no mask, no dtarget) of windows win0 .. win0 + nwin - 1 of scene
+ * [Bs][S*P][Hs][Ws], numbered as for msst_tokenize_scene_fwd_train, whose backward it is: dx0 [nwin][S*window*window][96], the values go
+ * to the windows' pixels of dscene [Bs][S*P][Hs][Ws], bit for bit what msst_tokenize_bwd_input gives for the copied windows.  Only
+ * stride == window (every pixel in at most one window: plain stores); other strides: MSST_ERR_UNSUPPORTED.  The calls of one batch
+ * (win0 = 0 first, together all Bs nr nq windows) leave all of dscene defined: the call with win0 == 0 also zeroes the trailing
+ * Hs % window rows and Ws % window columns, which belong to no window.  Argument checks of msst_tokenize_scene_fwd_train. */
+int msst_tokenize_bwd_input(const float* img, const float* pre_g, const float* pre_b, const float* w_emb, const float* b_emb,
+                            const float* post_g, const float* post_b, const uint8_t* mask /*optional*/, const float* dx0,
+                            const float* dtarget /*optional*/, float* dimg, int B, int S, int N, int P, float emb_dropout_p,
+                            uint32_t seed, void* stream);
+int msst_head_bwd_target(const float* dpred, const int32_t* csr_ptr, const int32_t* csr_pos, const float* gout /*optional*/,
+                         float* dtarget, int B, int S, int N, int P, int K, void* stream);
+int msst_tokenize_scene_bwd_input(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb, const float* b_emb,
+                                  const float* post_g, const float* post_b, const float* dx0, float* dscene, int Bs, int Hs, int Ws,
+                                  int window, int stride, long win0, int nwin, int S, int P, float emb_dropout_p, uint32_t seed,
+                                  void* stream);
+
 /* a17: classification head of ViTSpatialSpectral.forward (vit_spatial_spectral.py:536-564, :481-493):
  * mean over the spectral axis -> LayerNorm(96) -> Linear(96 -> n_classes); logits [B][n_classes][N].
  * Limits: N <= 64, S <= 64, any n_classes >= 1 (MSST_VERSION 108: the backward used to refuse n_classes > 32).  Both calls check

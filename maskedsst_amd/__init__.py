@@ -12,6 +12,8 @@ from .vit_simmim_original import SimMIMSpatialSpectral, BlockwiseToPixels, Recon
 from .recon import recon_report, ReconReport, window_masks_to_scene, scene_mask_to_windows  # noqa: F401
 from .masking import MaskGenerator  # noqa: F401
 from .scene import SceneEmbedding  # noqa: F401
+from .saliency import input_gradient, band_importance, integrated_gradients  # noqa: F401
 
 __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "MaskGenerator", "Reconstruction", "recon_report",
-           "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows", "SceneEmbedding"]
+           "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows", "SceneEmbedding",
+           "input_gradient", "band_importance", "integrated_gradients"]

@@ -246,7 +246,8 @@ int msst_profile_kernels(void) { return K_COUNT; }
 const char* msst_profile_name(int id) {
     static const char* names[K_COUNT] = {"prep_weights", "tokenize_fwd", "block_fwd", "head_fwd", "loss_reduce",
                                          "head_bwd", "reduce_slabs", "block_bwd_mlp", "block_bwd_attn",
-                                         "attn_slab_reduce", "block_bwd_ln1", "tokenize_bwd", "pos_split", "adamw", "block_bwd_ln1mlp", "layernorm", "adam_groups", "cross_entropy", "recon_fwd"};
+                                         "attn_slab_reduce", "block_bwd_ln1", "tokenize_bwd", "pos_split", "adamw", "block_bwd_ln1mlp", "layernorm", "adam_groups", "cross_entropy", "recon_fwd",
+                                         "tokenize_bwd_input", "head_bwd_target"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 
@@ -922,6 +923,57 @@ int msst_tokenize_scene_bwd(const float* scene, const float* pre_g, const float*
     if (int rc = launch_tokenize_scene_bwd(a, nchunk, st)) return fail(rc, "msst_tokenize_scene_bwd");
     return tokenize_bwd_reduce(slab, nchunk, dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, nullptr,
                                S, a.N, P, st);
+}
+
+// ---- input gradient (msst_input_grad.hip)
+int msst_tokenize_bwd_input(const float* img, const float* pre_g, const float* pre_b, const float* w_emb, const float* b_emb,
+                            const float* post_g, const float* post_b, const uint8_t* mask, const float* dx0, const float* dtarget,
+                            float* dimg, int B, int S, int N, int P, float emb_dropout_p, uint32_t seed, void* stream) {
+    if (B < 1 || S < 1 || N < 1 || P < 1) return fail(MSST_ERR_BADARG, "msst_tokenize_bwd_input");
+    if (N > 64 || S > 64 || P > 16) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_bwd_input");
+    if (!img || !pre_g || !pre_b || !w_emb || !b_emb || !post_g || !post_b || !dx0 || !dimg)
+        return fail(MSST_ERR_BADARG, "msst_tokenize_bwd_input");
+    TokInArgs a;
+    a.drop = make_drop(emb_dropout_p, seed, 255);
+    a.img = img; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb; a.post_g = post_g; a.post_b = post_b;
+    a.mask = mask; a.dx0 = dx0; a.dtarget = dtarget; a.dimg = dimg; a.B = B; a.S = S; a.N = N; a.T = S * N; a.P = P;
+    a.win0 = 0; a.Hs = a.Ws = a.win = a.stride = a.nq = a.wps = 0;
+    return fail(launch_tokenize_bwd_input(a, (hipStream_t)stream), "msst_tokenize_bwd_input");
+}
+
+int msst_head_bwd_target(const float* dpred, const int32_t* csr_ptr, const int32_t* csr_pos, const float* gout, float* dtarget,
+                         int B, int S, int N, int P, int K, void* stream) {
+    if (B < 1 || S < 1 || N < 1 || P < 1 || K < 1) return fail(MSST_ERR_BADARG, "msst_head_bwd_target");
+    if (N > 64 || S > 64 || P > 16) return fail(MSST_ERR_UNSUPPORTED, "msst_head_bwd_target");
+    if (!dpred || !csr_ptr || !csr_pos || !dtarget) return fail(MSST_ERR_BADARG, "msst_head_bwd_target");
+    const float gscale = (float)(1.0 / ((double)B * K * P) / K);   // the loss normalisation of msst_head_fwd: mean over B K P, then / K
+    return fail(launch_head_bwd_target(dpred, csr_ptr, csr_pos, gout, gscale, dtarget, B, S, N, P, K, (hipStream_t)stream),
+                "msst_head_bwd_target");
+}
+
+int msst_tokenize_scene_bwd_input(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb, const float* b_emb,
+                                  const float* post_g, const float* post_b, const float* dx0, float* dscene, int Bs, int Hs, int Ws,
+                                  int window, int stride, long win0, int nwin, int S, int P, float emb_dropout_p, uint32_t seed,
+                                  void* stream) {
+    int nq = 0;
+    long wps = 0;
+    const bool pointers = scene && pre_g && pre_b && w_emb && b_emb && post_g && post_b && dx0 && dscene;
+    if (int rc = scene_train_args(pointers, Bs, Hs, Ws, window, stride, win0, nwin, 0, S, P, 0, &nq, &wps))
+        return fail(rc, "msst_tokenize_scene_bwd_input");
+    // overlapping windows would have to add into a pixel: only the non-overlapping grid of the tile path is built
+    if (stride != window || S > 64) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_scene_bwd_input (stride != window)");
+    hipStream_t st = (hipStream_t)stream;
+    if (win0 == 0) {   // the call that starts a batch zeroes the pixels beyond the window grid
+        const int nr = (int)(wps / nq);
+        if (int rc = launch_scene_border_zero(dscene, (long)Bs * S * P * Hs, Hs, Ws, nr * window, nq * window, st))
+            return fail(rc, "msst_tokenize_scene_bwd_input(border)");
+    }
+    TokInArgs a;
+    a.drop = make_drop(emb_dropout_p, seed, 255);
+    a.img = scene; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb; a.post_g = post_g; a.post_b = post_b;
+    a.mask = nullptr; a.dx0 = dx0; a.dtarget = nullptr; a.dimg = dscene; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P;
+    a.win0 = win0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nq = nq; a.wps = (int)wps;
+    return fail(launch_tokenize_scene_bwd_input(a, st), "msst_tokenize_scene_bwd_input");
 }
 
 // shape of the default head: 0, MSST_ERR_BADARG (a size below 1) or MSST_ERR_UNSUPPORTED (beyond the kernels' limits; any n_classes)

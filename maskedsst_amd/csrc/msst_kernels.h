@@ -215,10 +215,30 @@ struct TokSceneBwdArgs : TokBwdArgs {
     int Hs, Ws, win, stride, nq, wps;
 };
 
+// msst_input_grad.hip (msst_tokenize_bwd_input, msst_tokenize_scene_bwd_input): d(loss)/d(img) from dx0
+struct TokInArgs {
+    const float* img; const float* pre_g; const float* pre_b; const float* w_emb; const float* b_emb;
+    const float* post_g; const float* post_b;
+    const uint8_t* mask;     // optional [B][T] (1 = masked)
+    const float* dx0;        // [B][T][96]
+    const float* dtarget;    // optional [B][S*P][N], added before the store
+    float* dimg;             // [B][S*P][N]; the scene instances: dscene [Bs][S*P][Hs][Ws]
+    int B, S, N, T, P;
+    Drop drop;
+    long win0;               // scene instances: the scene fields of TokArgs (img is the scene, sample b its window win0 + b)
+    int Hs, Ws, win, stride, nq, wps;
+};
+int launch_tokenize_bwd_input(const TokInArgs& a, hipStream_t st);
+int launch_tokenize_scene_bwd_input(const TokInArgs& a, hipStream_t st);
+int launch_scene_border_zero(float* dscene, long rows, int Hs, int Ws, int rows_in, int cols_in, hipStream_t st);
+int launch_head_bwd_target(const float* dpred, const int* csr_ptr, const int* csr_pos, const float* gout, float gscale, float* dtarget,
+                           int B, int S, int N, int P, int K, hipStream_t st);
+
 // ---- opt-in per-kernel timing with HIP events on the launch stream (bench.py roofline leg) ----
 enum KernelId {
     K_PREP = 0, K_TOK_FWD, K_BLOCK_FWD, K_HEAD_FWD, K_LOSS_REDUCE, K_HEAD_BWD, K_REDUCE, K_BWD_MLP, K_BWD_ATTN,
-    K_ATTN_REDUCE, K_BWD_LN1, K_TOK_BWD, K_POS_SPLIT, K_ADAMW, K_BWD_LN1MLP, K_LAYERNORM, K_ADAM_GROUPS, K_CE, K_RECON, K_COUNT
+    K_ATTN_REDUCE, K_BWD_LN1, K_TOK_BWD, K_POS_SPLIT, K_ADAMW, K_BWD_LN1MLP, K_LAYERNORM, K_ADAM_GROUPS, K_CE, K_RECON, K_TOK_BWD_INPUT,
+    K_HEAD_BWD_TARGET, K_COUNT
 };
 void prof_begin(int id, hipStream_t st);
 void prof_end(hipStream_t st);

@@ -892,6 +892,50 @@ class Engine:
             emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_scene_bwd")
         self._fire("tokenizer")
 
+    # ------------------------------------------------------------------ input gradient (msst_input_grad.hip)
+    def tokenize_input_bwd(self, img, mask_u8, dx0, dtarget=None, emb_drop=(0.0, 0)):
+        """d(loss)/d(img) through the tokenizer (msst_tokenize_bwd_input): img [B, C, H, W] as tokenize took it, mask_u8 [B, T] or None,
+        dx0 [B, T, 96] the gradient at the tokenizer's output, dtarget [B, S P, N] (head_bwd_target) added before the store -> a new
+        tensor of img's shape, written whole.  Reads only; the parameter gradients are tokenize_bwd's business."""
+        self._require_cuda(img)
+        B = img.shape[0]
+        S, N, P = self.S, self.N, self.P
+        fp = self.fp
+        dimg = torch.empty(img.shape, dtype=torch.float32, device=img.device)
+        V = ctypes.c_void_p
+        _lib.check(self.lib.msst_tokenize_bwd_input(
+            _p(img), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
+            V(fp.ptr("post_g")), V(fp.ptr("post_b")), _p(mask_u8), _p(dx0), _p(dtarget), _p(dimg), B, S, N, P,
+            emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_bwd_input")
+        return dimg
+
+    def tokenize_windows_input_bwd(self, img, dx0, emb_drop=(0.0, 0), tiles=False):
+        """the input gradient of tokenize_windows: of a window batch (tokenize_input_bwd, nothing masked), or with tiles=True of the
+        tiles [B, C, Ht, Wt] whose windows it read in place -- one msst_tokenize_scene_bwd_input over all windows, zeros in the
+        trailing rows and columns that belong to no window"""
+        if not tiles:
+            return self.tokenize_input_bwd(img, None, dx0, emb_drop=emb_drop)
+        self._require_cuda(img)
+        B, _, Ht, Wt = img.shape
+        s, nr, nq = self.tile_grid(img)
+        fp = self.fp
+        dtiles = torch.empty(img.shape, dtype=torch.float32, device=img.device)
+        V = ctypes.c_void_p
+        _lib.check(self.lib.msst_tokenize_scene_bwd_input(
+            _p(img), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
+            V(fp.ptr("post_g")), V(fp.ptr("post_b")), _p(dx0), _p(dtiles), B, Ht, Wt, s, s, 0, B * nr * nq, self.S, self.P,
+            emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_scene_bwd_input")
+        return dtiles
+
+    def head_bwd_target(self, dpred, csr_ptr, csr_pos, gout=None):
+        """the SimMIM loss's direct dependence on the input (msst_head_bwd_target): dpred [B, K, P] of head_fwd and the inverse CSR
+        head_bwd takes -> dtarget [B, S P, N], the gradient of the loss through its target (the raw pixels of the masked patches)"""
+        B, K, P = dpred.shape
+        dtarget = torch.empty(B, self.S * P, self.N, dtype=torch.float32, device=dpred.device)
+        _lib.check(self.lib.msst_head_bwd_target(_p(dpred), _p(csr_ptr), _p(csr_pos), _p(gout), _p(dtarget), B, self.S, self.N, P, K,
+                                                 _stream()), "msst_head_bwd_target")
+        return dtarget
+
     # ------------------------------------------------------------------ autograd entry (SimMIM loss)
     def trainable(self):
         """[(flat name, parameter)] of everything that receives a gradient in pre-training"""
@@ -967,7 +1011,7 @@ class Engine:
         mask_u8, idx32, csr_ptr, csr_pos = self._upload(dev, bm.astype(np.uint8), ix.astype(np.int32), ptr, pos)
         names = [n for n, _ in self.trainable()]
         params = [p for _, p in self.trainable()]
-        if not torch.is_grad_enabled() or not any(p.requires_grad for p in params):
+        if not torch.is_grad_enabled() or not (img.requires_grad or any(p.requires_grad for p in params)):
             self.prep_weights()
             x0 = self.tokenize(img, mask_u8)
             acts, _ = self.blocks_fwd(x0, save=False, drop=self.dropout_state())
@@ -1006,25 +1050,28 @@ class Engine:
         self._require_cuda(patches)
         self.ensure()
         B, S, N, P = patches.shape
-        img = patches.detach().permute(0, 1, 3, 2).reshape(B, S * P, N).contiguous().float()
+        want_input = torch.is_grad_enabled() and patches.requires_grad
+        # patches that require a gradient stay attached: the permute into the cube layout is a torch op, so d(patches) comes back
+        # in the [B, S, N, P] layout it was given
+        img = (patches if want_input else patches.detach()).permute(0, 1, 3, 2).reshape(B, S * P, N).contiguous().float()
         by_name = dict(self.trainable())
         names = self._embed_param_names()
         params = [by_name[n] for n in names]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        if torch.is_grad_enabled() and (want_input or any(p.requires_grad for p in params)):
             return _EmbedFn.apply(self, names, img, *params)
         return self.tokenize(img, None, with_pos=False)
 
     def features(self, img):
         """forward_features (reference :518-534): tokenize + pos (+ embedding dropout in training mode) -> transformer.
 
-        Differentiable like the reference's: when gradients are enabled and any encoder parameter requires one, the result is
+        Differentiable like the reference's: when gradients are enabled and any encoder parameter or the input requires one, the result is
         composed of the two autograd entry points (``embed_patches`` and ``transformer``) with the position add and the
         embedding dropout as ordinary torch ops in between -- exactly what the reference's own SimMIM wrapper does with this
         encoder -- so a custom head trained on these features trains the encoder too.  Otherwise (eval / no_grad) one fused
         tokenizer launch does embed + position + dropout."""
         enc = self.enc
         params = [q for _, q in self.trainable()]
-        if torch.is_grad_enabled() and any(q.requires_grad for q in params):
+        if torch.is_grad_enabled() and (img.requires_grad or any(q.requires_grad for q in params)):
             self._require_cuda(img)
             patches = enc.to_patch_embedding.to_patch(img.contiguous().float())
             tokens = self.embed_patches(patches).reshape(img.shape[0], -1, D)
@@ -1141,8 +1188,9 @@ class Engine:
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if (p > 0 or pe > 0) else 0
         drop, emb_drop = (p, seed), (pe, seed ^ 0x5bd1e995)
         params = [q for _, q in self.trainable()]
-        if self.mim is not None or not torch.is_grad_enabled() or not any(q.requires_grad for q in params):
-            if self.mim is not None and torch.is_grad_enabled() and any(q.requires_grad for q in params):
+        want = torch.is_grad_enabled() and (img.requires_grad or any(q.requires_grad for q in params))
+        if self.mim is not None or not want:
+            if self.mim is not None and want:
                 raise NotImplementedError("train the classifier through a bare ViTSpatialSpectral (as finetune.py "
                                           "does), not through an encoder wrapped in SimMIMSpatialSpectral")
             self.prep_weights()
@@ -1150,9 +1198,10 @@ class Engine:
             acts, _ = self.blocks_fwd(x0, save=False, drop=drop)
             return self._classify_view(self.head_logits(acts[-1]), B)
         named = self.trainable()
-        if not any(q.requires_grad for n, q in named if not n.startswith("mlp_head.")):
+        if not img.requires_grad and not any(q.requires_grad for n, q in named if not n.startswith("mlp_head.")):
             # linear evaluation (reference finetune.py:110-136: only mlp_head trains): the body runs as in a no-gradient forward --
-            # module still in training mode, so its dropout stays on -- with nothing saved, and only the head has a backward
+            # module still in training mode, so its dropout stays on -- with nothing saved, and only the head has a backward.  (An
+            # input that requires a gradient needs the full body backward: that call takes the full path below.)
             self.prep_weights()
             x0 = self.tokenize_windows(img, emb_drop, tiles)
             y = self.blocks_fwd_pingpong(x0, drop=drop)
@@ -1286,20 +1335,28 @@ class _SimMIMLossFn(torch.autograd.Function):
         eng = ctx.eng
         img, mask_u8, csr_ptr, csr_pos, acts, x1s, dpred = ctx.stash
         ctx.stash = None
-        _refuse_accumulation(eng, ctx.names)
+        needs = ctx.needs_input_grad[8:]
+        _refuse_accumulation(eng, ctx.names, needs)
         gout = gout.contiguous().float()
         dy = eng.head_bwd(acts[-1], dpred, csr_ptr, csr_pos, gout)
         dx0 = eng.blocks_bwd(acts, x1s, dy, drop=ctx.drop)
-        eng.tokenize_bwd(img, mask_u8, dx0)
-        return (None,) * 8 + _grad_views(eng, ctx.names)
+        dimg = None
+        if ctx.needs_input_grad[3]:   # the input asked for its gradient: two more launches that only read
+            dimg = eng.tokenize_input_bwd(img, mask_u8, dx0, eng.head_bwd_target(dpred, csr_ptr, csr_pos, gout))
+        if any(needs):   # (a fully frozen model: the tokenizer backward writes parameter gradients only, nobody reads them)
+            eng.tokenize_bwd(img, mask_u8, dx0)
+        return (None, None, None, dimg) + (None,) * 4 + _grad_views(eng, ctx.names, needs)
 
 
-def _refuse_accumulation(eng, names):
-    """called by every backward before it writes gradients: none of the parameters it returns gradients for (flat names) may
-    still hold the view of the flat gradient buffer that an earlier backward handed out"""
+def _refuse_accumulation(eng, names, needs=None):
+    """called by every backward before it writes gradients: none of the parameters it returns gradients for (flat names; needs: which of
+    them, ctx.needs_input_grad of their slots -- a frozen parameter receives None) may still hold the view of the flat gradient
+    buffer that an earlier backward handed out"""
     by_name = dict(eng.trainable())
     lo, hi = eng.fp.grad.data_ptr(), eng.fp.grad.data_ptr() + 4 * eng.fp.grad.numel()
-    for n in names:
+    for i, n in enumerate(names):
+        if needs is not None and not needs[i]:
+            continue
         p = by_name[n]
         if p.grad is not None and lo <= p.grad.data_ptr() < hi:
             raise RuntimeError(
@@ -1308,9 +1365,10 @@ def _refuse_accumulation(eng, names):
                 "in-place gradient accumulation across backward calls is not supported")
 
 
-def _grad_views(eng, names):
-    """the gradients a backward returns to autograd: views of the flat gradient buffer the kernels have just written"""
-    return tuple(eng.fp.view(n, eng.fp.grad) for n in names)
+def _grad_views(eng, names, needs=None):
+    """the gradients a backward returns to autograd: views of the flat gradient buffer the kernels have just written; None for the
+    parameters that do not require one (needs: ctx.needs_input_grad of their slots)"""
+    return tuple(eng.fp.view(n, eng.fp.grad) if needs is None or needs[i] else None for i, n in enumerate(names))
 
 
 class _TransformerFn(torch.autograd.Function):
@@ -1329,9 +1387,10 @@ class _TransformerFn(torch.autograd.Function):
         eng = ctx.eng
         acts, x1s = ctx.stash
         ctx.stash = None
-        _refuse_accumulation(eng, ctx.names)
+        needs = ctx.needs_input_grad[4:]
+        _refuse_accumulation(eng, ctx.names, needs)
         dx0 = eng.blocks_bwd(acts, x1s, dy.contiguous().float().clone(), drop=ctx.drop)
-        return (None, None, None, dx0) + _grad_views(eng, ctx.names)
+        return (None, None, None, dx0) + _grad_views(eng, ctx.names, needs)
 
 
 class _EmbedFn(torch.autograd.Function):
@@ -1348,10 +1407,14 @@ class _EmbedFn(torch.autograd.Function):
         eng = ctx.eng
         (img,) = ctx.stash
         ctx.stash = None
-        _refuse_accumulation(eng, ctx.names)
-        zero_mask = eng._zero_mask_for(img.shape[0] * eng.S * eng.N, img.device)
-        eng.tokenize_bwd(img, zero_mask, dtok.contiguous().float(), with_pos=False)
-        return (None, None, None) + _grad_views(eng, ctx.names)
+        needs = ctx.needs_input_grad[3:]
+        _refuse_accumulation(eng, ctx.names, needs)
+        dtok = dtok.contiguous().float()
+        dimg = eng.tokenize_input_bwd(img, None, dtok) if ctx.needs_input_grad[2] else None
+        if any(needs):
+            zero_mask = eng._zero_mask_for(img.shape[0] * eng.S * eng.N, img.device)
+            eng.tokenize_bwd(img, zero_mask, dtok, with_pos=False)
+        return (None, None, dimg) + _grad_views(eng, ctx.names, needs)
 
 
 class _ClassifyFn(torch.autograd.Function):
@@ -1373,11 +1436,16 @@ class _ClassifyFn(torch.autograd.Function):
         eng = ctx.eng
         img, acts, x1s = ctx.stash
         ctx.stash = None
-        _refuse_accumulation(eng, ctx.names)
+        needs = ctx.needs_input_grad[6:]
+        _refuse_accumulation(eng, ctx.names, needs)
         dy = eng.head_logits_bwd(acts[-1], dlogits.contiguous().float())
         dx0 = eng.blocks_bwd(acts, x1s, dy, drop=ctx.drop)
-        eng.tokenize_windows_bwd(img, dx0, emb_drop=ctx.emb_drop, tiles=ctx.tiles)
-        return (None,) * 6 + _grad_views(eng, ctx.names)
+        dimg = None
+        if ctx.needs_input_grad[5]:   # the input (window batch or tiles) asked for its gradient: one more launch that only reads
+            dimg = eng.tokenize_windows_input_bwd(img, dx0, emb_drop=ctx.emb_drop, tiles=ctx.tiles)
+        if any(needs):   # (a fully frozen model: the tokenizer backward writes parameter gradients only, nobody reads them)
+            eng.tokenize_windows_bwd(img, dx0, emb_drop=ctx.emb_drop, tiles=ctx.tiles)
+        return (None,) * 5 + (dimg,) + _grad_views(eng, ctx.names, needs)
 
 
 class _HeadOnlyFn(torch.autograd.Function):
@@ -1395,6 +1463,7 @@ class _HeadOnlyFn(torch.autograd.Function):
         eng = ctx.eng
         (y,) = ctx.stash
         ctx.stash = None
-        _refuse_accumulation(eng, ctx.names)
+        needs = ctx.needs_input_grad[3:]
+        _refuse_accumulation(eng, ctx.names, needs)
         eng.head_logits_bwd(y, dlogits.contiguous().float(), want_dy=False)
-        return (None, None, None) + _grad_views(eng, ctx.names)
+        return (None, None, None) + _grad_views(eng, ctx.names, needs)
