@@ -12,6 +12,7 @@ import torch.nn.functional as F
 from util import relerr, rel_l2, record
 from input_grad_util import (CASES, SIMMIM, CLASSIFIER, QUIRK, fixture, build_model, class_label, oracle_run, target_term_ref,
                              with_duplicates)
+from tok_head_util import tok_params, tok_ref
 
 pytestmark = pytest.mark.gpu
 BADARG, UNSUPPORTED = -3, -2
@@ -46,22 +47,6 @@ def _measure(key, **kv):
 
 
 # ---------------------------------------------------------------------------------------------- the kernel alone
-def tok_params(S, P, gen):
-    """pre-norm gamma / beta [P], W [S, 96, P], b [S, 96], post-norm gamma / beta [96]: float64 on the CPU, away from the init values"""
-    r = lambda *s: torch.randn(*s, generator=gen, dtype=torch.float64)   # noqa: E731
-    return dict(pre_g=1 + 0.3 * r(P), pre_b=0.2 * r(P), w=r(S, 96, P) / max(P, 1) ** 0.5, b=0.1 * r(S, 96), post_g=1 + 0.3 * r(96),
-                post_b=0.2 * r(96))
-
-
-def tok_ref(img, q, S, N, P):
-    """LN(P) -> per-block Linear -> LN(96) on img [B, S P, N] -> tokens [B, S N, 96] (token order c n), float64"""
-    B = img.shape[0]
-    patches = img.reshape(B, S, P, N).permute(0, 1, 3, 2)
-    xn = F.layer_norm(patches, (P,), q["pre_g"], q["pre_b"], 1e-5)
-    e = torch.einsum("bsnp,sdp->bsnd", xn, q["w"]) + q["b"][None, :, None, :]
-    return F.layer_norm(e, (96,), q["post_g"], q["post_b"], 1e-5).reshape(B, S * N, 96)
-
-
 def dev(q):
     return {k: v.float().cuda().contiguous() for k, v in q.items()}
 
