@@ -91,6 +91,10 @@ def build_parser():
     ap.add_argument("--val-saliency", action="store_true",
                     help="one more line per validation: the five bands with the largest mean |gradient x input| attribution "
                          "(maskedsst_amd.band_importance, argmax class) over the windows of the --val-scenes")
+    ap.add_argument("--val-attention", action="store_true",
+                    help="one more line per validation: the three spectral blocks that receive the most rollout attention "
+                         "(maskedsst_amd.attention_rollout of model.attention_maps(stack='spectral')) over the first batch of windows "
+                         "of the --val-scenes")
     return ap
 
 
@@ -208,6 +212,8 @@ def main():
                 validate_embedding(model, val, step, config.n_classes, config.ignored_label)
             if args.val_saliency:
                 validate_saliency(model, val, step)
+            if args.val_attention:
+                validate_attention(model, val, step)
 
 
 def validate(model, val, step, ignored_label, fused=False, report=False):
@@ -275,6 +281,24 @@ def validate_saliency(model, val, step, batch=256, top=5):
     order = torch.argsort(mean, descending=True)[:top].tolist()
     print(f"val-saliency step {step} top bands " + " ".join(f"{b}:{float(mean[b]):.3e}" for b in order) + f" windows {win.shape[0]}",
           flush=True)
+
+
+def validate_attention(model, val, step, batch=256, top=3):
+    """--val-attention: which spectral blocks the spectral stack looks at.  The first `batch` non-overlapping image_size windows of
+    the validation scenes go through model.attention_maps(stack="spectral") (eval forward, the module's mode untouched; the maps come
+    out of msst_attn_maps averaged over a window's positions); attention_rollout multiplies the blocks' head-averaged maps, and a
+    spectral block's score is the mean over windows and queries of its column."""
+    from maskedsst_amd import attention_rollout
+    img, _ = val
+    s = model.num_spatial_patches_sqrt
+    V, C, H, W = img.shape
+    nr, nq = H // s, W // s
+    win = img[:, :, :nr * s, :nq * s].reshape(V, C, nr, s, nq, s).permute(0, 2, 4, 1, 3, 5).reshape(V * nr * nq, C, s, s)[:batch].contiguous()
+    roll = attention_rollout(model.attention_maps(win, stack="spectral").spectral)    # [B, S, S] float64
+    received = roll.mean(dim=(0, 1)).cpu()
+    order = torch.argsort(received, descending=True)[:top].tolist()
+    print(f"val-attention step {step} top spectral blocks " + " ".join(f"{b}:{float(received[b]):.4f}" for b in order)
+          + f" windows {win.shape[0]}", flush=True)
 
 
 if __name__ == "__main__":

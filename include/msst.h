@@ -255,6 +255,25 @@ int msst_pool_spectral_fwd(const float* y, float* out, int B, int S, int N, void
 int msst_scene_embed_assemble(const float* win_feat, long win0, int nwin, float* feat, int32_t* cover, int Bs, int D, int Hs, int Ws,
                               int window, int stride, int finalize, int l2norm, void* stream);
 
+/* Attention maps (ViTSpatialSpectral.attention_maps).  Additive under MSST_VERSION 109: no struct and no existing signature changes.
+ * The probabilities P = softmax(q k^T dim_head^-0.5) of ONE block, q = LN1(x) Wq^T, k = LN1(x) Wk^T (LayerNorm eps 1e-5), rows =
+ * queries, columns = keys: the reference's `attn` (vit_spatial_spectral.py:67-74) before dropout, recomputed from the block's INPUT x
+ * [B][T][96] (the residual stream, T = S N).  A sequence and its length L are those of msst_block_fwd:
+ *   MSST_MODE_SPATIAL:  sequence (b, c), L = N, G = S sequences per sample;  MSST_MODE_SPECTRAL: sequence (b, n), L = S, G = N.
+ *   reduce = MSST_ATTN_PER_SEQ:  maps[b sample_stride + ((g heads + h) L + i) L + j], g in that order;
+ *   reduce = MSST_ATTN_MEAN_SEQ: maps[b sample_stride + (h L + i) L + j] = (sum over g = 0 .. G - 1, in that order from 0) / (float)G.
+ * wqkv is the fp32 master to_qkv.weight [3 heads 64][96], rows q | k | v head-major; only the q and k rows are read.  Arithmetic is
+ * fp32 throughout (v_mfma_f32_16x16x4_f32), independent of the model's precision and of msst_prep_weights.  One workgroup per
+ * (sample, head): no atomics, nothing to zero, two calls give the same bits, and a sample's maps have the same bits whatever batch it
+ * sits in and whatever its index there.  Floats of maps outside the samples' maps (sample_stride beyond one sample) are not written.
+ * Checked before anything is enqueued, in this order: MSST_ERR_BADARG for a size below 1; MSST_ERR_UNSUPPORTED for N > 64, S > 64 or
+ * heads > 16; MSST_ERR_BADARG for mode or reduce outside {0, 1}, a null pointer, x or maps not 16-byte aligned, or sample_stride
+ * smaller than one sample's maps. */
+#define MSST_ATTN_PER_SEQ 0
+#define MSST_ATTN_MEAN_SEQ 1
+int msst_attn_maps(const float* x, const float* ln_g, const float* ln_b, const float* wqkv, float* maps, long sample_stride, int mode,
+                   int B, int S, int N, int heads, int reduce, void* stream);
+
 /* a7-a10: one fused pre-norm transformer block (PreNorm+Attention+FeedForward+residuals,
  * vit_spatial_spectral.py:22-104) over all B*S*N tokens; mode selects the spatial or spectral
  * sequence grouping of vit_spatial_spectral.py:410-431 (no transposes are materialised).

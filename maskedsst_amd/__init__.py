@@ -13,7 +13,8 @@ from .recon import recon_report, ReconReport, window_masks_to_scene, scene_mask_
 from .masking import MaskGenerator  # noqa: F401
 from .scene import SceneEmbedding  # noqa: F401
 from .saliency import input_gradient, band_importance, integrated_gradients  # noqa: F401
+from .attention import AttentionMaps, attention_rollout, attention_received  # noqa: F401
 
 __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "MaskGenerator", "Reconstruction", "recon_report",
            "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows", "SceneEmbedding",
-           "input_gradient", "band_importance", "integrated_gradients"]
+           "input_gradient", "band_importance", "integrated_gradients", "AttentionMaps", "attention_rollout", "attention_received"]

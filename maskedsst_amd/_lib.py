@@ -58,6 +58,7 @@ PREP_HALF = 256               # include/msst.h: MSST_PREP_HALF
 CE_LOSS_SUM, CE_N_VALID, CE_N_CORRECT, CE_BAD_LABELS, CE_NONFINITE, CE_SUPPORT = range(6)   # include/msst.h: MSST_CE_* record slots
 CE_EXT_LOSS_SUM, CE_EXT_WEIGHT_SUM = range(2)   # include/msst.h: MSST_CE_EXT_* slots of the double sums of msst_ce_ext_fwd
 CE_CONFUSION_MAX_CLASSES = 128                  # include/msst.h: MSST_CE_CONFUSION_MAX_CLASSES
+ATTN_PER_SEQ, ATTN_MEAN_SEQ = 0, 1              # include/msst.h: MSST_ATTN_PER_SEQ, MSST_ATTN_MEAN_SEQ
 _SIGS = {
     "msst_version": (c_int, []),
     "msst_last_error": (c_char_p, []),
@@ -74,6 +75,7 @@ _SIGS = {
     "msst_scene_recon_assemble": (c_int, [_P, c_long, c_int, _P, _P, _P, _P, _P, _P] + [c_int] * 9 + [_P]),
     "msst_pool_spectral_fwd": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "msst_scene_embed_assemble": (c_int, [_P, c_long, c_int, _P, _P] + [c_int] * 8 + [_P]),
+    "msst_attn_maps": (c_int, [_P, _P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "msst_scene_assemble": (c_int, [_P, c_long, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "msst_cls_head_fwd": (c_int, [_P] * 6 + [c_int, c_int, c_int, c_int, _P]),
     "msst_cls_head_bwd": (c_int, [_P] * 11 + [c_int, c_int, c_int, c_int, _P]),

@@ -439,6 +439,21 @@ int msst_pool_spectral_fwd(const float* y, float* out, int B, int S, int N, void
     return fail(launch_pool_spectral(y, out, B, S, N, (hipStream_t)stream), "msst_pool_spectral_fwd");
 }
 
+int msst_attn_maps(const float* x, const float* ln_g, const float* ln_b, const float* wqkv, float* maps, long sample_stride, int mode,
+                   int B, int S, int N, int heads, int reduce, void* stream) {
+    if (B < 1 || S < 1 || N < 1 || heads < 1) return fail(MSST_ERR_BADARG, "msst_attn_maps");
+    if (N > 64 || S > 64 || heads > 16) return fail(MSST_ERR_UNSUPPORTED, "msst_attn_maps (N <= 64, S <= 64, heads <= 16)");
+    if ((mode != MSST_MODE_SPATIAL && mode != MSST_MODE_SPECTRAL) || (reduce != MSST_ATTN_PER_SEQ && reduce != MSST_ATTN_MEAN_SEQ))
+        return fail(MSST_ERR_BADARG, "msst_attn_maps (mode or reduce outside {0, 1})");
+    if (!x || !ln_g || !ln_b || !wqkv || !maps || ((uintptr_t)x & 15) || ((uintptr_t)maps & 15))
+        return fail(MSST_ERR_BADARG, "msst_attn_maps (null argument, or x / maps not 16-byte aligned)");
+    const long L = mode == MSST_MODE_SPATIAL ? N : S, G = mode == MSST_MODE_SPATIAL ? S : N;
+    if (sample_stride < (reduce == MSST_ATTN_PER_SEQ ? G : 1) * heads * L * L)
+        return fail(MSST_ERR_BADARG, "msst_attn_maps (sample_stride smaller than one sample's maps)");
+    return fail(launch_attn_maps(x, ln_g, ln_b, wqkv, maps, sample_stride, mode, B, S, N, heads, reduce, (hipStream_t)stream),
+                "msst_attn_maps");
+}
+
 int msst_scene_embed_assemble(const float* win_feat, long win0, int nwin, float* feat, int32_t* cover, int Bs, int D, int Hs, int Ws,
                               int window, int stride, int finalize, int l2norm, void* stream) {
     if (Bs < 1 || D < 1 || Hs < 1 || Ws < 1 || window < 1 || stride < 1 || nwin < 0 || win0 < 0)

@@ -440,4 +440,9 @@ int launch_pool_spectral(const float* y, float* out, int B, int S, int N, hipStr
 int launch_scene_embed_accumulate(const SceneEmbedArgs& a, long pixels, hipStream_t st);
 int launch_scene_embed_finalize(const SceneEmbedArgs& a, hipStream_t st);
 
+// msst_attn_maps.hip (msst_attn_maps): the fp32 attention probabilities of one block from its input, per sequence or averaged over a
+// sample's sequences; one workgroup per (sample, head)
+int launch_attn_maps(const float* x, const float* ln_g, const float* ln_b, const float* wqkv, float* maps, long sample_stride,
+                     int mode, int B, int S, int N, int heads, int reduce, hipStream_t st);
+
 }  // namespace msst

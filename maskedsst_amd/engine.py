@@ -1296,6 +1296,75 @@ class Engine:
                            "msst_scene_embed_assemble")
             return feat, cover
 
+    # ------------------------------------------------------------------ attention maps (msst_attn_maps.hip)
+    def attn_maps_block(self, i, x, out, reduce):
+        """msst_attn_maps of block i (index into _layers()) on its input x [B, T, 96] fp32: the fp32 softmax(q k^T / 8) of every
+        sequence and head, written into out -- a tensor (or a view of one) whose dim 0 is the sample and whose remaining dims are
+        one sample's maps, contiguous: [G, heads, L, L] (reduce = ATTN_PER_SEQ) or [heads, L, L] (ATTN_MEAN_SEQ); out.stride(0) is
+        the call's sample_stride.  Reads the block's ln1_g / ln1_b and the fp32 master to_qkv.weight in the flat parameter buffer: no
+        operand copy, so it is independent of prep_weights and of the precision.  The current stream."""
+        self.ensure()
+        sname, l = self._layers()[i]
+        B = x.shape[0]
+        V = ctypes.c_void_p
+        fp = self.fp
+        _lib.check(self.lib.msst_attn_maps(_p(x), V(fp.ptr(f"{sname}.{l}.ln1_g")), V(fp.ptr(f"{sname}.{l}.ln1_b")),
+                                           V(fp.ptr(f"{sname}.{l}.wqkv")), _p(out), out.stride(0) if B > 1 else out[0].numel(),
+                                           _MODE[sname], B, self.S, self.N, self.enc.heads, reduce, _stream()), "msst_attn_maps")
+        return out
+
+    def _maps_storage(self, B, nblk, tail, device):
+        """the result [B, nblk, *tail] fp32 of one stack.  Every (sample, block) slice must start on 16 bytes (msst_attn_maps stores
+        into it in place): when one block's maps are not a multiple of 4 floats (odd toy shapes; never with 8 heads) the slices lie
+        a padded stride apart and the result is a strided view of that storage."""
+        per = int(np.prod(tail))
+        pad = (per + 3) // 4 * 4
+        flat = torch.empty(B * nblk * pad, dtype=torch.float32, device=device)
+        strides, s = [], 1
+        for d in reversed(tail):
+            strides.insert(0, s)
+            s *= d
+        return torch.as_strided(flat, (B, nblk) + tuple(tail), (nblk * pad, pad) + tuple(strides))
+
+    def attention_maps_tokens(self, x0, stacks, blocks, reduce):
+        """attention_maps on tokens x0 [B, T, 96] (overwritten): the loop of blocks_fwd_pingpong, with msst_attn_maps on the input
+        of every wanted block after that block's launch and before the next block overwrites the buffer."""
+        B = x0.shape[0]
+        S, N, H = self.S, self.N, self.enc.heads
+        out = {}
+        for sname in stacks:
+            L, G = (N, S) if sname == "spatial" else (S, N)
+            tail = (H, L, L) if reduce == _lib.ATTN_MEAN_SEQ else (G, H, L, L)
+            out[sname] = self._maps_storage(B, len(blocks), tail, x0.device)
+        flags = _kernel_flags()
+        prec = self.prec | flags | self._half_flag(flags)
+        x, y = x0, torch.empty_like(x0)
+        wrote = ctypes.c_int(0)
+        st = _stream()
+        layers = self._layers()
+        last = max((i for i, (sname, l) in enumerate(layers) if sname in out and l in blocks), default=-1)
+        for i, (sname, l) in enumerate(layers):
+            if i > last:
+                break   # nothing wanted reads a later block's input
+            _lib.check(self.lib.msst_block_fwd(ctypes.byref(self._bw[i]), _p(x), _p(y), None, _MODE[sname], B, S, N, H, prec, self.max_grid,
+                                               0.0, 0, i, None, None, ctypes.byref(wrote), st), "msst_block_fwd")
+            if sname in out and l in blocks:
+                self.attn_maps_block(i, x, out[sname][:, blocks.index(l)], reduce)
+            x, y = y, x
+        return out.get("spatial"), out.get("spectral")
+
+    def attention_maps(self, img, mask_u8, stacks, blocks, reduce):
+        """Eval forward of the encoder (encode_scene's / reconstruct's: prep_weights, tokenizer -- with the mask token where mask_u8
+        [B, T] uint8 marks a token, None: nothing masked --, the blocks on two token buffers with no dropout and nothing saved, at the
+        model's precision, the current stream) that hands out the attention probabilities of the wanted blocks.
+        stacks: names out of ("spatial", "spectral"); blocks: layer indices within a stack; reduce: _lib.ATTN_PER_SEQ / ATTN_MEAN_SEQ.
+        -> (spatial, spectral), fp32 [B, len(blocks), heads, L, L] or [B, len(blocks), G, heads, L, L]; None for a stack not asked for."""
+        self._require_cuda(img)
+        with torch.no_grad():
+            self.prep_weights()
+            x0 = self.tokenize(img.contiguous().float(), mask_u8)
+            return self.attention_maps_tokens(x0, tuple(stacks), list(blocks), reduce)
+
     # ------------------------------------------------------------------ staged forward (tests / debugging)
     def simmim_forward_stages(self, img, bool_mask, idx, drop=(0.0, 0)):
         """Forward only, returning the intermediates the golden fixtures pin."""

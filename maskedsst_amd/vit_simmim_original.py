@@ -186,3 +186,16 @@ class SimMIMSpatialSpectral(nn.Module):
         cube, err, cnt, cover = eng.reconstruct_scene(scene, mask_u8, stride, blend, max_windows)
         counted = (mask_u8.bool() & (cover > 0)[:, None]).view(Bs, S, 1, Hs, Ws).expand(Bs, S, P, Hs, Ws).reshape(Bs, C, Hs, Ws)
         return SceneReconstruction(cube, counted, err, cnt, cover)
+
+    def attention_maps(self, img, masks=None, stack="both", reduce="mean", blocks=None):
+        """``ViTSpatialSpectral.attention_maps`` of the encoder as the SimMIM model runs it: the tokens of `masks` are replaced by the
+        mask token before the blocks.  masks: the (bool_mask, idx) pair ``forward`` takes or a bare bool [B, T] tensor; None = no
+        token masked (the bare encoder's maps, bit for bit).  stack, reduce, blocks, the result, the precision rule and the errors:
+        as there.  Always an eval forward under no_grad, whatever the module's mode, which is left as it is."""
+        from .attention import _attention_maps
+        mask_u8 = None
+        if masks is not None:
+            if not torch.is_tensor(img) or img.dim() != 4:
+                raise ValueError(f"img must be a 4-D tensor [batch, bands, H, W], got {getattr(img, 'shape', type(img))}")
+            mask_u8 = self._token_mask(masks, img.shape[0]).to(device=img.device, dtype=torch.uint8).contiguous()
+        return _attention_maps(self.encoder, img, mask_u8, stack, reduce, blocks)

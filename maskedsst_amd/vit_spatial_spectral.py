@@ -380,3 +380,24 @@ class ViTSpatialSpectral(nn.Module):
         the wrong rank or band count, one smaller than a window, or a stride outside its range; a CPU tensor raises as everywhere."""
         from .scene import encode_scene, SCENE_MAX_WINDOWS
         return encode_scene(self, scene, stride, normalize, SCENE_MAX_WINDOWS if max_windows is None else max_windows)
+
+    def attention_maps(self, img, stack="both", reduce="mean", blocks=None):
+        """The attention probabilities of the transformer blocks for img [B, channels, image_size, image_size] (fp32, on the device):
+        AttentionMaps(spatial, spectral), fp32 on the device; the stack not asked for is None.
+          stack   "spatial" | "spectral" | "both".  A spatial sequence is the N = image_size^2 positions of one spectral block (L = N,
+                  S sequences per sample); a spectral sequence the S spectral blocks of one position (L = S, N sequences per sample).
+          blocks  layer indices within a stack (None: all, in order); nblk = len(blocks).
+          reduce  "mean": spatial [B, nblk, heads, N, N], spectral [B, nblk, heads, S, S] -- the mean over the sample's sequences,
+                  added in sequence order in fp32 and divided once;  None: every sequence, spatial [B, nblk, S, heads, N, N], spectral
+                  [B, nblk, N, heads, S, S] -- B S heads N^2 4 bytes per spatial block (EnMAP window, 8 heads: 2.6 MB per sample and
+                  block), B N heads S^2 4 bytes per spectral block.
+        Rows are queries, columns keys; every row sums to 1 (the reference's `attn` before dropout, vit_spatial_spectral.py:67-74).
+        Precision: the maps are the fp32 softmax (``msst_attn_maps``: fp32 LayerNorm, projections and scores, whatever the model's
+        precision) of the block inputs that the model's own forward produced.  For a bf16 model they therefore differ from the
+        probabilities inside its block kernel by the half rounding of that kernel's operands -- not by more.
+        Eval forward (no dropout, no mask token) under no_grad on the current stream, whatever the module's mode, which is left
+        unchanged; no gradient flows.  Raises ValueError, before any launch, for an img of the wrong rank, band count or size, an
+        unknown stack or reduce, or a block index out of range; a CPU tensor raises as everywhere (no CPU fallback).  When a block's
+        maps are not a multiple of 4 floats (toy shapes; never with 8 heads) the result is a strided view."""
+        from .attention import _attention_maps
+        return _attention_maps(self, img, None, stack, reduce, blocks)
