@@ -70,6 +70,14 @@ def build_parser():
     ap.add_argument("--shifting-window", action="store_true", default=None,
                     help="train on every non-overlapping window of each 64 x 64 tile at once (reference shifting_window=True; overrides "
                          "the config's shifting_window) instead of one random crop per tile")
+    ap.add_argument("--train-at", default=None, choices=["labelled", "random"],
+                    help="train on windows at listed positions of the step's resident tiles (ViTSpatialSpectral.forward_at, the reference's "
+                         "Houston2018 sampling): labelled -- windows centred at labelled pixels, one class each (pixelwise models); random "
+                         "-- windows at random positions that hold a labelled pixel (patch heads)")
+    ap.add_argument("--windows-per-step", type=int, default=512, metavar="N", help="windows drawn per step under --train-at")
+    ap.add_argument("--val-at", action="store_true",
+                    help="validate with predict_at on the windows centred at the validation tiles' labelled pixels (--val-scenes defaults "
+                         "to 2 and --val-every to --steps when they are not given)")
     ap.add_argument("--linear-eval", action="store_true", default=None,
                     help="linear evaluation (reference finetune.py:110-136; overrides the config's linear_eval): everything outside "
                          "mlp_head is frozen, the optimizer sees the head only, the step runs no block or tokenizer backward")
@@ -172,6 +180,15 @@ def main():
         for n, p in model.named_parameters():
             p.requires_grad_("mlp_head" in n)
     optimizer = make_optimizer(model, config, args.optimizer)
+    if args.train_at == "labelled" and not config.pixelwise:
+        raise SystemExit("--train-at labelled draws one class per window: it needs a pixelwise model (--pixelwise)")
+    if args.train_at == "random" and config.pixelwise:
+        raise SystemExit("--train-at random trains on label patches: it needs a patch head (no --pixelwise)")
+    if args.train_at and args.windows_per_step < 1:
+        raise SystemExit("--windows-per-step must be at least 1")
+    if args.val_at:
+        args.val_scenes = args.val_scenes or 2
+        args.val_every = args.val_every or args.steps
     if not 0.0 <= args.label_smoothing < 1.0:
         raise SystemExit("--label-smoothing must lie in [0, 1)")
     # --class-weights inverse: the weights come from the first step's labels, so the criterion is made there
@@ -190,6 +207,8 @@ def main():
     # samples of a step: the tiles, or under shifting_window the windows they are cut into (train_step's condition)
     s = config.image_size - config.patch_sub
     per_step = config.batch_size * ((64 // s) ** 2 if config.shifting_window and config.image_size != 64 else 1)
+    if args.train_at:
+        per_step = args.windows_per_step
     model.train()
     t0 = time.time()
     for step in range(1, args.steps + 1):
@@ -201,19 +220,68 @@ def main():
             weight = inverse_frequency_weights(label, config.n_classes, config.ignored_label)
             print("class weights " + " ".join(f"{v:.4f}" for v in weight.tolist()), flush=True)
             criterion = make_criterion(args.loss, config.ignored_label, weight, args.label_smoothing).to(device)
-        loss, acc, macro_acc = train_step(img, label, model, config, device, criterion, optimizer)
+        if args.train_at:
+            loss, acc, macro_acc = train_step_at_listed(img.to(device), label, model, config, criterion, optimizer, args.train_at,
+                                                        args.windows_per_step, gen)
+        else:
+            loss, acc, macro_acc = train_step(img, label, model, config, device, criterion, optimizer)
         if step % config.logging_freq == 0:
             macro = f" macro_acc {float(macro_acc):.3f}" if fused else ""   # (the eager path has no macro accuracy: it repeats acc)
             print(f"step {step} loss {loss.item():.4f} acc {float(acc):.3f}{macro} {step * per_step / (time.time() - t0):.1f} samples/s",
                   flush=True)
         if val is not None and step % args.val_every == 0:
-            validate(model, val, step, config.ignored_label, fused=fused, report=args.val_report)
+            if args.val_at:
+                validate_at(model, val, step, config.ignored_label, report=args.val_report)
+            else:
+                validate(model, val, step, config.ignored_label, fused=fused, report=args.val_report)
             if args.val_embed:
                 validate_embedding(model, val, step, config.n_classes, config.ignored_label)
             if args.val_saliency:
                 validate_saliency(model, val, step)
             if args.val_attention:
                 validate_attention(model, val, step)
+
+
+def train_step_at_listed(scene, label, model, config, criterion, optimizer, mode, n, gen):
+    """--train-at: one step on n windows of the resident tiles scene [B, C, 64, 64] (on the device; label [B, 64, 64] on the host, where
+    the table is drawn).  labelled: n of centre_origins' rows, drawn without replacement (all of them when there are fewer), each with
+    its centre's class; random: n random_origins that hold a labelled pixel, with their label patches."""
+    from maskedsst_amd import centre_origins, random_origins, window_labels
+    from maskedsst_amd.utils import train_step_at
+    s = config.image_size - config.patch_sub
+    if mode == "labelled":
+        origins, labels = centre_origins(label, s, config.ignored_label)
+        if origins.shape[0] == 0:
+            raise SystemExit("--train-at labelled: the step's tiles hold no labelled pixel whose window fits")
+        pick = torch.randperm(origins.shape[0], generator=gen)[:n]
+        origins, labels = origins[pick], labels[pick]
+    else:
+        origins = random_origins(label.shape[0], label.shape[1], label.shape[2], s, n, generator=gen, labels=label,
+                                 ignore_index=config.ignored_label)
+        labels = window_labels(label, origins, s)
+    return train_step_at(scene, labels, origins, model, config, criterion, optimizer)
+
+
+def validate_at(model, val, step, ignored_label, report=False):
+    """--val-at: the Houston test protocol -- predictions only where a label exists.  One predict_at pass over the windows centred at
+    the validation tiles' labelled pixels (a patch head: the logits at the window's centre), then loss, accuracies and with report
+    the confusion-matrix line from one pass of the fused loss over those logits."""
+    from maskedsst_amd import centre_origins
+    from maskedsst_amd.ops import confusion_report, cross_entropy_stats
+    img, label = val
+    w = model.num_spatial_patches_sqrt
+    origins, labels = centre_origins(label, w, ignored_label)
+    _, logits = model.predict_at(img, origins, return_logits=True)
+    if logits.dim() == 4:
+        logits = logits[:, :, w // 2, w // 2].contiguous()
+    with torch.no_grad():
+        _, stats = cross_entropy_stats(logits, labels, ignored_label, confusion=report)
+    h = stats.host()
+    print(f"val step {step} loss {h.loss:.4f} acc {h.acc:.3f} macro_acc {h.macro_acc:.3f} windows {origins.shape[0]}", flush=True)
+    if report:
+        r = confusion_report(h.confusion)
+        print(f"val step {step} report OA {r.oa:.4f} AA {r.aa:.4f} kappa {r.kappa:.4f} mIoU {r.mean_iou:.4f} mF1 {r.mean_f1:.4f} "
+              f"pixels {r.total}", flush=True)
 
 
 def validate(model, val, step, ignored_label, fused=False, report=False):

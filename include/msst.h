@@ -176,6 +176,33 @@ int msst_tokenize_scene_bwd(const float* scene, const float* pre_g, const float*
                             float* dpost_b, float* dpos_a, float* dpos_b, int pos_split, int Bs, int Hs, int Ws, int window,
                             int stride, long win0, int nwin, int S, int P, float emb_dropout_p, uint32_t seed, void* stream);
 
+/* Training and prediction on windows at listed scene positions (the reference's pixelwise and random-position sampling of a
+ * sparsely labelled scene, src/data_houston2018.py:303-329: one window per labelled pixel, or windows at random positions).
+ * Additive under MSST_VERSION 109.  The kernels are those of msst_tokenize_scene_fwd_train / msst_tokenize_scene_bwd with the
+ * origin of a window read from a table instead of computed from its number: origins is a device table [nwin][3] of int32 --
+ * scene index, y0, x0 of the window's top-left pixel -- and sample i of the call is the window at origins[i].  Windows may overlap,
+ * repeat and come in any order; the scene is only read.  The C layer cannot see the table's values: THE CALLER GUARANTEES
+ * 0 <= scene < Bs, 0 <= y0 <= Hs - window and 0 <= x0 <= Ws - window for every row (a row outside reads outside the scene).
+ *
+ * msst_tokenize_at_fwd: out [nwin][S*window*window][96]; a dropout element is addressed by its place in out, so for every
+ * (emb_dropout_p, seed) out is bit-identical to msst_tokenize_fwd on the copied windows, and to msst_tokenize_scene_fwd_train when
+ * the table lists a regular grid in grid order.
+ * msst_tokenize_at_bwd: msst_tokenize_bwd of those windows (B = nwin): slab, nchunk, the gradient outputs, pos_split and the dropout
+ * regeneration as for msst_tokenize_scene_bwd; for equal nchunk every gradient is bit-identical to msst_tokenize_bwd on the copied
+ * windows.  Parameter gradients only: the scene is never written.  nwin >= 1.
+ * Both check their arguments before anything is enqueued: MSST_ERR_BADARG for a size below 1 (nwin = 0 is an empty forward call,
+ * nwin < 0 an error) or a null required pointer (dpos_a may be null as in msst_tokenize_bwd); MSST_ERR_UNSUPPORTED outside
+ * window <= Hs, Ws, window * window <= 64, P <= 16 (forward, for P != 10 or window != 8: also nwin <= 65535 per call). */
+int msst_tokenize_at_fwd(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
+                         const float* b_emb, const float* post_g, const float* post_b, const float* pos_a, const float* pos_b,
+                         int pos_split, float* out, int Bs, int Hs, int Ws, int window, int nwin, int S, int P,
+                         float emb_dropout_p, uint32_t seed, void* stream);
+int msst_tokenize_at_bwd(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
+                         const float* b_emb, const float* post_g, const float* post_b, const float* dx0, float* slab, int nchunk,
+                         float* dpre_g, float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g, float* dpost_b, float* dpos_a,
+                         float* dpos_b, int pos_split, int Bs, int Hs, int Ws, int window, int nwin, int S, int P,
+                         float emb_dropout_p, uint32_t seed, void* stream);
+
 /* msst_scene_assemble: adds the per-window logits win_logits [nwin][n_classes][window*window] (msst_cls_head_fwd of windows
  * win0 .. win0 + nwin - 1) into the running per-pixel sums logits [Bs][n_classes][Hs][Ws] (fp32).  The calls of one scene batch
  * must cover windows 0, 1, ... in order (any split into calls); logits needs no initialisation.  finalize != 0 (the last call, after

@@ -11,10 +11,11 @@ from .vit_spatial_spectral import ViTSpatialSpectral  # noqa: F401
 from .vit_simmim_original import SimMIMSpatialSpectral, BlockwiseToPixels, Reconstruction, SceneReconstruction  # noqa: F401
 from .recon import recon_report, ReconReport, window_masks_to_scene, scene_mask_to_windows  # noqa: F401
 from .masking import MaskGenerator  # noqa: F401
-from .scene import SceneEmbedding  # noqa: F401
+from .scene import SceneEmbedding, centre_origins, random_origins, window_labels  # noqa: F401
 from .saliency import input_gradient, band_importance, integrated_gradients  # noqa: F401
 from .attention import AttentionMaps, attention_rollout, attention_received  # noqa: F401
 
 __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "MaskGenerator", "Reconstruction", "recon_report",
            "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows", "SceneEmbedding",
-           "input_gradient", "band_importance", "integrated_gradients", "AttentionMaps", "attention_rollout", "attention_received"]
+           "input_gradient", "band_importance", "integrated_gradients", "AttentionMaps", "attention_rollout", "attention_received",
+           "centre_origins", "random_origins", "window_labels"]

@@ -372,6 +372,31 @@ int msst_tokenize_scene_fwd_train(const float* scene, const float* pre_g, const 
     return fail(launch_tokenize_scene_fwd(a, (hipStream_t)stream), "msst_tokenize_scene_fwd_train");
 }
 
+// the shared argument check of msst_tokenize_at_fwd / msst_tokenize_at_bwd, in the order of scene_train_args
+static int at_args(bool pointers, int Bs, int Hs, int Ws, int window, int nwin, int min_nwin, int S, int P, int pos_split) {
+    if (Bs < 1 || Hs < 1 || Ws < 1 || window < 1 || S < 1 || P < 1 || nwin < min_nwin) return MSST_ERR_BADARG;
+    if (window > Hs || window > Ws || window > 8 || P > 16) return MSST_ERR_UNSUPPORTED;   // 8: at most 64 pixels per window
+    if (!pointers || pos_split < 0 || pos_split >= 96) return MSST_ERR_BADARG;
+    return 0;
+}
+
+int msst_tokenize_at_fwd(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
+                         const float* b_emb, const float* post_g, const float* post_b, const float* pos_a, const float* pos_b,
+                         int pos_split, float* out, int Bs, int Hs, int Ws, int window, int nwin, int S, int P,
+                         float emb_dropout_p, uint32_t seed, void* stream) {
+    const bool pointers = scene && origins && pre_g && pre_b && w_emb && b_emb && post_g && post_b && pos_a && (pos_b || !pos_split) && out;
+    if (int rc = at_args(pointers, Bs, Hs, Ws, window, nwin, 0, S, P, pos_split)) return fail(rc, "msst_tokenize_at_fwd");
+    if ((P != 10 || window != 8) && nwin > 65535) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_at_fwd (more than 65535 windows)");
+    TokArgs a;
+    a.drop = make_drop(emb_dropout_p, seed, 255);
+    a.img = scene; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb;
+    a.post_g = post_g; a.post_b = post_b; a.pos_a = pos_a; a.pos_b = pos_b; a.mask_token = nullptr; a.mask = nullptr;
+    a.out = out; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P; a.pos_split = pos_split;
+    a.win0 = 0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = window; a.nq = 1; a.wps = 1;
+    a.origins = origins;
+    return fail(launch_tokenize_at_fwd(a, (hipStream_t)stream), "msst_tokenize_at_fwd");
+}
+
 int msst_scene_assemble(const float* win_logits, long win0, int nwin, float* logits, int64_t* classes, int Bs,
                         int n_classes, int Hs, int Ws, int window, int stride, int finalize, void* stream) {
     int nr = 0, nq = 0;
@@ -936,6 +961,27 @@ int msst_tokenize_scene_bwd(const float* scene, const float* pre_g, const float*
     a.post_b = post_b; a.mask = nullptr; a.dx0 = dx0; a.slab = slab; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P;
     a.win0 = win0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nq = nq; a.wps = (int)wps;
     if (int rc = launch_tokenize_scene_bwd(a, nchunk, st)) return fail(rc, "msst_tokenize_scene_bwd");
+    return tokenize_bwd_reduce(slab, nchunk, dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, nullptr,
+                               S, a.N, P, st);
+}
+
+int msst_tokenize_at_bwd(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
+                         const float* b_emb, const float* post_g, const float* post_b, const float* dx0, float* slab, int nchunk,
+                         float* dpre_g, float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g, float* dpost_b, float* dpos_a,
+                         float* dpos_b, int pos_split, int Bs, int Hs, int Ws, int window, int nwin, int S, int P,
+                         float emb_dropout_p, uint32_t seed, void* stream) {
+    const bool pointers = scene && origins && pre_g && pre_b && w_emb && b_emb && post_g && post_b && dx0 && slab && dpre_g && dpre_b &&
+                          dw_emb && db_emb && dpost_g && dpost_b && (dpos_b || !pos_split || !dpos_a);
+    if (int rc = at_args(pointers, Bs, Hs, Ws, window, nwin, 1, S, P, pos_split)) return fail(rc, "msst_tokenize_at_bwd");
+    if (nchunk < 1) return fail(MSST_ERR_BADARG, "msst_tokenize_at_bwd");
+    hipStream_t st = (hipStream_t)stream;
+    TokAtBwdArgs a;
+    a.drop = make_drop(emb_dropout_p, seed, 255);
+    a.img = scene; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb; a.post_g = post_g;
+    a.post_b = post_b; a.mask = nullptr; a.dx0 = dx0; a.slab = slab; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P;
+    a.win0 = 0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = window; a.nq = 1; a.wps = 1;
+    a.origins = origins;
+    if (int rc = launch_tokenize_at_bwd(a, nchunk, st)) return fail(rc, "msst_tokenize_at_bwd");
     return tokenize_bwd_reduce(slab, nchunk, dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, nullptr,
                                S, a.N, P, st);
 }

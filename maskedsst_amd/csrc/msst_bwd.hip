@@ -1364,7 +1364,8 @@ __global__ __launch_bounds__(256) void block_bwd_ln1_kernel(Ln1BwdArgs a) {
 // ==========================================================================================
 // PC: pixels per patch as a compile-time constant (10; 0 = run-time value), see tokenize_fwd_kernel
 // SCENE, Args: addressing policy of the source pixels, as in tokenize_fwd_body.  false: a batch of cubes img [B][S*P][N] and its token mask;
-// true: sample b is window win0 + b of a scene (TokSceneBwdArgs), nothing masked (the classification path).  The arithmetic
+// true: sample b is window win0 + b of a scene (TokSceneBwdArgs), or the window at origins[b] (TokAtBwdArgs: scene_window_origin's
+// overload reads the table), nothing masked (the classification path).  The arithmetic
 // and every summation order are the same: equal pixels and equal dx0 give equal bits.
 template <int PC, bool SCENE, class Args>
 __global__ __launch_bounds__(256) void tokenize_bwd_kernel(Args a) {
@@ -1912,6 +1913,17 @@ int launch_tokenize_scene_bwd(const TokSceneBwdArgs& a, int nchunk, hipStream_t 
     if (a.P == 10 && a.N == 64) hipLaunchKernelGGL((tokenize_bwd_mfma_kernel<true, TokSceneBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
     else if (a.P == 10) hipLaunchKernelGGL((tokenize_bwd_kernel<10, true, TokSceneBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((tokenize_bwd_kernel<0, true, TokSceneBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
+    return (int)hipGetLastError();
+}
+
+// ... SCENE instances over TokAtBwdArgs (a.origins: the windows of the call)
+int launch_tokenize_at_bwd(const TokAtBwdArgs& a, int nchunk, hipStream_t st) {
+    if (a.P > 16 || a.N > 64) return MSST_ERR_UNSUPPORTED;
+    if (a.B < 1 || nchunk < 1 || nchunk > 65535) return MSST_ERR_BADARG;
+    ProfScope ps(K_TOK_BWD, st);
+    if (a.P == 10 && a.N == 64) hipLaunchKernelGGL((tokenize_bwd_mfma_kernel<true, TokAtBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
+    else if (a.P == 10) hipLaunchKernelGGL((tokenize_bwd_kernel<10, true, TokAtBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((tokenize_bwd_kernel<0, true, TokAtBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 

@@ -24,12 +24,18 @@ namespace msst {
 // SRC: addressing policy of the source pixels and of the token mask.  TOK_BATCH: img[b, c P + k, n] of a batch of cubes [B][S*P][N],
 // mask [B][T];  TOK_SCENE: the same pixel of window b of a scene, scene[s, c P + k, y0 + n / win, x0 + n % win] (TokArgs scene fields;
 // no mask);  TOK_SCENE_MASKED: those pixels, and token (c, n) is masked where the scene mask [Bs][S][Hs][Ws] (a.mask) is non-zero at
-// (s, c, y0 + n / win, x0 + n % win) (msst_tokenize_scene_fwd_masked).  Nothing else differs: the embedding dropout addresses an
-// element by its place in `out` in all three (msst_tokenize_scene_fwd / _fwd_masked pass p = 0).
-enum { TOK_BATCH = 0, TOK_SCENE = 1, TOK_SCENE_MASKED = 2 };
+// (s, c, y0 + n / win, x0 + n % win) (msst_tokenize_scene_fwd_masked);  TOK_AT: TOK_SCENE with (s, y0, x0) of window b read from the
+// table a.origins instead of computed from its number (msst_tokenize_at_fwd).  Nothing else differs: the embedding dropout addresses
+// an element by its place in `out` in all four (msst_tokenize_scene_fwd / _fwd_masked pass p = 0).
+enum { TOK_BATCH = 0, TOK_SCENE = 1, TOK_SCENE_MASKED = 2, TOK_AT = 3 };
+template <int SRC>
+__device__ __forceinline__ const float* tok_window_origin(const TokArgs& a, int b) {
+    if constexpr (SRC == TOK_AT) return listed_window_origin(a, b);
+    else return scene_window_origin(a, b);
+}
 template <int PC, int SRC>
 __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
-    constexpr bool SCENE = SRC != TOK_BATCH;
+    constexpr bool SCENE = SRC != TOK_BATCH, NOMASK = SRC == TOK_SCENE || SRC == TOK_AT;
     __shared__ float patch[16][64];
     __shared__ float W[96][17];
     __shared__ float bias[96];
@@ -37,7 +43,7 @@ __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
     const int P = PC ? PC : a.P, N = a.N;
     if constexpr (SCENE) {
         const long plane = (long)a.Hs * a.Ws;
-        const float* src = scene_window_origin(a, b) + (long)c * P * plane;
+        const float* src = tok_window_origin<SRC>(a, b) + (long)c * P * plane;
         for (int i = tid; i < P * N; i += 256) {
             const int k = i / N, n = i % N;
             patch[k][n] = src[k * plane + (long)(n / a.win) * a.Ws + n % a.win];
@@ -87,7 +93,7 @@ __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
     const float rstd2 = rsqrtf(v2 * (1.f / 96.f) + 1e-5f);
     const int t = c * N + n;
     bool masked;
-    if constexpr (SRC == TOK_SCENE) masked = false;
+    if constexpr (NOMASK) masked = false;
     else if constexpr (SRC == TOK_SCENE_MASKED) masked = scene_window_mask(a, b, c)[(long)(n / a.win) * a.Ws + n % a.win] != 0;
     else masked = a.mask[(long)b * a.T + t] != 0;
     float* dst = a.out + ((long)b * a.T + t) * 96 + part * 4;
@@ -98,7 +104,7 @@ __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
         if (a.pos_split) pos = d < a.pos_split ? a.pos_a[n * a.pos_split + d] : a.pos_b[c * (96 - a.pos_split) + d - a.pos_split];
         else pos = a.pos_a[(long)t * 96 + d];
         const float tok = (e[i] - m2) * rstd2 * a.post_g[d] + a.post_b[d];
-        e[i] = (SRC != TOK_SCENE && masked ? a.mask_token[d] : tok) + pos;
+        e[i] = (!NOMASK && masked ? a.mask_token[d] : tok) + pos;
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -114,6 +120,8 @@ template <int PC>
 __global__ __launch_bounds__(256) void tokenize_scene_fwd_kernel(TokArgs a) { tokenize_fwd_body<PC, TOK_SCENE>(a); }
 template <int PC>
 __global__ __launch_bounds__(256) void tokenize_scene_fwd_masked_kernel(TokArgs a) { tokenize_fwd_body<PC, TOK_SCENE_MASKED>(a); }
+template <int PC>
+__global__ __launch_bounds__(256) void tokenize_at_fwd_kernel(TokArgs a) { tokenize_fwd_body<PC, TOK_AT>(a); }
 
 
 // ------------------------------------------------------------------------------------------
@@ -127,7 +135,8 @@ __global__ __launch_bounds__(256) void tokenize_scene_fwd_masked_kernel(TokArgs 
 // grid (S, nchunk), 256 threads: wave w <-> tokens 16 w .. + 15 of spectral block c, samples chunk, chunk + nchunk, ...
 // Position rows, bias, both LayerNorms' vectors and the mask token are tile invariant for a wave: registers / LDS.
 // SRC: the source addressing policy of tokenize_fwd_body (TOK_SCENE: windows of a scene instead of a batch of cubes, no mask;
-// TOK_SCENE_MASKED: with the scene mask).
+// TOK_SCENE_MASKED: with the scene mask; TOK_AT: windows at listed origins, one table row read per window where the next sample's
+// pixels are requested).
 // ------------------------------------------------------------------------------------------
 template <int SRC>
 __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
@@ -135,7 +144,7 @@ __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
     constexpr int P = 10, N = 64;
     __shared__ __attribute__((aligned(16))) float vec[3][96];   // post_g | post_b | mask_token
     const int c = blockIdx.x, tid = threadIdx.x, w = tid >> 6, l = tid & 63, g = l >> 4, j = l & 15;
-    if (tid < 96) { vec[0][tid] = a.post_g[tid]; vec[1][tid] = a.post_b[tid]; vec[2][tid] = SRC == TOK_SCENE ? 0.f : a.mask_token[tid]; }
+    if (tid < 96) { vec[0][tid] = a.post_g[tid]; vec[1][tid] = a.post_b[tid]; vec[2][tid] = (SRC == TOK_SCENE || SRC == TOK_AT) ? 0.f : a.mask_token[tid]; }
     // A fragments of W_c [96][10]: lane (i = l & 15, kq = l >> 4) holds W[16 mt + i][4 ks + kq] (zero beyond k = 9)
     float wf[6][3];
 #pragma unroll
@@ -173,7 +182,7 @@ __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
         const int bc = b < a.B ? b : a.B - 1;
         if constexpr (SCENE) {
             const long plane = (long)a.Hs * a.Ws;
-            const float* src = scene_window_origin(a, bc) + (long)c * P * plane + (long)(n / a.win) * a.Ws + n % a.win;
+            const float* src = tok_window_origin<SRC>(a, bc) + (long)c * P * plane + (long)(n / a.win) * a.Ws + n % a.win;
 #pragma unroll
             for (int ks = 0; ks < 3; ++ks) { const int k = 4 * ks + g; px[ks] = src[(k < P ? k : 0) * plane]; }
             if constexpr (SRC == TOK_SCENE_MASKED) mk = scene_window_mask(a, bc, c)[(long)(n / a.win) * a.Ws + n % a.win];
@@ -237,6 +246,7 @@ __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
 __global__ __launch_bounds__(256, 2) void tokenize_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<TOK_BATCH>(a); }
 __global__ __launch_bounds__(256, 2) void tokenize_scene_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<TOK_SCENE>(a); }
 __global__ __launch_bounds__(256, 2) void tokenize_scene_fwd_masked_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<TOK_SCENE_MASKED>(a); }
+__global__ __launch_bounds__(256, 2) void tokenize_at_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<TOK_AT>(a); }
 
 // ==========================================================================================
 // fused transformer block, forward.  Reference vit_spatial_spectral.py:22-29 (PreNorm),
@@ -919,6 +929,24 @@ int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st) {
         if (a.B > 65535) return MSST_ERR_UNSUPPORTED;   // one workgroup row per window (grid y)
         if (a.P == 10) hipLaunchKernelGGL(tokenize_scene_fwd_kernel<10>, dim3(a.S, a.B), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(tokenize_scene_fwd_kernel<0>, dim3(a.S, a.B), dim3(256), 0, st, a);
+    }
+    return (int)hipGetLastError();
+}
+
+// ... TOK_AT instances (a.origins: the windows of the call)
+int launch_tokenize_at_fwd(const TokArgs& a, hipStream_t st) {
+    if (a.P > 16 || a.N > 64) return MSST_ERR_UNSUPPORTED;
+    if (a.B < 1) return 0;
+    ProfScope ps(K_TOK_FWD, st);
+    if (a.P == 10 && a.N == 64) {
+        int nchunk = 1024 / (a.S > 0 ? a.S : 1);
+        if (nchunk < 1) nchunk = 1;
+        if (nchunk > a.B) nchunk = a.B;
+        hipLaunchKernelGGL(tokenize_at_fwd_mfma_kernel, dim3(a.S, nchunk), dim3(256), 0, st, a);
+    } else {
+        if (a.B > 65535) return MSST_ERR_UNSUPPORTED;   // one workgroup row per window (grid y)
+        if (a.P == 10) hipLaunchKernelGGL(tokenize_at_fwd_kernel<10>, dim3(a.S, a.B), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(tokenize_at_fwd_kernel<0>, dim3(a.S, a.B), dim3(256), 0, st, a);
     }
     return (int)hipGetLastError();
 }

@@ -83,6 +83,9 @@ struct TokArgs {
     // sample b is window win0 + b, row-major over (scene, window row, window column), origin (r * stride, q * stride), win x win pixels
     long win0;
     int Hs, Ws, win, stride, nq, wps;   // nq: windows per window row, wps: windows per scene
+    // listed origins (msst_tokenize_at_fwd, the kernels' TOK_AT instances only): sample b is the win x win window of scene origins[b][0]
+    // with its top-left pixel at row origins[b][1], column origins[b][2]; of the scene fields only Hs, Ws and win are read
+    const int32_t* origins;  // [B][3]
 };
 
 // img pointer of sample b's window origin (scene s, band 0, row r * stride, column q * stride); 64-bit: scenes may be large
@@ -93,6 +96,14 @@ __device__ __forceinline__ const float* scene_window_origin(const Args& a, int b
     const long s = i / a.wps;
     const int rem = (int)(i - s * a.wps), r = rem / a.nq, q = rem - r * a.nq;
     return a.img + ((s * a.S * a.P) * a.Hs + (long)r * a.stride) * a.Ws + (long)q * a.stride;
+}
+
+// the same pointer with the origin read from a table [B][3] of (scene, y0, x0) (Args: TokArgs or TokAtBwdArgs); one 12-byte read per call
+template <class Args>
+__device__ __forceinline__ const float* listed_window_origin(const Args& a, int b) {
+    const int32_t* o = a.origins + 3 * (long)b;
+    const long s = o[0];
+    return a.img + ((s * a.S * a.P) * a.Hs + (long)o[1]) * a.Ws + (long)o[2];
 }
 
 // mask byte of token (c, n = 0) of sample b's window in a scene mask [Bs][S][Hs][Ws] (TOK_SCENE_MASKED: TokArgs.mask): one byte per
@@ -214,6 +225,11 @@ struct TokSceneBwdArgs : TokBwdArgs {
     long win0;
     int Hs, Ws, win, stride, nq, wps;
 };
+// msst_tokenize_at_bwd (SCENE = true instances over this type): sample b is the window at origins[b] = (scene, y0, x0), TokArgs.origins
+struct TokAtBwdArgs : TokSceneBwdArgs {
+    const int32_t* origins;   // [B][3]
+};
+__device__ __forceinline__ const float* scene_window_origin(const TokAtBwdArgs& a, int b) { return listed_window_origin(a, b); }
 
 // msst_input_grad.hip (msst_tokenize_bwd_input, msst_tokenize_scene_bwd_input): d(loss)/d(img) from dx0
 struct TokInArgs {
@@ -291,6 +307,7 @@ int launch_scene_centre_fill(const SceneArgs& a, hipStream_t st);
 int launch_tokenize_fwd(const TokArgs& a, hipStream_t st);
 int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st);   // the same kernels reading windows of a scene (TokArgs scene fields)
 int launch_tokenize_scene_fwd_masked(const TokArgs& a, hipStream_t st);   // ... with a scene mask (a.mask [Bs][S][Hs][Ws]) and the mask token
+int launch_tokenize_at_fwd(const TokArgs& a, hipStream_t st);      // ... reading the windows listed in a.origins (no mask)
 int launch_head_bwd(const HeadBwdArgs& a, int nchunk, hipStream_t st);
 // One reduction segment: dst[(i / row_len) * row_stride + i % row_len] = sum_{k < nslab} src[k * slab_stride + i], i < n
 struct RSeg {
@@ -334,6 +351,7 @@ int launch_block_bwd_ln1(const Ln1BwdArgs& a, int grid, int prec, hipStream_t st
 int launch_block_bwd_ln1mlp(const LnMlpArgs& a, int grid, hipStream_t st);   // msst_bwd5.hip (bf16: LN1 backward of block i + MLP backward of block i - 1)
 int launch_tokenize_bwd(const TokBwdArgs& a, int nchunk, hipStream_t st);
 int launch_tokenize_scene_bwd(const TokSceneBwdArgs& a, int nchunk, hipStream_t st);   // the same kernels reading windows of a scene (no mask)
+int launch_tokenize_at_bwd(const TokAtBwdArgs& a, int nchunk, hipStream_t st);   // ... reading the windows listed in a.origins (no mask)
 int launch_pos_split(const float* dpos, int S, int N, int split, float* dpe, float* dce, hipStream_t st);
 int launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                  float wd, int step, float clamp, float gscale, hipStream_t st);

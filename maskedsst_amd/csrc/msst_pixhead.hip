@@ -39,7 +39,11 @@ __device__ __forceinline__ float sum8(float v) {
     return v;   // the butterfly leaves the same bits on all 8 lanes of the row
 }
 
-__device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
+// the four terms in one fixed order, as explicit fused multiply-adds.  Written as a0 b0 + a1 b1 + a2 b2 + a3 b3 the compiler packed
+// the dot products of two neighbouring samples into one v_pk_fma_f32 chain and, to do so, commuted the first sum of the upper one
+// (fma(a0, b0, a1 b1) beside fma(a1, b1, a0 b0)): the last bits of a sample's logits then depended on whether its index in the launch
+// was even or odd.  This is the order one sample of every such pair always had.
+__device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return fmaf(a[3], b[3], fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0]))); }
 
 // row (b, n): lane part (0..7) owns features 12 part .. 12 part + 11.  m <- the mean over the S tokens; (mean, rstd) of LayerNorm(96)
 __device__ __forceinline__ void pix_row(const PixHeadArgs& a, int b, int n, int part, float (&m)[12], float& mean, float& rstd) {

@@ -398,10 +398,14 @@ class Engine:
         s = self.enc.num_spatial_patches_sqrt
         return s, tiles.shape[-2] // s, tiles.shape[-1] // s
 
-    def tokenize_windows(self, img, emb_drop=(0.0, 0), tiles=False):
+    def tokenize_windows(self, img, emb_drop=(0.0, 0), tiles=False, origins=None):
         """the classification path's tokens (nothing masked, position added, embedding dropout): of a window batch img [B, C, s, s]
         (tokenize), or with tiles=True of every window of tiles [B, C, Ht, Wt] in stack_image_batch's order, read straight out of
-        the tiles (msst_tokenize_scene_fwd_train) -> [B nr nq, T, 96], bit for bit what tokenize gives for the stacked copy"""
+        the tiles (msst_tokenize_scene_fwd_train) -> [B nr nq, T, 96], bit for bit what tokenize gives for the stacked copy; or with
+        origins (int32 [n, 3] on img's device: scene, y0, x0) of the n listed s x s windows of the scenes img [Bs, C, Hs, Ws]
+        (msst_tokenize_at_fwd) -> [n, T, 96], the same bits again"""
+        if origins is not None:
+            return self._tokenize_at(img, origins, emb_drop)
         if not tiles:
             return self.tokenize(img, None, emb_drop=emb_drop)
         self._require_cuda(img)
@@ -424,6 +428,28 @@ class Engine:
                 _p(img), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
                 V(fp.ptr("post_g")), V(fp.ptr("post_b")), V(pos_a), V(pos_b), split, _p(out[win0:]), B, Ht, Wt, s, s, win0,
                 min(chunk, total - win0), S, P, emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_scene_fwd_train")
+        return out
+
+    def _tokenize_at(self, scene, origins, emb_drop):
+        self._require_cuda(scene)
+        self.ensure()
+        Bs, _, Hs, Ws = scene.shape
+        S, N, P = self.S, self.N, self.P
+        s = self.enc.num_spatial_patches_sqrt
+        total = origins.shape[0]
+        out = torch.empty(total, S * N, D, dtype=torch.float32, device=scene.device)
+        chunk = total if (P == 10 and s == 8) else min(total, self.TILE_WINDOWS_PER_LAUNCH)
+        if chunk < total and emb_drop[0] > 0:
+            raise NotImplementedError(f"embedding dropout over {total} windows in one step needs more than one launch of the generic "
+                                      f"tokenizer ({self.TILE_WINDOWS_PER_LAUNCH} windows each): list fewer windows per step")
+        fp = self.fp
+        split, pos_a, pos_b = self._pos_tables()
+        V = ctypes.c_void_p
+        for win0 in range(0, total, max(chunk, 1)):
+            _lib.check(self.lib.msst_tokenize_at_fwd(
+                _p(scene), _p(origins[win0:]), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
+                V(fp.ptr("post_g")), V(fp.ptr("post_b")), V(pos_a), V(pos_b), split, _p(out[win0:]), Bs, Hs, Ws, s,
+                min(chunk, total - win0), S, P, emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_at_fwd")
         return out
 
     def blocks_fwd(self, x0, save=True, drop=(0.0, 0)):
@@ -868,9 +894,29 @@ class Engine:
         if with_pos:
             self._fire("tokenizer")
 
-    def tokenize_windows_bwd(self, img, dx0, emb_drop=(0.0, 0), tiles=False):
+    def tokenize_windows_bwd(self, img, dx0, emb_drop=(0.0, 0), tiles=False, origins=None):
         """backward of tokenize_windows: dx0 [windows, T, 96] -> the tokenizer's gradients in the flat buffer.  Tiles: one
-        msst_tokenize_scene_bwd over all windows, with the nchunk tokenize_bwd takes for as many samples -- the same bits."""
+        msst_tokenize_scene_bwd over all windows, with the nchunk tokenize_bwd takes for as many samples -- the same bits.
+        Origins: one msst_tokenize_at_bwd over the listed windows, likewise."""
+        if origins is not None:
+            Bs, _, Hs, Ws = img.shape
+            S, N, P = self.S, self.N, self.P
+            s = self.enc.num_spatial_patches_sqrt
+            total = origins.shape[0]
+            nchunk = max(1, min(total, self.tok_chunks))
+            ss = N * 96 + 96 * P + 96 * 4 + 32
+            slab = torch.empty(S * nchunk * ss + S * N * 96, dtype=torch.float32, device=img.device)
+            fp, g = self.fp, self.fp.grad
+            V = ctypes.c_void_p
+            split, dpa, dpb = self._pos_tables(g)
+            _lib.check(self.lib.msst_tokenize_at_bwd(
+                _p(img), _p(origins), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
+                V(fp.ptr("post_g")), V(fp.ptr("post_b")), _p(dx0), _p(slab), nchunk,
+                V(fp.ptr("pre_g", g)), V(fp.ptr("pre_b", g)), V(fp.ptr("embed.w.0", g)), V(fp.ptr("embed.b.0", g)),
+                V(fp.ptr("post_g", g)), V(fp.ptr("post_b", g)), V(dpa), V(dpb), split, Bs, Hs, Ws, s, total, S, P,
+                emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_at_bwd")
+            self._fire("tokenizer")
+            return
         if not tiles:
             zero_mask = self._zero_mask_for(img.shape[0] * self.S * self.N, img.device)
             return self.tokenize_bwd(img, zero_mask, dx0, emb_drop=emb_drop)
@@ -1181,8 +1227,20 @@ class Engine:
             raise ValueError(f"tiles of {tuple(tiles.shape[-2:])} hold no {s} x {s} window")
         return self._classify(tiles, tiles.shape[0] * nr * nq, True)
 
+    def classify_at(self, scene, origins):
+        """classify(the stacked s x s windows of scene [Bs, C, Hs, Ws] at origins [n, 3] = (scene, y0, x0)) without the stacked copy:
+        both tokenizer passes read the listed windows in place (msst_tokenize_at_fwd / _bwd).  origins: int32, contiguous, on the
+        scene's device, every row inside the scene (ViTSpatialSpectral.forward_at checks).  Shapes, regimes, seeds and limits of
+        classify_tiles; n = 0 is refused."""
+        self._require_cuda(scene)
+        self.ensure()
+        if origins.shape[0] < 1:
+            raise ValueError("origins lists no window")
+        return self._classify(scene.contiguous().float(), origins.shape[0], origins)
+
     def _classify(self, img, B, tiles):
-        """classify / classify_tiles: img a batch of B windows, or (tiles) the tiles that hold B windows"""
+        """classify / classify_tiles / classify_at: img a batch of B windows, or (tiles is True) the tiles that hold B windows, or
+        (tiles an origins table) the scenes the B listed windows lie in"""
         p = float(self.enc.dropout_p) if self.enc.training else 0.0
         pe = float(self.enc.emb_dropout_p) if self.enc.training else 0.0
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if (p > 0 or pe > 0) else 0
@@ -1194,7 +1252,7 @@ class Engine:
                 raise NotImplementedError("train the classifier through a bare ViTSpatialSpectral (as finetune.py "
                                           "does), not through an encoder wrapped in SimMIMSpatialSpectral")
             self.prep_weights()
-            x0 = self.tokenize_windows(img, emb_drop, tiles)
+            x0 = self.tokenize_windows(img, emb_drop, **_window_kw(tiles))
             acts, _ = self.blocks_fwd(x0, save=False, drop=drop)
             return self._classify_view(self.head_logits(acts[-1]), B)
         named = self.trainable()
@@ -1203,7 +1261,7 @@ class Engine:
             # module still in training mode, so its dropout stays on -- with nothing saved, and only the head has a backward.  (An
             # input that requires a gradient needs the full body backward: that call takes the full path below.)
             self.prep_weights()
-            x0 = self.tokenize_windows(img, emb_drop, tiles)
+            x0 = self.tokenize_windows(img, emb_drop, **_window_kw(tiles))
             y = self.blocks_fwd_pingpong(x0, drop=drop)
             head = [(n, q) for n, q in named if n.startswith("mlp_head.")]
             out = _HeadOnlyFn.apply(self, [n for n, _ in head], y, *[q for _, q in head])
@@ -1486,14 +1544,21 @@ class _EmbedFn(torch.autograd.Function):
         return (None, None, dimg) + _grad_views(eng, ctx.names, needs)
 
 
+def _window_kw(tiles):
+    """the `tiles` slot of _classify / _ClassifyFn as tokenize_windows' keywords: a flag (window batch or tiles), or the int32 origins
+    table [n, 3] of classify_at (the windows listed in it, read out of the scenes)"""
+    return {"origins": tiles} if torch.is_tensor(tiles) else {"tiles": tiles}
+
+
 class _ClassifyFn(torch.autograd.Function):
     """logits = encoder(img) for the classification path; backward through the same HIP kernels.  img: a window batch, or (tiles) tiles
-    whose windows both tokenizer passes read in place (Engine.tokenize_windows) -- the stash holds img as it came."""
+    whose windows both tokenizer passes read in place (Engine.tokenize_windows) -- the stash holds img as it came.  The tiles slot
+    may hold an origins table instead of a flag (_window_kw): img is then the scenes, and ctx keeps the table for the backward."""
 
     @staticmethod
     def forward(ctx, eng, names, drop, emb_drop, tiles, img, *params):
         eng.prep_weights()
-        x0 = eng.tokenize_windows(img, emb_drop, tiles)
+        x0 = eng.tokenize_windows(img, emb_drop, **_window_kw(tiles))
         acts, x1s = eng.blocks_fwd(x0, save=True, drop=drop)
         logits = eng.head_logits(acts[-1])
         ctx.eng, ctx.names, ctx.drop, ctx.emb_drop, ctx.tiles = eng, names, drop, emb_drop, tiles
@@ -1511,9 +1576,12 @@ class _ClassifyFn(torch.autograd.Function):
         dx0 = eng.blocks_bwd(acts, x1s, dy, drop=ctx.drop)
         dimg = None
         if ctx.needs_input_grad[5]:   # the input (window batch or tiles) asked for its gradient: one more launch that only reads
+            if torch.is_tensor(ctx.tiles):
+                raise NotImplementedError("no input gradient through windows at listed origins: they overlap, so d(scene) would "
+                                          "need an accumulating scatter")
             dimg = eng.tokenize_windows_input_bwd(img, dx0, emb_drop=ctx.emb_drop, tiles=ctx.tiles)
         if any(needs):   # (a fully frozen model: the tokenizer backward writes parameter gradients only, nobody reads them)
-            eng.tokenize_windows_bwd(img, dx0, emb_drop=ctx.emb_drop, tiles=ctx.tiles)
+            eng.tokenize_windows_bwd(img, dx0, emb_drop=ctx.emb_drop, **_window_kw(ctx.tiles))
         return (None,) * 5 + (dimg,) + _grad_views(eng, ctx.names, needs)
 
 

@@ -15,6 +15,11 @@ width ``image_size // 2``, and with a stride above 1 every pixel that is no wind
 
 ``ViTSpatialSpectral.encode_scene`` runs the same windows through the same encoder and stops before the head: per-pixel embedding
 maps ``[Bs, 96, Hs, Ws]`` (``msst_pool_spectral_fwd``, ``msst_scene_embed_assemble``), NaN where no window covers a pixel.
+
+Windows at listed positions (``ViTSpatialSpectral.forward_at`` / ``predict_at``, ``msst_tokenize_at_fwd`` / ``_bwd``): the sampling
+protocol of the reference's ``Houston2018Dataset`` (``src/data_houston2018.py``) on a sparsely labelled scene -- one window centred at
+every labelled pixel, or windows at random positions -- with the windows read in place.  ``centre_origins``, ``random_origins`` and
+``window_labels`` build the origin tables and the labels that go with them.
 """
 from collections import namedtuple
 
@@ -70,6 +75,140 @@ def encode_scene(model, scene, stride=None, normalize=False, max_windows=SCENE_M
     stride, max_windows = _check_scene(model, scene, stride, max_windows)
     features, cover = model.engine().encode_scene(scene, stride, bool(normalize), max_windows)
     return SceneEmbedding(features, cover)
+
+
+def _check_labels(labels, window):
+    if not torch.is_tensor(labels) or labels.dim() != 3:
+        raise ValueError(f"labels must be a 3-D tensor [scenes, H, W], got {getattr(labels, 'shape', type(labels))}")
+    if isinstance(window, bool) or int(window) != window or int(window) < 1:
+        raise ValueError(f"window must be a positive integer, got {window!r}")
+    return int(window)
+
+
+def centre_origins(labels, window, ignore_index=-1):
+    """The windows centred at the labelled pixels of label maps [Bs, Hs, Ws] (the reference's Houston2018Dataset(pixelwise=True),
+    src/data_houston2018.py:248-255 and :303-317): every pixel (y, x) whose label is not ignore_index and whose window fits --
+    y >= window // 2, y + window // 2 < Hs, likewise x -- gives the window with origin (y - window // 2, x - window // 2); for an
+    even window the centre sits at index window // 2 of the window.  Returns (origins [n, 3] int32 = (scene, y0, x0), centre_labels
+    [n] int64), on the labels' device, rows in the order of nonzero()."""
+    window = _check_labels(labels, window)
+    h = window // 2
+    Hs, Ws = labels.shape[1:]
+    idx = (labels != ignore_index).nonzero()
+    ok = (idx[:, 1] >= h) & (idx[:, 1] + h < Hs) & (idx[:, 2] >= h) & (idx[:, 2] + h < Ws)
+    idx = idx[ok]
+    centre_labels = labels[idx[:, 0], idx[:, 1], idx[:, 2]].long()
+    origins = torch.stack((idx[:, 0], idx[:, 1] - h, idx[:, 2] - h), dim=1).to(torch.int32)
+    return origins, centre_labels
+
+
+def window_labels(labels, origins, window):
+    """The label patches [n, window, window] (int64) of the windows listed in origins [n, 3] = (scene, y0, x0) out of label maps
+    [Bs, Hs, Ws]: what a patch head trains against (:324).  A gather of labels only, on the labels' device."""
+    window = _check_labels(labels, window)
+    o = origins.to(labels.device).long()
+    r = torch.arange(window, device=labels.device)
+    ys = (o[:, 1, None] + r)[:, :, None]
+    xs = (o[:, 2, None] + r)[:, None, :]
+    return labels[o[:, 0, None, None], ys, xs].long()
+
+
+def random_origins(Bs, Hs, Ws, window, n, generator=None, labels=None, ignore_index=-1):
+    """n windows at random positions (:319-329): scene uniform over Bs, origin uniform over [0, Hs - window] x [0, Ws - window].
+    -> origins [n, 3] int32 on the labels' device (the CPU without labels), drawn with `generator` on its own device.  With labels
+    [Bs, Hs, Ws] (the reference's drop_unlabeled, :326-327): a window that holds no pixel with a label other than ignore_index is
+    drawn again -- only the rejected rows, in a loop, no recursion.  Raises ValueError when no window of the maps holds a labelled
+    pixel (the loop would not end)."""
+    if min(int(Bs), int(Hs), int(Ws), int(window)) < 1 or int(n) < 0 or window > Hs or window > Ws:
+        raise ValueError(f"no {window} x {window} window in {Bs} scenes of {Hs} x {Ws}, or a negative count {n}")
+    Bs, Hs, Ws, window, n = int(Bs), int(Hs), int(Ws), int(window), int(n)
+    dev = generator.device if generator is not None else (labels.device if labels is not None else torch.device("cpu"))
+    out_dev = labels.device if labels is not None else torch.device("cpu")
+
+    def draw(k):
+        cols = [torch.randint(0, hi, (k,), generator=generator, device=dev) for hi in (Bs, Hs - window + 1, Ws - window + 1)]
+        return torch.stack(cols, dim=1).to(out_dev)
+
+    origins = draw(n)
+    if labels is not None:
+        _check_labels(labels, window)
+        if tuple(labels.shape) != (Bs, Hs, Ws):
+            raise ValueError(f"labels {tuple(labels.shape)} are not [{Bs}, {Hs}, {Ws}]")
+        if not bool((labels != ignore_index).any()):
+            raise ValueError("no labelled pixel: every random window would be rejected")
+        while n:
+            empty = (window_labels(labels, origins, window) == ignore_index).flatten(1).all(dim=1).nonzero().flatten()
+            if empty.numel() == 0:
+                break
+            origins[empty] = draw(empty.numel())
+    return origins.to(torch.int32)
+
+
+def _check_origins(model, scene, origins, check):
+    """forward_at / predict_at: shapes and dtypes (no device needed), then with check the value ranges -- one reduction, one read-back"""
+    if not torch.is_tensor(scene) or scene.dim() != 4:
+        raise ValueError(f"scene must be a 4-D tensor [scenes, bands, H, W], got {getattr(scene, 'shape', type(scene))}")
+    bands = model.num_spectral_patches * model.patch_depth
+    if scene.shape[1] != bands:
+        raise ValueError(f"scene has {scene.shape[1]} bands, the model expects {bands}")
+    w = model.num_spatial_patches_sqrt
+    if scene.shape[0] < 1 or scene.shape[2] < w or scene.shape[3] < w:
+        raise ValueError(f"scene {tuple(scene.shape)} is smaller than one {w} x {w} window")
+    if not torch.is_tensor(origins) or origins.dim() != 2 or origins.shape[1] != 3:
+        raise ValueError(f"origins must be an integer tensor [n, 3] of (scene, y0, x0), got {getattr(origins, 'shape', type(origins))}")
+    if origins.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+        raise ValueError(f"origins must be an integer tensor, got {origins.dtype}")
+    if check and origins.shape[0]:
+        hi = (scene.shape[0] - 1, scene.shape[2] - w, scene.shape[3] - w)
+        lo_seen, hi_seen = (v.tolist() for v in torch.stack(torch.aminmax(origins, dim=0)).cpu())   # one reduction, the one read-back
+        if min(lo_seen) < 0 or any(a > b for a, b in zip(hi_seen, hi)):
+            o = origins.cpu()   # the error path alone looks at the rows
+            first = int(((o < 0) | (o > torch.tensor(hi))).any(dim=1).int().argmax())
+            raise ValueError(f"origins row {first} = {o[first].tolist()} is outside the scenes: (scene, y0, x0) must lie in "
+                             f"[0, {hi[0]}] x [0, {hi[1]}] x [0, {hi[2]}]")
+
+
+def forward_at(model, scene, origins, check=True):
+    """See ViTSpatialSpectral.forward_at."""
+    _check_origins(model, scene, origins, check)
+    if scene.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("forward_at gives no gradient for the scene: listed windows overlap, so d(loss)/d(scene) needs an "
+                                  "accumulating scatter the tokenizer backward does not have; detach the scene (parameter gradients "
+                                  "are computed), or stack the windows and call the model on them")
+    eng = model.engine()
+    eng._require_cuda(scene)
+    return eng.classify_at(scene, origins.to(device=scene.device, dtype=torch.int32).contiguous())
+
+
+def predict_at(model, scene, origins, return_logits=False, max_windows=SCENE_MAX_WINDOWS):
+    """See ViTSpatialSpectral.predict_at."""
+    if isinstance(max_windows, bool) or int(max_windows) != max_windows or int(max_windows) < 1:
+        raise ValueError(f"max_windows must be a positive integer, got {max_windows!r}")
+    _check_origins(model, scene, origins, True)
+    n, nc = origins.shape[0], model.num_classes
+    w = model.num_spatial_patches_sqrt
+    pix = bool(getattr(model, "pixelwise", False))
+    step = int(max_windows)
+    was_training = model.training
+    if was_training:   # (a walk over every module each way: skipped for a model that is in eval() already)
+        model.eval()
+    try:
+        with torch.no_grad():
+            parts = []
+            for i in range(0, n, step):
+                o = origins[i:i + step]
+                out = forward_at(model, scene, o, check=False)
+                parts.append(out.reshape((o.shape[0], nc) if pix else (o.shape[0], nc, w, w)))
+            if parts:
+                logits = torch.cat(parts) if len(parts) > 1 else parts[0]
+            else:
+                model.engine()._require_cuda(scene)
+                logits = torch.empty((0, nc) if pix else (0, nc, w, w), dtype=torch.float32, device=scene.device)
+            classes = logits.argmax(dim=1)
+    finally:
+        if was_training:
+            model.train()
+    return (classes, logits) if return_logits else classes
 
 
 def scene_metrics(logits, classes, labels, ignore_index=-1, fused=False):

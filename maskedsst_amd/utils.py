@@ -143,6 +143,45 @@ def train_step(img, label, model, config, device, criterion, optimizer, acc_crit
     return loss, acc, macro_acc
 
 
+def train_step_at(scene, labels, origins, model, config, criterion, optimizer, acc_criterion=None):
+    """train_step on the windows of resident scenes listed in origins [n, 3] = (scene, y0, x0) (the reference's Houston2018 sampling,
+    src/data_houston2018.py:303-329): train_step's body with ``model.forward_at(scene, origins)`` in place of crop, stack and
+    ``model(img)`` -- no window is copied.  scene [Bs, C, Hs, Ws] is on the device already; labels and origins are moved to it.
+    labels: one entry per window -- [n] for a pixelwise model (``centre_origins``' second result), [n, s, s] for the patch heads
+    (``window_labels``) -- or the label maps [Bs, Hs, Ws] of the scenes, from which exactly those are gathered here (pixelwise: the
+    label at the window's centre, index s // 2 of the window).  Loss, accuracy, backward and optimizer step as in train_step, the
+    fused criterion included."""
+    from .scene import window_labels
+    s = config.image_size - getattr(config, "patch_sub", 0)
+    if labels.dim() == 3 and tuple(labels.shape) == (scene.shape[0],) + tuple(scene.shape[-2:]):
+        if getattr(config, "pixelwise", False):
+            o = origins.to(labels.device).long()
+            label = labels[o[:, 0], o[:, 1] + s // 2, o[:, 2] + s // 2].long()
+        else:
+            label = window_labels(labels, origins, s)
+    else:
+        label = labels
+        if getattr(config, "pixelwise", False) and label.dim() == 3:
+            label = label[:, s // 2, s // 2]
+    if label.shape[0] != origins.shape[0]:
+        raise ValueError(f"{label.shape[0]} labels for {origins.shape[0]} windows")
+    label = label.to(scene.device)
+    optimizer.zero_grad()
+    output = model.forward_at(scene, origins)
+    if getattr(criterion, "fused_stats", False):
+        return _fused_tail(output, label, criterion, optimizer)
+    loss = criterion(output, label)
+    if torch.isnan(loss):
+        raise ValueError("Loss is NaN")
+    pred = output.argmax(dim=1)
+    valid = label != config.ignored_label
+    acc = (pred[valid] == label[valid]).sum() / max(int(valid.sum()), 1)
+    macro_acc = acc_criterion(pred[valid].to(int), label[valid]) if (acc_criterion is not None and valid.any()) else acc
+    loss.backward()
+    optimizer.step()
+    return loss, acc, macro_acc
+
+
 def _fused_tail(output, label, criterion, optimizer):
     """train_step from the loss on, for a FusedCrossEntropy: loss + record (two launches), ONE read-back of the record, the
     reference's NaN check on it (before the backward, as there), backward (one launch up to the head's), optimizer step.

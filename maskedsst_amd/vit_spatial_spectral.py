@@ -352,6 +352,32 @@ class ViTSpatialSpectral(nn.Module):
             raise ValueError(f"tiles of {tuple(tiles.shape[2:])} are smaller than one {s} x {s} window")
         return self.engine().classify_tiles(tiles)
 
+    def forward_at(self, scene, origins, check=True):
+        """forward(the stacked windows of scene at origins) without the stacked copy: the sampling of a sparsely labelled scene (the
+        reference's Houston2018Dataset, src/data_houston2018.py:303-329 -- a window centred at every labelled pixel, or windows at
+        random positions).  scene [Bs, channels, Hs, Ws] fp32 on the device; origins an integer tensor [n, 3] on either device, row i
+        = (scene index, y0, x0) of the top-left pixel of window i (maskedsst_amd.centre_origins / random_origins build such tables).
+        Windows may overlap, repeat and come in any order.  -> [n, num_classes, image_size, image_size]; pixelwise: [n, num_classes]
+        (forward's squeeze for n = 1).  Differentiable in the parameters exactly as forward is -- the same bits, in training (dropout,
+        full finetune, linear_eval) and in eval().
+        check=True validates the table's values (one reduction and one read-back) and raises ValueError naming the first row outside
+        0 <= scene < Bs, 0 <= y0 <= Hs - image_size, 0 <= x0 <= Ws - image_size; check=False skips that read-back: the kernels then
+        trust the table.  Raises ValueError -- before a device is asked for -- for a scene of the wrong rank or band count or smaller
+        than one window, and for a table of the wrong shape or dtype or with no row; NotImplementedError for a scene that requires a
+        gradient (overlapping windows would need an accumulating input gradient), for an encoder wrapped in SimMIM under grad, and
+        for the embedding-dropout limit of forward_windows."""
+        from .scene import forward_at
+        return forward_at(self, scene, origins, check)
+
+    def predict_at(self, scene, origins, return_logits=False, max_windows=None):
+        """Classes at listed windows (the Houston test protocol: predictions only where a label exists): forward_at under no_grad as
+        an eval() model, whatever the module's mode, which is left unchanged, in chunks of at most max_windows windows (None:
+        maskedsst_amd.scene.SCENE_MAX_WINDOWS; the result does not depend on it).  Returns classes = argmax over the class axis ([n, image_size, image_size] int64;
+        pixelwise [n]) and, with return_logits, also the logits ([n, num_classes, image_size, image_size]; pixelwise [n, num_classes],
+        never squeezed).  The table's values are always checked."""
+        from .scene import predict_at, SCENE_MAX_WINDOWS
+        return predict_at(self, scene, origins, return_logits, SCENE_MAX_WINDOWS if max_windows is None else max_windows)
+
     def predict_scene(self, scene, stride=None, return_logits=False, max_windows=None):
         """Classify whole scenes [Bs, channels, Hs, Ws] with sliding windows of image_size (the window loop of the reference's
         inference_example.ipynb, one batched pass): returns the class map [Bs, Hs, Ws] (int64; -1 where no window covers a
