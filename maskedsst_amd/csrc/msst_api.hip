@@ -192,6 +192,58 @@ static BlockWeights to_bw(const MsstBlockWeights* w) {
     return b;
 }
 
+// ------------------------------------------------------------------------------------------
+// the tokenizer's argument blocks, filled in one place each
+// ------------------------------------------------------------------------------------------
+// what TokArgs, TokBwdArgs (and its scene variants) and TokInArgs share: the source, the parameters, the shape, the dropout stream
+template <class Args>
+static void fill_tok_common(Args& a, const float* img, const float* pre_g, const float* pre_b, const float* w_emb, const float* b_emb,
+                            const float* post_g, const float* post_b, int B, int S, int N, int P, Drop drop) {
+    a.img = img; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb; a.post_g = post_g; a.post_b = post_b;
+    a.B = B; a.S = S; a.N = N; a.T = S * N; a.P = P; a.drop = drop;
+}
+static void fill_tok(TokArgs& a, const float* img, const float* pre_g, const float* pre_b, const float* w_emb, const float* b_emb,
+                     const float* post_g, const float* post_b, const float* pos_a, const float* pos_b, const float* mask_token,
+                     const uint8_t* mask, float* out, int B, int S, int N, int P, int pos_split, Drop drop) {
+    a = TokArgs{};   // no window grid, no origins: fill_window and the caller add them
+    fill_tok_common(a, img, pre_g, pre_b, w_emb, b_emb, post_g, post_b, B, S, N, P, drop);
+    a.pos_a = pos_a; a.pos_b = pos_b; a.mask_token = mask_token; a.mask = mask; a.out = out; a.pos_split = pos_split;
+}
+static void fill_tok_bwd(TokBwdArgs& a, const float* img, const float* pre_g, const float* pre_b, const float* w_emb,
+                         const float* b_emb, const float* post_g, const float* post_b, const uint8_t* mask, const float* dx0,
+                         float* slab, int B, int S, int N, int P, Drop drop) {
+    fill_tok_common(a, img, pre_g, pre_b, w_emb, b_emb, post_g, post_b, B, S, N, P, drop);
+    a.mask = mask; a.dx0 = dx0; a.slab = slab;
+}
+static void fill_tok_in(TokInArgs& a, const float* img, const float* pre_g, const float* pre_b, const float* w_emb, const float* b_emb,
+                        const float* post_g, const float* post_b, const uint8_t* mask, const float* dx0, const float* dtarget,
+                        float* dimg, int B, int S, int N, int P, Drop drop) {
+    fill_tok_common(a, img, pre_g, pre_b, w_emb, b_emb, post_g, post_b, B, S, N, P, drop);
+    a.mask = mask; a.dx0 = dx0; a.dtarget = dtarget; a.dimg = dimg;
+}
+// the window grid of the scene sources (Args: TokArgs, TokSceneBwdArgs, TokInArgs): sample b is window win0 + b.  Listed origins
+// (msst_tokenize_at_*) pass stride = win, nq = wps = 1, win0 = 0: of these only Hs, Ws and win are read there
+template <class Args>
+static void fill_window(Args& a, int Hs, int Ws, int win, int stride, int nq, long wps, long win0) {
+    a.win0 = win0; a.Hs = Hs; a.Ws = Ws; a.win = win; a.stride = stride; a.nq = nq; a.wps = (int)wps;
+}
+
+// the window grid of an assemble call into its argument block
+static void fill_grid(SceneGrid& g, long win0, int nwin, int Bs, int Hs, int Ws, int window, int stride, int nr, int nq) {
+    g.win0 = win0; g.row0 = 0; g.nwin = nwin; g.Bs = Bs; g.Hs = Hs; g.Ws = Ws; g.win = window; g.stride = stride; g.nr = nr; g.nq = nq;
+}
+// the flattened (scene, pixel row) rows the windows of a call reach: first window's top row .. last window's bottom row.  Sets
+// g.row0 and returns the pixels of those rows (0 for a call without windows): the launch size of launch_scene_fold
+static long scene_call_rows(SceneGrid& g, long wps) {
+    if (g.nwin < 1) return 0;
+    const long g0 = g.win0, g1 = g.win0 + g.nwin - 1;
+    const long s0 = g0 / wps, s1 = g1 / wps;
+    const long r0 = (g0 - s0 * wps) / g.nq, r1 = (g1 - s1 * wps) / g.nq;
+    g.row0 = s0 * g.Hs + r0 * g.stride;
+    const long rows = s1 * g.Hs + r1 * g.stride + g.win - g.row0;
+    return rows * g.Ws;
+}
+
 }  // namespace msst
 
 using namespace msst;
@@ -286,10 +338,8 @@ int msst_tokenize_fwd(const float* img, const float* pre_g, const float* pre_b, 
                       const float* pos_b, int pos_split, const float* mask_token, const uint8_t* mask,
                       float* out, int B, int S, int N, int P, float emb_dropout_p, uint32_t seed, void* stream) {
     TokArgs a;
-    a.drop = make_drop(emb_dropout_p, seed, 255);
-    a.img = img; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb;
-    a.post_g = post_g; a.post_b = post_b; a.pos_a = pos_a; a.pos_b = pos_b; a.mask_token = mask_token;
-    a.mask = mask; a.out = out; a.B = B; a.S = S; a.N = N; a.T = S * N; a.P = P; a.pos_split = pos_split;
+    fill_tok(a, img, pre_g, pre_b, w_emb, b_emb, post_g, post_b, pos_a, pos_b, mask_token, mask, out, B, S, N, P, pos_split,
+             make_drop(emb_dropout_p, seed, 255));
     return fail(launch_tokenize_fwd(a, (hipStream_t)stream), "msst_tokenize_fwd");
 }
 
@@ -312,11 +362,9 @@ int msst_tokenize_scene_fwd(const float* scene, const float* pre_g, const float*
     if (wps > 0x7fffffffL || win0 + nwin > (long)Bs * wps) return fail(MSST_ERR_BADARG, "msst_tokenize_scene_fwd (windows out of range)");
     if (window > 8) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_scene_fwd (more than 64 pixels per window)");
     TokArgs a;
-    a.drop = make_drop(0.f, 0, 255);
-    a.img = scene; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb;
-    a.post_g = post_g; a.post_b = post_b; a.pos_a = pos_a; a.pos_b = pos_b; a.mask_token = nullptr; a.mask = nullptr;
-    a.out = out; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P; a.pos_split = pos_split;
-    a.win0 = win0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nq = nq; a.wps = (int)wps;
+    fill_tok(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, pos_a, pos_b, nullptr, nullptr, out, nwin, S, window * window, P,
+             pos_split, make_drop(0.f, 0, 255));
+    fill_window(a, Hs, Ws, window, stride, nq, wps, win0);
     return fail(launch_tokenize_scene_fwd(a, (hipStream_t)stream), "msst_tokenize_scene_fwd");
 }
 
@@ -332,11 +380,9 @@ int msst_tokenize_scene_fwd_masked(const float* scene, const float* pre_g, const
     if (wps > 0x7fffffffL || win0 + nwin > (long)Bs * wps) return fail(MSST_ERR_BADARG, "msst_tokenize_scene_fwd_masked (windows out of range)");
     if (window > 8) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_scene_fwd_masked (more than 64 pixels per window)");
     TokArgs a;
-    a.drop = make_drop(0.f, 0, 255);
-    a.img = scene; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb;
-    a.post_g = post_g; a.post_b = post_b; a.pos_a = pos_a; a.pos_b = pos_b; a.mask_token = mask_token; a.mask = scene_mask;
-    a.out = out; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P; a.pos_split = pos_split;
-    a.win0 = win0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nq = nq; a.wps = (int)wps;
+    fill_tok(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, pos_a, pos_b, mask_token, scene_mask, out, nwin, S, window * window,
+             P, pos_split, make_drop(0.f, 0, 255));
+    fill_window(a, Hs, Ws, window, stride, nq, wps, win0);
     return fail(launch_tokenize_scene_fwd_masked(a, (hipStream_t)stream), "msst_tokenize_scene_fwd_masked");
 }
 
@@ -364,11 +410,9 @@ int msst_tokenize_scene_fwd_train(const float* scene, const float* pre_g, const 
     if (int rc = scene_train_args(pointers, Bs, Hs, Ws, window, stride, win0, nwin, 0, S, P, pos_split, &nq, &wps))
         return fail(rc, "msst_tokenize_scene_fwd_train");
     TokArgs a;
-    a.drop = make_drop(emb_dropout_p, seed, 255);
-    a.img = scene; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb;
-    a.post_g = post_g; a.post_b = post_b; a.pos_a = pos_a; a.pos_b = pos_b; a.mask_token = nullptr; a.mask = nullptr;
-    a.out = out; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P; a.pos_split = pos_split;
-    a.win0 = win0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nq = nq; a.wps = (int)wps;
+    fill_tok(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, pos_a, pos_b, nullptr, nullptr, out, nwin, S, window * window, P,
+             pos_split, make_drop(emb_dropout_p, seed, 255));
+    fill_window(a, Hs, Ws, window, stride, nq, wps, win0);
     return fail(launch_tokenize_scene_fwd(a, (hipStream_t)stream), "msst_tokenize_scene_fwd_train");
 }
 
@@ -388,11 +432,9 @@ int msst_tokenize_at_fwd(const float* scene, const int32_t* origins, const float
     if (int rc = at_args(pointers, Bs, Hs, Ws, window, nwin, 0, S, P, pos_split)) return fail(rc, "msst_tokenize_at_fwd");
     if ((P != 10 || window != 8) && nwin > 65535) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_at_fwd (more than 65535 windows)");
     TokArgs a;
-    a.drop = make_drop(emb_dropout_p, seed, 255);
-    a.img = scene; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb;
-    a.post_g = post_g; a.post_b = post_b; a.pos_a = pos_a; a.pos_b = pos_b; a.mask_token = nullptr; a.mask = nullptr;
-    a.out = out; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P; a.pos_split = pos_split;
-    a.win0 = 0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = window; a.nq = 1; a.wps = 1;
+    fill_tok(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, pos_a, pos_b, nullptr, nullptr, out, nwin, S, window * window, P,
+             pos_split, make_drop(emb_dropout_p, seed, 255));
+    fill_window(a, Hs, Ws, window, window, 1, 1, 0);
     a.origins = origins;
     return fail(launch_tokenize_at_fwd(a, (hipStream_t)stream), "msst_tokenize_at_fwd");
 }
@@ -406,19 +448,10 @@ int msst_scene_assemble(const float* win_logits, long win0, int nwin, float* log
     const long wps = (long)nr * nq;
     if (win0 + nwin > (long)Bs * wps) return fail(MSST_ERR_BADARG, "msst_scene_assemble (windows out of range)");
     SceneArgs a;
-    a.win_logits = win_logits; a.logits = logits; a.classes = classes; a.win0 = win0; a.nwin = nwin;
-    a.Bs = Bs; a.NC = n_classes; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nr = nr; a.nq = nq;
+    fill_grid(a, win0, nwin, Bs, Hs, Ws, window, stride, nr, nq);
+    a.win_logits = win_logits; a.logits = logits; a.classes = classes; a.NC = n_classes;
     hipStream_t st = (hipStream_t)stream;
-    int rc = 0;
-    if (nwin > 0) {
-        // the flattened (scene, pixel row) rows the windows of this call reach: first window's top row .. last window's bottom row
-        const long g0 = win0, g1 = win0 + nwin - 1;
-        const long s0 = g0 / wps, s1 = g1 / wps;
-        const long r0 = (g0 - s0 * wps) / nq, r1 = (g1 - s1 * wps) / nq;
-        a.row0 = s0 * Hs + r0 * stride;
-        const long rows = s1 * Hs + r1 * stride + window - a.row0;
-        rc = launch_scene_accumulate(a, rows * Ws, st);
-    }
+    int rc = launch_scene_fold(a, win_logits, logits, n_classes, 16, scene_call_rows(a, wps), st);
     if (!rc && finalize) rc = launch_scene_finalize(a, st);
     return fail(rc, "msst_scene_assemble");
 }
@@ -439,20 +472,11 @@ int msst_scene_recon_assemble(const float* win_recon, long win0, int nwin, const
     // both launches' grids fit (so nothing is refused after the first one is enqueued)
     if (((long)Bs * Hs * Ws + 255) / 256 > 0x7fffffffL || (long)Bs * S * P > 0x7fffffffL) return fail(MSST_ERR_UNSUPPORTED, "msst_scene_recon_assemble (scene batch too large)");
     SceneReconArgs a;
+    fill_grid(a, win0, nwin, Bs, Hs, Ws, window, stride, nr, nq);
     a.win_recon = win_recon; a.scene = scene; a.scene_mask = scene_mask; a.cube = cube; a.band_err = band_err; a.band_cnt = band_cnt;
-    a.cover = cover; a.win0 = win0; a.row0 = 0; a.nwin = nwin; a.Bs = Bs; a.S = S; a.P = P; a.Hs = Hs; a.Ws = Ws; a.win = window;
-    a.stride = stride; a.nr = nr; a.nq = nq; a.blend = blend != 0;
+    a.cover = cover; a.S = S; a.P = P; a.blend = blend != 0;
     hipStream_t st = (hipStream_t)stream;
-    int rc = 0;
-    if (nwin > 0) {
-        // the flattened (scene, pixel row) rows the windows of this call reach, as in msst_scene_assemble
-        const long g0 = win0, g1 = win0 + nwin - 1;
-        const long s0 = g0 / wps, s1 = g1 / wps;
-        const long r0 = (g0 - s0 * wps) / nq, r1 = (g1 - s1 * wps) / nq;
-        a.row0 = s0 * Hs + r0 * stride;
-        const long rows = s1 * Hs + r1 * stride + window - a.row0;
-        rc = launch_scene_recon_accumulate(a, rows * Ws, st);
-    }
+    int rc = launch_scene_fold(a, win_recon, cube, S * P, P, scene_call_rows(a, wps), st);   // a spectral block's P bands per grid row
     if (!rc && finalize) rc = launch_scene_recon_finalize(a, st);
     return fail(rc, "msst_scene_recon_assemble");
 }
@@ -493,19 +517,10 @@ int msst_scene_embed_assemble(const float* win_feat, long win0, int nwin, float*
     // both launches' grids fit (so nothing is refused after the first one is enqueued)
     if (((long)Bs * Hs * Ws + 255) / 256 > 0x7fffffffL) return fail(MSST_ERR_UNSUPPORTED, "msst_scene_embed_assemble (scene batch too large)");
     SceneEmbedArgs a;
-    a.win_feat = win_feat; a.feat = feat; a.cover = cover; a.win0 = win0; a.row0 = 0; a.nwin = nwin; a.Bs = Bs; a.D = D; a.Hs = Hs;
-    a.Ws = Ws; a.win = window; a.stride = stride; a.nr = nr; a.nq = nq; a.l2norm = l2norm != 0;
+    fill_grid(a, win0, nwin, Bs, Hs, Ws, window, stride, nr, nq);
+    a.win_feat = win_feat; a.feat = feat; a.cover = cover; a.D = D; a.l2norm = l2norm != 0;
     hipStream_t st = (hipStream_t)stream;
-    int rc = 0;
-    if (nwin > 0) {
-        // the flattened (scene, pixel row) rows the windows of this call reach, as in msst_scene_assemble
-        const long g0 = win0, g1 = win0 + nwin - 1;
-        const long s0 = g0 / wps, s1 = g1 / wps;
-        const long r0 = (g0 - s0 * wps) / nq, r1 = (g1 - s1 * wps) / nq;
-        a.row0 = s0 * Hs + r0 * stride;
-        const long rows = s1 * Hs + r1 * stride + window - a.row0;
-        rc = launch_scene_embed_accumulate(a, rows * Ws, st);
-    }
+    int rc = launch_scene_fold(a, win_feat, feat, D, 16, scene_call_rows(a, wps), st);
     if (!rc && finalize) rc = launch_scene_embed_finalize(a, st);
     return fail(rc, "msst_scene_embed_assemble");
 }
@@ -933,9 +948,7 @@ int msst_tokenize_bwd(const float* img, const float* pre_g, const float* pre_b, 
     if (nchunk < 1) return fail(MSST_ERR_BADARG, "msst_tokenize_bwd");
     hipStream_t st = (hipStream_t)stream;
     TokBwdArgs a;
-    a.drop = make_drop(emb_dropout_p, seed, 255);
-    a.img = img; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb; a.post_g = post_g;
-    a.post_b = post_b; a.mask = mask; a.dx0 = dx0; a.slab = slab; a.B = B; a.S = S; a.N = N; a.T = S * N; a.P = P;
+    fill_tok_bwd(a, img, pre_g, pre_b, w_emb, b_emb, post_g, post_b, mask, dx0, slab, B, S, N, P, make_drop(emb_dropout_p, seed, 255));
     int rc = launch_tokenize_bwd(a, nchunk, st);
     if (rc) return fail(rc, "msst_tokenize_bwd");
     return tokenize_bwd_reduce(slab, nchunk, dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, dmask_token,
@@ -956,10 +969,9 @@ int msst_tokenize_scene_bwd(const float* scene, const float* pre_g, const float*
     if (nchunk < 1) return fail(MSST_ERR_BADARG, "msst_tokenize_scene_bwd");
     hipStream_t st = (hipStream_t)stream;
     TokSceneBwdArgs a;
-    a.drop = make_drop(emb_dropout_p, seed, 255);
-    a.img = scene; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb; a.post_g = post_g;
-    a.post_b = post_b; a.mask = nullptr; a.dx0 = dx0; a.slab = slab; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P;
-    a.win0 = win0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nq = nq; a.wps = (int)wps;
+    fill_tok_bwd(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, nullptr, dx0, slab, nwin, S, window * window, P,
+                 make_drop(emb_dropout_p, seed, 255));
+    fill_window(a, Hs, Ws, window, stride, nq, wps, win0);
     if (int rc = launch_tokenize_scene_bwd(a, nchunk, st)) return fail(rc, "msst_tokenize_scene_bwd");
     return tokenize_bwd_reduce(slab, nchunk, dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, nullptr,
                                S, a.N, P, st);
@@ -976,10 +988,9 @@ int msst_tokenize_at_bwd(const float* scene, const int32_t* origins, const float
     if (nchunk < 1) return fail(MSST_ERR_BADARG, "msst_tokenize_at_bwd");
     hipStream_t st = (hipStream_t)stream;
     TokAtBwdArgs a;
-    a.drop = make_drop(emb_dropout_p, seed, 255);
-    a.img = scene; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb; a.post_g = post_g;
-    a.post_b = post_b; a.mask = nullptr; a.dx0 = dx0; a.slab = slab; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P;
-    a.win0 = 0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = window; a.nq = 1; a.wps = 1;
+    fill_tok_bwd(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, nullptr, dx0, slab, nwin, S, window * window, P,
+                 make_drop(emb_dropout_p, seed, 255));
+    fill_window(a, Hs, Ws, window, window, 1, 1, 0);
     a.origins = origins;
     if (int rc = launch_tokenize_at_bwd(a, nchunk, st)) return fail(rc, "msst_tokenize_at_bwd");
     return tokenize_bwd_reduce(slab, nchunk, dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, nullptr,
@@ -995,10 +1006,9 @@ int msst_tokenize_bwd_input(const float* img, const float* pre_g, const float* p
     if (!img || !pre_g || !pre_b || !w_emb || !b_emb || !post_g || !post_b || !dx0 || !dimg)
         return fail(MSST_ERR_BADARG, "msst_tokenize_bwd_input");
     TokInArgs a;
-    a.drop = make_drop(emb_dropout_p, seed, 255);
-    a.img = img; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb; a.post_g = post_g; a.post_b = post_b;
-    a.mask = mask; a.dx0 = dx0; a.dtarget = dtarget; a.dimg = dimg; a.B = B; a.S = S; a.N = N; a.T = S * N; a.P = P;
-    a.win0 = 0; a.Hs = a.Ws = a.win = a.stride = a.nq = a.wps = 0;
+    fill_tok_in(a, img, pre_g, pre_b, w_emb, b_emb, post_g, post_b, mask, dx0, dtarget, dimg, B, S, N, P,
+                make_drop(emb_dropout_p, seed, 255));
+    fill_window(a, 0, 0, 0, 0, 0, 0, 0);   // a batch of cubes: no window grid
     return fail(launch_tokenize_bwd_input(a, (hipStream_t)stream), "msst_tokenize_bwd_input");
 }
 
@@ -1030,10 +1040,9 @@ int msst_tokenize_scene_bwd_input(const float* scene, const float* pre_g, const 
             return fail(rc, "msst_tokenize_scene_bwd_input(border)");
     }
     TokInArgs a;
-    a.drop = make_drop(emb_dropout_p, seed, 255);
-    a.img = scene; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb; a.post_g = post_g; a.post_b = post_b;
-    a.mask = nullptr; a.dx0 = dx0; a.dtarget = nullptr; a.dimg = dscene; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P;
-    a.win0 = win0; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nq = nq; a.wps = (int)wps;
+    fill_tok_in(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, nullptr, dx0, nullptr, dscene, nwin, S, window * window, P,
+                make_drop(emb_dropout_p, seed, 255));
+    fill_window(a, Hs, Ws, window, stride, nq, wps, win0);
     return fail(launch_tokenize_scene_bwd_input(a, st), "msst_tokenize_scene_bwd_input");
 }
 
@@ -1176,9 +1185,9 @@ int msst_scene_centre_assemble(const float* win_logits, long win0, int nwin, flo
         return fail(MSST_ERR_BADARG, "msst_scene_centre_assemble");
     const long wps = (long)nr * nq;
     if (win0 + nwin > (long)Bs * wps) return fail(MSST_ERR_BADARG, "msst_scene_centre_assemble (windows out of range)");
-    SceneArgs a = {};
-    a.win_logits = win_logits; a.logits = logits; a.classes = classes; a.win0 = win0; a.nwin = nwin;
-    a.Bs = Bs; a.NC = n_classes; a.Hs = Hs; a.Ws = Ws; a.win = window; a.stride = stride; a.nr = nr; a.nq = nq;
+    SceneArgs a;
+    fill_grid(a, win0, nwin, Bs, Hs, Ws, window, stride, nr, nq);
+    a.win_logits = win_logits; a.logits = logits; a.classes = classes; a.NC = n_classes;
     hipStream_t st = (hipStream_t)stream;
     int rc = launch_scene_centre_scatter(a, st);
     if (!rc && finalize) rc = launch_scene_centre_fill(a, st);

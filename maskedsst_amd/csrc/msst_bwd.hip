@@ -1896,36 +1896,23 @@ int launch_block_bwd_ln1(const Ln1BwdArgs& a, int grid, int prec, hipStream_t st
     return (int)hipGetLastError();
 }
 
-int launch_tokenize_bwd(const TokBwdArgs& a, int nchunk, hipStream_t st) {
+// The one kernel selection of the tokenizer backward (that of launch_tokenize_fwd_src, msst_fwd.hip), whatever the source.  Args:
+// TokBwdArgs, a batch of cubes; TokSceneBwdArgs / TokAtBwdArgs, the SCENE instances (a.B = windows of the call).  Not uniform, and
+// kept so: a batch of cubes is launched as given, the window sources refuse an empty call and an nchunk no grid holds.
+template <class Args>
+static int launch_tokenize_bwd_src(const Args& a, int nchunk, hipStream_t st) {
+    constexpr bool SCENE = !std::is_same<Args, TokBwdArgs>::value;
     if (a.P > 16 || a.N > 64) return MSST_ERR_UNSUPPORTED;
+    if (SCENE && (a.B < 1 || nchunk < 1 || nchunk > 65535)) return MSST_ERR_BADARG;
     ProfScope ps(K_TOK_BWD, st);
-    if (a.P == 10 && a.N == 64) hipLaunchKernelGGL((tokenize_bwd_mfma_kernel<false, TokBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
-    else if (a.P == 10) hipLaunchKernelGGL((tokenize_bwd_kernel<10, false, TokBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((tokenize_bwd_kernel<0, false, TokBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
+    if (a.P == 10 && a.N == 64) hipLaunchKernelGGL((tokenize_bwd_mfma_kernel<SCENE, Args>), dim3(a.S, nchunk), dim3(256), 0, st, a);
+    else if (a.P == 10) hipLaunchKernelGGL((tokenize_bwd_kernel<10, SCENE, Args>), dim3(a.S, nchunk), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((tokenize_bwd_kernel<0, SCENE, Args>), dim3(a.S, nchunk), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
-
-// the same kernel selection as launch_tokenize_bwd, SCENE instances (a.B = windows of the call, at least one)
-int launch_tokenize_scene_bwd(const TokSceneBwdArgs& a, int nchunk, hipStream_t st) {
-    if (a.P > 16 || a.N > 64) return MSST_ERR_UNSUPPORTED;
-    if (a.B < 1 || nchunk < 1 || nchunk > 65535) return MSST_ERR_BADARG;
-    ProfScope ps(K_TOK_BWD, st);
-    if (a.P == 10 && a.N == 64) hipLaunchKernelGGL((tokenize_bwd_mfma_kernel<true, TokSceneBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
-    else if (a.P == 10) hipLaunchKernelGGL((tokenize_bwd_kernel<10, true, TokSceneBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((tokenize_bwd_kernel<0, true, TokSceneBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
-    return (int)hipGetLastError();
-}
-
-// ... SCENE instances over TokAtBwdArgs (a.origins: the windows of the call)
-int launch_tokenize_at_bwd(const TokAtBwdArgs& a, int nchunk, hipStream_t st) {
-    if (a.P > 16 || a.N > 64) return MSST_ERR_UNSUPPORTED;
-    if (a.B < 1 || nchunk < 1 || nchunk > 65535) return MSST_ERR_BADARG;
-    ProfScope ps(K_TOK_BWD, st);
-    if (a.P == 10 && a.N == 64) hipLaunchKernelGGL((tokenize_bwd_mfma_kernel<true, TokAtBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
-    else if (a.P == 10) hipLaunchKernelGGL((tokenize_bwd_kernel<10, true, TokAtBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((tokenize_bwd_kernel<0, true, TokAtBwdArgs>), dim3(a.S, nchunk), dim3(256), 0, st, a);
-    return (int)hipGetLastError();
-}
+int launch_tokenize_bwd(const TokBwdArgs& a, int nchunk, hipStream_t st) { return launch_tokenize_bwd_src(a, nchunk, st); }
+int launch_tokenize_scene_bwd(const TokSceneBwdArgs& a, int nchunk, hipStream_t st) { return launch_tokenize_bwd_src(a, nchunk, st); }
+int launch_tokenize_at_bwd(const TokAtBwdArgs& a, int nchunk, hipStream_t st) { return launch_tokenize_bwd_src(a, nchunk, st); }
 
 int launch_pos_split(const float* dpos, int S, int N, int split, float* dpe, float* dce, hipStream_t st) {
     const int n = N * split + S * (96 - split);

@@ -114,15 +114,8 @@ __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
     }
 }
 
-template <int PC>
-__global__ __launch_bounds__(256) void tokenize_fwd_kernel(TokArgs a) { tokenize_fwd_body<PC, TOK_BATCH>(a); }
-template <int PC>
-__global__ __launch_bounds__(256) void tokenize_scene_fwd_kernel(TokArgs a) { tokenize_fwd_body<PC, TOK_SCENE>(a); }
-template <int PC>
-__global__ __launch_bounds__(256) void tokenize_scene_fwd_masked_kernel(TokArgs a) { tokenize_fwd_body<PC, TOK_SCENE_MASKED>(a); }
-template <int PC>
-__global__ __launch_bounds__(256) void tokenize_at_fwd_kernel(TokArgs a) { tokenize_fwd_body<PC, TOK_AT>(a); }
-
+template <int PC, int SRC>
+__global__ __launch_bounds__(256) void tokenize_fwd_kernel(TokArgs a) { tokenize_fwd_body<PC, SRC>(a); }
 
 // ------------------------------------------------------------------------------------------
 // The same tokenizer for the reference's shapes (P = 10 pixels per patch, N = 64 spatial tokens) on the fp32 matrix cores
@@ -243,10 +236,8 @@ __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
     }
 }
 
-__global__ __launch_bounds__(256, 2) void tokenize_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<TOK_BATCH>(a); }
-__global__ __launch_bounds__(256, 2) void tokenize_scene_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<TOK_SCENE>(a); }
-__global__ __launch_bounds__(256, 2) void tokenize_scene_fwd_masked_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<TOK_SCENE_MASKED>(a); }
-__global__ __launch_bounds__(256, 2) void tokenize_at_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<TOK_AT>(a); }
+template <int SRC>
+__global__ __launch_bounds__(256, 2) void tokenize_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<SRC>(a); }
 
 // ==========================================================================================
 // fused transformer block, forward.  Reference vit_spatial_spectral.py:22-29 (PreNorm),
@@ -902,72 +893,32 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* partial, 
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
-int launch_tokenize_fwd(const TokArgs& a, hipStream_t st) {
+// The one kernel selection of the tokenizer forward, whatever the source (SRC, see tokenize_fwd_body): the fp32 matrix-core kernel,
+// persistent over the batch, for the reference's shapes (P = 10, N = 64), else one workgroup row per sample (grid y) with P = 10
+// unrolled or P at run time.  a.B: samples = windows of the call.  Not uniform, and kept so: a batch of cubes (TOK_BATCH) is launched
+// as given -- no early return for B < 1, no refusal of more than 65535 grid rows (the launch itself fails then) -- while the window
+// sources return at once for an empty call and refuse what the grid cannot hold.
+template <int SRC>
+static int launch_tokenize_fwd_src(const TokArgs& a, hipStream_t st) {
     if (a.P > 16 || a.N > 64) return MSST_ERR_UNSUPPORTED;
-    ProfScope ps(K_TOK_FWD, st);
-    if (a.P == 10 && a.N == 64) {   // the reference's shapes: fp32 matrix cores, persistent over the batch
-        int nchunk = 1024 / (a.S > 0 ? a.S : 1);
-        if (nchunk < 1) nchunk = 1;
-        if (nchunk > a.B) nchunk = a.B;
-        hipLaunchKernelGGL(tokenize_fwd_mfma_kernel, dim3(a.S, nchunk), dim3(256), 0, st, a);
-    } else if (a.P == 10) hipLaunchKernelGGL(tokenize_fwd_kernel<10>, dim3(a.S, a.B), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(tokenize_fwd_kernel<0>, dim3(a.S, a.B), dim3(256), 0, st, a);
-    return (int)hipGetLastError();
-}
-
-// the same kernel selection as launch_tokenize_fwd, SCENE instances (a.B = windows of the call)
-int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st) {
-    if (a.P > 16 || a.N > 64) return MSST_ERR_UNSUPPORTED;
-    if (a.B < 1) return 0;
+    if (SRC != TOK_BATCH && a.B < 1) return 0;
     ProfScope ps(K_TOK_FWD, st);
     if (a.P == 10 && a.N == 64) {
         int nchunk = 1024 / (a.S > 0 ? a.S : 1);
         if (nchunk < 1) nchunk = 1;
         if (nchunk > a.B) nchunk = a.B;
-        hipLaunchKernelGGL(tokenize_scene_fwd_mfma_kernel, dim3(a.S, nchunk), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(tokenize_fwd_mfma_kernel<SRC>, dim3(a.S, nchunk), dim3(256), 0, st, a);
     } else {
-        if (a.B > 65535) return MSST_ERR_UNSUPPORTED;   // one workgroup row per window (grid y)
-        if (a.P == 10) hipLaunchKernelGGL(tokenize_scene_fwd_kernel<10>, dim3(a.S, a.B), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(tokenize_scene_fwd_kernel<0>, dim3(a.S, a.B), dim3(256), 0, st, a);
+        if (SRC != TOK_BATCH && a.B > 65535) return MSST_ERR_UNSUPPORTED;   // one workgroup row per window (grid y)
+        if (a.P == 10) hipLaunchKernelGGL((tokenize_fwd_kernel<10, SRC>), dim3(a.S, a.B), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((tokenize_fwd_kernel<0, SRC>), dim3(a.S, a.B), dim3(256), 0, st, a);
     }
     return (int)hipGetLastError();
 }
-
-// ... TOK_AT instances (a.origins: the windows of the call)
-int launch_tokenize_at_fwd(const TokArgs& a, hipStream_t st) {
-    if (a.P > 16 || a.N > 64) return MSST_ERR_UNSUPPORTED;
-    if (a.B < 1) return 0;
-    ProfScope ps(K_TOK_FWD, st);
-    if (a.P == 10 && a.N == 64) {
-        int nchunk = 1024 / (a.S > 0 ? a.S : 1);
-        if (nchunk < 1) nchunk = 1;
-        if (nchunk > a.B) nchunk = a.B;
-        hipLaunchKernelGGL(tokenize_at_fwd_mfma_kernel, dim3(a.S, nchunk), dim3(256), 0, st, a);
-    } else {
-        if (a.B > 65535) return MSST_ERR_UNSUPPORTED;   // one workgroup row per window (grid y)
-        if (a.P == 10) hipLaunchKernelGGL(tokenize_at_fwd_kernel<10>, dim3(a.S, a.B), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(tokenize_at_fwd_kernel<0>, dim3(a.S, a.B), dim3(256), 0, st, a);
-    }
-    return (int)hipGetLastError();
-}
-
-// the same selection once more, TOK_SCENE_MASKED instances (a.mask: the scene mask, a.mask_token set)
-int launch_tokenize_scene_fwd_masked(const TokArgs& a, hipStream_t st) {
-    if (a.P > 16 || a.N > 64) return MSST_ERR_UNSUPPORTED;
-    if (a.B < 1) return 0;
-    ProfScope ps(K_TOK_FWD, st);
-    if (a.P == 10 && a.N == 64) {
-        int nchunk = 1024 / (a.S > 0 ? a.S : 1);
-        if (nchunk < 1) nchunk = 1;
-        if (nchunk > a.B) nchunk = a.B;
-        hipLaunchKernelGGL(tokenize_scene_fwd_masked_mfma_kernel, dim3(a.S, nchunk), dim3(256), 0, st, a);
-    } else {
-        if (a.B > 65535) return MSST_ERR_UNSUPPORTED;   // one workgroup row per window (grid y)
-        if (a.P == 10) hipLaunchKernelGGL(tokenize_scene_fwd_masked_kernel<10>, dim3(a.S, a.B), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(tokenize_scene_fwd_masked_kernel<0>, dim3(a.S, a.B), dim3(256), 0, st, a);
-    }
-    return (int)hipGetLastError();
-}
+int launch_tokenize_fwd(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_BATCH>(a, st); }
+int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_SCENE>(a, st); }
+int launch_tokenize_scene_fwd_masked(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_SCENE_MASKED>(a, st); }
+int launch_tokenize_at_fwd(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_AT>(a, st); }
 
 template <class P>
 static int launch_block_fwd_t(const BlockArgs& a, int grid, hipStream_t st) {
@@ -1096,19 +1047,23 @@ int launch_cls_head_fwd(const ClsArgs& a, hipStream_t st) {
 }
 
 // ==========================================================================================
-// scene assembly: per-window logits [nwin][NC][win * win] (cls_head_fwd_kernel of windows of a scene) -> scene logit map = mean of
-// the logits of every window covering a pixel, class map = argmax.  Replaces the window loop of the reference's
-// inference_example.ipynb (model(window).argmax(1) written into the class map) and of validate_downstream (src/utils.py:497-541).
+// scene fold: per-window planes src [nwin][C][win * win] of windows of a scene -> running per-pixel sums dst [Bs][C][Hs][Ws], the
+// accumulate half of every scene feature: msst_scene_assemble (logits: C = NC, 16 per grid row), msst_scene_recon_assemble
+// (msst_scene_recon.hip; C = S P, the P bands of a spectral block per grid row) and msst_scene_embed_assemble (msst_scene_embed.hip;
+// C = D, 16 per grid row).  Replaces the window loop of the reference's inference_example.ipynb (model(window).argmax(1) written into
+// the class map) and of validate_downstream (src/utils.py:497-541).
 // The windows covering pixel (y, x) are the rectangle of window rows r in [ceil((y - win + 1) / stride), y / stride] and columns
-// likewise, clipped to the grid; each thread owns one pixel and sums them in window order (row, then column): no atomics, a fixed
-// order, so the map is bitwise reproducible and independent of how the windows were split into calls.  (scene_cover: msst_kernels.h,
-// shared with msst_scene_recon.hip.)
+// likewise, clipped to the grid (scene_cover, msst_kernels.h).  grid (256-pixel pieces of the flattened (scene, pixel row) rows the
+// call's windows reach, channel group), one thread per (pixel, group): lanes run along x, so a wave reads runs of consecutive floats
+// of a window row of src (one run per covering window column) and reads / writes consecutive floats of dst.  The channels of the
+// group are independent sums held in 16 registers; each adds its windows in window order (row, then column): no atomics, a fixed
+// order, so the map is bitwise reproducible and independent of how the windows were split into calls.  A pixel whose first covering
+// window is in this call starts from 0 (nothing to zero beforehand), one with no window in this call is not touched.
 // ==========================================================================================
-// adds the windows win0 .. win0 + nwin - 1 into the running sums; pixel p of the launch = flattened row row0 + p / Ws, column p % Ws.
-// A pixel whose first covering window is in this call starts from 0 (no memset); one with no window in this call is not touched.
-__global__ __launch_bounds__(256) void scene_accumulate_kernel(SceneArgs a, long pixels) {
+__global__ __launch_bounds__(256) void scene_fold_kernel(SceneGrid a, const float* src, float* dst, int C, int group, long pixels) {
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p >= pixels) return;
+    const int c0 = blockIdx.y * group, cn = min(group, C - c0);
     const long R = a.row0 + p / a.Ws;
     const int x = (int)(p % a.Ws);
     const long s = R / a.Hs;
@@ -1120,19 +1075,24 @@ __global__ __launch_bounds__(256) void scene_accumulate_kernel(SceneArgs a, long
     if (last < a.win0 || first >= end) return;
     const int N = a.win * a.win;
     const long plane = (long)a.Hs * a.Ws;
-    float* out = a.logits + s * a.NC * plane + (long)y * a.Ws + x;
-    for (int k = 0; k < a.NC; ++k) {
-        float acc = first >= a.win0 ? 0.f : out[k * plane];
-        for (int r = rlo; r <= rhi; ++r) {
-            const long g0 = base + (long)r * a.nq;
-            for (int q = qlo; q <= qhi; ++q) {
-                const long g = g0 + q;
-                if (g < a.win0 || g >= end) continue;
-                acc += a.win_logits[((g - a.win0) * a.NC + k) * N + (y - r * a.stride) * a.win + (x - q * a.stride)];
-            }
+    float* out = dst + (s * C + c0) * plane + (long)y * a.Ws + x;
+    float acc[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc[k] = (k < cn && first < a.win0) ? out[k * plane] : 0.f;
+    for (int r = rlo; r <= rhi; ++r) {
+        const long g0 = base + (long)r * a.nq;
+        for (int q = qlo; q <= qhi; ++q) {
+            const long g = g0 + q;
+            if (g < a.win0 || g >= end) continue;
+            const float* w = src + ((g - a.win0) * C + c0) * N + (y - r * a.stride) * a.win + (x - q * a.stride);
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (k < cn) acc[k] += w[k * N];
         }
-        out[k * plane] = acc;
     }
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (k < cn) out[k * plane] = acc[k];
 }
 
 // sums -> means (sum / windows covering the pixel), argmax over classes (first maximum, NaN counts as the maximum: torch.argmax);
@@ -1161,11 +1121,11 @@ __global__ __launch_bounds__(256) void scene_finalize_kernel(SceneArgs a) {
     a.classes[p] = arg;
 }
 
-int launch_scene_accumulate(const SceneArgs& a, long pixels, hipStream_t st) {
+int launch_scene_fold(const SceneGrid& g, const float* src, float* dst, int C, int group, long pixels, hipStream_t st) {
     if (pixels < 1) return 0;
-    const long grid = (pixels + 255) / 256;
-    if (grid > 0x7fffffffL) return MSST_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(scene_accumulate_kernel, dim3((unsigned)grid), dim3(256), 0, st, a, pixels);
+    const long grid = (pixels + 255) / 256, ny = ((long)C + group - 1) / group;
+    if (group > 16 || grid > 0x7fffffffL || ny > 65535) return MSST_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(scene_fold_kernel, dim3((unsigned)grid, (unsigned)ny), dim3(256), 0, st, g, src, dst, C, group, pixels);
     return (int)hipGetLastError();
 }
 

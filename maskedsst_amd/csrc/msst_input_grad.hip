@@ -201,8 +201,12 @@ __global__ __launch_bounds__(256) void scene_border_zero_kernel(float* dscene, l
     }
 }
 
+// one launcher for both sources (SCENE: windows of a scene, where an empty call is no launch); KC = ceil(P / 4)
 template <bool SCENE>
-static void launch_input_kc(const TokInArgs& a, hipStream_t st) {
+static int launch_tokenize_bwd_input_src(const TokInArgs& a, hipStream_t st) {
+    if (a.P > 16 || a.N > 64 || (long)a.B * a.S > 0x7fffffffL) return MSST_ERR_UNSUPPORTED;
+    if (SCENE && a.B < 1) return 0;
+    ProfScope ps(K_TOK_BWD_INPUT, st);
     const dim3 grid((unsigned)((long)a.B * a.S));
     switch ((a.P + 3) / 4) {
     case 1: hipLaunchKernelGGL((tokenize_bwd_input_kernel<1, SCENE>), grid, dim3(256), 0, st, a); break;
@@ -210,22 +214,10 @@ static void launch_input_kc(const TokInArgs& a, hipStream_t st) {
     case 3: hipLaunchKernelGGL((tokenize_bwd_input_kernel<3, SCENE>), grid, dim3(256), 0, st, a); break;
     default: hipLaunchKernelGGL((tokenize_bwd_input_kernel<4, SCENE>), grid, dim3(256), 0, st, a); break;
     }
-}
-
-int launch_tokenize_bwd_input(const TokInArgs& a, hipStream_t st) {
-    if (a.P > 16 || a.N > 64 || (long)a.B * a.S > 0x7fffffffL) return MSST_ERR_UNSUPPORTED;
-    ProfScope ps(K_TOK_BWD_INPUT, st);
-    launch_input_kc<false>(a, st);
     return (int)hipGetLastError();
 }
-
-int launch_tokenize_scene_bwd_input(const TokInArgs& a, hipStream_t st) {
-    if (a.P > 16 || a.N > 64 || (long)a.B * a.S > 0x7fffffffL) return MSST_ERR_UNSUPPORTED;
-    if (a.B < 1) return 0;
-    ProfScope ps(K_TOK_BWD_INPUT, st);
-    launch_input_kc<true>(a, st);
-    return (int)hipGetLastError();
-}
+int launch_tokenize_bwd_input(const TokInArgs& a, hipStream_t st) { return launch_tokenize_bwd_input_src<false>(a, st); }
+int launch_tokenize_scene_bwd_input(const TokInArgs& a, hipStream_t st) { return launch_tokenize_bwd_input_src<true>(a, st); }
 
 int launch_scene_border_zero(float* dscene, long rows, int Hs, int Ws, int rows_in, int cols_in, hipStream_t st) {
     if (rows_in >= Hs && cols_in >= Ws) return 0;

@@ -126,15 +126,25 @@ __device__ __forceinline__ bool scene_cover(const Args& a, int y, int x, int& rl
     return rlo <= rhi && qlo <= qhi;
 }
 
-// scene assembly (msst_scene_assemble): per-window logits -> running per-pixel sums (accumulate), then mean / argmax (finalize)
-struct SceneArgs {
+// the window grid of a batch of scenes and the windows of one call: windows win0 .. win0 + nwin - 1, row-major over (scene, window
+// row, window column), nr x nq per scene, origin (r * stride, q * stride), win x win pixels.  The argument blocks of the three scene
+// folds (SceneArgs, SceneReconArgs, SceneEmbedArgs) inherit it; scene_cover reads it.
+struct SceneGrid {
+    long win0, row0;           // row0: first flattened (scene, pixel row) row the windows of the call touch (scene_call_rows, msst_api.hip)
+    int nwin, Bs, Hs, Ws, win, stride, nr, nq;
+};
+// The one fold of per-window planes into per-scene planes (scene_fold_kernel, msst_fwd.hip): src [nwin][C][win * win] of the call's windows is
+// added into the running sums dst [Bs][C][Hs][Ws]; a launch's `pixels` start at flattened row g.row0; `group` (at most 16) consecutive
+// channels per grid row y, C <= 65535 * group.  Every scene feature accumulates through it, so a split into calls leaves every bit.
+int launch_scene_fold(const SceneGrid& g, const float* src, float* dst, int C, int group, long pixels, hipStream_t st);
+
+// scene assembly (msst_scene_assemble): per-window logits -> running per-pixel sums (launch_scene_fold), then mean / argmax (finalize)
+struct SceneArgs : SceneGrid {
     const float* win_logits;   // [nwin][NC][win * win] of windows win0 .. win0 + nwin - 1
     float* logits;             // [Bs][NC][Hs][Ws]: the running sums, then the means
     int64_t* classes;          // [Bs][Hs][Ws]
-    long win0, row0;           // row0: first flattened (scene, pixel row) row the windows of the call touch (accumulate)
-    int nwin, Bs, NC, Hs, Ws, win, stride, nr, nq;
+    int NC;
 };
-int launch_scene_accumulate(const SceneArgs& a, long pixels, hipStream_t st);
 int launch_scene_finalize(const SceneArgs& a, hipStream_t st);
 
 struct HeadArgs {
@@ -428,9 +438,9 @@ struct ReconArgs {
 };
 int launch_recon_fwd(const ReconArgs& a, hipStream_t st);
 
-// msst_scene_recon.hip (msst_scene_recon_assemble): per-window pixel predictions -> running per-pixel sums (accumulate), then the mean, the
-// blend with the scene, the per-band masked |pred - scene| sums and the cover map (finalize)
-struct SceneReconArgs {
+// msst_scene_recon.hip (msst_scene_recon_assemble): per-window pixel predictions -> running per-pixel sums (launch_scene_fold), then the
+// mean, the blend with the scene, the per-band masked |pred - scene| sums and the cover map (finalize)
+struct SceneReconArgs : SceneGrid {
     const float* win_recon;      // [nwin][S*P][win * win] of windows win0 .. win0 + nwin - 1 (msst_recon_fwd, blend = 0)
     const float* scene;          // [Bs][S*P][Hs][Ws]
     const uint8_t* scene_mask;   // [Bs][S][Hs][Ws] (non-zero = masked)
@@ -438,24 +448,20 @@ struct SceneReconArgs {
     double* band_err;            // optional [Bs][S*P] (with band_cnt)
     int32_t* band_cnt;           // optional [Bs][S*P]
     int32_t* cover;              // [Bs][Hs][Ws]: windows covering the pixel
-    long win0, row0;             // row0: first flattened (scene, pixel row) row the windows of the call touch (accumulate)
-    int nwin, Bs, S, P, Hs, Ws, win, stride, nr, nq, blend;
+    int S, P, blend;
 };
-int launch_scene_recon_accumulate(const SceneReconArgs& a, long pixels, hipStream_t st);
 int launch_scene_recon_finalize(const SceneReconArgs& a, hipStream_t st);
 
 // msst_scene_embed.hip (msst_pool_spectral_fwd, msst_scene_embed_assemble): encoder output -> per-window features (mean over the
-// spectral tokens of a position) -> running per-pixel sums (accumulate), then the mean, the optional L2 normalisation, NaN where no
-// window covers a pixel and the cover map (finalize)
-struct SceneEmbedArgs {
+// spectral tokens of a position) -> running per-pixel sums (launch_scene_fold), then the mean, the optional L2 normalisation, NaN where
+// no window covers a pixel and the cover map (finalize)
+struct SceneEmbedArgs : SceneGrid {
     const float* win_feat;       // [nwin][D][win * win] of windows win0 .. win0 + nwin - 1 (msst_pool_spectral_fwd)
     float* feat;                 // [Bs][D][Hs][Ws]: the running sums, then the result
     int32_t* cover;              // [Bs][Hs][Ws]: windows covering the pixel
-    long win0, row0;             // row0: first flattened (scene, pixel row) row the windows of the call touch (accumulate)
-    int nwin, Bs, D, Hs, Ws, win, stride, nr, nq, l2norm;
+    int D, l2norm;
 };
 int launch_pool_spectral(const float* y, float* out, int B, int S, int N, hipStream_t st);   // y [B][S N][96] -> out [B][96][N]
-int launch_scene_embed_accumulate(const SceneEmbedArgs& a, long pixels, hipStream_t st);
 int launch_scene_embed_finalize(const SceneEmbedArgs& a, hipStream_t st);
 
 // msst_attn_maps.hip (msst_attn_maps): the fp32 attention probabilities of one block from its input, per sequence or averaged over a

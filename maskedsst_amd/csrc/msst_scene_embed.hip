@@ -13,11 +13,9 @@
 //             bank (n + 4 d4 + j) % 32: 4 d4 % 32 takes 8 values over the 24 pieces of a row, three pieces per value, whatever the
 //             pitch; so the lanes write component (j + d4 / 8) % 4 in step j, which gives the three pieces of a value three
 //             different banks: no conflict inside a row, two lanes on a bank at most where a half-wave spans two rows.
-// scene_embed_accumulate / scene_embed_finalize   scene_recon_accumulate / _finalize (msst_scene_recon.hip) with D feature planes in
-//             the place of the S P bands: one thread per (pixel, group of 16 planes), lanes along x, each plane's sum in a register,
-//             windows added in window order (row, then column), a pixel starting from 0 in the call that holds its first window
-//             (no atomics, nothing to zero, any split into calls gives the same bits).  Finalize: one thread per pixel, lanes along
-//             x; sum / k written back plane by plane while the squares are added in the order d = 0 .. D - 1, then (l2norm) a
+// scene_embed_finalize   the running sums are the shared fold's (scene_fold_kernel, msst_fwd.hip; launch_scene_fold with C = D, 16
+//             planes per grid row: any split into calls gives the same bits).  Finalize: one thread per pixel, lanes along x;
+//             sum / k written back plane by plane while the squares are added in the order d = 0 .. D - 1, then (l2norm) a
 //             second pass over the planes it has just written divides by max(sqrt(sum of squares), 1e-12) -- F.normalize.
 // Memory-bound VALU work: no MFMA, no inline assembly.
 #include "msst_dev.h"
@@ -59,41 +57,6 @@ __global__ __launch_bounds__(256) void pool_spectral_kernel(const float* __restr
     }
 }
 
-__global__ __launch_bounds__(256) void scene_embed_accumulate_kernel(SceneEmbedArgs a, long pixels) {
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= pixels) return;
-    const int d0 = blockIdx.y * 16, dn = min(16, a.D - d0);
-    const long R = a.row0 + p / a.Ws;
-    const int x = (int)(p % a.Ws);
-    const long s = R / a.Hs;
-    const int y = (int)(R - s * a.Hs);
-    int rlo, rhi, qlo, qhi;
-    if (!scene_cover(a, y, x, rlo, rhi, qlo, qhi)) return;
-    const long wps = (long)a.nr * a.nq, base = s * wps;
-    const long first = base + (long)rlo * a.nq + qlo, last = base + (long)rhi * a.nq + qhi, end = a.win0 + a.nwin;
-    if (last < a.win0 || first >= end) return;
-    const int N = a.win * a.win;
-    const long plane = (long)a.Hs * a.Ws;
-    float* out = a.feat + (s * a.D + d0) * plane + (long)y * a.Ws + x;
-    float acc[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) acc[k] = (k < dn && first < a.win0) ? out[k * plane] : 0.f;
-    for (int r = rlo; r <= rhi; ++r) {
-        const long g0 = base + (long)r * a.nq;
-        for (int q = qlo; q <= qhi; ++q) {
-            const long g = g0 + q;
-            if (g < a.win0 || g >= end) continue;
-            const float* src = a.win_feat + ((g - a.win0) * a.D + d0) * N + (y - r * a.stride) * a.win + (x - q * a.stride);
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                if (k < dn) acc[k] += src[k * N];
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < dn) out[k * plane] = acc[k];
-}
-
 __global__ __launch_bounds__(256) void scene_embed_finalize_kernel(SceneEmbedArgs a) {
     const long plane = (long)a.Hs * a.Ws;
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
@@ -126,14 +89,6 @@ __global__ __launch_bounds__(256) void scene_embed_finalize_kernel(SceneEmbedArg
 int launch_pool_spectral(const float* y, float* out, int B, int S, int N, hipStream_t st) {
     if (N > 64 || S > 64) return MSST_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(pool_spectral_kernel, dim3((unsigned)B), dim3(256), 0, st, y, out, S, N);
-    return (int)hipGetLastError();
-}
-
-int launch_scene_embed_accumulate(const SceneEmbedArgs& a, long pixels, hipStream_t st) {
-    if (pixels < 1) return 0;
-    const long grid = (pixels + 255) / 256;
-    if (grid > 0x7fffffffL || a.D > 16 * 65535) return MSST_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(scene_embed_accumulate_kernel, dim3((unsigned)grid, (a.D + 15) / 16), dim3(256), 0, st, a, pixels);
     return (int)hipGetLastError();
 }
 

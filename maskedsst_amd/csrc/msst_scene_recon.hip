@@ -1,14 +1,10 @@
-// Whole-scene SimMIM reconstruction, the assembling end (msst_scene_recon_assemble): the counterpart of scene_accumulate / scene_finalize
-// (msst_fwd.hip) for pixels.  Per-window predictions win_recon [nwin][S P][win * win] (msst_recon_fwd, blend = 0, of windows of a scene)
-// -> the scene cube [Bs][S P][Hs][Ws] = mean of the predictions of every window covering a pixel, blended with the scene where the
-// token is not masked, with the per-band |prediction - scene| sums over the masked covered pixels and the cover map.
+// Whole-scene SimMIM reconstruction, the assembling end (msst_scene_recon_assemble).  Per-window predictions win_recon
+// [nwin][S P][win * win] (msst_recon_fwd, blend = 0, of windows of a scene) -> the scene cube [Bs][S P][Hs][Ws] = mean of the
+// predictions of every window covering a pixel, blended with the scene where the token is not masked, with the per-band
+// |prediction - scene| sums over the masked covered pixels and the cover map.
 //
-// scene_recon_accumulate   grid (256-pixel pieces of the flattened (scene, pixel row) rows the call's windows reach, spectral block c),
-//             one thread per (pixel, block): lanes run along x, so a wave reads runs of consecutive floats of a window row of
-//             win_recon (one run per covering window column) and reads / writes consecutive floats of `cube`.  The P bands of the
-//             block are P independent sums held in registers; each adds its windows in window order (row, then column): no atomics, a
-//             fixed order, whatever the split into calls.  A pixel whose first covering window is in this call starts from 0 (nothing to
-//             zero beforehand), one with no window in this call is not touched.
+// The running sums are the shared fold's (scene_fold_kernel, msst_fwd.hip; launch_scene_fold with C = S P and the P bands of a
+// spectral block per grid row); this file holds what is particular to pixels:
 // scene_recon_finalize     one workgroup per (scene, band) plane, 256 threads, pixel i of the plane <-> thread i % 256 (lanes along x).
 //             sum / k (k = windows covering the pixel), blend, NaN where nothing covers the pixel and nothing is blended.  The
 //             plane's |prediction - scene| terms (formed in double: exact) are added in one fixed order: each thread its pixels
@@ -21,41 +17,6 @@
 namespace msst {
 
 namespace {
-
-__global__ __launch_bounds__(256) void scene_recon_accumulate_kernel(SceneReconArgs a, long pixels) {
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= pixels) return;
-    const int c = blockIdx.y, P = a.P;
-    const long R = a.row0 + p / a.Ws;
-    const int x = (int)(p % a.Ws);
-    const long s = R / a.Hs;
-    const int y = (int)(R - s * a.Hs);
-    int rlo, rhi, qlo, qhi;
-    if (!scene_cover(a, y, x, rlo, rhi, qlo, qhi)) return;
-    const long wps = (long)a.nr * a.nq, base = s * wps;
-    const long first = base + (long)rlo * a.nq + qlo, last = base + (long)rhi * a.nq + qhi, end = a.win0 + a.nwin;
-    if (last < a.win0 || first >= end) return;
-    const int N = a.win * a.win;
-    const long plane = (long)a.Hs * a.Ws;
-    float* out = a.cube + ((s * a.S + c) * P) * plane + (long)y * a.Ws + x;
-    float acc[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) acc[k] = (k < P && first < a.win0) ? out[k * plane] : 0.f;
-    for (int r = rlo; r <= rhi; ++r) {
-        const long g0 = base + (long)r * a.nq;
-        for (int q = qlo; q <= qhi; ++q) {
-            const long g = g0 + q;
-            if (g < a.win0 || g >= end) continue;
-            const float* src = a.win_recon + (((g - a.win0) * a.S + c) * P) * N + (y - r * a.stride) * a.win + (x - q * a.stride);
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-                if (k < P) acc[k] += src[k * N];
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < P) out[k * plane] = acc[k];
-}
 
 __global__ __launch_bounds__(256) void scene_recon_finalize_kernel(SceneReconArgs a) {
     __shared__ double werr[4];
@@ -102,15 +63,6 @@ __global__ __launch_bounds__(256) void scene_recon_finalize_kernel(SceneReconArg
 }
 
 }  // namespace
-
-int launch_scene_recon_accumulate(const SceneReconArgs& a, long pixels, hipStream_t st) {
-    if (pixels < 1) return 0;
-    if (a.P > 16 || a.S > 65535) return MSST_ERR_UNSUPPORTED;
-    const long grid = (pixels + 255) / 256;
-    if (grid > 0x7fffffffL) return MSST_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(scene_recon_accumulate_kernel, dim3((unsigned)grid, a.S), dim3(256), 0, st, a, pixels);
-    return (int)hipGetLastError();
-}
 
 int launch_scene_recon_finalize(const SceneReconArgs& a, hipStream_t st) {
     const long grid = (long)a.Bs * a.S * a.P;

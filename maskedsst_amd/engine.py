@@ -363,6 +363,30 @@ class Engine:
             self._zero_mask = torch.zeros(n, dtype=torch.uint8, device=device)
         return self._zero_mask
 
+    def _tok_params(self, grad=False):
+        """the tokenizer's parameters as every tokenizer entry point takes them (pre_g, pre_b, w_emb, b_emb, post_g, post_b), or with
+        grad=True their places in the gradient buffer"""
+        buf = self.fp.grad if grad else None
+        return tuple(ctypes.c_void_p(self.fp.ptr(k, buf)) for k in ("pre_g", "pre_b", "embed.w.0", "embed.b.0", "post_g", "post_b"))
+
+    def _tok_bwd_slab(self, nsamples, device):
+        """(nchunk, slab) of a tokenizer backward over nsamples samples: nchunk partial-gradient slabs per spectral block, then the
+        [S][N][96] position-gradient staging"""
+        S, N, P = self.S, self.N, self.P
+        nchunk = max(1, min(nsamples, self.tok_chunks))
+        ss = N * 96 + 96 * P + 96 * 4 + 32
+        return nchunk, torch.empty(S * nchunk * ss + S * N * 96, dtype=torch.float32, device=device)
+
+    def _launch_chunk(self, total, s, emb_drop, what):
+        """windows per tokenizer launch: all of them for the fp32-MFMA kernels, else TILE_WINDOWS_PER_LAUNCH at most -- and then without
+        embedding dropout (a dropout element is addressed by its place in one launch's output: launches in turn would repeat the
+        first one's masks).  what: the advice that ends the refusal"""
+        chunk = total if (self.P == 10 and s == 8) else min(total, self.TILE_WINDOWS_PER_LAUNCH)
+        if chunk < total and emb_drop[0] > 0:
+            raise NotImplementedError(f"embedding dropout over {total} windows in one step needs more than one launch of the generic "
+                                      f"tokenizer ({self.TILE_WINDOWS_PER_LAUNCH} windows each): {what} per step")
+        return chunk
+
     def tokenize(self, img, mask_u8=None, with_pos=True, emb_drop=(0.0, 0)):
         """img [B, C, H, W] fp32 cuda -> tokens [B, T, 96] (pos added, mask token substituted)"""
         self._require_cuda(img)
@@ -384,8 +408,7 @@ class Engine:
         mt = fp.ptr("mask_token") if self.mim is not None else fp.ptr("post_b")
         V = ctypes.c_void_p
         _lib.check(self.lib.msst_tokenize_fwd(
-            _p(img), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
-            V(fp.ptr("post_g")), V(fp.ptr("post_b")), V(pos_a), V(pos_b), split, V(mt), _p(mask_u8), _p(out),
+            _p(img), *self._tok_params(), V(pos_a), V(pos_b), split, V(mt), _p(mask_u8), _p(out),
             B, S, N, P, emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_fwd")
         return out
 
@@ -415,18 +438,12 @@ class Engine:
         s, nr, nq = self.tile_grid(img)
         total = B * nr * nq
         out = torch.empty(total, S * N, D, dtype=torch.float32, device=img.device)
-        chunk = total if (P == 10 and s == 8) else min(total, self.TILE_WINDOWS_PER_LAUNCH)
-        if chunk < total and emb_drop[0] > 0:
-            # a dropout element is addressed by its place in one launch's output: launches in turn would repeat the first one's masks
-            raise NotImplementedError(f"embedding dropout over {total} windows in one step needs more than one launch of the generic "
-                                      f"tokenizer ({self.TILE_WINDOWS_PER_LAUNCH} windows each): use fewer tiles per step")
-        fp = self.fp
+        chunk = self._launch_chunk(total, s, emb_drop, "use fewer tiles")
         split, pos_a, pos_b = self._pos_tables()
         V = ctypes.c_void_p
         for win0 in range(0, total, chunk):
             _lib.check(self.lib.msst_tokenize_scene_fwd_train(
-                _p(img), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
-                V(fp.ptr("post_g")), V(fp.ptr("post_b")), V(pos_a), V(pos_b), split, _p(out[win0:]), B, Ht, Wt, s, s, win0,
+                _p(img), *self._tok_params(), V(pos_a), V(pos_b), split, _p(out[win0:]), B, Ht, Wt, s, s, win0,
                 min(chunk, total - win0), S, P, emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_scene_fwd_train")
         return out
 
@@ -438,17 +455,12 @@ class Engine:
         s = self.enc.num_spatial_patches_sqrt
         total = origins.shape[0]
         out = torch.empty(total, S * N, D, dtype=torch.float32, device=scene.device)
-        chunk = total if (P == 10 and s == 8) else min(total, self.TILE_WINDOWS_PER_LAUNCH)
-        if chunk < total and emb_drop[0] > 0:
-            raise NotImplementedError(f"embedding dropout over {total} windows in one step needs more than one launch of the generic "
-                                      f"tokenizer ({self.TILE_WINDOWS_PER_LAUNCH} windows each): list fewer windows per step")
-        fp = self.fp
+        chunk = self._launch_chunk(total, s, emb_drop, "list fewer windows")
         split, pos_a, pos_b = self._pos_tables()
         V = ctypes.c_void_p
         for win0 in range(0, total, max(chunk, 1)):
             _lib.check(self.lib.msst_tokenize_at_fwd(
-                _p(scene), _p(origins[win0:]), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
-                V(fp.ptr("post_g")), V(fp.ptr("post_b")), V(pos_a), V(pos_b), split, _p(out[win0:]), Bs, Hs, Ws, s,
+                _p(scene), _p(origins[win0:]), *self._tok_params(), V(pos_a), V(pos_b), split, _p(out[win0:]), Bs, Hs, Ws, s,
                 min(chunk, total - win0), S, P, emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_at_fwd")
         return out
 
@@ -663,8 +675,7 @@ class Engine:
         split, pos_a, pos_b = self._pos_tables()
         V = ctypes.c_void_p
         _lib.check(self.lib.msst_tokenize_scene_fwd_masked(
-            _p(scene), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
-            V(fp.ptr("post_g")), V(fp.ptr("post_b")), V(pos_a), V(pos_b), split, V(fp.ptr("mask_token")), _p(scene_mask_u8), _p(out),
+            _p(scene), *self._tok_params(), V(pos_a), V(pos_b), split, V(fp.ptr("mask_token")), _p(scene_mask_u8), _p(out),
             Bs, Hs, Ws, w, stride, win0, nwin, S, P, _stream()), "msst_tokenize_scene_fwd_masked")
         return out
 
@@ -686,12 +697,8 @@ class Engine:
             Bs, C, Hs, Ws = scene.shape
             S, N, P = self.S, self.N, self.P
             w = self.enc.num_spatial_patches_sqrt
-            nr, nq = (Hs - w) // stride + 1, (Ws - w) // stride + 1
-            total = Bs * nr * nq
-            chunk = max(1, min(int(max_windows), total, 65535))   # 65535: the generic tokenizer runs one grid row per window
+            total, chunk = self._scene_chunking(scene, stride, max_windows)
             dev = scene.device
-            self.prep_weights()
-            bufs = [torch.empty(chunk, S * N, D, dtype=torch.float32, device=dev) for _ in range(2)]
             # msst_recon_fwd reads a cube and a token mask whatever blend is: with blend = 0 and no statistics neither reaches its output
             no_img = torch.zeros(chunk, S * P, N, dtype=torch.float32, device=dev)
             no_mask = self._zero_mask_for(chunk * S * N, dev)
@@ -703,10 +710,7 @@ class Engine:
             per_block = 1 if hasattr(self.mim.to_pixels, "layers") else 0
             V = ctypes.c_void_p
             st = _stream()
-            for win0 in range(0, total, chunk):
-                n = min(chunk, total - win0)
-                self.tokenize_scene_masked(scene, scene_mask_u8, stride, win0, n, out=bufs[0])
-                y = self.blocks_fwd_pingpong(bufs[0], other=bufs[1], n=n, stream=st)
+            for win0, n, y in self._scene_encoder_chunks(scene, stride, total, chunk, st, scene_mask_u8):
                 _lib.check(self.lib.msst_recon_fwd(_p(y), _p(no_img), _p(no_mask), V(self.fp.ptr("to_pixels.w.0")),
                                                    V(self.fp.ptr("to_pixels.b.0")), per_block, 0, _p(win_recon), None, None, n, S, N, P, st),
                            "msst_recon_fwd")
@@ -877,19 +881,14 @@ class Engine:
         token were applied outside the kernel, by the caller's own autograd ops)"""
         B = img.shape[0]
         S, N, P = self.S, self.N, self.P
-        dev = img.device
-        nchunk = max(1, min(B, self.tok_chunks))
-        ss = N * 96 + 96 * P + 96 * 4 + 32
-        slab = torch.empty(S * nchunk * ss + S * N * 96, dtype=torch.float32, device=dev)
+        nchunk, slab = self._tok_bwd_slab(B, img.device)
         fp, g = self.fp, self.fp.grad
         V = ctypes.c_void_p
         split, dpa, dpb = self._pos_tables(g) if with_pos else (0, 0, 0)
         dmt = fp.ptr("mask_token", g) if (self.mim is not None and with_pos) else 0
         _lib.check(self.lib.msst_tokenize_bwd(
-            _p(img), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
-            V(fp.ptr("post_g")), V(fp.ptr("post_b")), _p(mask_u8), _p(dx0), _p(slab), nchunk,
-            V(fp.ptr("pre_g", g)), V(fp.ptr("pre_b", g)), V(fp.ptr("embed.w.0", g)), V(fp.ptr("embed.b.0", g)),
-            V(fp.ptr("post_g", g)), V(fp.ptr("post_b", g)), V(dpa), V(dpb), split, V(dmt), B, S, N, P,
+            _p(img), *self._tok_params(), _p(mask_u8), _p(dx0), _p(slab), nchunk,
+            *self._tok_params(grad=True), V(dpa), V(dpb), split, V(dmt), B, S, N, P,
             emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_bwd")
         if with_pos:
             self._fire("tokenizer")
@@ -900,20 +899,14 @@ class Engine:
         Origins: one msst_tokenize_at_bwd over the listed windows, likewise."""
         if origins is not None:
             Bs, _, Hs, Ws = img.shape
-            S, N, P = self.S, self.N, self.P
             s = self.enc.num_spatial_patches_sqrt
             total = origins.shape[0]
-            nchunk = max(1, min(total, self.tok_chunks))
-            ss = N * 96 + 96 * P + 96 * 4 + 32
-            slab = torch.empty(S * nchunk * ss + S * N * 96, dtype=torch.float32, device=img.device)
-            fp, g = self.fp, self.fp.grad
+            nchunk, slab = self._tok_bwd_slab(total, img.device)
             V = ctypes.c_void_p
-            split, dpa, dpb = self._pos_tables(g)
+            split, dpa, dpb = self._pos_tables(self.fp.grad)
             _lib.check(self.lib.msst_tokenize_at_bwd(
-                _p(img), _p(origins), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
-                V(fp.ptr("post_g")), V(fp.ptr("post_b")), _p(dx0), _p(slab), nchunk,
-                V(fp.ptr("pre_g", g)), V(fp.ptr("pre_b", g)), V(fp.ptr("embed.w.0", g)), V(fp.ptr("embed.b.0", g)),
-                V(fp.ptr("post_g", g)), V(fp.ptr("post_b", g)), V(dpa), V(dpb), split, Bs, Hs, Ws, s, total, S, P,
+                _p(img), _p(origins), *self._tok_params(), _p(dx0), _p(slab), nchunk,
+                *self._tok_params(grad=True), V(dpa), V(dpb), split, Bs, Hs, Ws, s, total, self.S, self.P,
                 emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_at_bwd")
             self._fire("tokenizer")
             return
@@ -921,20 +914,14 @@ class Engine:
             zero_mask = self._zero_mask_for(img.shape[0] * self.S * self.N, img.device)
             return self.tokenize_bwd(img, zero_mask, dx0, emb_drop=emb_drop)
         B, _, Ht, Wt = img.shape
-        S, N, P = self.S, self.N, self.P
         s, nr, nq = self.tile_grid(img)
         total = B * nr * nq
-        nchunk = max(1, min(total, self.tok_chunks))
-        ss = N * 96 + 96 * P + 96 * 4 + 32
-        slab = torch.empty(S * nchunk * ss + S * N * 96, dtype=torch.float32, device=img.device)
-        fp, g = self.fp, self.fp.grad
+        nchunk, slab = self._tok_bwd_slab(total, img.device)
         V = ctypes.c_void_p
-        split, dpa, dpb = self._pos_tables(g)
+        split, dpa, dpb = self._pos_tables(self.fp.grad)
         _lib.check(self.lib.msst_tokenize_scene_bwd(
-            _p(img), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
-            V(fp.ptr("post_g")), V(fp.ptr("post_b")), _p(dx0), _p(slab), nchunk,
-            V(fp.ptr("pre_g", g)), V(fp.ptr("pre_b", g)), V(fp.ptr("embed.w.0", g)), V(fp.ptr("embed.b.0", g)),
-            V(fp.ptr("post_g", g)), V(fp.ptr("post_b", g)), V(dpa), V(dpb), split, B, Ht, Wt, s, s, 0, total, S, P,
+            _p(img), *self._tok_params(), _p(dx0), _p(slab), nchunk,
+            *self._tok_params(grad=True), V(dpa), V(dpb), split, B, Ht, Wt, s, s, 0, total, self.S, self.P,
             emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_scene_bwd")
         self._fire("tokenizer")
 
@@ -946,12 +933,9 @@ class Engine:
         self._require_cuda(img)
         B = img.shape[0]
         S, N, P = self.S, self.N, self.P
-        fp = self.fp
         dimg = torch.empty(img.shape, dtype=torch.float32, device=img.device)
-        V = ctypes.c_void_p
         _lib.check(self.lib.msst_tokenize_bwd_input(
-            _p(img), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
-            V(fp.ptr("post_g")), V(fp.ptr("post_b")), _p(mask_u8), _p(dx0), _p(dtarget), _p(dimg), B, S, N, P,
+            _p(img), *self._tok_params(), _p(mask_u8), _p(dx0), _p(dtarget), _p(dimg), B, S, N, P,
             emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_bwd_input")
         return dimg
 
@@ -964,12 +948,9 @@ class Engine:
         self._require_cuda(img)
         B, _, Ht, Wt = img.shape
         s, nr, nq = self.tile_grid(img)
-        fp = self.fp
         dtiles = torch.empty(img.shape, dtype=torch.float32, device=img.device)
-        V = ctypes.c_void_p
         _lib.check(self.lib.msst_tokenize_scene_bwd_input(
-            _p(img), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
-            V(fp.ptr("post_g")), V(fp.ptr("post_b")), _p(dx0), _p(dtiles), B, Ht, Wt, s, s, 0, B * nr * nq, self.S, self.P,
+            _p(img), *self._tok_params(), _p(dx0), _p(dtiles), B, Ht, Wt, s, s, 0, B * nr * nq, self.S, self.P,
             emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_scene_bwd_input")
         return dtiles
 
@@ -1306,13 +1287,13 @@ class Engine:
         total = Bs * nr * nq
         return total, max(1, min(int(max_windows), total, 65535))   # 65535: the generic tokenizer runs one grid row per window
 
-    def _scene_encoder_chunks(self, scene, stride, total, chunk, st):
-        """the front of scene_forward and encode_scene: for every chunk of windows of scene (contiguous fp32) yields (win0, n, y), y the
-        encoder output [>= n, T, 96] of windows win0 .. win0 + n - 1 -- one msst_tokenize_scene_fwd launch reads them out of the scene,
-        the blocks run on two token buffers in turn.  y is one of the two buffers: the next chunk overwrites it."""
+    def _scene_encoder_chunks(self, scene, stride, total, chunk, st, scene_mask_u8=None):
+        """the front of scene_forward, encode_scene and reconstruct_scene: for every chunk of windows of scene (contiguous fp32) yields
+        (win0, n, y), y the encoder output [>= n, T, 96] of windows win0 .. win0 + n - 1 -- one msst_tokenize_scene_fwd launch (with
+        scene_mask_u8 [Bs, S, Hs, Ws]: tokenize_scene_masked) reads them out of the scene, the blocks run on two token buffers in turn.
+        y is one of the two buffers: the next chunk overwrites it."""
         self.ensure()
         Bs, _, Hs, Ws = scene.shape
-        fp = self.fp
         S, N, P = self.S, self.N, self.P
         w = self.enc.num_spatial_patches_sqrt
         self.prep_weights()
@@ -1321,10 +1302,12 @@ class Engine:
         V = ctypes.c_void_p
         for win0 in range(0, total, chunk):
             n = min(chunk, total - win0)
-            _lib.check(self.lib.msst_tokenize_scene_fwd(
-                _p(scene), V(fp.ptr("pre_g")), V(fp.ptr("pre_b")), V(fp.ptr("embed.w.0")), V(fp.ptr("embed.b.0")),
-                V(fp.ptr("post_g")), V(fp.ptr("post_b")), V(pos_a), V(pos_b), split, _p(bufs[0]), Bs, Hs, Ws, w, stride, win0, n, S, P, st),
-                "msst_tokenize_scene_fwd")
+            if scene_mask_u8 is not None:
+                self.tokenize_scene_masked(scene, scene_mask_u8, stride, win0, n, out=bufs[0])
+            else:
+                _lib.check(self.lib.msst_tokenize_scene_fwd(
+                    _p(scene), *self._tok_params(), V(pos_a), V(pos_b), split, _p(bufs[0]), Bs, Hs, Ws, w, stride, win0, n, S, P, st),
+                    "msst_tokenize_scene_fwd")
             yield win0, n, self.blocks_fwd_pingpong(bufs[0], other=bufs[1], n=n, stream=st)
 
     # ------------------------------------------------------------------ scene embedding maps (msst_scene_embed.hip)

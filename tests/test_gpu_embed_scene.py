@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from conftest import ROOT, load_golden, oracle_cfg_from, seed_all
-from util import record, rel_l2, relerr
+from util import host_fold, record, rel_l2, relerr
 
 pytestmark = pytest.mark.gpu
 
@@ -62,27 +62,6 @@ def test_pool_spectral_against_float64(B, S, N):
 
 
 # -------------------------------------------------------------------------------------------------------------------- 2. assembler
-def host_fold(win, Bs, Hs, Ws, w, stride):
-    """float64 fold of win [Bs nr nq, D, w w] (window order): (sum, sum of |terms|, cover [Bs, Hs, Ws] int32, owner: the index of the
-    last window covering a pixel, -1 where none does)"""
-    from maskedsst_amd.scene import scene_windows
-    D = win.shape[1]
-    org = scene_windows(Hs, Ws, w, stride)
-    acc = torch.zeros(Bs, D, Hs, Ws, dtype=torch.float64)
-    mag = torch.zeros(Bs, D, Hs, Ws, dtype=torch.float64)
-    cover = torch.zeros(Bs, Hs, Ws, dtype=torch.int32)
-    i = 0
-    for s in range(Bs):
-        for (y, x) in org:
-            v = win[i].double().view(D, w, w)
-            acc[s, :, y:y + w, x:x + w] += v
-            mag[s, :, y:y + w, x:x + w] += v.abs()
-            cover[s, y:y + w, x:x + w] += 1
-            i += 1
-    assert i == win.shape[0]
-    return acc, mag, cover
-
-
 def run_assemble(win_d, Bs, D, Hs, Ws, w, stride, splits, l2norm=0):
     """msst_scene_embed_assemble over the windows in calls of the given sizes -> (feat, cover), both prefilled (NaN, 12345) to show
     that nothing needs initialising"""

@@ -1,5 +1,5 @@
 """GPU: spectral patch depths P other than the shipped 10 (config key band_patch_size; the constructor accepts 1 .. 16).  Every P != 10
-runs the run-time-P kernels: tokenize_fwd_kernel<0>, tokenize_bwd_kernel<0>, tokenize_scene_fwd_kernel<0> and the generic SimMIM
+runs the run-time-P kernels: tokenize_fwd_kernel<0, TOK_BATCH>, tokenize_bwd_kernel<0>, tokenize_fwd_kernel<0, TOK_SCENE> and the generic SimMIM
 to-pixels head (head_fwd_kernel / head_bwd_kernel).  Against the CPU oracle (OracleConfig(spectral_patch=P)) at the bars of
 tests/test_gpu_forward.py / tests/test_gpu_backward.py / tests/test_gpu_finetune.py, and against the reference captures of
 tools/make_golden.py patch."""

@@ -96,6 +96,28 @@ def saved_lse_rows(lse, heads, L, nseq):
     return got.reshape(ntiles * TS, heads, L)[:nseq], lse[ntiles * heads * 64:]
 
 
+def host_fold(win, Bs, Hs, Ws, w, stride, dtype=torch.float64):
+    """fold of win [Bs nr nq, D, w w] (window order) into scene planes, the running sums in `dtype`: (sum, sum of |terms|, cover
+    [Bs, Hs, Ws] int32).  float64: the reference of the error bounds.  float32: every pixel's sum takes its covering windows in the
+    order of the scene kernels (window row, then column), one rounded addition each -- their bits."""
+    from maskedsst_amd.scene import scene_windows
+    D = win.shape[1]
+    org = scene_windows(Hs, Ws, w, stride)
+    acc = torch.zeros(Bs, D, Hs, Ws, dtype=dtype)
+    mag = torch.zeros(Bs, D, Hs, Ws, dtype=dtype)
+    cover = torch.zeros(Bs, Hs, Ws, dtype=torch.int32)
+    i = 0
+    for s in range(Bs):
+        for (y, x) in org:
+            v = win[i].to(dtype).view(D, w, w)
+            acc[s, :, y:y + w, x:x + w] += v
+            mag[s, :, y:y + w, x:x + w] += v.abs()
+            cover[s, y:y + w, x:x + w] += 1
+            i += 1
+    assert i == win.shape[0]
+    return acc, mag, cover
+
+
 def relerr(a, b):
     a = a.detach().double().cpu()
     b = b.detach().double().cpu()
