@@ -99,6 +99,10 @@ def build_parser():
     ap.add_argument("--val-saliency", action="store_true",
                     help="one more line per validation: the five bands with the largest mean |gradient x input| attribution "
                          "(maskedsst_amd.band_importance, argmax class) over the windows of the --val-scenes")
+    ap.add_argument("--val-saliency-scene", action="store_true",
+                    help="one more line per validation: the five bands with the largest mean |gradient x input| attribution of the "
+                         "whole --val-scenes' class maps (maskedsst_amd.band_importance_scene: the overlapping windows of predict_scene "
+                         "read in place, their input gradients folded into the scene); needs --val-scenes")
     ap.add_argument("--val-attention", action="store_true",
                     help="one more line per validation: the three spectral blocks that receive the most rollout attention "
                          "(maskedsst_amd.attention_rollout of model.attention_maps(stack='spectral')) over the first batch of windows "
@@ -189,6 +193,8 @@ def main():
     if args.val_at:
         args.val_scenes = args.val_scenes or 2
         args.val_every = args.val_every or args.steps
+    if args.val_saliency_scene and args.val_scenes < 1:
+        raise SystemExit("--val-saliency-scene attributes the validation scenes: it needs --val-scenes")
     if not 0.0 <= args.label_smoothing < 1.0:
         raise SystemExit("--label-smoothing must lie in [0, 1)")
     # --class-weights inverse: the weights come from the first step's labels, so the criterion is made there
@@ -238,6 +244,8 @@ def main():
                 validate_embedding(model, val, step, config.n_classes, config.ignored_label)
             if args.val_saliency:
                 validate_saliency(model, val, step)
+            if args.val_saliency_scene:
+                validate_saliency_scene(model, val, step)
             if args.val_attention:
                 validate_attention(model, val, step)
 
@@ -348,6 +356,19 @@ def validate_saliency(model, val, step, batch=256, top=5):
     mean = (total / win.shape[0]).cpu()
     order = torch.argsort(mean, descending=True)[:top].tolist()
     print(f"val-saliency step {step} top bands " + " ".join(f"{b}:{float(mean[b]):.3e}" for b in order) + f" windows {win.shape[0]}",
+          flush=True)
+
+
+def validate_saliency_scene(model, val, step, top=5):
+    """--val-saliency-scene: which bands drive the class maps of the whole validation scenes.  band_importance_scene (gradient x input of
+    predict_scene's logit map at its own classes, the windows read in place and their input gradients folded into the scenes by
+    msst_scene_fold_at) at predict_scene's default stride; the bands are ranked by the mean |attribution| over the scenes.  Eval forward,
+    the module's mode and its parameters' flags and gradients left as found."""
+    from maskedsst_amd import band_importance_scene
+    img, _ = val
+    mean = band_importance_scene(model, img).abs().double().mean(dim=0).cpu()
+    order = torch.argsort(mean, descending=True)[:top].tolist()
+    print(f"val-saliency-scene step {step} top bands " + " ".join(f"{b}:{float(mean[b]):.3e}" for b in order) + f" scenes {img.shape[0]}",
           flush=True)
 
 

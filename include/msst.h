@@ -494,6 +494,34 @@ int msst_tokenize_scene_bwd_input(const float* scene, const float* pre_g, const 
                                   int window, int stride, long win0, int nwin, int S, int P, float emb_dropout_p, uint32_t seed,
                                   void* stream);
 
+/* Scene gradients through windows at listed origins (additive under MSST_VERSION 109): listed windows overlap, so d(loss)/d(scene) is a
+ * per-window input gradient and a fold that sums, per pixel, the windows covering it -- in a fixed order, without atomics.
+ *
+ * msst_tokenize_at_bwd_input: msst_tokenize_bwd_input (no mask, no dtarget) of the windows listed in origins [nwin][3] int32 = (scene,
+ * y0, x0), the table of msst_tokenize_at_bwd; the pixels are read from the scene at the listed origin, the result is stored stacked:
+ * dwin [nwin][S*P][window*window], plain stores, written whole.  For every (emb_dropout_p, seed) dwin is bit-identical to
+ * msst_tokenize_bwd_input on the copied windows.  Checked before anything is enqueued: MSST_ERR_BADARG for a size below 1, nwin < 0 or
+ * a null pointer (nwin = 0 is an empty call that launches nothing), MSST_ERR_UNSUPPORTED outside window <= Hs, Ws, window * window <=
+ * 64, P <= 16.  THE CALLER GUARANTEES the table's value ranges, as for msst_tokenize_at_fwd.
+ *
+ * msst_scene_fold_at: dscene [Bs][C][Hs][Ws] gets, per pixel, the sum of dwin [nwin][C][window*window] over every listed window that
+ * covers it.  The windows are found through an inverse index over origin cells -- a window's cell is (scene * Hs + y0) * Ws + x0:
+ * cell_ptr int32 [Bs*Hs*Ws + 1], the CSR row pointers; cell_win int32 [nwin], window numbers sorted by cell, ascending window number
+ * within a cell (maskedsst_amd.scene.origins_csr builds both).  THE SUMMATION ORDER IS PART OF THE CONTRACT: pixel (s, y, x) visits
+ * y0 = max(0, y - window + 1) .. min(y, Hs - window) ascending (outer), x0 likewise (inner), and a cell's list in order; its addends
+ * are added one at a time in that order, ascending (y0, x0, window number).  accumulate == 0: the sum starts from 0.f and uncovered
+ * pixels are written 0.f -- dscene is defined whole.  accumulate != 0: the sum starts from the value in dscene, and a pixel no window of
+ * this call covers is not touched; so a table that lists a regular grid in grid order may be split into consecutive calls and every
+ * bit stays.  One thread per (pixel, group of `group` <= 16 consecutive channels; group = P for the tokenizer's planes); no atomics: bitwise
+ * reproducible.  MSST_ERR_BADARG for a null pointer (dwin and cell_win may be null when nwin = 0), a size below 1 or nwin < 0;
+ * MSST_ERR_UNSUPPORTED for group > 16, window * window > 64, window > Hs or Ws, or a grid beyond the launch limits (Bs*Hs*Ws above
+ * 2^31 * 256 pixels, more than 65535 channel groups).  The caller guarantees a consistent index (entries outside [0, nwin) are skipped). */
+int msst_tokenize_at_bwd_input(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
+                               const float* b_emb, const float* post_g, const float* post_b, const float* dx0, float* dwin, int Bs,
+                               int Hs, int Ws, int window, int nwin, int S, int P, float emb_dropout_p, uint32_t seed, void* stream);
+int msst_scene_fold_at(const float* dwin, const int32_t* cell_ptr, const int32_t* cell_win, float* dscene, int Bs, int C, int Hs, int Ws,
+                       int window, int nwin, int group, int accumulate, void* stream);
+
 /* a17: classification head of ViTSpatialSpectral.forward (vit_spatial_spectral.py:536-564, :481-493):
  * mean over the spectral axis -> LayerNorm(96) -> Linear(96 -> n_classes); logits [B][n_classes][N].
  * Limits: N <= 64, S <= 64, any n_classes >= 1 (MSST_VERSION 108: the backward used to refuse n_classes > 32).  Both calls check

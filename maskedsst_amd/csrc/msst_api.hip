@@ -1046,6 +1046,31 @@ int msst_tokenize_scene_bwd_input(const float* scene, const float* pre_g, const 
     return fail(launch_tokenize_scene_bwd_input(a, st), "msst_tokenize_scene_bwd_input");
 }
 
+int msst_tokenize_at_bwd_input(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
+                               const float* b_emb, const float* post_g, const float* post_b, const float* dx0, float* dwin, int Bs,
+                               int Hs, int Ws, int window, int nwin, int S, int P, float emb_dropout_p, uint32_t seed, void* stream) {
+    const bool pointers = scene && origins && pre_g && pre_b && w_emb && b_emb && post_g && post_b && dx0 && dwin;
+    if (int rc = at_args(pointers, Bs, Hs, Ws, window, nwin, 0, S, P, 0)) return fail(rc, "msst_tokenize_at_bwd_input");
+    TokInAtArgs a;
+    fill_tok_in(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, nullptr, dx0, nullptr, dwin, nwin, S, window * window, P,
+                make_drop(emb_dropout_p, seed, 255));
+    fill_window(a, Hs, Ws, window, window, 1, 1, 0);
+    a.origins = origins;
+    return fail(launch_tokenize_at_bwd_input(a, (hipStream_t)stream), "msst_tokenize_at_bwd_input");
+}
+
+int msst_scene_fold_at(const float* dwin, const int32_t* cell_ptr, const int32_t* cell_win, float* dscene, int Bs, int C, int Hs, int Ws,
+                       int window, int nwin, int group, int accumulate, void* stream) {
+    if (Bs < 1 || C < 1 || Hs < 1 || Ws < 1 || window < 1 || group < 1 || nwin < 0) return fail(MSST_ERR_BADARG, "msst_scene_fold_at");
+    if (group > 16 || window > 8 || window > Hs || window > Ws) return fail(MSST_ERR_UNSUPPORTED, "msst_scene_fold_at");
+    if (!cell_ptr || !dscene || (nwin > 0 && (!dwin || !cell_win))) return fail(MSST_ERR_BADARG, "msst_scene_fold_at");
+    if (nwin == 0 && accumulate) return 0;   // nothing to add; without accumulate the launch writes the zeros
+    SceneFoldAtArgs a;
+    a.dwin = dwin; a.cell_ptr = cell_ptr; a.cell_win = cell_win; a.dscene = dscene;
+    a.Bs = Bs; a.C = C; a.Hs = Hs; a.Ws = Ws; a.win = window; a.nwin = nwin; a.group = group; a.accumulate = accumulate != 0;
+    return fail(launch_scene_fold_at(a, (hipStream_t)stream), "msst_scene_fold_at");
+}
+
 // shape of the default head: 0, MSST_ERR_BADARG (a size below 1) or MSST_ERR_UNSUPPORTED (beyond the kernels' limits; any n_classes)
 static int cls_head_shape(int B, int S, int N, int n_classes) {
     if (B < 1 || S < 1 || N < 1 || n_classes < 1) return MSST_ERR_BADARG;

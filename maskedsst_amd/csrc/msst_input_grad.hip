@@ -6,6 +6,8 @@
 //   head_bwd_target      the SimMIM L1 loss's direct dependence on the input (its target is the raw pixels of the masked patches),
 //                        gathered through the inverse CSR of head_bwd
 //   scene_border_zero    the pixels of a tile batch that belong to no window
+//   scene_fold_at        per-window input gradients of windows at listed origins, which overlap -> d(loss)/d(scene): every pixel sums
+//                        the windows covering it in a fixed order, found through an inverse index over origin cells
 //
 // tokenize_bwd_kernel (msst_bwd.hip) computes the same dxn on its way to the pre-norm weight gradient, but it is organised for the
 // cross-sample weight reductions: grid (S, nchunk), serial over its samples, at the 256-register limit.  Nothing is reduced over
@@ -29,10 +31,13 @@ __device__ __forceinline__ long scene_window_offset(const TokInArgs& a, int b) {
 // threads of a token read rows 4 apart = 80 floats = banks 16 apart, the 16 tokens of a wave the same addresses (broadcast).
 // thread <-> (token n = tid / 4, features 16 (i / 4) + 4 part + i % 4, i < 24): the mapping of tokenize_fwd_kernel / tokenize_bwd_kernel,
 // so a dropout group (four consecutive features) is one thread's f32x4 and has their element address.
-// SCENE: sample b is window win0 + b of a scene (stride == window: every pixel in at most one window, plain stores), no mask,
-// no dtarget.
-template <int KC, bool SCENE>
-__global__ __launch_bounds__(256) void tokenize_bwd_input_kernel(TokInArgs a) {
+// SRC, the source of sample b's pixels and the place of its gradient.  TOKIN_BATCH: cube b of a batch, dimg of the batch's shape.
+// TOKIN_SCENE: window win0 + b of a scene, stored to the window's pixels of dscene (stride == window: every pixel in at most one
+// window, plain stores), no mask, no dtarget.  TOKIN_AT: the window at origins[b] of a scene (listed_window_origin), stored stacked
+// as for a batch -- dwin [B][S*P][N], plain stores; listed windows overlap, scene_fold_at_kernel below sums them; no mask, no dtarget.
+enum { TOKIN_BATCH = 0, TOKIN_SCENE = 1, TOKIN_AT = 2 };
+template <int KC, int SRC, class Args>
+__global__ __launch_bounds__(256) void tokenize_bwd_input_kernel(Args a) {
     constexpr int KP = 4 * KC;
     __shared__ float patch[16][64];
     __shared__ float outp[16][64];
@@ -48,12 +53,20 @@ __global__ __launch_bounds__(256) void tokenize_bwd_input_kernel(TokInArgs a) {
     if (tid < 96) { bias[tid] = a.b_emb[c * 96 + tid]; postg[tid] = a.post_g[tid]; }
     if (tid < 16) { preg[tid] = tid < P ? a.pre_g[tid] : 0.f; preb[tid] = tid < P ? a.pre_b[tid] : 0.f; }
     long org = 0, plane = 0;
-    if constexpr (SCENE) {
+    if constexpr (SRC == TOKIN_SCENE) {
         plane = (long)a.Hs * a.Ws;
         org = scene_window_offset(a, b) + (long)c * P * plane;
         for (int i = tid; i < P * N; i += 256) {
             const int k = i / N, nn = i - k * N;
             patch[k][nn] = a.img[org + k * plane + (long)(nn / a.win) * a.Ws + nn % a.win];
+        }
+    } else if constexpr (SRC == TOKIN_AT) {
+        plane = (long)a.Hs * a.Ws;
+        org = ((long)b * a.S + c) * P * N;   // of the stacked store
+        const float* src = listed_window_origin(a, b) + (long)c * P * plane;
+        for (int i = tid; i < P * N; i += 256) {
+            const int k = i / N, nn = i - k * N;
+            patch[k][nn] = src[k * plane + (long)(nn / a.win) * a.Ws + nn % a.win];
         }
     } else {
         org = ((long)b * a.S + c) * P * N;
@@ -157,7 +170,7 @@ __global__ __launch_bounds__(256) void tokenize_bwd_input_kernel(TokInArgs a) {
         }
     }
     __syncthreads();
-    if constexpr (SCENE) {
+    if constexpr (SRC == TOKIN_SCENE) {
         for (int i = tid; i < P * N; i += 256) {
             const int k = i / N, nn = i - k * N;
             a.dimg[org + k * plane + (long)(nn / a.win) * a.Ws + nn % a.win] = outp[k][nn];
@@ -201,23 +214,85 @@ __global__ __launch_bounds__(256) void scene_border_zero_kernel(float* dscene, l
     }
 }
 
-// one launcher for both sources (SCENE: windows of a scene, where an empty call is no launch); KC = ceil(P / 4)
-template <bool SCENE>
-static int launch_tokenize_bwd_input_src(const TokInArgs& a, hipStream_t st) {
+// dscene [Bs][C][Hs][Ws] (+)= the per-window planes dwin [nwin][C][win * win] of windows at listed origins, summed per pixel over the
+// windows covering it.  The windows are found through an inverse index over origin cells (maskedsst_amd.scene.origins_csr): the cell of a
+// window is (scene * Hs + y0) * Ws + x0, cell_ptr [Bs Hs Ws + 1] the CSR row pointers, cell_win [nwin] the window numbers sorted by
+// cell, ascending within a cell.  Pixel (s, y, x) is covered by the windows whose origin lies in the rectangle y0 in [max(0, y - win + 1),
+// min(y, Hs - win)] x x0 likewise: it walks the rows y0 ascending, in a row the cells x0 ascending (consecutive cells: one more pointer
+// read per cell), in a cell its list in order -- ascending (y0, x0, window number), a fixed order without atomics, so equal inputs give
+// equal bits and a table that lists a regular grid in grid order may be split into consecutive calls (accumulate).
+// The shape of scene_fold_kernel (msst_fwd.hip): grid (256-pixel pieces of the flattened scenes, channel group), one thread per (pixel,
+// group), lanes along x -- the lanes of a wave that sit in the same window read consecutive floats of one of its rows and all lanes
+// read / write consecutive floats of dscene; the group's channels are independent sums in 16 registers; no LDS.
+// accumulate == 0: the sum starts from 0 and every pixel is written (0 where no window covers it).  Otherwise it starts from the value
+// in dscene, and a pixel no window of this call covers is not touched.  An entry outside [0, nwin) is skipped.
+__global__ __launch_bounds__(256) void scene_fold_at_kernel(SceneFoldAtArgs a) {
+    const long plane = (long)a.Hs * a.Ws;
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (long)a.Bs * plane) return;
+    const int c0 = blockIdx.y * a.group, cn = min(a.group, a.C - c0);
+    const long s = p / plane;
+    const int pix = (int)(p - s * plane);
+    const int y = pix / a.Ws, x = pix - y * a.Ws;
+    const int ylo = max(0, y - a.win + 1), yhi = min(y, a.Hs - a.win);
+    const int xlo = max(0, x - a.win + 1), xhi = min(x, a.Ws - a.win);
+    const int N = a.win * a.win;
+    float* out = a.dscene + (s * a.C + c0) * plane + pix;
+    float acc[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc[k] = (k < cn && a.accumulate) ? out[k * plane] : 0.f;
+    bool any = false;
+    for (int y0 = ylo; y0 <= yhi; ++y0) {
+        const int32_t* row = a.cell_ptr + (s * a.Hs + y0) * a.Ws;
+        int e0 = xlo <= xhi ? max(row[xlo], 0) : 0;
+        for (int x0 = xlo; x0 <= xhi; ++x0) {
+            const int e1 = min(row[x0 + 1], a.nwin);
+            const int off = (y - y0) * a.win + (x - x0);
+            for (int e = e0; e < e1; ++e) {
+                const int i = a.cell_win[e];
+                if ((unsigned)i >= (unsigned)a.nwin) continue;
+                const float* w = a.dwin + ((long)i * a.C + c0) * N + off;
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    if (k < cn) acc[k] += w[k * N];
+                any = true;
+            }
+            e0 = max(e1, e0);
+        }
+    }
+    if (!any && a.accumulate) return;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (k < cn) out[k * plane] = acc[k];
+}
+
+// one launcher for the three sources (windows of a scene, numbered or listed: an empty call is no launch); KC = ceil(P / 4)
+template <int SRC, class Args>
+static int launch_tokenize_bwd_input_src(const Args& a, hipStream_t st) {
     if (a.P > 16 || a.N > 64 || (long)a.B * a.S > 0x7fffffffL) return MSST_ERR_UNSUPPORTED;
-    if (SCENE && a.B < 1) return 0;
+    if (SRC != TOKIN_BATCH && a.B < 1) return 0;
     ProfScope ps(K_TOK_BWD_INPUT, st);
     const dim3 grid((unsigned)((long)a.B * a.S));
     switch ((a.P + 3) / 4) {
-    case 1: hipLaunchKernelGGL((tokenize_bwd_input_kernel<1, SCENE>), grid, dim3(256), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((tokenize_bwd_input_kernel<2, SCENE>), grid, dim3(256), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((tokenize_bwd_input_kernel<3, SCENE>), grid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((tokenize_bwd_input_kernel<4, SCENE>), grid, dim3(256), 0, st, a); break;
+    case 1: hipLaunchKernelGGL((tokenize_bwd_input_kernel<1, SRC, Args>), grid, dim3(256), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((tokenize_bwd_input_kernel<2, SRC, Args>), grid, dim3(256), 0, st, a); break;
+    case 3: hipLaunchKernelGGL((tokenize_bwd_input_kernel<3, SRC, Args>), grid, dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((tokenize_bwd_input_kernel<4, SRC, Args>), grid, dim3(256), 0, st, a); break;
     }
     return (int)hipGetLastError();
 }
-int launch_tokenize_bwd_input(const TokInArgs& a, hipStream_t st) { return launch_tokenize_bwd_input_src<false>(a, st); }
-int launch_tokenize_scene_bwd_input(const TokInArgs& a, hipStream_t st) { return launch_tokenize_bwd_input_src<true>(a, st); }
+int launch_tokenize_bwd_input(const TokInArgs& a, hipStream_t st) { return launch_tokenize_bwd_input_src<TOKIN_BATCH>(a, st); }
+int launch_tokenize_scene_bwd_input(const TokInArgs& a, hipStream_t st) { return launch_tokenize_bwd_input_src<TOKIN_SCENE>(a, st); }
+int launch_tokenize_at_bwd_input(const TokInAtArgs& a, hipStream_t st) { return launch_tokenize_bwd_input_src<TOKIN_AT>(a, st); }
+
+int launch_scene_fold_at(const SceneFoldAtArgs& a, hipStream_t st) {
+    const long pixels = (long)a.Bs * a.Hs * a.Ws;
+    const long grid = (pixels + 255) / 256, ny = ((long)a.C + a.group - 1) / a.group;
+    if (a.group > 16 || a.win * a.win > 64 || grid > 0x7fffffffL || ny > 65535) return MSST_ERR_UNSUPPORTED;
+    ProfScope ps(K_TOK_BWD_INPUT, st);
+    hipLaunchKernelGGL(scene_fold_at_kernel, dim3((unsigned)grid, (unsigned)ny), dim3(256), 0, st, a);
+    return (int)hipGetLastError();
+}
 
 int launch_scene_border_zero(float* dscene, long rows, int Hs, int Ws, int rows_in, int cols_in, hipStream_t st) {
     if (rows_in >= Hs && cols_in >= Ws) return 0;

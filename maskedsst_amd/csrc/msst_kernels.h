@@ -241,7 +241,7 @@ struct TokAtBwdArgs : TokSceneBwdArgs {
 };
 __device__ __forceinline__ const float* scene_window_origin(const TokAtBwdArgs& a, int b) { return listed_window_origin(a, b); }
 
-// msst_input_grad.hip (msst_tokenize_bwd_input, msst_tokenize_scene_bwd_input): d(loss)/d(img) from dx0
+// msst_input_grad.hip (msst_tokenize_bwd_input, msst_tokenize_scene_bwd_input, msst_tokenize_at_bwd_input): d(loss)/d(img) from dx0
 struct TokInArgs {
     const float* img; const float* pre_g; const float* pre_b; const float* w_emb; const float* b_emb;
     const float* post_g; const float* post_b;
@@ -254,8 +254,20 @@ struct TokInArgs {
     long win0;               // scene instances: the scene fields of TokArgs (img is the scene, sample b its window win0 + b)
     int Hs, Ws, win, stride, nq, wps;
 };
+// msst_tokenize_at_bwd_input: sample b is the window at origins[b] = (scene, y0, x0) (TokArgs.origins); dimg is dwin [B][S*P][N], stacked
+struct TokInAtArgs : TokInArgs {
+    const int32_t* origins;   // [B][3]
+};
+// msst_scene_fold_at: dwin [nwin][C][win * win] of windows at listed origins, summed per pixel into dscene [Bs][C][Hs][Ws] through the
+// inverse index cell_ptr [Bs Hs Ws + 1] / cell_win [nwin] over origin cells (scene_fold_at_kernel, msst_input_grad.hip)
+struct SceneFoldAtArgs {
+    const float* dwin; const int32_t* cell_ptr; const int32_t* cell_win; float* dscene;
+    int Bs, C, Hs, Ws, win, nwin, group, accumulate;
+};
 int launch_tokenize_bwd_input(const TokInArgs& a, hipStream_t st);
 int launch_tokenize_scene_bwd_input(const TokInArgs& a, hipStream_t st);
+int launch_tokenize_at_bwd_input(const TokInAtArgs& a, hipStream_t st);
+int launch_scene_fold_at(const SceneFoldAtArgs& a, hipStream_t st);
 int launch_scene_border_zero(float* dscene, long rows, int Hs, int Ws, int rows_in, int cols_in, hipStream_t st);
 int launch_head_bwd_target(const float* dpred, const int* csr_ptr, const int* csr_pos, const float* gout, float gscale, float* dtarget,
                            int B, int S, int N, int P, int K, hipStream_t st);

@@ -939,10 +939,33 @@ class Engine:
             emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_bwd_input")
         return dimg
 
-    def tokenize_windows_input_bwd(self, img, dx0, emb_drop=(0.0, 0), tiles=False):
+    def tokenize_windows_input_bwd(self, img, dx0, emb_drop=(0.0, 0), tiles=False, origins=None, csr=None, out=None, accumulate=False):
         """the input gradient of tokenize_windows: of a window batch (tokenize_input_bwd, nothing masked), or with tiles=True of the
         tiles [B, C, Ht, Wt] whose windows it read in place -- one msst_tokenize_scene_bwd_input over all windows, zeros in the
-        trailing rows and columns that belong to no window"""
+        trailing rows and columns that belong to no window.
+        origins [n, 3] (int32, on the device) with csr = scene.origins_csr(origins, ...): of the scenes img [Bs, C, Hs, Ws] whose listed
+        windows it read in place.  They overlap: one msst_tokenize_at_bwd_input writes the per-window gradients dwin [n, C, N], one
+        msst_scene_fold_at sums them per pixel in its fixed order into dscene -- a new tensor written whole (zeros where no window
+        lies), or `out` [Bs, C, Hs, Ws] fp32; with accumulate the sums start from out's values (a caller's running map)."""
+        if origins is not None:
+            self._require_cuda(img)
+            Bs, C, Hs, Ws = img.shape
+            s, n = self.enc.num_spatial_patches_sqrt, origins.shape[0]
+            if accumulate and out is None:
+                raise ValueError("accumulate needs the running map: out=")
+            if out is None:
+                out = torch.empty(img.shape, dtype=torch.float32, device=img.device)
+            elif tuple(out.shape) != tuple(img.shape) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != img.device:
+                raise ValueError(f"out must be a contiguous fp32 tensor {tuple(img.shape)} on the scene's device")
+            cell_ptr, cell_win = csr
+            dwin = torch.empty(n, C, self.N, dtype=torch.float32, device=img.device)
+            st = _stream()
+            _lib.check(self.lib.msst_tokenize_at_bwd_input(
+                _p(img), _p(origins), *self._tok_params(), _p(dx0), _p(dwin), Bs, Hs, Ws, s, n, self.S, self.P,
+                emb_drop[0], emb_drop[1], st), "msst_tokenize_at_bwd_input")
+            _lib.check(self.lib.msst_scene_fold_at(_p(dwin), _p(cell_ptr), _p(cell_win), _p(out), Bs, C, Hs, Ws, s, n, self.P,
+                                                   int(bool(accumulate)), st), "msst_scene_fold_at")
+            return out
         if not tiles:
             return self.tokenize_input_bwd(img, None, dx0, emb_drop=emb_drop)
         self._require_cuda(img)
@@ -1217,7 +1240,23 @@ class Engine:
         self.ensure()
         if origins.shape[0] < 1:
             raise ValueError("origins lists no window")
-        return self._classify(scene.contiguous().float(), origins.shape[0], origins)
+        return self._classify(scene.contiguous().float(), origins.shape[0], origins)   # (or a ListedWindows: the scene's gradient too)
+
+    def window_alignment(self):
+        """A: a window's logits and gradients keep their bits when its place in the batch moves by a multiple of A windows.  The block
+        kernels pack whole sequences of several windows into 64-row tiles (TileMap, msst_dev.h: 64 // S spectral sequences, 64 // N
+        spatial ones), and a sequence's slot in its tile decides how its few non-zero terms fall into the MFMAs' partial sums -- the
+        last bit of a window's result (1e-7 relative in fp32) depends on its place in the batch modulo A.  saliency.scene_saliency
+        cuts its chunks so that every window keeps its place modulo A."""
+        from math import gcd
+        a = b = 1
+        if 0 < self.S <= 64:
+            ts = 64 // self.S
+            a = ts // gcd(self.N, ts)
+        if 0 < self.N <= 64:
+            ts = 64 // self.N
+            b = ts // gcd(self.S, ts)
+        return a * b // gcd(a, b)
 
     def _classify(self, img, B, tiles):
         """classify / classify_tiles / classify_at: img a batch of B windows, or (tiles is True) the tiles that hold B windows, or
@@ -1527,9 +1566,30 @@ class _EmbedFn(torch.autograd.Function):
         return (None, None, dimg) + _grad_views(eng, ctx.names, needs)
 
 
+class SceneGradSink:
+    """a running scene gradient map (saliency.scene_saliency): every backward of a forward_at(..., scene_grad=sink) folds its windows
+    into `out` [Bs, C, Hs, Ws] fp32 -- the first one writes it whole, the later ones accumulate (msst_scene_fold_at) -- and autograd
+    gets no gradient for the scene"""
+
+    def __init__(self, out):
+        self.out, self.started = out, False
+
+
+class ListedWindows:
+    """the `tiles` slot of _classify / _ClassifyFn for classify_at when the scene's gradient was opted into (forward_at(...,
+    scene_grad=True)): the int32 origins table [n, 3], its inverse index (scene.origins_csr) and optionally the sink the backward
+    folds into.  A bare table in the slot keeps refusing the scene's gradient."""
+
+    def __init__(self, origins, csr, sink=None):
+        self.origins, self.csr, self.sink = origins, csr, sink
+        self.shape = origins.shape
+
+
 def _window_kw(tiles):
     """the `tiles` slot of _classify / _ClassifyFn as tokenize_windows' keywords: a flag (window batch or tiles), or the int32 origins
-    table [n, 3] of classify_at (the windows listed in it, read out of the scenes)"""
+    table [n, 3] of classify_at (the windows listed in it, read out of the scenes; a ListedWindows: its table)"""
+    if isinstance(tiles, ListedWindows):
+        return {"origins": tiles.origins}
     return {"origins": tiles} if torch.is_tensor(tiles) else {"tiles": tiles}
 
 
@@ -1560,9 +1620,16 @@ class _ClassifyFn(torch.autograd.Function):
         dimg = None
         if ctx.needs_input_grad[5]:   # the input (window batch or tiles) asked for its gradient: one more launch that only reads
             if torch.is_tensor(ctx.tiles):
-                raise NotImplementedError("no input gradient through windows at listed origins: they overlap, so d(scene) would "
-                                          "need an accumulating scatter")
-            dimg = eng.tokenize_windows_input_bwd(img, dx0, emb_drop=ctx.emb_drop, tiles=ctx.tiles)
+                raise NotImplementedError("no input gradient through windows at listed origins unless the forward opted in "
+                                          "(forward_at(..., scene_grad=True)): they overlap, so d(scene) is an accumulating fold")
+            if isinstance(ctx.tiles, ListedWindows):   # two more launches that only read: per-window gradients, then the fold
+                at, sink = ctx.tiles, ctx.tiles.sink
+                dimg = eng.tokenize_windows_input_bwd(img, dx0, emb_drop=ctx.emb_drop, origins=at.origins, csr=at.csr,
+                                                      out=sink.out if sink else None, accumulate=bool(sink and sink.started))
+                if sink:
+                    sink.started, dimg = True, None
+            else:
+                dimg = eng.tokenize_windows_input_bwd(img, dx0, emb_drop=ctx.emb_drop, tiles=ctx.tiles)
         if any(needs):   # (a fully frozen model: the tokenizer backward writes parameter gradients only, nobody reads them)
             eng.tokenize_windows_bwd(img, dx0, emb_drop=ctx.emb_drop, **_window_kw(ctx.tiles))
         return (None,) * 5 + (dimg,) + _grad_views(eng, ctx.names, needs)

@@ -19,7 +19,9 @@ maps ``[Bs, 96, Hs, Ws]`` (``msst_pool_spectral_fwd``, ``msst_scene_embed_assemb
 Windows at listed positions (``ViTSpatialSpectral.forward_at`` / ``predict_at``, ``msst_tokenize_at_fwd`` / ``_bwd``): the sampling
 protocol of the reference's ``Houston2018Dataset`` (``src/data_houston2018.py``) on a sparsely labelled scene -- one window centred at
 every labelled pixel, or windows at random positions -- with the windows read in place.  ``centre_origins``, ``random_origins`` and
-``window_labels`` build the origin tables and the labels that go with them.
+``window_labels`` build the origin tables and the labels that go with them.  ``forward_at(..., scene_grad=True)`` also gives the scene its
+gradient: listed windows overlap, so the per-window input gradients (``msst_tokenize_at_bwd_input``) are summed per pixel in a fixed order
+(``msst_scene_fold_at``) through the inverse index ``origins_csr`` builds.
 """
 from collections import namedtuple
 
@@ -168,16 +170,37 @@ def _check_origins(model, scene, origins, check):
                              f"[0, {hi[0]}] x [0, {hi[1]}] x [0, {hi[2]}]")
 
 
-def forward_at(model, scene, origins, check=True):
-    """See ViTSpatialSpectral.forward_at."""
+def origins_csr(origins, Bs, Hs, Ws):
+    """The inverse index of an origins table [n, 3] = (scene, y0, x0) over origin cells, what ``msst_scene_fold_at`` finds the windows
+    covering a pixel through: a window's cell is (scene * Hs + y0) * Ws + x0.  -> (cell_ptr int32 [Bs Hs Ws + 1], the CSR row pointers;
+    cell_win int32 [n], the window numbers sorted by cell, ascending within a cell).  Torch ops on the table's device (a stable sort of
+    the cell key, bincount, cumsum), no read-back; the rows must lie inside the scenes (``forward_at`` checks)."""
+    o = origins.long()
+    cells = int(Bs) * int(Hs) * int(Ws)
+    key = (o[:, 0] * int(Hs) + o[:, 1]) * int(Ws) + o[:, 2]
+    cell_win = torch.sort(key, stable=True).indices.to(torch.int32)
+    cell_ptr = torch.zeros(cells + 1, dtype=torch.int32, device=o.device)
+    cell_ptr[1:] = torch.cumsum(torch.bincount(key, minlength=cells)[:cells], dim=0)
+    return cell_ptr, cell_win
+
+
+def forward_at(model, scene, origins, check=True, scene_grad=False):
+    """See ViTSpatialSpectral.forward_at.  scene_grad may also be an ``engine.SceneGradSink`` (``saliency.scene_saliency``): the backward
+    then folds into the sink's running map instead of handing autograd a gradient for the scene."""
     _check_origins(model, scene, origins, check)
-    if scene.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError("forward_at gives no gradient for the scene: listed windows overlap, so d(loss)/d(scene) needs an "
-                                  "accumulating scatter the tokenizer backward does not have; detach the scene (parameter gradients "
-                                  "are computed), or stack the windows and call the model on them")
+    wants = scene.requires_grad and torch.is_grad_enabled()
+    if wants and not scene_grad:
+        raise NotImplementedError("forward_at gives no gradient for the scene unless asked: listed windows overlap, so d(loss)/d(scene) "
+                                  "is an accumulating fold of the per-window input gradients -- pass scene_grad=True for it, or detach "
+                                  "the scene (parameter gradients are computed)")
     eng = model.engine()
     eng._require_cuda(scene)
-    return eng.classify_at(scene, origins.to(device=scene.device, dtype=torch.int32).contiguous())
+    table = origins.to(device=scene.device, dtype=torch.int32).contiguous()
+    if wants:
+        from .engine import ListedWindows, SceneGradSink
+        Bs, _, Hs, Ws = scene.shape
+        table = ListedWindows(table, origins_csr(table, Bs, Hs, Ws), scene_grad if isinstance(scene_grad, SceneGradSink) else None)
+    return eng.classify_at(scene, table)
 
 
 def predict_at(model, scene, origins, return_logits=False, max_windows=SCENE_MAX_WINDOWS):

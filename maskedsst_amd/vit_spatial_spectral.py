@@ -352,7 +352,7 @@ class ViTSpatialSpectral(nn.Module):
             raise ValueError(f"tiles of {tuple(tiles.shape[2:])} are smaller than one {s} x {s} window")
         return self.engine().classify_tiles(tiles)
 
-    def forward_at(self, scene, origins, check=True):
+    def forward_at(self, scene, origins, check=True, scene_grad=False):
         """forward(the stacked windows of scene at origins) without the stacked copy: the sampling of a sparsely labelled scene (the
         reference's Houston2018Dataset, src/data_houston2018.py:303-329 -- a window centred at every labelled pixel, or windows at
         random positions).  scene [Bs, channels, Hs, Ws] fp32 on the device; origins an integer tensor [n, 3] on either device, row i
@@ -364,10 +364,15 @@ class ViTSpatialSpectral(nn.Module):
         0 <= scene < Bs, 0 <= y0 <= Hs - image_size, 0 <= x0 <= Ws - image_size; check=False skips that read-back: the kernels then
         trust the table.  Raises ValueError -- before a device is asked for -- for a scene of the wrong rank or band count or smaller
         than one window, and for a table of the wrong shape or dtype or with no row; NotImplementedError for a scene that requires a
-        gradient (overlapping windows would need an accumulating input gradient), for an encoder wrapped in SimMIM under grad, and
-        for the embedding-dropout limit of forward_windows."""
+        gradient without scene_grad (the windows overlap: its gradient is an accumulating fold, opt-in), for an encoder wrapped in
+        SimMIM under grad, and for the embedding-dropout limit of forward_windows.
+        scene_grad=True: a scene that requires a gradient gets it -- scene.grad = the per-window input gradients (what forward gives
+        the stacked windows) summed per pixel over the windows covering it, in the fixed order of msst_scene_fold_at (ascending y0, x0,
+        row of the table): no atomics, equal bits on every run; zero where no window lies.  In training (dropout, full finetune,
+        linear_eval) and on a frozen eval() model; the two launches only read, so the parameter gradients keep the bits of a run with
+        the scene detached."""
         from .scene import forward_at
-        return forward_at(self, scene, origins, check)
+        return forward_at(self, scene, origins, check, scene_grad)
 
     def predict_at(self, scene, origins, return_logits=False, max_windows=None):
         """Classes at listed windows (the Houston test protocol: predictions only where a label exists): forward_at under no_grad as
