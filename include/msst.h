@@ -203,6 +203,37 @@ int msst_tokenize_at_bwd(const float* scene, const int32_t* origins, const float
                          float* dpos_b, int pos_split, int Bs, int Hs, int Ws, int window, int nwin, int S, int P,
                          float emb_dropout_p, uint32_t seed, void* stream);
 
+/* SimMIM pre-training on windows at listed scene positions (SimMIMSpatialSpectral.forward_at / forward_windows: the masked loss of
+ * windows read straight out of resident tiles, no stacked copy).  Additive under MSST_VERSION 109: no struct and no existing
+ * signature changes.  origins, the scene and THE CALLER'S GUARANTEE of the table's ranges: as for msst_tokenize_at_fwd.
+ *
+ * msst_tokenize_at_fwd_masked: msst_tokenize_at_fwd plus mask_token [96] and mask [nwin][T] (uint8, 1 = masked), T = S window window,
+ * in WINDOW coordinates: the layout of msst_tokenize_fwd's mask.  No embedding dropout (the SimMIM path has none).  out is
+ * bit-identical to msst_tokenize_fwd on the copied windows with the same mask.
+ * msst_tokenize_at_bwd_masked: msst_tokenize_at_bwd plus that mask and dmask_token [96] (may be null, as in msst_tokenize_bwd): a
+ * masked token's gradient goes to the mask token and the position table only.  For equal nchunk every gradient output, dmask_token
+ * included, is bit-identical to msst_tokenize_bwd on the copied windows.  nwin >= 1.
+ * msst_head_at_fwd: msst_head_fwd of nwin windows with its reconstruction target read from the scene:
+ * target = scene[s][c P + p][y0 + n / window][x0 + n % window] for masked token idx = c N + n of the window at (s, y0, x0).  The same
+ * kernel body, grid, partial sums and final reduction: loss, dpred, pred and partial have the bits of msst_head_fwd on the copied
+ * windows.  msst_head_bwd takes its results as they are (it never reads the image).  nwin >= 1, 1 <= K <= T.
+ * All three check their arguments before anything is enqueued, in the order of msst_tokenize_at_fwd: MSST_ERR_BADARG for a size below
+ * 1 (nwin = 0 is an empty call of the forward tokenizer only, nwin < 0 always an error); MSST_ERR_UNSUPPORTED outside window <= Hs, Ws,
+ * window * window <= 64, P <= 16 (the head: also nwin <= 65535; the forward tokenizer: that for P != 10 or window != 8);
+ * MSST_ERR_BADARG for a null required pointer (pred, dpos_a and dmask_token may be null) or K > T. */
+int msst_tokenize_at_fwd_masked(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
+                                const float* b_emb, const float* post_g, const float* post_b, const float* pos_a, const float* pos_b,
+                                int pos_split, const float* mask_token, const uint8_t* mask, float* out, int Bs, int Hs, int Ws,
+                                int window, int nwin, int S, int P, void* stream);
+int msst_tokenize_at_bwd_masked(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
+                                const float* b_emb, const float* post_g, const float* post_b, const uint8_t* mask, const float* dx0,
+                                float* slab, int nchunk, float* dpre_g, float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g,
+                                float* dpost_b, float* dpos_a, float* dpos_b, int pos_split, float* dmask_token, int Bs, int Hs, int Ws,
+                                int window, int nwin, int S, int P, void* stream);
+int msst_head_at_fwd(const float* y, const float* scene, const int32_t* origins, const int32_t* idx, const float* w_pix,
+                     const float* b_pix, int per_block, float* dpred, float* pred /*optional*/, float* partial, float* loss, int Bs,
+                     int Hs, int Ws, int window, int nwin, int S, int P, int K, void* stream);
+
 /* msst_scene_assemble: adds the per-window logits win_logits [nwin][n_classes][window*window] (msst_cls_head_fwd of windows
  * win0 .. win0 + nwin - 1) into the running per-pixel sums logits [Bs][n_classes][Hs][Ws] (fp32).  The calls of one scene batch
  * must cover windows 0, 1, ... in order (any split into calls); logits needs no initialisation.  finalize != 0 (the last call, after

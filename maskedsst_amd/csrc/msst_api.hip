@@ -439,6 +439,22 @@ int msst_tokenize_at_fwd(const float* scene, const int32_t* origins, const float
     return fail(launch_tokenize_at_fwd(a, (hipStream_t)stream), "msst_tokenize_at_fwd");
 }
 
+int msst_tokenize_at_fwd_masked(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
+                                const float* b_emb, const float* post_g, const float* post_b, const float* pos_a, const float* pos_b,
+                                int pos_split, const float* mask_token, const uint8_t* mask, float* out, int Bs, int Hs, int Ws,
+                                int window, int nwin, int S, int P, void* stream) {
+    const bool pointers = scene && origins && pre_g && pre_b && w_emb && b_emb && post_g && post_b && pos_a && (pos_b || !pos_split) &&
+                          mask_token && mask && out;
+    if (int rc = at_args(pointers, Bs, Hs, Ws, window, nwin, 0, S, P, pos_split)) return fail(rc, "msst_tokenize_at_fwd_masked");
+    if ((P != 10 || window != 8) && nwin > 65535) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_at_fwd_masked (more than 65535 windows)");
+    TokArgs a;
+    fill_tok(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, pos_a, pos_b, mask_token, mask, out, nwin, S, window * window, P,
+             pos_split, make_drop(0.f, 0, 255));
+    fill_window(a, Hs, Ws, window, window, 1, 1, 0);
+    a.origins = origins;
+    return fail(launch_tokenize_at_fwd_masked(a, (hipStream_t)stream), "msst_tokenize_at_fwd_masked");
+}
+
 int msst_scene_assemble(const float* win_logits, long win0, int nwin, float* logits, int64_t* classes, int Bs,
                         int n_classes, int Hs, int Ws, int window, int stride, int finalize, void* stream) {
     int nr = 0, nq = 0;
@@ -669,7 +685,23 @@ int msst_head_fwd(const float* y, const float* img, const int32_t* idx, const fl
     HeadArgs a;
     a.y = y; a.img = img; a.idx = idx; a.w_pix = w_pix; a.b_pix = b_pix; a.dpred = dpred; a.pred = pred;
     a.partial = partial; a.B = B; a.S = S; a.N = N; a.T = S * N; a.P = P; a.K = K; a.per_block = per_block;
+    a.origins = nullptr; a.Hs = 0; a.Ws = 0; a.win = 0;   // (msst_head_at_fwd's target source: unread here)
     return fail(launch_head_fwd(a, loss, (hipStream_t)stream), "msst_head_fwd");
+}
+
+int msst_head_at_fwd(const float* y, const float* scene, const int32_t* origins, const int32_t* idx, const float* w_pix,
+                     const float* b_pix, int per_block, float* dpred, float* pred, float* partial, float* loss, int Bs, int Hs, int Ws,
+                     int window, int nwin, int S, int P, int K, void* stream) {
+    if (Bs < 1 || Hs < 1 || Ws < 1 || window < 1 || S < 1 || P < 1 || K < 1 || nwin < 1) return fail(MSST_ERR_BADARG, "msst_head_at_fwd");
+    if (window > Hs || window > Ws || window > 8 || P > 16 || nwin > 65535)   // 65535: one workgroup row per window (grid y)
+        return fail(MSST_ERR_UNSUPPORTED, "msst_head_at_fwd (window <= Hs, Ws, window * window <= 64, P <= 16, nwin <= 65535)");
+    if (!y || !scene || !origins || !idx || !w_pix || !b_pix || !dpred || !partial || !loss || K > S * window * window)
+        return fail(MSST_ERR_BADARG, "msst_head_at_fwd");
+    HeadArgs a;
+    a.y = y; a.img = scene; a.idx = idx; a.w_pix = w_pix; a.b_pix = b_pix; a.dpred = dpred; a.pred = pred;
+    a.partial = partial; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P; a.K = K; a.per_block = per_block;
+    a.origins = origins; a.Hs = Hs; a.Ws = Ws; a.win = window;
+    return fail(launch_head_at_fwd(a, loss, (hipStream_t)stream), "msst_head_at_fwd");
 }
 
 int msst_head_bwd(const float* y, const float* dpred, const int32_t* csr_ptr, const int32_t* csr_pos,
@@ -994,6 +1026,26 @@ int msst_tokenize_at_bwd(const float* scene, const int32_t* origins, const float
     a.origins = origins;
     if (int rc = launch_tokenize_at_bwd(a, nchunk, st)) return fail(rc, "msst_tokenize_at_bwd");
     return tokenize_bwd_reduce(slab, nchunk, dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, nullptr,
+                               S, a.N, P, st);
+}
+
+int msst_tokenize_at_bwd_masked(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
+                                const float* b_emb, const float* post_g, const float* post_b, const uint8_t* mask, const float* dx0,
+                                float* slab, int nchunk, float* dpre_g, float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g,
+                                float* dpost_b, float* dpos_a, float* dpos_b, int pos_split, float* dmask_token, int Bs, int Hs, int Ws,
+                                int window, int nwin, int S, int P, void* stream) {
+    const bool pointers = scene && origins && pre_g && pre_b && w_emb && b_emb && post_g && post_b && mask && dx0 && slab && dpre_g &&
+                          dpre_b && dw_emb && db_emb && dpost_g && dpost_b && (dpos_b || !pos_split || !dpos_a);
+    if (int rc = at_args(pointers, Bs, Hs, Ws, window, nwin, 1, S, P, pos_split)) return fail(rc, "msst_tokenize_at_bwd_masked");
+    if (nchunk < 1) return fail(MSST_ERR_BADARG, "msst_tokenize_at_bwd_masked");
+    hipStream_t st = (hipStream_t)stream;
+    TokAtBwdArgs a;
+    fill_tok_bwd(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, mask, dx0, slab, nwin, S, window * window, P,
+                 make_drop(0.f, 0, 255));
+    fill_window(a, Hs, Ws, window, window, 1, 1, 0);
+    a.origins = origins;
+    if (int rc = launch_tokenize_at_bwd(a, nchunk, st)) return fail(rc, "msst_tokenize_at_bwd_masked");
+    return tokenize_bwd_reduce(slab, nchunk, dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, dmask_token,
                                S, a.N, P, st);
 }
 

@@ -25,12 +25,13 @@ namespace msst {
 // mask [B][T];  TOK_SCENE: the same pixel of window b of a scene, scene[s, c P + k, y0 + n / win, x0 + n % win] (TokArgs scene fields;
 // no mask);  TOK_SCENE_MASKED: those pixels, and token (c, n) is masked where the scene mask [Bs][S][Hs][Ws] (a.mask) is non-zero at
 // (s, c, y0 + n / win, x0 + n % win) (msst_tokenize_scene_fwd_masked);  TOK_AT: TOK_SCENE with (s, y0, x0) of window b read from the
-// table a.origins instead of computed from its number (msst_tokenize_at_fwd).  Nothing else differs: the embedding dropout addresses
-// an element by its place in `out` in all four (msst_tokenize_scene_fwd / _fwd_masked pass p = 0).
-enum { TOK_BATCH = 0, TOK_SCENE = 1, TOK_SCENE_MASKED = 2, TOK_AT = 3 };
+// table a.origins instead of computed from its number (msst_tokenize_at_fwd);  TOK_AT_MASKED: TOK_AT's pixels with TOK_BATCH's mask, [B][T]
+// in window coordinates (msst_tokenize_at_fwd_masked).  Nothing else differs: the embedding dropout addresses an element by its place
+// in `out` in all five (msst_tokenize_scene_fwd / _fwd_masked / _at_fwd_masked pass p = 0).
+enum { TOK_BATCH = 0, TOK_SCENE = 1, TOK_SCENE_MASKED = 2, TOK_AT = 3, TOK_AT_MASKED = 4 };
 template <int SRC>
 __device__ __forceinline__ const float* tok_window_origin(const TokArgs& a, int b) {
-    if constexpr (SRC == TOK_AT) return listed_window_origin(a, b);
+    if constexpr (SRC == TOK_AT || SRC == TOK_AT_MASKED) return listed_window_origin(a, b);
     else return scene_window_origin(a, b);
 }
 template <int PC, int SRC>
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(256) void tokenize_fwd_kernel(TokArgs a) { tokenize
 // Position rows, bias, both LayerNorms' vectors and the mask token are tile invariant for a wave: registers / LDS.
 // SRC: the source addressing policy of tokenize_fwd_body (TOK_SCENE: windows of a scene instead of a batch of cubes, no mask;
 // TOK_SCENE_MASKED: with the scene mask; TOK_AT: windows at listed origins, one table row read per window where the next sample's
-// pixels are requested).
+// pixels are requested; TOK_AT_MASKED: those, and the mask byte of a batch of cubes).
 // ------------------------------------------------------------------------------------------
 template <int SRC>
 __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
@@ -179,6 +180,7 @@ __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
 #pragma unroll
             for (int ks = 0; ks < 3; ++ks) { const int k = 4 * ks + g; px[ks] = src[(k < P ? k : 0) * plane]; }
             if constexpr (SRC == TOK_SCENE_MASKED) mk = scene_window_mask(a, bc, c)[(long)(n / a.win) * a.Ws + n % a.win];
+            else if constexpr (SRC == TOK_AT_MASKED) mk = a.mask[(long)bc * a.T + t];
             else mk = 0;
         } else {
             const float* src = a.img + ((long)bc * a.S + c) * P * N + n;
@@ -834,7 +836,10 @@ template __global__ void block_fwd_kernel<PBF16>(BlockArgs);
 // grid (ceil(K/64), B), 256 threads: 4 threads per masked entry, 24 features each.
 // Writes per-workgroup partial |.| sums (deterministic two-stage reduction) and
 // dpred = sign(pred - target) for the backward.
+// AT: the target source.  false: the stacked cube img [B][S*P][N]; true: the scene, at the window origins[b] (msst_head_at_fwd: HeadArgs
+// scene fields).  The grid, the thread-to-entry map and every sum are the same: equal pixels give equal bits.
 // ==========================================================================================
+template <bool AT>
 __global__ __launch_bounds__(256) void head_fwd_kernel(HeadArgs a) {
     __shared__ float red[4];
     const int tid = threadIdx.x, e = tid >> 2, part = tid & 3;
@@ -853,6 +858,10 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadArgs a) {
         }
         const int wc = a.per_block ? c : 0;
         const float* Wp = a.w_pix + (long)wc * P * 96 + part * 24;
+        // AT: band 0 of the token's patch at its pixel of the window, and the floats from one band of the scene to the next
+        const long plane = AT ? (long)a.Hs * a.Ws : 0;
+        const float* tsrc = nullptr;
+        if constexpr (AT) tsrc = listed_window_origin(a, b) + (long)c * P * plane + (long)(n / a.win) * a.Ws + n % a.win;
         for (int p = 0; p < P; ++p) {
             float acc = 0.f;
 #pragma unroll
@@ -860,7 +869,9 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadArgs a) {
             acc += __shfl_xor(acc, 1); acc += __shfl_xor(acc, 2);
             if (part == 0) {
                 const float pred = acc + a.b_pix[wc * P + p];
-                const float target = a.img[((long)b * a.S * P + (long)c * P + p) * a.N + n];
+                float target;
+                if constexpr (AT) target = tsrc[p * plane];
+                else target = a.img[((long)b * a.S * P + (long)c * P + p) * a.N + n];
                 const float d = pred - target;
                 lsum += fabsf(d);
                 a.dpred[((long)b * a.K + k) * P + p] = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
@@ -919,6 +930,7 @@ int launch_tokenize_fwd(const TokArgs& a, hipStream_t st) { return launch_tokeni
 int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_SCENE>(a, st); }
 int launch_tokenize_scene_fwd_masked(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_SCENE_MASKED>(a, st); }
 int launch_tokenize_at_fwd(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_AT>(a, st); }
+int launch_tokenize_at_fwd_masked(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_AT_MASKED>(a, st); }
 
 template <class P>
 static int launch_block_fwd_t(const BlockArgs& a, int grid, hipStream_t st) {
@@ -986,17 +998,20 @@ bool block_fwd_writes_xn(const BlockArgs& a, int prec) {
     return prec == MSST_PREC_BF16 && !(a.dbg & 16);   // both tuned bf16 kernels (head-per-wave for 8 heads, 4-wave otherwise) store their LN1 rows
 }
 
-int launch_head_fwd(const HeadArgs& a, float* loss, hipStream_t st) {
+template <bool AT>
+static int launch_head_fwd_src(const HeadArgs& a, float* loss, hipStream_t st) {
     if (a.P > 16) return MSST_ERR_UNSUPPORTED;
     dim3 grid((a.K + 63) / 64, a.B);
     { ProfScope ps(K_HEAD_FWD, st);
-    hipLaunchKernelGGL(head_fwd_kernel, grid, dim3(256), 0, st, a); }
+    hipLaunchKernelGGL(head_fwd_kernel<AT>, grid, dim3(256), 0, st, a); }
     const int np = grid.x * grid.y;
     const float scale = 1.0f / ((float)a.B * (float)a.K * (float)a.P) / (float)a.K;
     ProfScope ps(K_LOSS_REDUCE, st);
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, st, a.partial, np, scale, loss);
     return (int)hipGetLastError();
 }
+int launch_head_fwd(const HeadArgs& a, float* loss, hipStream_t st) { return launch_head_fwd_src<false>(a, loss, st); }
+int launch_head_at_fwd(const HeadArgs& a, float* loss, hipStream_t st) { return launch_head_fwd_src<true>(a, loss, st); }
 
 }  // namespace msst
 

@@ -83,8 +83,9 @@ struct TokArgs {
     // sample b is window win0 + b, row-major over (scene, window row, window column), origin (r * stride, q * stride), win x win pixels
     long win0;
     int Hs, Ws, win, stride, nq, wps;   // nq: windows per window row, wps: windows per scene
-    // listed origins (msst_tokenize_at_fwd, the kernels' TOK_AT instances only): sample b is the win x win window of scene origins[b][0]
-    // with its top-left pixel at row origins[b][1], column origins[b][2]; of the scene fields only Hs, Ws and win are read
+    // listed origins (msst_tokenize_at_fwd / _at_fwd_masked, the kernels' TOK_AT* instances only): sample b is the win x win window of scene
+    // origins[b][0] with its top-left pixel at row origins[b][1], column origins[b][2]; of the scene fields only Hs, Ws and win are read.
+    // TOK_AT_MASKED: mask is [B][T] in window coordinates, as for a batch of cubes
     const int32_t* origins;  // [B][3]
 };
 
@@ -157,6 +158,10 @@ struct HeadArgs {
     float* pred;         // optional [B][K][P]
     float* partial;      // [B * ceil(K/64)]
     int B, S, N, T, P, K, per_block;
+    // msst_head_at_fwd (head_fwd_kernel<true> only): img is a scene [Bs][S*P][Hs][Ws] and sample b's target the win x win window at
+    // origins[b] = (scene, y0, x0) (listed_window_origin)
+    const int32_t* origins;  // [B][3]
+    int Hs, Ws, win;
 };
 
 struct HeadBwdArgs {
@@ -235,7 +240,8 @@ struct TokSceneBwdArgs : TokBwdArgs {
     long win0;
     int Hs, Ws, win, stride, nq, wps;
 };
-// msst_tokenize_at_bwd (SCENE = true instances over this type): sample b is the window at origins[b] = (scene, y0, x0), TokArgs.origins
+// msst_tokenize_at_bwd / _at_bwd_masked (SCENE = true instances over this type): sample b is the window at origins[b] = (scene, y0, x0),
+// TokArgs.origins; mask null (nothing masked) or [B][T] in window coordinates
 struct TokAtBwdArgs : TokSceneBwdArgs {
     const int32_t* origins;   // [B][3]
 };
@@ -330,6 +336,7 @@ int launch_tokenize_fwd(const TokArgs& a, hipStream_t st);
 int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st);   // the same kernels reading windows of a scene (TokArgs scene fields)
 int launch_tokenize_scene_fwd_masked(const TokArgs& a, hipStream_t st);   // ... with a scene mask (a.mask [Bs][S][Hs][Ws]) and the mask token
 int launch_tokenize_at_fwd(const TokArgs& a, hipStream_t st);      // ... reading the windows listed in a.origins (no mask)
+int launch_tokenize_at_fwd_masked(const TokArgs& a, hipStream_t st);   // ... with a per-window token mask (a.mask [B][T]) and the mask token
 int launch_head_bwd(const HeadBwdArgs& a, int nchunk, hipStream_t st);
 // One reduction segment: dst[(i / row_len) * row_stride + i % row_len] = sum_{k < nslab} src[k * slab_stride + i], i < n
 struct RSeg {
@@ -373,7 +380,7 @@ int launch_block_bwd_ln1(const Ln1BwdArgs& a, int grid, int prec, hipStream_t st
 int launch_block_bwd_ln1mlp(const LnMlpArgs& a, int grid, hipStream_t st);   // msst_bwd5.hip (bf16: LN1 backward of block i + MLP backward of block i - 1)
 int launch_tokenize_bwd(const TokBwdArgs& a, int nchunk, hipStream_t st);
 int launch_tokenize_scene_bwd(const TokSceneBwdArgs& a, int nchunk, hipStream_t st);   // the same kernels reading windows of a scene (no mask)
-int launch_tokenize_at_bwd(const TokAtBwdArgs& a, int nchunk, hipStream_t st);   // ... reading the windows listed in a.origins (no mask)
+int launch_tokenize_at_bwd(const TokAtBwdArgs& a, int nchunk, hipStream_t st);   // ... reading the windows listed in a.origins (a.mask optional)
 int launch_pos_split(const float* dpos, int S, int N, int split, float* dpe, float* dce, hipStream_t st);
 int launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                  float wd, int step, float clamp, float gscale, hipStream_t st);
@@ -401,6 +408,7 @@ int launch_block_fwd(const BlockArgs& a, int prec, hipStream_t st);
 bool block_fwd_writes_xn(const BlockArgs& a, int prec);   // does the kernel launch_block_fwd selects honour a.xn_out?
 bool block_fwd_writes_lse(const BlockArgs& a, int prec);  // ... a.lse_out?  (the role-split kernel: bf16, 8 heads, no selection flags)
 int launch_head_fwd(const HeadArgs& a, float* loss, hipStream_t st);
+int launch_head_at_fwd(const HeadArgs& a, float* loss, hipStream_t st);   // the same kernel, targets read from the scene at a.origins
 // msst_ln.hip: stand-alone LayerNorm over the last axis (D <= 128; D = 96 vectorised)
 int launch_layernorm_fwd(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd, long rows, int D,
                          float eps, hipStream_t st);

@@ -16,8 +16,12 @@ N(0, 1), what ``StandardizeEnMAP`` produces, ``src/data_enmap.py:454-457``) and 
   the launching thread never blocks on it; a staging buffer is reused only after the copy that read
   it has completed (event).
 
-There is no CPU fallback for the model; the loader itself also runs without a GPU (``device="cpu"``
-returns the pinned-or-pageable batch) so that its logic is testable here.
+``ResidentTileLoader`` keeps the same pool on the device instead and hands out positions only: each step is
+``(tiles, origins)`` for ``SimMIMSpatialSpectral.forward_at``, which reads the windows where they lie -- no host
+crop, no staging, nothing but a [B, 3] table crosses PCIe, and a step may take a position per window.
+
+There is no CPU fallback for the model; the loaders themselves also run without a GPU (``device="cpu"``
+returns the pinned-or-pageable batch, or the pool on the host) so that their logic is testable here.
 """
 import queue
 import threading
@@ -105,3 +109,52 @@ class SyntheticCubeLoader:
                 self.ready.get_nowait()
         except queue.Empty:
             pass
+
+
+class ResidentTileLoader:
+    """SyntheticCubeLoader's pool, uploaded once; a step is (tiles [pool_tiles, bands, tile_size, tile_size] on the device -- the same
+    tensor every step --, origins int32 [B, 3] on the host) for ``SimMIMSpatialSpectral.forward_at``.  The same constructor and the
+    same ``draw()`` random stream: with crop="batch" (one position per batch, the contract of the reference's pretrain.py:99-107) the
+    listed windows are SyntheticCubeLoader's batches at the same seed.  crop="sample" draws one position per window instead (after the
+    tile indices, from the same generator).  SyntheticCubeLoader's x is the row offset (``pool[:, :, x:x+S, y:y+S]``), so an origin row
+    is (tile, x, y).  No worker thread, no pinned staging: the table is 12 bytes per window."""
+
+    def __init__(self, batch_size, bands, image_size=8, tile_size=64, pool_tiles=64, steps=None, seed=5,
+                 device="cuda", prefetch=2, zero_pad_bands=0, crop="batch"):
+        if crop not in ("batch", "sample"):
+            raise ValueError(f"crop must be 'batch' (one position per batch) or 'sample' (one per window), got {crop!r}")
+        self.B, self.C, self.S, self.TS = batch_size, bands, image_size, tile_size
+        self.steps, self.crop = steps, crop
+        self.device = torch.device(device)
+        self.rng = np.random.default_rng(seed)
+        g = torch.Generator().manual_seed(seed)
+        pool = torch.randn(pool_tiles, bands, tile_size, tile_size, generator=g)
+        if zero_pad_bands:
+            pool[:, bands - zero_pad_bands:] = 0.0
+        self.pool = pool.to(self.device)
+        self._n = 0
+
+    def draw(self):
+        """(tile indices [B], window origins (x [B], y [B])) of the next batch -- the only random decisions; crop="batch": the draws of
+        SyntheticCubeLoader.draw, its one position repeated"""
+        idx = self.rng.integers(0, self.pool.shape[0], size=self.B)
+        n = self.B if self.crop == "sample" else 1
+        if self.S != self.TS:
+            xy = self.rng.integers(0, self.TS - self.S, size=(n, 2) if self.crop == "sample" else 2).reshape(n, 2)
+        else:
+            xy = np.zeros((n, 2), dtype=np.int64)
+        xy = np.broadcast_to(xy, (self.B, 2))
+        return idx, (xy[:, 0], xy[:, 1])
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self.steps is not None and self._n >= self.steps:
+            raise StopIteration
+        self._n += 1
+        idx, (x, y) = self.draw()
+        return self.pool, torch.from_numpy(np.stack((idx, x, y), axis=1).astype(np.int32))
+
+    def close(self):
+        pass

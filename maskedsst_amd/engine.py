@@ -464,6 +464,23 @@ class Engine:
                 min(chunk, total - win0), S, P, emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_at_fwd")
         return out
 
+    def tokenize_at_masked(self, scene, origins, mask_u8):
+        """the SimMIM path's tokens (mask token substituted, position added, no embedding dropout) of the n listed s x s windows of the
+        scenes scene [Bs, C, Hs, Ws], origins int32 [n, 3] and mask_u8 [n, T] on its device (msst_tokenize_at_fwd_masked) -> [n, T, 96],
+        bit for bit what tokenize gives for the stacked copy with the same mask.  One launch: n <= TILE_WINDOWS_PER_LAUNCH"""
+        self._require_cuda(scene)
+        self.ensure()
+        Bs, _, Hs, Ws = scene.shape
+        S, N, P = self.S, self.N, self.P
+        total = origins.shape[0]
+        out = torch.empty(total, S * N, D, dtype=torch.float32, device=scene.device)
+        split, pos_a, pos_b = self._pos_tables()
+        V = ctypes.c_void_p
+        _lib.check(self.lib.msst_tokenize_at_fwd_masked(
+            _p(scene), _p(origins), *self._tok_params(), V(pos_a), V(pos_b), split, V(self.fp.ptr("mask_token")), _p(mask_u8), _p(out),
+            Bs, Hs, Ws, self.enc.num_spatial_patches_sqrt, total, S, P, _stream()), "msst_tokenize_at_fwd_masked")
+        return out
+
     def blocks_fwd(self, x0, save=True, drop=(0.0, 0)):
         """run the 2*depth fused blocks; returns (list of activations [x0 .. x_2L], list of x1)"""
         acts = [x0]
@@ -615,7 +632,9 @@ class Engine:
                 x1s.append(None)
         return True
 
-    def head_fwd(self, y, img, idx32, want_pred=False):
+    def head_fwd(self, y, img, idx32, want_pred=False, origins=None):
+        """the masked-L1 head over y [B, T, 96] -> (loss, dpred, pred); the targets come from the batch img [B, C, s, s], or with origins
+        (int32 [B, 3] on the device) from the windows listed there of the scenes img [Bs, C, Hs, Ws] (msst_head_at_fwd): the same bits"""
         B, T, _ = y.shape
         S, N, P = self.S, self.N, self.P
         K = idx32.shape[1]
@@ -626,6 +645,13 @@ class Engine:
         loss = torch.empty((), dtype=torch.float32, device=dev)
         per_block = 1 if hasattr(self.mim.to_pixels, "layers") else 0
         V = ctypes.c_void_p
+        if origins is not None:
+            Bs, _, Hs, Ws = img.shape
+            _lib.check(self.lib.msst_head_at_fwd(
+                _p(y), _p(img), _p(origins), _p(idx32), V(self.fp.ptr("to_pixels.w.0")), V(self.fp.ptr("to_pixels.b.0")), per_block,
+                _p(dpred), _p(pred), _p(partial), _p(loss), Bs, Hs, Ws, self.enc.num_spatial_patches_sqrt, B, S, P, K, _stream()),
+                "msst_head_at_fwd")
+            return loss, dpred, pred
         _lib.check(self.lib.msst_head_fwd(
             _p(y), _p(img), _p(idx32), V(self.fp.ptr("to_pixels.w.0")), V(self.fp.ptr("to_pixels.b.0")), per_block,
             _p(dpred), _p(pred), _p(partial), _p(loss), B, S, N, P, K, _stream()), "msst_head_fwd")
@@ -893,6 +919,22 @@ class Engine:
         if with_pos:
             self._fire("tokenizer")
 
+    def tokenize_at_masked_bwd(self, scene, origins, mask_u8, dx0):
+        """backward of tokenize_at_masked: dx0 [n, T, 96] -> the tokenizer's gradients, the position tables' and the mask token's in the
+        flat buffer.  One msst_tokenize_at_bwd_masked over the listed windows, with the nchunk tokenize_bwd takes for as many samples:
+        the same bits"""
+        Bs, _, Hs, Ws = scene.shape
+        total = origins.shape[0]
+        nchunk, slab = self._tok_bwd_slab(total, scene.device)
+        fp, g = self.fp, self.fp.grad
+        V = ctypes.c_void_p
+        split, dpa, dpb = self._pos_tables(g)
+        _lib.check(self.lib.msst_tokenize_at_bwd_masked(
+            _p(scene), _p(origins), *self._tok_params(), _p(mask_u8), _p(dx0), _p(slab), nchunk,
+            *self._tok_params(grad=True), V(dpa), V(dpb), split, V(fp.ptr("mask_token", g)), Bs, Hs, Ws,
+            self.enc.num_spatial_patches_sqrt, total, self.S, self.P, _stream()), "msst_tokenize_at_bwd_masked")
+        self._fire("tokenizer")
+
     def tokenize_windows_bwd(self, img, dx0, emb_drop=(0.0, 0), tiles=False, origins=None):
         """backward of tokenize_windows: dx0 [windows, T, 96] -> the tokenizer's gradients in the flat buffer.  Tiles: one
         msst_tokenize_scene_bwd over all windows, with the nchunk tokenize_bwd takes for as many samples -- the same bits.
@@ -1068,6 +1110,31 @@ class Engine:
             loss, _, _ = self.head_fwd(acts[-1], img, idx32)
             return loss
         return _SimMIMLossFn.apply(self, names, self.dropout_state(), img, mask_u8, idx32, csr_ptr, csr_pos, *params)
+
+    def simmim_loss_at(self, tiles, origins, bool_mask, idx):
+        """simmim_loss of the windows listed in origins (int32 [n, 3] on the tiles' device: tile, y0, x0) of the resident tiles
+        [Bs, C, Ht, Wt], read where they lie: no stacked copy.  bool_mask / idx: one row per window, as simmim_loss takes them.  The
+        loss and, through autograd, every parameter gradient have the bits of simmim_loss on the stacked windows; the tiles get no
+        gradient (SimMIMSpatialSpectral.forward_at refuses tiles that ask for one)"""
+        self._require_cuda(tiles)
+        self.ensure()
+        dev = tiles.device
+        T = self.S * self.N
+        tiles = tiles.contiguous()
+        from .masking import inverse_csr
+        bm = bool_mask.cpu().numpy() if torch.is_tensor(bool_mask) else np.asarray(bool_mask)
+        ix = idx.cpu().numpy() if torch.is_tensor(idx) else np.asarray(idx)
+        ptr, pos = inverse_csr(ix, T)
+        mask_u8, idx32, csr_ptr, csr_pos = self._upload(dev, bm.astype(np.uint8), ix.astype(np.int32), ptr, pos)
+        names = [n for n, _ in self.trainable()]
+        params = [p for _, p in self.trainable()]
+        if not torch.is_grad_enabled() or not any(p.requires_grad for p in params):
+            self.prep_weights()
+            x0 = self.tokenize_at_masked(tiles, origins, mask_u8)
+            acts, _ = self.blocks_fwd(x0, save=False, drop=self.dropout_state())
+            loss, _, _ = self.head_fwd(acts[-1], tiles, idx32, origins=origins)
+            return loss
+        return _SimMIMLossAtFn.apply(self, names, self.dropout_state(), tiles, origins, mask_u8, idx32, csr_ptr, csr_pos, *params)
 
     # ------------------------------------------------------------------ encoder-level API (inference)
     def _block_param_names(self):
@@ -1495,6 +1562,37 @@ class _SimMIMLossFn(torch.autograd.Function):
         if any(needs):   # (a fully frozen model: the tokenizer backward writes parameter gradients only, nobody reads them)
             eng.tokenize_bwd(img, mask_u8, dx0)
         return (None, None, None, dimg) + (None,) * 4 + _grad_views(eng, ctx.names, needs)
+
+
+class _SimMIMLossAtFn(torch.autograd.Function):
+    """_SimMIMLossFn over windows at listed positions of resident tiles (Engine.simmim_loss_at): the tokenizer and the head read the
+    windows out of the tiles, everything between them is the same sequence.  The tiles receive no gradient."""
+
+    @staticmethod
+    def forward(ctx, eng, names, drop, tiles, origins, mask_u8, idx32, csr_ptr, csr_pos, *params):
+        eng.prep_weights()
+        x0 = eng.tokenize_at_masked(tiles, origins, mask_u8)
+        acts, x1s = eng.blocks_fwd(x0, save=True, drop=drop)
+        ctx.drop = drop
+        loss, dpred, _ = eng.head_fwd(acts[-1], tiles, idx32, origins=origins)
+        ctx.eng = eng
+        ctx.names = names
+        ctx.stash = (tiles, origins, mask_u8, csr_ptr, csr_pos, acts, x1s, dpred)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        eng = ctx.eng
+        tiles, origins, mask_u8, csr_ptr, csr_pos, acts, x1s, dpred = ctx.stash
+        ctx.stash = None
+        needs = ctx.needs_input_grad[9:]
+        _refuse_accumulation(eng, ctx.names, needs)
+        gout = gout.contiguous().float()
+        dy = eng.head_bwd(acts[-1], dpred, csr_ptr, csr_pos, gout)
+        dx0 = eng.blocks_bwd(acts, x1s, dy, drop=ctx.drop)
+        if any(needs):   # (a fully frozen model: the tokenizer backward writes parameter gradients only, nobody reads them)
+            eng.tokenize_at_masked_bwd(tiles, origins, mask_u8, dx0)
+        return (None,) * 9 + _grad_views(eng, ctx.names, needs)
 
 
 def _refuse_accumulation(eng, names, needs=None):

@@ -111,6 +111,62 @@ class SimMIMSpatialSpectral(nn.Module):
         self.last_masks = masks
         return eng.simmim_loss(img, masks[0], masks[1])
 
+    # one window per row of the masked-L1 head's grid (msst_head_at_fwd)
+    MAX_WINDOWS_AT = 65535
+
+    def forward_at(self, tiles, origins, masks=None, check=True):
+        """forward(the stacked windows of tiles at origins, masks) without the stacked copy: pre-training on windows read straight out
+        of resident tiles -- several windows per tile, or windows at chosen positions (labelled or cloud-free pixels).  tiles
+        [Bs, bands, Ht, Wt] fp32 on the device; origins an integer tensor [n, 3] on either device, row i = (tile index, y0, x0) of the
+        top-left pixel of window i.  Windows may overlap, repeat and come in any order.  masks: None draws ``draw_masks(n)``; or the
+        (bool_mask, idx) pair ``forward`` takes, one row per window; ``last_masks`` is set as ``forward`` sets it.  -> the scalar loss,
+        bit for bit ``self(stacked windows, masks)``, and through ``backward`` the same parameter gradients, in training (dropout) and
+        in eval() / under no_grad.
+        check=True validates the table's values (one reduction and one read-back) and raises ValueError naming the first row outside
+        the tiles; check=False skips that read-back: the kernels then trust the table.  Raises ValueError -- before a device is asked
+        for -- for tiles of the wrong rank, dtype or band count or smaller than one window, a table of the wrong shape or dtype or
+        with no row or with more than 65535 rows, and masks that are not [n, tokens] / [n, masked tokens]; NotImplementedError for
+        tiles that require a gradient (a fold of the tokenizer's input gradient plus the target's: not built)."""
+        from .scene import _check_origins
+        enc = self.encoder
+        _check_origins(enc, tiles, origins, check)
+        if tiles.dtype != torch.float32:
+            raise ValueError(f"tiles must be a float32 tensor, got {tiles.dtype}")
+        n = origins.shape[0]
+        if n < 1 or n > self.MAX_WINDOWS_AT:
+            raise ValueError(f"origins lists {n} windows: one call takes 1 to {self.MAX_WINDOWS_AT} (one row of the head's grid each)")
+        if masks is not None:
+            T, K = enc.num_patches, int(self.masking_ratio * enc.num_patches)
+            pair = [np.asarray(m.cpu() if torch.is_tensor(m) else m) for m in masks] if isinstance(masks, (tuple, list)) else []
+            if len(pair) != 2 or pair[0].dtype != np.bool_ or pair[0].shape != (n, T) or pair[1].dtype.kind not in "iu" or pair[1].shape != (n, K):
+                raise ValueError(f"masks must be the pair (bool [{n}, {T}] token mask, integer [{n}, {K}] masked token indices) that "
+                                 f"draw_masks({n}) gives, got {[(str(m.dtype), m.shape) for m in pair] or type(masks)}")
+        if tiles.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("forward_at gives no gradient for the tiles: it would be a fold of the tokenizer's input gradient "
+                                      "plus the reconstruction target's over overlapping windows -- detach the tiles (parameter "
+                                      "gradients are computed)")
+        eng = self.engine()
+        eng._require_cuda(tiles)
+        if masks is None:
+            masks = self.draw_masks(n)
+        self.last_masks = masks
+        table = origins.to(device=tiles.device, dtype=torch.int32).contiguous()
+        return eng.simmim_loss_at(tiles, table, masks[0], masks[1])
+
+    def forward_windows(self, tiles, masks=None):
+        """forward(stack_image_batch(tiles), masks) without the stacked copy: the loss over every non-overlapping image_size x
+        image_size window of tiles [B, bands, Ht, Wt], windows ordered (tile, window row, window column), trailing Ht % image_size rows
+        and Wt % image_size columns dropped.  ``forward_at`` with that grid as its table: the same kernels, masks, errors and bits."""
+        from .scene import scene_windows
+        s = self.encoder.num_spatial_patches_sqrt
+        if not torch.is_tensor(tiles) or tiles.dim() != 4:
+            raise ValueError(f"scene must be a 4-D tensor [scenes, bands, H, W], got {getattr(tiles, 'shape', type(tiles))}")
+        if tiles.shape[2] < s or tiles.shape[3] < s:
+            raise ValueError(f"scene {tuple(tiles.shape)} is smaller than one {s} x {s} window")
+        grid = scene_windows(tiles.shape[2], tiles.shape[3], s, s)
+        table = torch.tensor([(b, y, x) for b in range(tiles.shape[0]) for y, x in grid], dtype=torch.int32).reshape(-1, 3)
+        return self.forward_at(tiles, table, masks, check=False)
+
     def _token_mask(self, masks, B):
         """the bool [B, T] token mask of `masks`: the (bool_mask, idx) pair forward takes, or the bool mask alone"""
         T = self.encoder.num_patches

@@ -7,7 +7,9 @@ Differences from the reference script, all opt-in or forced by the environment:
   * data: the GeoTIFF readers are out of scope -> ``--synthetic`` (default) samples a pool of standardised
     random tiles shaped like ``EnMAPWorldCoverDataset`` output ([bands, 64, 64]) and takes the same random
     8x8 crop per batch (reference pretrain.py:99-107) through ``maskedsst_amd.data.SyntheticCubeLoader``
-    (worker thread, pinned staging, asynchronous host->device copies);
+    (worker thread, pinned staging, asynchronous host->device copies); ``--resident-tiles`` keeps the pool on the device instead and
+    trains through ``model.forward_at`` on windows read where they lie (``ResidentTileLoader``; ``--crop sample``: a position per
+    window instead of one per batch);
   * wandb is optional (absent here); losses are printed every ``logging_freq`` steps;
   * ``--dp``: one process per GPU under ``python -m torch.distributed.run`` (RCCL gradient all-reduce);
   * optimizer: fused AdamW over the flat parameter buffer (``--torch-optim`` keeps torch.optim.AdamW
@@ -24,7 +26,7 @@ import torch
 
 from maskedsst_amd import ViTSpatialSpectral, SimMIMSpatialSpectral
 from maskedsst_amd.config import get_pretrain_config
-from maskedsst_amd.data import SyntheticCubeLoader
+from maskedsst_amd.data import ResidentTileLoader, SyntheticCubeLoader
 from maskedsst_amd.optim import FusedAdamW, attach_data_parallel, dp_mean
 
 SEED = 5
@@ -69,6 +71,11 @@ def build_parser():
     ap.add_argument("--recon-tiles", action="store_true",
                     help="after every validation pass print one more line: the masked mean absolute error of model.reconstruct_scene "
                          "over the whole validation tiles (every window), and its three worst bands")
+    ap.add_argument("--resident-tiles", action="store_true",
+                    help="keep the synthetic tile pool on the device and train through model.forward_at on windows read straight out "
+                         "of it (no host crop, no per-step copy of the windows); with --crop batch the same losses as the default loader")
+    ap.add_argument("--crop", default="batch", choices=["batch", "sample"],
+                    help="with --resident-tiles: one window position per batch (the reference's crop) or one per window")
     return ap
 
 
@@ -91,6 +98,8 @@ def recon_line(model, window, epoch):
 
 def main():
     args = build_parser().parse_args()
+    if args.crop != "batch" and not args.resident_tiles:
+        raise SystemExit("--crop sample needs --resident-tiles (the host loader cuts one position per batch)")
 
     random.seed(SEED); np.random.seed(SEED); torch.manual_seed(SEED)
     if not torch.cuda.is_available():
@@ -165,11 +174,19 @@ def main():
     step, losses, t0 = 0, [], time.time()
     for epoch in range(config.epoch):
         model.train()
-        loader = SyntheticCubeLoader(per_rank, config.n_bands, image_size=config.image_size, pool_tiles=args.pool_tiles,
-                                     steps=steps_per_epoch, seed=SEED + 1000 * rank + epoch, device=device)
+        loader_kw = dict(image_size=config.image_size, pool_tiles=args.pool_tiles, steps=steps_per_epoch,
+                         seed=SEED + 1000 * rank + epoch, device=device)
+        if args.resident_tiles:
+            loader = ResidentTileLoader(per_rank, config.n_bands, crop=args.crop, **loader_kw)
+        else:
+            loader = SyntheticCubeLoader(per_rank, config.n_bands, **loader_kw)
         for img in loader:
             optimizer.zero_grad()
-            loss = model(img)
+            if args.resident_tiles:
+                tiles, origins = img
+                loss = model.forward_at(tiles, origins, check=False)   # the loader's own table: inside the tiles by construction
+            else:
+                loss = model(img)
             loss.backward()
             if reducer is not None:
                 s = reducer.finish()
@@ -190,6 +207,9 @@ def main():
         loader.close()
         if epoch % config.model_save_freq == 0:     # reference pretrain.py:135-151
             if args.save_dir and rank == 0:
+                if args.resident_tiles:   # the checkpoint's "input": the last step's windows, as the host loader would have cut them
+                    s_ = config.image_size
+                    img = torch.stack([tiles[t, :, x:x + s_, y:y + s_] for t, x, y in origins.tolist()])
                 save_checkpoint(args.save_dir, epoch, model, optimizer, config, losses, img)
             if epoch == 10 and config.model_save_freq == 1:
                 config.model_save_freq = 10
