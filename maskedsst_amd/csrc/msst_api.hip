@@ -193,39 +193,85 @@ static BlockWeights to_bw(const MsstBlockWeights* w) {
 }
 
 // ------------------------------------------------------------------------------------------
-// the tokenizer's argument blocks, filled in one place each
+// the tokenizer: host-only pointer groups and window source, one argument check, and the argument blocks filled in one place each
 // ------------------------------------------------------------------------------------------
-// what TokArgs, TokBwdArgs (and its scene variants) and TokInArgs share: the source, the parameters, the shape, the dropout stream
+// what every tokenizer entry point reads: the source tensor (a batch, tiles or scenes) and the six parameter tensors
+struct TokPtrs {
+    const float *img, *pre_g, *pre_b, *w_emb, *b_emb, *post_g, *post_b;
+    bool all_set() const { return img && pre_g && pre_b && w_emb && b_emb && post_g && post_b; }
+};
+// where a parameter backward writes: the six parameter gradients, the position tables' (dpos_a null: applied by the caller) and the
+// mask token's (null: none)
+struct TokGradPtrs {
+    float *dpre_g, *dpre_b, *dw_emb, *db_emb, *dpost_g, *dpost_b, *dpos_a, *dpos_b;
+    int pos_split;
+    float* dmask_token;
+    bool all_set() const { return dpre_g && dpre_b && dw_emb && db_emb && dpost_g && dpost_b && (dpos_b || !pos_split || !dpos_a); }
+};
+// where the samples of a call lie in scenes [Bs][S*P][Hs][Ws]: sample b is window win0 + b of the grid (window, stride), row-major over
+// (scene, window row, window column) -- the checks fill nq (windows per window row) and wps (windows per scene) -- or, listed, the
+// window at origins[b] = (scene, y0, x0): stride = window, win0 = 0, of which the kernels read only Hs, Ws and window
+struct WinSrc {
+    int Bs, Hs, Ws, window, stride;
+    long win0;
+    int nwin;
+    bool listed = false;
+    const int32_t* origins = nullptr;
+    int nq = 1;
+    long wps = 1;
+};
+// window grid of a scene: false when the shapes are not a valid (scene, window, stride) triple
+static bool scene_grid(int Bs, int Hs, int Ws, int window, int stride, int* nr, int* nq) {
+    if (Bs < 1 || window < 1 || stride < 1 || stride > window || Hs < window || Ws < window) return false;
+    *nr = (Hs - window) / stride + 1;
+    *nq = (Ws - window) / stride + 1;
+    return true;
+}
+// the argument check of every training entry point over a window source, in this order: sizes below 1 (BADARG), shapes outside the
+// kernels' limits (UNSUPPORTED), a null required pointer (the caller's `pointers`; a listed source's table counts) or a pos_split outside
+// [0, 96) (BADARG), windows beyond the scenes' grids (BADARG; the value ranges of a listed table are the caller's guarantee).
+// min_nwin: 0 or 1
+static int check_src(WinSrc& w, bool pointers, int min_nwin, int S, int P, int pos_split) {
+    if (w.Bs < 1 || w.Hs < 1 || w.Ws < 1 || w.window < 1 || w.stride < 1 || S < 1 || P < 1 || w.nwin < min_nwin || w.win0 < 0)
+        return MSST_ERR_BADARG;
+    if (w.stride > w.window || w.window > w.Hs || w.window > w.Ws || w.window > 8 || P > 16) return MSST_ERR_UNSUPPORTED;   // 8: at most 64 pixels per window
+    if (!pointers || (w.listed && !w.origins) || pos_split < 0 || pos_split >= 96) return MSST_ERR_BADARG;
+    if (w.listed) return 0;
+    int nr = 0;
+    scene_grid(w.Bs, w.Hs, w.Ws, w.window, w.stride, &nr, &w.nq);
+    w.wps = (long)nr * w.nq;
+    return (w.wps > 0x7fffffffL || w.win0 + w.nwin > (long)w.Bs * w.wps) ? MSST_ERR_BADARG : 0;
+}
+
+// msst_last_error names the entry point that was called (`what`), then what it refused
+static int fail(int code, const char* what, const char* suffix) {
+    char buf[128];
+    snprintf(buf, sizeof(buf), "%s%s", what, suffix);
+    return fail(code, buf);
+}
+
+// what TokArgs, TokBwdArgs (and its scene variants) and TokInArgs share: the source, the parameters, the shape, the dropout stream; the
+// blocks come zeroed (no window grid, no origins: fill_src adds them)
 template <class Args>
-static void fill_tok_common(Args& a, const float* img, const float* pre_g, const float* pre_b, const float* w_emb, const float* b_emb,
-                            const float* post_g, const float* post_b, int B, int S, int N, int P, Drop drop) {
-    a.img = img; a.pre_g = pre_g; a.pre_b = pre_b; a.w_emb = w_emb; a.b_emb = b_emb; a.post_g = post_g; a.post_b = post_b;
+static void fill_tok_common(Args& a, const TokPtrs& p, int B, int S, int N, int P, Drop drop) {
+    a.img = p.img; a.pre_g = p.pre_g; a.pre_b = p.pre_b; a.w_emb = p.w_emb; a.b_emb = p.b_emb; a.post_g = p.post_g; a.post_b = p.post_b;
     a.B = B; a.S = S; a.N = N; a.T = S * N; a.P = P; a.drop = drop;
 }
-static void fill_tok(TokArgs& a, const float* img, const float* pre_g, const float* pre_b, const float* w_emb, const float* b_emb,
-                     const float* post_g, const float* post_b, const float* pos_a, const float* pos_b, const float* mask_token,
-                     const uint8_t* mask, float* out, int B, int S, int N, int P, int pos_split, Drop drop) {
-    a = TokArgs{};   // no window grid, no origins: fill_window and the caller add them
-    fill_tok_common(a, img, pre_g, pre_b, w_emb, b_emb, post_g, post_b, B, S, N, P, drop);
+static void fill_tok(TokArgs& a, const TokPtrs& p, const float* pos_a, const float* pos_b, int pos_split, const float* mask_token,
+                     const uint8_t* mask, float* out, int B, int S, int N, int P, Drop drop) {
+    fill_tok_common(a, p, B, S, N, P, drop);
     a.pos_a = pos_a; a.pos_b = pos_b; a.mask_token = mask_token; a.mask = mask; a.out = out; a.pos_split = pos_split;
 }
-static void fill_tok_bwd(TokBwdArgs& a, const float* img, const float* pre_g, const float* pre_b, const float* w_emb,
-                         const float* b_emb, const float* post_g, const float* post_b, const uint8_t* mask, const float* dx0,
-                         float* slab, int B, int S, int N, int P, Drop drop) {
-    fill_tok_common(a, img, pre_g, pre_b, w_emb, b_emb, post_g, post_b, B, S, N, P, drop);
-    a.mask = mask; a.dx0 = dx0; a.slab = slab;
-}
-static void fill_tok_in(TokInArgs& a, const float* img, const float* pre_g, const float* pre_b, const float* w_emb, const float* b_emb,
-                        const float* post_g, const float* post_b, const uint8_t* mask, const float* dx0, const float* dtarget,
-                        float* dimg, int B, int S, int N, int P, Drop drop) {
-    fill_tok_common(a, img, pre_g, pre_b, w_emb, b_emb, post_g, post_b, B, S, N, P, drop);
+static void fill_tok_in(TokInArgs& a, const TokPtrs& p, const uint8_t* mask, const float* dx0, const float* dtarget, float* dimg, int B,
+                        int S, int N, int P, Drop drop) {
+    fill_tok_common(a, p, B, S, N, P, drop);
     a.mask = mask; a.dx0 = dx0; a.dtarget = dtarget; a.dimg = dimg;
 }
-// the window grid of the scene sources (Args: TokArgs, TokSceneBwdArgs, TokInArgs): sample b is window win0 + b.  Listed origins
-// (msst_tokenize_at_*) pass stride = win, nq = wps = 1, win0 = 0: of these only Hs, Ws and win are read there
+// the source fields of any argument block (Args: TokArgs, TokAtBwdArgs, TokInAtArgs)
 template <class Args>
-static void fill_window(Args& a, int Hs, int Ws, int win, int stride, int nq, long wps, long win0) {
-    a.win0 = win0; a.Hs = Hs; a.Ws = Ws; a.win = win; a.stride = stride; a.nq = nq; a.wps = (int)wps;
+static void fill_src(Args& a, const WinSrc& w) {
+    a.win0 = w.win0; a.Hs = w.Hs; a.Ws = w.Ws; a.win = w.window; a.stride = w.stride; a.nq = w.nq; a.wps = (int)w.wps;
+    a.origins = w.origins;
 }
 
 // the window grid of an assemble call into its argument block
@@ -337,122 +383,83 @@ int msst_tokenize_fwd(const float* img, const float* pre_g, const float* pre_b, 
                       const float* b_emb, const float* post_g, const float* post_b, const float* pos_a,
                       const float* pos_b, int pos_split, const float* mask_token, const uint8_t* mask,
                       float* out, int B, int S, int N, int P, float emb_dropout_p, uint32_t seed, void* stream) {
-    TokArgs a;
-    fill_tok(a, img, pre_g, pre_b, w_emb, b_emb, post_g, post_b, pos_a, pos_b, mask_token, mask, out, B, S, N, P, pos_split,
+    TokArgs a{};
+    fill_tok(a, {img, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, pos_a, pos_b, pos_split, mask_token, mask, out, B, S, N, P,
              make_drop(emb_dropout_p, seed, 255));
     return fail(launch_tokenize_fwd(a, (hipStream_t)stream), "msst_tokenize_fwd");
 }
 
-// window grid of a scene: false when the shapes are not a valid (scene, window, stride) triple
-static bool scene_grid(int Bs, int Hs, int Ws, int window, int stride, int* nr, int* nq) {
-    if (Bs < 1 || window < 1 || stride < 1 || stride > window || Hs < window || Ws < window) return false;
-    *nr = (Hs - window) / stride + 1;
-    *nq = (Ws - window) / stride + 1;
-    return true;
+// the two inference forwards over a scene's window grid (no dropout; masked: the scene mask and the mask token).  Their own precedence:
+// BADARG for everything, a stride above the window included, then UNSUPPORTED for a window of more than 64 pixels
+static int tokenize_scene_fwd(const char* what, bool masked, const TokPtrs& p, const float* pos_a, const float* pos_b, int pos_split,
+                              const float* mask_token, const uint8_t* scene_mask, float* out, WinSrc w, int S, int P, void* stream) {
+    int nr = 0;
+    if (!p.img || !out || (masked && (!mask_token || !scene_mask)) || S < 1 || P < 1 || w.nwin < 0 || w.win0 < 0 ||
+        !scene_grid(w.Bs, w.Hs, w.Ws, w.window, w.stride, &nr, &w.nq))
+        return fail(MSST_ERR_BADARG, what);
+    w.wps = (long)nr * w.nq;
+    if (w.wps > 0x7fffffffL || w.win0 + w.nwin > (long)w.Bs * w.wps) return fail(MSST_ERR_BADARG, what, " (windows out of range)");
+    if (w.window > 8) return fail(MSST_ERR_UNSUPPORTED, what, " (more than 64 pixels per window)");
+    TokArgs a{};
+    fill_tok(a, p, pos_a, pos_b, pos_split, mask_token, scene_mask, out, w.nwin, S, w.window * w.window, P, make_drop(0.f, 0, 255));
+    fill_src(a, w);
+    return fail((masked ? launch_tokenize_scene_fwd_masked : launch_tokenize_scene_fwd)(a, (hipStream_t)stream), what);
 }
 
 int msst_tokenize_scene_fwd(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb,
                             const float* b_emb, const float* post_g, const float* post_b, const float* pos_a,
                             const float* pos_b, int pos_split, float* out, int Bs, int Hs, int Ws, int window, int stride,
                             long win0, int nwin, int S, int P, void* stream) {
-    int nr = 0, nq = 0;
-    if (!scene || !out || S < 1 || P < 1 || nwin < 0 || win0 < 0 || !scene_grid(Bs, Hs, Ws, window, stride, &nr, &nq))
-        return fail(MSST_ERR_BADARG, "msst_tokenize_scene_fwd");
-    const long wps = (long)nr * nq;
-    if (wps > 0x7fffffffL || win0 + nwin > (long)Bs * wps) return fail(MSST_ERR_BADARG, "msst_tokenize_scene_fwd (windows out of range)");
-    if (window > 8) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_scene_fwd (more than 64 pixels per window)");
-    TokArgs a;
-    fill_tok(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, pos_a, pos_b, nullptr, nullptr, out, nwin, S, window * window, P,
-             pos_split, make_drop(0.f, 0, 255));
-    fill_window(a, Hs, Ws, window, stride, nq, wps, win0);
-    return fail(launch_tokenize_scene_fwd(a, (hipStream_t)stream), "msst_tokenize_scene_fwd");
+    return tokenize_scene_fwd("msst_tokenize_scene_fwd", false, {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, pos_a, pos_b,
+                              pos_split, nullptr, nullptr, out, WinSrc{Bs, Hs, Ws, window, stride, win0, nwin}, S, P, stream);
 }
 
 int msst_tokenize_scene_fwd_masked(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb,
                                    const float* b_emb, const float* post_g, const float* post_b, const float* pos_a,
                                    const float* pos_b, int pos_split, const float* mask_token, const uint8_t* scene_mask, float* out,
                                    int Bs, int Hs, int Ws, int window, int stride, long win0, int nwin, int S, int P, void* stream) {
-    int nr = 0, nq = 0;
-    if (!scene || !out || !mask_token || !scene_mask || S < 1 || P < 1 || nwin < 0 || win0 < 0 ||
-        !scene_grid(Bs, Hs, Ws, window, stride, &nr, &nq))
-        return fail(MSST_ERR_BADARG, "msst_tokenize_scene_fwd_masked");
-    const long wps = (long)nr * nq;
-    if (wps > 0x7fffffffL || win0 + nwin > (long)Bs * wps) return fail(MSST_ERR_BADARG, "msst_tokenize_scene_fwd_masked (windows out of range)");
-    if (window > 8) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_scene_fwd_masked (more than 64 pixels per window)");
-    TokArgs a;
-    fill_tok(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, pos_a, pos_b, mask_token, scene_mask, out, nwin, S, window * window,
-             P, pos_split, make_drop(0.f, 0, 255));
-    fill_window(a, Hs, Ws, window, stride, nq, wps, win0);
-    return fail(launch_tokenize_scene_fwd_masked(a, (hipStream_t)stream), "msst_tokenize_scene_fwd_masked");
+    return tokenize_scene_fwd("msst_tokenize_scene_fwd_masked", true, {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, pos_a, pos_b,
+                              pos_split, mask_token, scene_mask, out, WinSrc{Bs, Hs, Ws, window, stride, win0, nwin}, S, P, stream);
 }
 
-// the shared argument check of msst_tokenize_scene_fwd_train / msst_tokenize_scene_bwd, in this order: sizes below 1 (BADARG), shapes
-// outside the kernels' limits (UNSUPPORTED), a null required pointer (BADARG), windows beyond the scenes' grids (BADARG).  min_nwin: 0 or 1
-static int scene_train_args(bool pointers, int Bs, int Hs, int Ws, int window, int stride, long win0, int nwin, int min_nwin, int S,
-                            int P, int pos_split, int* nq, long* wps) {
-    if (Bs < 1 || Hs < 1 || Ws < 1 || window < 1 || stride < 1 || S < 1 || P < 1 || nwin < min_nwin || win0 < 0) return MSST_ERR_BADARG;
-    if (stride > window || window > Hs || window > Ws || window > 8 || P > 16) return MSST_ERR_UNSUPPORTED;   // 8: at most 64 pixels per window
-    if (!pointers || pos_split < 0 || pos_split >= 96) return MSST_ERR_BADARG;
-    int nr = 0;
-    scene_grid(Bs, Hs, Ws, window, stride, &nr, nq);
-    *wps = (long)nr * *nq;
-    if (*wps > 0x7fffffffL || win0 + nwin > (long)Bs * *wps) return MSST_ERR_BADARG;
-    return 0;
+// the training forwards over a window source: a grid (no mask), listed windows, listed windows with a per-window token mask
+static int tokenize_src_fwd(const char* what, bool masked, const TokPtrs& p, const float* pos_a, const float* pos_b, int pos_split,
+                            const float* mask_token, const uint8_t* mask, float* out, WinSrc w, int S, int P, Drop drop, void* stream) {
+    const bool pointers = p.all_set() && pos_a && (pos_b || !pos_split) && (!masked || (mask_token && mask)) && out;
+    if (int rc = check_src(w, pointers, 0, S, P, pos_split)) return fail(rc, what);
+    if (w.listed && (P != 10 || w.window != 8) && w.nwin > 65535) return fail(MSST_ERR_UNSUPPORTED, what, " (more than 65535 windows)");
+    TokArgs a{};
+    fill_tok(a, p, pos_a, pos_b, pos_split, mask_token, mask, out, w.nwin, S, w.window * w.window, P, drop);
+    fill_src(a, w);
+    return fail((!w.listed ? launch_tokenize_scene_fwd : masked ? launch_tokenize_at_fwd_masked : launch_tokenize_at_fwd)(a, (hipStream_t)stream),
+                what);
 }
 
 int msst_tokenize_scene_fwd_train(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb,
                                   const float* b_emb, const float* post_g, const float* post_b, const float* pos_a,
                                   const float* pos_b, int pos_split, float* out, int Bs, int Hs, int Ws, int window, int stride,
                                   long win0, int nwin, int S, int P, float emb_dropout_p, uint32_t seed, void* stream) {
-    int nq = 0;
-    long wps = 0;
-    const bool pointers = scene && pre_g && pre_b && w_emb && b_emb && post_g && post_b && pos_a && (pos_b || !pos_split) && out;
-    if (int rc = scene_train_args(pointers, Bs, Hs, Ws, window, stride, win0, nwin, 0, S, P, pos_split, &nq, &wps))
-        return fail(rc, "msst_tokenize_scene_fwd_train");
-    TokArgs a;
-    fill_tok(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, pos_a, pos_b, nullptr, nullptr, out, nwin, S, window * window, P,
-             pos_split, make_drop(emb_dropout_p, seed, 255));
-    fill_window(a, Hs, Ws, window, stride, nq, wps, win0);
-    return fail(launch_tokenize_scene_fwd(a, (hipStream_t)stream), "msst_tokenize_scene_fwd_train");
-}
-
-// the shared argument check of msst_tokenize_at_fwd / msst_tokenize_at_bwd, in the order of scene_train_args
-static int at_args(bool pointers, int Bs, int Hs, int Ws, int window, int nwin, int min_nwin, int S, int P, int pos_split) {
-    if (Bs < 1 || Hs < 1 || Ws < 1 || window < 1 || S < 1 || P < 1 || nwin < min_nwin) return MSST_ERR_BADARG;
-    if (window > Hs || window > Ws || window > 8 || P > 16) return MSST_ERR_UNSUPPORTED;   // 8: at most 64 pixels per window
-    if (!pointers || pos_split < 0 || pos_split >= 96) return MSST_ERR_BADARG;
-    return 0;
+    return tokenize_src_fwd("msst_tokenize_scene_fwd_train", false, {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, pos_a, pos_b,
+                            pos_split, nullptr, nullptr, out, WinSrc{Bs, Hs, Ws, window, stride, win0, nwin}, S, P,
+                            make_drop(emb_dropout_p, seed, 255), stream);
 }
 
 int msst_tokenize_at_fwd(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
                          const float* b_emb, const float* post_g, const float* post_b, const float* pos_a, const float* pos_b,
                          int pos_split, float* out, int Bs, int Hs, int Ws, int window, int nwin, int S, int P,
                          float emb_dropout_p, uint32_t seed, void* stream) {
-    const bool pointers = scene && origins && pre_g && pre_b && w_emb && b_emb && post_g && post_b && pos_a && (pos_b || !pos_split) && out;
-    if (int rc = at_args(pointers, Bs, Hs, Ws, window, nwin, 0, S, P, pos_split)) return fail(rc, "msst_tokenize_at_fwd");
-    if ((P != 10 || window != 8) && nwin > 65535) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_at_fwd (more than 65535 windows)");
-    TokArgs a;
-    fill_tok(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, pos_a, pos_b, nullptr, nullptr, out, nwin, S, window * window, P,
-             pos_split, make_drop(emb_dropout_p, seed, 255));
-    fill_window(a, Hs, Ws, window, window, 1, 1, 0);
-    a.origins = origins;
-    return fail(launch_tokenize_at_fwd(a, (hipStream_t)stream), "msst_tokenize_at_fwd");
+    return tokenize_src_fwd("msst_tokenize_at_fwd", false, {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, pos_a, pos_b, pos_split,
+                            nullptr, nullptr, out, WinSrc{Bs, Hs, Ws, window, window, 0, nwin, true, origins}, S, P,
+                            make_drop(emb_dropout_p, seed, 255), stream);
 }
 
 int msst_tokenize_at_fwd_masked(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
                                 const float* b_emb, const float* post_g, const float* post_b, const float* pos_a, const float* pos_b,
                                 int pos_split, const float* mask_token, const uint8_t* mask, float* out, int Bs, int Hs, int Ws,
                                 int window, int nwin, int S, int P, void* stream) {
-    const bool pointers = scene && origins && pre_g && pre_b && w_emb && b_emb && post_g && post_b && pos_a && (pos_b || !pos_split) &&
-                          mask_token && mask && out;
-    if (int rc = at_args(pointers, Bs, Hs, Ws, window, nwin, 0, S, P, pos_split)) return fail(rc, "msst_tokenize_at_fwd_masked");
-    if ((P != 10 || window != 8) && nwin > 65535) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_at_fwd_masked (more than 65535 windows)");
-    TokArgs a;
-    fill_tok(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, pos_a, pos_b, mask_token, mask, out, nwin, S, window * window, P,
-             pos_split, make_drop(0.f, 0, 255));
-    fill_window(a, Hs, Ws, window, window, 1, 1, 0);
-    a.origins = origins;
-    return fail(launch_tokenize_at_fwd_masked(a, (hipStream_t)stream), "msst_tokenize_at_fwd_masked");
+    return tokenize_src_fwd("msst_tokenize_at_fwd_masked", true, {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, pos_a, pos_b,
+                            pos_split, mask_token, mask, out, WinSrc{Bs, Hs, Ws, window, window, 0, nwin, true, origins}, S, P, make_drop(0.f, 0, 255),
+                            stream);
 }
 
 int msst_scene_assemble(const float* win_logits, long win0, int nwin, float* logits, int64_t* classes, int Bs,
@@ -937,22 +944,20 @@ int msst_block_bwd_reduce(const MsstBlockGrads* g, const MsstBlockGrads* g_prev,
 
 // the tokenizer backward's second half: the slabs its kernel wrote, summed into the gradients (msst_tokenize_bwd and
 // msst_tokenize_scene_bwd: one table, one summation order)
-static int tokenize_bwd_reduce(float* slab, int nchunk, float* dpre_g, float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g,
-                               float* dpost_b, float* dpos_a, float* dpos_b, int pos_split, float* dmask_token, int S, int N, int P,
-                               hipStream_t st) {
+static int tokenize_bwd_reduce(float* slab, int nchunk, const TokGradPtrs& g, int S, int N, int P, hipStream_t st) {
     int rc = 0;
     const long ss = (long)N * 96 + 96 * P + 96 * 4 + 32;
     const long bs = (long)nchunk * ss;
     float* stage = slab + (long)S * nchunk * ss;  // [S][N][96] position-gradient staging
-    float* dpos_dst = pos_split ? stage : dpos_a;
+    float* dpos_dst = g.pos_split ? stage : g.dpos_a;
     const long v0 = (long)N * 96 + 96 * P;
     RSegBuilder rb;
     bool ok = true;
     for (int c = 0; c < S && ok; ++c) {   // per spectral block: position rows, embed weight, embed bias
         const float* sc = slab + c * bs;
-        if (dpos_a) ok = rb.add(sc, ss, nchunk, dpos_dst + (long)c * N * 96, N * 96);   // null: position table applied by the caller
-        ok = ok && rb.add(sc + N * 96, ss, nchunk, dw_emb + (long)c * 96 * P, 96 * P);
-        ok = ok && rb.add(sc + v0, ss, nchunk, db_emb + (long)c * 96, 96);
+        if (g.dpos_a) ok = rb.add(sc, ss, nchunk, dpos_dst + (long)c * N * 96, N * 96);   // null: position table applied by the caller
+        ok = ok && rb.add(sc + N * 96, ss, nchunk, g.dw_emb + (long)c * 96 * P, 96 * P);
+        ok = ok && rb.add(sc + v0, ss, nchunk, g.db_emb + (long)c * 96, 96);
         if (rb.r.nseg > MSST_MAX_RSEG - 8) {
             rc = launch_reduce_segs(rb.r, st);
             if (rc) return fail(rc, "msst_tokenize_bwd(reduce)");
@@ -960,15 +965,34 @@ static int tokenize_bwd_reduce(float* slab, int nchunk, float* dpre_g, float* dp
         }
     }
     // shared across blocks
-    ok = ok && rb.add(slab + v0 + 96, ss, S * nchunk, dpost_g, 96);
-    ok = ok && rb.add(slab + v0 + 192, ss, S * nchunk, dpost_b, 96);
-    if (dmask_token) ok = ok && rb.add(slab + v0 + 288, ss, S * nchunk, dmask_token, 96);
-    ok = ok && rb.add(slab + v0 + 384, ss, S * nchunk, dpre_g, P);
-    ok = ok && rb.add(slab + v0 + 384 + 16, ss, S * nchunk, dpre_b, P);
+    ok = ok && rb.add(slab + v0 + 96, ss, S * nchunk, g.dpost_g, 96);
+    ok = ok && rb.add(slab + v0 + 192, ss, S * nchunk, g.dpost_b, 96);
+    if (g.dmask_token) ok = ok && rb.add(slab + v0 + 288, ss, S * nchunk, g.dmask_token, 96);
+    ok = ok && rb.add(slab + v0 + 384, ss, S * nchunk, g.dpre_g, P);
+    ok = ok && rb.add(slab + v0 + 384 + 16, ss, S * nchunk, g.dpre_b, P);
     if (!ok) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_bwd(reduce table)");
     rc = launch_reduce_segs(rb.r, st);
-    if (!rc && pos_split && dpos_a) rc = launch_pos_split(stage, S, N, pos_split, dpos_a, dpos_b, st);
+    if (!rc && g.pos_split && g.dpos_a) rc = launch_pos_split(stage, S, N, g.pos_split, g.dpos_a, g.dpos_b, st);
     return fail(rc, "msst_tokenize_bwd(reduce)");
+}
+
+// the four parameter backwards: the argument check of a window source (w null: a batch of cubes, unchecked as ever), nchunk, one launch
+// over all samples, the slab reduction
+static int tokenize_src_bwd(const char* what, const TokPtrs& p, const uint8_t* mask, bool masked, const float* dx0, float* slab, int nchunk,
+                            const TokGradPtrs& g, WinSrc* w, int B, int S, int N, int P, Drop drop, void* stream) {
+    if (w) {
+        const bool pointers = p.all_set() && (!masked || mask) && dx0 && slab && g.all_set();
+        if (int rc = check_src(*w, pointers, 1, S, P, g.pos_split)) return fail(rc, what);
+    }
+    if (nchunk < 1) return fail(MSST_ERR_BADARG, what);
+    hipStream_t st = (hipStream_t)stream;
+    TokAtBwdArgs a{};   // its bases are the argument blocks of the other two launchers
+    fill_tok_common(a, p, B, S, N, P, drop);
+    a.mask = mask; a.dx0 = dx0; a.slab = slab;
+    if (w) fill_src(a, *w);
+    if (int rc = !w ? launch_tokenize_bwd(a, nchunk, st) : w->listed ? launch_tokenize_at_bwd(a, nchunk, st) : launch_tokenize_scene_bwd(a, nchunk, st))
+        return fail(rc, what);
+    return tokenize_bwd_reduce(slab, nchunk, g, S, N, P, st);
 }
 
 int msst_tokenize_bwd(const float* img, const float* pre_g, const float* pre_b, const float* w_emb,
@@ -977,14 +1001,9 @@ int msst_tokenize_bwd(const float* img, const float* pre_g, const float* pre_b, 
                       float* dw_emb, float* db_emb, float* dpost_g, float* dpost_b, float* dpos_a,
                       float* dpos_b, int pos_split, float* dmask_token, int B, int S, int N, int P,
                       float emb_dropout_p, uint32_t seed, void* stream) {
-    if (nchunk < 1) return fail(MSST_ERR_BADARG, "msst_tokenize_bwd");
-    hipStream_t st = (hipStream_t)stream;
-    TokBwdArgs a;
-    fill_tok_bwd(a, img, pre_g, pre_b, w_emb, b_emb, post_g, post_b, mask, dx0, slab, B, S, N, P, make_drop(emb_dropout_p, seed, 255));
-    int rc = launch_tokenize_bwd(a, nchunk, st);
-    if (rc) return fail(rc, "msst_tokenize_bwd");
-    return tokenize_bwd_reduce(slab, nchunk, dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, dmask_token,
-                               S, N, P, st);
+    return tokenize_src_bwd("msst_tokenize_bwd", {img, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, mask, false, dx0, slab, nchunk,
+                            {dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, dmask_token}, nullptr, B, S, N, P,
+                            make_drop(emb_dropout_p, seed, 255), stream);
 }
 
 int msst_tokenize_scene_bwd(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb,
@@ -992,21 +1011,10 @@ int msst_tokenize_scene_bwd(const float* scene, const float* pre_g, const float*
                             int nchunk, float* dpre_g, float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g,
                             float* dpost_b, float* dpos_a, float* dpos_b, int pos_split, int Bs, int Hs, int Ws, int window,
                             int stride, long win0, int nwin, int S, int P, float emb_dropout_p, uint32_t seed, void* stream) {
-    int nq = 0;
-    long wps = 0;
-    const bool pointers = scene && pre_g && pre_b && w_emb && b_emb && post_g && post_b && dx0 && slab && dpre_g && dpre_b && dw_emb &&
-                          db_emb && dpost_g && dpost_b && (dpos_b || !pos_split || !dpos_a);
-    if (int rc = scene_train_args(pointers, Bs, Hs, Ws, window, stride, win0, nwin, 1, S, P, pos_split, &nq, &wps))
-        return fail(rc, "msst_tokenize_scene_bwd");
-    if (nchunk < 1) return fail(MSST_ERR_BADARG, "msst_tokenize_scene_bwd");
-    hipStream_t st = (hipStream_t)stream;
-    TokSceneBwdArgs a;
-    fill_tok_bwd(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, nullptr, dx0, slab, nwin, S, window * window, P,
-                 make_drop(emb_dropout_p, seed, 255));
-    fill_window(a, Hs, Ws, window, stride, nq, wps, win0);
-    if (int rc = launch_tokenize_scene_bwd(a, nchunk, st)) return fail(rc, "msst_tokenize_scene_bwd");
-    return tokenize_bwd_reduce(slab, nchunk, dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, nullptr,
-                               S, a.N, P, st);
+    WinSrc w = WinSrc{Bs, Hs, Ws, window, stride, win0, nwin};
+    return tokenize_src_bwd("msst_tokenize_scene_bwd", {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, nullptr, false, dx0, slab,
+                            nchunk, {dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, nullptr}, &w, nwin, S,
+                            window * window, P, make_drop(emb_dropout_p, seed, 255), stream);
 }
 
 int msst_tokenize_at_bwd(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
@@ -1014,19 +1022,10 @@ int msst_tokenize_at_bwd(const float* scene, const int32_t* origins, const float
                          float* dpre_g, float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g, float* dpost_b, float* dpos_a,
                          float* dpos_b, int pos_split, int Bs, int Hs, int Ws, int window, int nwin, int S, int P,
                          float emb_dropout_p, uint32_t seed, void* stream) {
-    const bool pointers = scene && origins && pre_g && pre_b && w_emb && b_emb && post_g && post_b && dx0 && slab && dpre_g && dpre_b &&
-                          dw_emb && db_emb && dpost_g && dpost_b && (dpos_b || !pos_split || !dpos_a);
-    if (int rc = at_args(pointers, Bs, Hs, Ws, window, nwin, 1, S, P, pos_split)) return fail(rc, "msst_tokenize_at_bwd");
-    if (nchunk < 1) return fail(MSST_ERR_BADARG, "msst_tokenize_at_bwd");
-    hipStream_t st = (hipStream_t)stream;
-    TokAtBwdArgs a;
-    fill_tok_bwd(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, nullptr, dx0, slab, nwin, S, window * window, P,
-                 make_drop(emb_dropout_p, seed, 255));
-    fill_window(a, Hs, Ws, window, window, 1, 1, 0);
-    a.origins = origins;
-    if (int rc = launch_tokenize_at_bwd(a, nchunk, st)) return fail(rc, "msst_tokenize_at_bwd");
-    return tokenize_bwd_reduce(slab, nchunk, dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, nullptr,
-                               S, a.N, P, st);
+    WinSrc w = WinSrc{Bs, Hs, Ws, window, window, 0, nwin, true, origins};
+    return tokenize_src_bwd("msst_tokenize_at_bwd", {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, nullptr, false, dx0, slab, nchunk,
+                            {dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, nullptr}, &w, nwin, S,
+                            window * window, P, make_drop(emb_dropout_p, seed, 255), stream);
 }
 
 int msst_tokenize_at_bwd_masked(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
@@ -1034,33 +1033,22 @@ int msst_tokenize_at_bwd_masked(const float* scene, const int32_t* origins, cons
                                 float* slab, int nchunk, float* dpre_g, float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g,
                                 float* dpost_b, float* dpos_a, float* dpos_b, int pos_split, float* dmask_token, int Bs, int Hs, int Ws,
                                 int window, int nwin, int S, int P, void* stream) {
-    const bool pointers = scene && origins && pre_g && pre_b && w_emb && b_emb && post_g && post_b && mask && dx0 && slab && dpre_g &&
-                          dpre_b && dw_emb && db_emb && dpost_g && dpost_b && (dpos_b || !pos_split || !dpos_a);
-    if (int rc = at_args(pointers, Bs, Hs, Ws, window, nwin, 1, S, P, pos_split)) return fail(rc, "msst_tokenize_at_bwd_masked");
-    if (nchunk < 1) return fail(MSST_ERR_BADARG, "msst_tokenize_at_bwd_masked");
-    hipStream_t st = (hipStream_t)stream;
-    TokAtBwdArgs a;
-    fill_tok_bwd(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, mask, dx0, slab, nwin, S, window * window, P,
-                 make_drop(0.f, 0, 255));
-    fill_window(a, Hs, Ws, window, window, 1, 1, 0);
-    a.origins = origins;
-    if (int rc = launch_tokenize_at_bwd(a, nchunk, st)) return fail(rc, "msst_tokenize_at_bwd_masked");
-    return tokenize_bwd_reduce(slab, nchunk, dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, dmask_token,
-                               S, a.N, P, st);
+    WinSrc w = WinSrc{Bs, Hs, Ws, window, window, 0, nwin, true, origins};
+    return tokenize_src_bwd("msst_tokenize_at_bwd_masked", {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, mask, true, dx0, slab,
+                            nchunk, {dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, dmask_token}, &w, nwin, S,
+                            window * window, P, make_drop(0.f, 0, 255), stream);
 }
 
 // ---- input gradient (msst_input_grad.hip)
 int msst_tokenize_bwd_input(const float* img, const float* pre_g, const float* pre_b, const float* w_emb, const float* b_emb,
                             const float* post_g, const float* post_b, const uint8_t* mask, const float* dx0, const float* dtarget,
                             float* dimg, int B, int S, int N, int P, float emb_dropout_p, uint32_t seed, void* stream) {
+    const TokPtrs p{img, pre_g, pre_b, w_emb, b_emb, post_g, post_b};
     if (B < 1 || S < 1 || N < 1 || P < 1) return fail(MSST_ERR_BADARG, "msst_tokenize_bwd_input");
     if (N > 64 || S > 64 || P > 16) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_bwd_input");
-    if (!img || !pre_g || !pre_b || !w_emb || !b_emb || !post_g || !post_b || !dx0 || !dimg)
-        return fail(MSST_ERR_BADARG, "msst_tokenize_bwd_input");
-    TokInArgs a;
-    fill_tok_in(a, img, pre_g, pre_b, w_emb, b_emb, post_g, post_b, mask, dx0, dtarget, dimg, B, S, N, P,
-                make_drop(emb_dropout_p, seed, 255));
-    fill_window(a, 0, 0, 0, 0, 0, 0, 0);   // a batch of cubes: no window grid
+    if (!p.all_set() || !dx0 || !dimg) return fail(MSST_ERR_BADARG, "msst_tokenize_bwd_input");
+    TokInArgs a{};   // a batch of cubes: no window grid
+    fill_tok_in(a, p, mask, dx0, dtarget, dimg, B, S, N, P, make_drop(emb_dropout_p, seed, 255));
     return fail(launch_tokenize_bwd_input(a, (hipStream_t)stream), "msst_tokenize_bwd_input");
 }
 
@@ -1074,41 +1062,40 @@ int msst_head_bwd_target(const float* dpred, const int32_t* csr_ptr, const int32
                 "msst_head_bwd_target");
 }
 
+// the input gradient over a window source: into the scenes themselves (a grid of windows that do not overlap), or stacked per window
+// (listed windows: msst_scene_fold_at sums them)
+static int tokenize_src_bwd_input(const char* what, const TokPtrs& p, const float* dx0, float* dimg, WinSrc w, int S, int P, Drop drop,
+                                  void* stream) {
+    if (int rc = check_src(w, p.all_set() && dx0 && dimg, 0, S, P, 0)) return fail(rc, what);
+    hipStream_t st = (hipStream_t)stream;
+    if (!w.listed) {
+        // overlapping windows would have to add into a pixel: only the non-overlapping grid of the tile path is built
+        if (w.stride != w.window || S > 64) return fail(MSST_ERR_UNSUPPORTED, what, " (stride != window)");
+        if (w.win0 == 0) {   // the call that starts a batch zeroes the pixels beyond the window grid
+            const int nr = (int)(w.wps / w.nq);
+            if (int rc = launch_scene_border_zero(dimg, (long)w.Bs * S * P * w.Hs, w.Hs, w.Ws, nr * w.window, w.nq * w.window, st))
+                return fail(rc, what, "(border)");
+        }
+    }
+    TokInAtArgs a{};   // its base is the argument block of the grid launcher
+    fill_tok_in(a, p, nullptr, dx0, nullptr, dimg, w.nwin, S, w.window * w.window, P, drop);
+    fill_src(a, w);
+    return fail(w.listed ? launch_tokenize_at_bwd_input(a, st) : launch_tokenize_scene_bwd_input(a, st), what);
+}
+
 int msst_tokenize_scene_bwd_input(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb, const float* b_emb,
                                   const float* post_g, const float* post_b, const float* dx0, float* dscene, int Bs, int Hs, int Ws,
                                   int window, int stride, long win0, int nwin, int S, int P, float emb_dropout_p, uint32_t seed,
                                   void* stream) {
-    int nq = 0;
-    long wps = 0;
-    const bool pointers = scene && pre_g && pre_b && w_emb && b_emb && post_g && post_b && dx0 && dscene;
-    if (int rc = scene_train_args(pointers, Bs, Hs, Ws, window, stride, win0, nwin, 0, S, P, 0, &nq, &wps))
-        return fail(rc, "msst_tokenize_scene_bwd_input");
-    // overlapping windows would have to add into a pixel: only the non-overlapping grid of the tile path is built
-    if (stride != window || S > 64) return fail(MSST_ERR_UNSUPPORTED, "msst_tokenize_scene_bwd_input (stride != window)");
-    hipStream_t st = (hipStream_t)stream;
-    if (win0 == 0) {   // the call that starts a batch zeroes the pixels beyond the window grid
-        const int nr = (int)(wps / nq);
-        if (int rc = launch_scene_border_zero(dscene, (long)Bs * S * P * Hs, Hs, Ws, nr * window, nq * window, st))
-            return fail(rc, "msst_tokenize_scene_bwd_input(border)");
-    }
-    TokInArgs a;
-    fill_tok_in(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, nullptr, dx0, nullptr, dscene, nwin, S, window * window, P,
-                make_drop(emb_dropout_p, seed, 255));
-    fill_window(a, Hs, Ws, window, stride, nq, wps, win0);
-    return fail(launch_tokenize_scene_bwd_input(a, st), "msst_tokenize_scene_bwd_input");
+    return tokenize_src_bwd_input("msst_tokenize_scene_bwd_input", {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, dx0, dscene,
+                                  WinSrc{Bs, Hs, Ws, window, stride, win0, nwin}, S, P, make_drop(emb_dropout_p, seed, 255), stream);
 }
 
 int msst_tokenize_at_bwd_input(const float* scene, const int32_t* origins, const float* pre_g, const float* pre_b, const float* w_emb,
                                const float* b_emb, const float* post_g, const float* post_b, const float* dx0, float* dwin, int Bs,
                                int Hs, int Ws, int window, int nwin, int S, int P, float emb_dropout_p, uint32_t seed, void* stream) {
-    const bool pointers = scene && origins && pre_g && pre_b && w_emb && b_emb && post_g && post_b && dx0 && dwin;
-    if (int rc = at_args(pointers, Bs, Hs, Ws, window, nwin, 0, S, P, 0)) return fail(rc, "msst_tokenize_at_bwd_input");
-    TokInAtArgs a;
-    fill_tok_in(a, scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b, nullptr, dx0, nullptr, dwin, nwin, S, window * window, P,
-                make_drop(emb_dropout_p, seed, 255));
-    fill_window(a, Hs, Ws, window, window, 1, 1, 0);
-    a.origins = origins;
-    return fail(launch_tokenize_at_bwd_input(a, (hipStream_t)stream), "msst_tokenize_at_bwd_input");
+    return tokenize_src_bwd_input("msst_tokenize_at_bwd_input", {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, dx0, dwin,
+                                  WinSrc{Bs, Hs, Ws, window, window, 0, nwin, true, origins}, S, P, make_drop(emb_dropout_p, seed, 255), stream);
 }
 
 int msst_scene_fold_at(const float* dwin, const int32_t* cell_ptr, const int32_t* cell_win, float* dscene, int Bs, int C, int Hs, int Ws,

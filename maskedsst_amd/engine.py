@@ -40,6 +40,46 @@ _HEADS = {
 }
 
 
+class Windows:
+    """Where the samples of a tokenizer or head call lie -- the one thing the Engine methods, the autograd Functions and the C entry
+    points below them are told about it.  kind:
+      batch   img [B, C, s, s]: the samples themselves (what a bare tensor means wherever a source is taken);
+      tiles   img [B, C, Ht, Wt]: its non-overlapping s x s windows in the reference's stack_image_batch order (src/utils.py:451-474:
+              tile, window row, window column; trailing Ht % s rows / Wt % s columns dropped) -- grid = (nr, nq) per tile;
+      listed  img [Bs, C, Hs, Ws] and origins int32 [n, 3] = (scene, y0, x0) on its device; csr = scene.origins_csr(origins, ...) opts
+              into the scenes' gradient (the windows overlap: it is a fold over that index), sink a SceneGradSink that receives it.
+    img is held contiguous and fp32; n: the number of windows."""
+
+    def __init__(self, kind, img, origins=None, csr=None, sink=None, s=None):
+        self.kind, self.img, self.origins, self.csr, self.sink = kind, img.contiguous().float(), origins, csr, sink
+        if kind == "tiles":
+            self.grid = (img.shape[-2] // s, img.shape[-1] // s)
+            self.n = img.shape[0] * self.grid[0] * self.grid[1]
+        else:
+            self.n = origins.shape[0] if kind == "listed" else img.shape[0]
+
+
+# (kind, token mask given?) -> entry point of Engine.tokenize / tokenize_bwd / tokenize_input_bwd; no key, no entry point
+_TOK_FWD = {("batch", False): "msst_tokenize_fwd", ("batch", True): "msst_tokenize_fwd", ("tiles", False): "msst_tokenize_scene_fwd_train",
+            ("listed", False): "msst_tokenize_at_fwd", ("listed", True): "msst_tokenize_at_fwd_masked"}
+_TOK_BWD = {("batch", False): "msst_tokenize_bwd", ("batch", True): "msst_tokenize_bwd", ("tiles", False): "msst_tokenize_scene_bwd",
+            ("listed", False): "msst_tokenize_at_bwd", ("listed", True): "msst_tokenize_at_bwd_masked"}
+_TOK_INPUT_BWD = {("batch", False): "msst_tokenize_bwd_input", ("batch", True): "msst_tokenize_bwd_input",
+                  ("tiles", False): "msst_tokenize_scene_bwd_input", ("listed", False): "msst_tokenize_at_bwd_input"}
+
+
+def _tok_entry(table, method, src, masked, emb_drop=(0.0, 0)):
+    """(entry point, its dropout arguments) of `method` on src; the masked listed entry points take no embedding dropout"""
+    name = table.get((src.kind, masked))
+    if name is None:
+        raise NotImplementedError(f"{method}: no entry point for {src.kind} windows {'with' if masked else 'without'} a token mask")
+    if masked and src.kind == "listed":
+        if emb_drop[0] > 0:
+            raise NotImplementedError(f"{method}: no entry point for listed windows with a token mask and embedding dropout")
+        return name, ()
+    return name, tuple(emb_drop)
+
+
 def _prec_of(name):
     name = (name or os.environ.get("MSST_PRECISION", "bf16")).lower()
     if name in ("fp32", "f32", "32-true", "float32"):
@@ -377,108 +417,65 @@ class Engine:
         ss = N * 96 + 96 * P + 96 * 4 + 32
         return nchunk, torch.empty(S * nchunk * ss + S * N * 96, dtype=torch.float32, device=device)
 
-    def _launch_chunk(self, total, s, emb_drop, what):
-        """windows per tokenizer launch: all of them for the fp32-MFMA kernels, else TILE_WINDOWS_PER_LAUNCH at most -- and then without
-        embedding dropout (a dropout element is addressed by its place in one launch's output: launches in turn would repeat the
-        first one's masks).  what: the advice that ends the refusal"""
-        chunk = total if (self.P == 10 and s == 8) else min(total, self.TILE_WINDOWS_PER_LAUNCH)
-        if chunk < total and emb_drop[0] > 0:
-            raise NotImplementedError(f"embedding dropout over {total} windows in one step needs more than one launch of the generic "
-                                      f"tokenizer ({self.TILE_WINDOWS_PER_LAUNCH} windows each): {what} per step")
-        return chunk
-
-    def tokenize(self, img, mask_u8=None, with_pos=True, emb_drop=(0.0, 0)):
-        """img [B, C, H, W] fp32 cuda -> tokens [B, T, 96] (pos added, mask token substituted)"""
-        self._require_cuda(img)
-        self.ensure()
-        B = img.shape[0]
-        S, N, P = self.S, self.N, self.P
-        T = S * N
-        img = img.contiguous().float()
-        out = torch.empty(B, T, D, dtype=torch.float32, device=img.device)
-        if mask_u8 is None:
-            mask_u8 = self._zero_mask_for(B * T, img.device)
-        fp = self.fp
-        if not with_pos:
-            if getattr(self, "_zero_pos", None) is None or self._zero_pos.numel() < T * D:
-                self._zero_pos = torch.zeros(T * D, dtype=torch.float32, device=img.device)
-            split, pos_a, pos_b = 0, self._zero_pos.data_ptr(), 0
-        else:
-            split, pos_a, pos_b = self._pos_tables()
-        mt = fp.ptr("mask_token") if self.mim is not None else fp.ptr("post_b")
-        V = ctypes.c_void_p
-        _lib.check(self.lib.msst_tokenize_fwd(
-            _p(img), *self._tok_params(), V(pos_a), V(pos_b), split, V(mt), _p(mask_u8), _p(out),
-            B, S, N, P, emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_fwd")
-        return out
-
     # the generic tokenizer kernels run one grid row per window; the fp32-MFMA ones (P = 10, 8 x 8 windows) walk any number
     TILE_WINDOWS_PER_LAUNCH = 65535
 
-    def tile_grid(self, tiles):
-        """(s, nr, nq): the window side and the window grid of one tile of tiles [B, C, Ht, Wt] -- the reference's stack_image_batch
-        (src/utils.py:451-474): non-overlapping s x s windows, s = the model's image size, trailing Ht % s rows / Wt % s columns dropped"""
+    def _launch_chunk(self, src, emb_drop):
+        """windows of src per tokenizer launch: all of them for the fp32-MFMA kernels, else TILE_WINDOWS_PER_LAUNCH at most -- and then
+        without embedding dropout (a dropout element is addressed by its place in one launch's output: launches in turn would repeat
+        the first one's masks)"""
+        total = src.n
+        chunk = total if (self.P == 10 and self.enc.num_spatial_patches_sqrt == 8) else min(total, self.TILE_WINDOWS_PER_LAUNCH)
+        if chunk < total and emb_drop[0] > 0:
+            raise NotImplementedError(f"embedding dropout over {total} windows in one step needs more than one launch of the generic "
+                                      f"tokenizer ({self.TILE_WINDOWS_PER_LAUNCH} windows each): "
+                                      f"{'use fewer tiles' if src.kind == 'tiles' else 'list fewer windows'} per step")
+        return chunk
+
+    def _src(self, src):
+        return src if isinstance(src, Windows) else Windows("batch", src)
+
+    def _src_args(self, src, win0, n):
+        """what a tokenizer entry point is told of windows win0 .. win0 + n - 1 of src: (its leading pointers, its shape integers)"""
+        S, P = self.S, self.P
+        if src.kind == "batch":
+            return (_p(src.img),), (n, S, self.N, P)
+        Bs, _, Hs, Ws = src.img.shape
         s = self.enc.num_spatial_patches_sqrt
-        return s, tiles.shape[-2] // s, tiles.shape[-1] // s
+        if src.kind == "tiles":
+            return (_p(src.img),), (Bs, Hs, Ws, s, s, win0, n, S, P)
+        return (_p(src.img), _p(src.origins[win0:] if win0 else src.origins)), (Bs, Hs, Ws, s, n, S, P)
 
-    def tokenize_windows(self, img, emb_drop=(0.0, 0), tiles=False, origins=None):
-        """the classification path's tokens (nothing masked, position added, embedding dropout): of a window batch img [B, C, s, s]
-        (tokenize), or with tiles=True of every window of tiles [B, C, Ht, Wt] in stack_image_batch's order, read straight out of
-        the tiles (msst_tokenize_scene_fwd_train) -> [B nr nq, T, 96], bit for bit what tokenize gives for the stacked copy; or with
-        origins (int32 [n, 3] on img's device: scene, y0, x0) of the n listed s x s windows of the scenes img [Bs, C, Hs, Ws]
-        (msst_tokenize_at_fwd) -> [n, T, 96], the same bits again"""
-        if origins is not None:
-            return self._tokenize_at(img, origins, emb_drop)
-        if not tiles:
-            return self.tokenize(img, None, emb_drop=emb_drop)
-        self._require_cuda(img)
+    def tokenize(self, src, mask_u8=None, with_pos=True, emb_drop=(0.0, 0)):
+        """tokens [n, T, 96] (position added, embedding dropout) of the n windows of src, a Windows or a bare batch img [B, C, H, W] fp32
+        cuda; with mask_u8 [n, T] the mask token substituted.  Tiles and listed windows are read where they lie, bit for bit what the
+        stacked copy gives.  One launch, or for tiles / unmasked listed windows under the generic kernels several (_launch_chunk)."""
+        src = self._src(src)
+        self._require_cuda(src.img)
         self.ensure()
-        B, _, Ht, Wt = img.shape
-        S, N, P = self.S, self.N, self.P
-        s, nr, nq = self.tile_grid(img)
-        total = B * nr * nq
-        out = torch.empty(total, S * N, D, dtype=torch.float32, device=img.device)
-        chunk = self._launch_chunk(total, s, emb_drop, "use fewer tiles")
-        split, pos_a, pos_b = self._pos_tables()
-        V = ctypes.c_void_p
-        for win0 in range(0, total, chunk):
-            _lib.check(self.lib.msst_tokenize_scene_fwd_train(
-                _p(img), *self._tok_params(), V(pos_a), V(pos_b), split, _p(out[win0:]), B, Ht, Wt, s, s, win0,
-                min(chunk, total - win0), S, P, emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_scene_fwd_train")
-        return out
-
-    def _tokenize_at(self, scene, origins, emb_drop):
-        self._require_cuda(scene)
-        self.ensure()
-        Bs, _, Hs, Ws = scene.shape
-        S, N, P = self.S, self.N, self.P
-        s = self.enc.num_spatial_patches_sqrt
-        total = origins.shape[0]
-        out = torch.empty(total, S * N, D, dtype=torch.float32, device=scene.device)
-        chunk = self._launch_chunk(total, s, emb_drop, "list fewer windows")
-        split, pos_a, pos_b = self._pos_tables()
-        V = ctypes.c_void_p
-        for win0 in range(0, total, max(chunk, 1)):
-            _lib.check(self.lib.msst_tokenize_at_fwd(
-                _p(scene), _p(origins[win0:]), *self._tok_params(), V(pos_a), V(pos_b), split, _p(out[win0:]), Bs, Hs, Ws, s,
-                min(chunk, total - win0), S, P, emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_at_fwd")
-        return out
-
-    def tokenize_at_masked(self, scene, origins, mask_u8):
-        """the SimMIM path's tokens (mask token substituted, position added, no embedding dropout) of the n listed s x s windows of the
-        scenes scene [Bs, C, Hs, Ws], origins int32 [n, 3] and mask_u8 [n, T] on its device (msst_tokenize_at_fwd_masked) -> [n, T, 96],
-        bit for bit what tokenize gives for the stacked copy with the same mask.  One launch: n <= TILE_WINDOWS_PER_LAUNCH"""
-        self._require_cuda(scene)
-        self.ensure()
-        Bs, _, Hs, Ws = scene.shape
-        S, N, P = self.S, self.N, self.P
-        total = origins.shape[0]
-        out = torch.empty(total, S * N, D, dtype=torch.float32, device=scene.device)
-        split, pos_a, pos_b = self._pos_tables()
-        V = ctypes.c_void_p
-        _lib.check(self.lib.msst_tokenize_at_fwd_masked(
-            _p(scene), _p(origins), *self._tok_params(), V(pos_a), V(pos_b), split, V(self.fp.ptr("mask_token")), _p(mask_u8), _p(out),
-            Bs, Hs, Ws, self.enc.num_spatial_patches_sqrt, total, S, P, _stream()), "msst_tokenize_at_fwd_masked")
+        masked = mask_u8 is not None
+        name, drop_args = _tok_entry(_TOK_FWD, "tokenize", src, masked, emb_drop)
+        S, N, total = self.S, self.N, src.n
+        T = S * N
+        dev = src.img.device
+        out = torch.empty(total, T, D, dtype=torch.float32, device=dev)
+        fp, V = self.fp, ctypes.c_void_p
+        if not with_pos:
+            if getattr(self, "_zero_pos", None) is None or self._zero_pos.numel() < T * D:
+                self._zero_pos = torch.zeros(T * D, dtype=torch.float32, device=dev)
+            split, pos_a, pos_b = 0, self._zero_pos.data_ptr(), 0
+        else:
+            split, pos_a, pos_b = self._pos_tables()
+        mask_args, chunk = (), total
+        if src.kind == "batch" or masked:   # these entry points take the mask token and a mask (nothing masked: the zero mask), one launch
+            mask_args = (V(fp.ptr("mask_token") if self.mim is not None else fp.ptr("post_b")),
+                         _p(mask_u8 if masked else self._zero_mask_for(total * T, dev)))
+        else:
+            chunk = self._launch_chunk(src, emb_drop)
+        fn, par, st = getattr(self.lib, name), self._tok_params(), _stream()
+        for win0 in (range(0, total, chunk) if chunk < total else (0,)):
+            lead, dims = self._src_args(src, win0, min(chunk, total - win0))
+            _lib.check(fn(*lead, *par, V(pos_a), V(pos_b), split, *mask_args, _p(out[win0:] if win0 else out), *dims, *drop_args, st), name)
         return out
 
     def blocks_fwd(self, x0, save=True, drop=(0.0, 0)):
@@ -632,29 +629,26 @@ class Engine:
                 x1s.append(None)
         return True
 
-    def head_fwd(self, y, img, idx32, want_pred=False, origins=None):
-        """the masked-L1 head over y [B, T, 96] -> (loss, dpred, pred); the targets come from the batch img [B, C, s, s], or with origins
-        (int32 [B, 3] on the device) from the windows listed there of the scenes img [Bs, C, Hs, Ws] (msst_head_at_fwd): the same bits"""
+    def head_fwd(self, y, src, idx32, want_pred=False):
+        """the masked-L1 head over y [B, T, 96] -> (loss, dpred, pred); the targets come from src: a batch img [B, C, s, s], or listed
+        windows, read where they lie in their scenes (msst_head_at_fwd): the same bits"""
+        src = self._src(src)
+        if src.kind == "tiles":
+            raise NotImplementedError("head_fwd: no entry point for tiles windows")
         B, T, _ = y.shape
-        S, N, P = self.S, self.N, self.P
         K = idx32.shape[1]
         dev = y.device
-        dpred = torch.empty(B, K, P, dtype=torch.float32, device=dev)
-        pred = torch.empty(B, K, P, dtype=torch.float32, device=dev) if want_pred else None
+        dpred = torch.empty(B, K, self.P, dtype=torch.float32, device=dev)
+        pred = torch.empty(B, K, self.P, dtype=torch.float32, device=dev) if want_pred else None
         partial = torch.empty(B * ((K + 63) // 64), dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         per_block = 1 if hasattr(self.mim.to_pixels, "layers") else 0
         V = ctypes.c_void_p
-        if origins is not None:
-            Bs, _, Hs, Ws = img.shape
-            _lib.check(self.lib.msst_head_at_fwd(
-                _p(y), _p(img), _p(origins), _p(idx32), V(self.fp.ptr("to_pixels.w.0")), V(self.fp.ptr("to_pixels.b.0")), per_block,
-                _p(dpred), _p(pred), _p(partial), _p(loss), Bs, Hs, Ws, self.enc.num_spatial_patches_sqrt, B, S, P, K, _stream()),
-                "msst_head_at_fwd")
-            return loss, dpred, pred
-        _lib.check(self.lib.msst_head_fwd(
-            _p(y), _p(img), _p(idx32), V(self.fp.ptr("to_pixels.w.0")), V(self.fp.ptr("to_pixels.b.0")), per_block,
-            _p(dpred), _p(pred), _p(partial), _p(loss), B, S, N, P, K, _stream()), "msst_head_fwd")
+        name = "msst_head_at_fwd" if src.kind == "listed" else "msst_head_fwd"
+        lead, dims = self._src_args(src, 0, B)
+        _lib.check(getattr(self.lib, name)(
+            _p(y), *lead, _p(idx32), V(self.fp.ptr("to_pixels.w.0")), V(self.fp.ptr("to_pixels.b.0")), per_block,
+            _p(dpred), _p(pred), _p(partial), _p(loss), *dims, K, _stream()), name)
         return loss, dpred, pred
 
     def recon_fwd(self, y, img, mask_u8, blend=True, stats=True):
@@ -902,122 +896,70 @@ class Engine:
             drop[0], drop[1], i, _p(getattr(x1, "_msst_xn", None)), _p(getattr(x1, "_msst_lse", None)), _p(dab), _stream()), "msst_block_bwd")
         return dx
 
-    def tokenize_bwd(self, img, mask_u8, dx0, emb_drop=(0.0, 0), with_pos=True):
-        """with_pos=False: gradients of the embedding / its two LayerNorms only (the position table and the mask
-        token were applied outside the kernel, by the caller's own autograd ops)"""
-        B = img.shape[0]
-        S, N, P = self.S, self.N, self.P
-        nchunk, slab = self._tok_bwd_slab(B, img.device)
-        fp, g = self.fp, self.fp.grad
-        V = ctypes.c_void_p
+    def tokenize_bwd(self, src, mask_u8, dx0, emb_drop=(0.0, 0), with_pos=True):
+        """backward of tokenize(src, mask_u8, with_pos, emb_drop): dx0 [n, T, 96] -> the tokenizer's gradients, the position tables' and
+        (a SimMIM model's batch, or any masked source) the mask token's in the flat buffer.  One launch over all windows, with the nchunk
+        a batch of as many samples takes: the same bits.  with_pos=False: gradients of the embedding / its two LayerNorms only (the
+        position table and the mask token were applied outside the kernel, by the caller's own autograd ops)"""
+        src = self._src(src)
+        masked = mask_u8 is not None
+        name, drop_args = _tok_entry(_TOK_BWD, "tokenize_bwd", src, masked, emb_drop)
+        total, dev = src.n, src.img.device
+        nchunk, slab = self._tok_bwd_slab(total, dev)
+        g, V = self.fp.grad, ctypes.c_void_p
         split, dpa, dpb = self._pos_tables(g) if with_pos else (0, 0, 0)
-        dmt = fp.ptr("mask_token", g) if (self.mim is not None and with_pos) else 0
-        _lib.check(self.lib.msst_tokenize_bwd(
-            _p(img), *self._tok_params(), _p(mask_u8), _p(dx0), _p(slab), nchunk,
-            *self._tok_params(grad=True), V(dpa), V(dpb), split, V(dmt), B, S, N, P,
-            emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_bwd")
+        mask_args = dmt_args = ()
+        if src.kind == "batch" or masked:   # these entry points take a mask (nothing masked: the zero mask) and the mask token's gradient
+            mask_args = (_p(mask_u8 if masked else self._zero_mask_for(total * self.S * self.N, dev)),)
+            dmt_args = (V(self.fp.ptr("mask_token", g) if (self.mim is not None and with_pos) else 0),)
+        lead, dims = self._src_args(src, 0, total)
+        _lib.check(getattr(self.lib, name)(
+            *lead, *self._tok_params(), *mask_args, _p(dx0), _p(slab), nchunk, *self._tok_params(grad=True), V(dpa), V(dpb), split,
+            *dmt_args, *dims, *drop_args, _stream()), name)
         if with_pos:
             self._fire("tokenizer")
 
-    def tokenize_at_masked_bwd(self, scene, origins, mask_u8, dx0):
-        """backward of tokenize_at_masked: dx0 [n, T, 96] -> the tokenizer's gradients, the position tables' and the mask token's in the
-        flat buffer.  One msst_tokenize_at_bwd_masked over the listed windows, with the nchunk tokenize_bwd takes for as many samples:
-        the same bits"""
-        Bs, _, Hs, Ws = scene.shape
-        total = origins.shape[0]
-        nchunk, slab = self._tok_bwd_slab(total, scene.device)
-        fp, g = self.fp, self.fp.grad
-        V = ctypes.c_void_p
-        split, dpa, dpb = self._pos_tables(g)
-        _lib.check(self.lib.msst_tokenize_at_bwd_masked(
-            _p(scene), _p(origins), *self._tok_params(), _p(mask_u8), _p(dx0), _p(slab), nchunk,
-            *self._tok_params(grad=True), V(dpa), V(dpb), split, V(fp.ptr("mask_token", g)), Bs, Hs, Ws,
-            self.enc.num_spatial_patches_sqrt, total, self.S, self.P, _stream()), "msst_tokenize_at_bwd_masked")
-        self._fire("tokenizer")
-
-    def tokenize_windows_bwd(self, img, dx0, emb_drop=(0.0, 0), tiles=False, origins=None):
-        """backward of tokenize_windows: dx0 [windows, T, 96] -> the tokenizer's gradients in the flat buffer.  Tiles: one
-        msst_tokenize_scene_bwd over all windows, with the nchunk tokenize_bwd takes for as many samples -- the same bits.
-        Origins: one msst_tokenize_at_bwd over the listed windows, likewise."""
-        if origins is not None:
-            Bs, _, Hs, Ws = img.shape
-            s = self.enc.num_spatial_patches_sqrt
-            total = origins.shape[0]
-            nchunk, slab = self._tok_bwd_slab(total, img.device)
-            V = ctypes.c_void_p
-            split, dpa, dpb = self._pos_tables(self.fp.grad)
-            _lib.check(self.lib.msst_tokenize_at_bwd(
-                _p(img), _p(origins), *self._tok_params(), _p(dx0), _p(slab), nchunk,
-                *self._tok_params(grad=True), V(dpa), V(dpb), split, Bs, Hs, Ws, s, total, self.S, self.P,
-                emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_at_bwd")
-            self._fire("tokenizer")
-            return
-        if not tiles:
-            zero_mask = self._zero_mask_for(img.shape[0] * self.S * self.N, img.device)
-            return self.tokenize_bwd(img, zero_mask, dx0, emb_drop=emb_drop)
-        B, _, Ht, Wt = img.shape
-        s, nr, nq = self.tile_grid(img)
-        total = B * nr * nq
-        nchunk, slab = self._tok_bwd_slab(total, img.device)
-        V = ctypes.c_void_p
-        split, dpa, dpb = self._pos_tables(self.fp.grad)
-        _lib.check(self.lib.msst_tokenize_scene_bwd(
-            _p(img), *self._tok_params(), _p(dx0), _p(slab), nchunk,
-            *self._tok_params(grad=True), V(dpa), V(dpb), split, B, Ht, Wt, s, s, 0, total, self.S, self.P,
-            emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_scene_bwd")
-        self._fire("tokenizer")
-
     # ------------------------------------------------------------------ input gradient (msst_input_grad.hip)
-    def tokenize_input_bwd(self, img, mask_u8, dx0, dtarget=None, emb_drop=(0.0, 0)):
-        """d(loss)/d(img) through the tokenizer (msst_tokenize_bwd_input): img [B, C, H, W] as tokenize took it, mask_u8 [B, T] or None,
-        dx0 [B, T, 96] the gradient at the tokenizer's output, dtarget [B, S P, N] (head_bwd_target) added before the store -> a new
-        tensor of img's shape, written whole.  Reads only; the parameter gradients are tokenize_bwd's business."""
+    def tokenize_input_bwd(self, src, mask_u8, dx0, dtarget=None, emb_drop=(0.0, 0)):
+        """d(loss)/d(src.img) through the tokenizer: dx0 [n, T, 96] the gradient at its output.  Reads only; the parameter gradients are
+        tokenize_bwd's business.
+        batch: mask_u8 [B, T] or None, dtarget [B, S P, N] (head_bwd_target) added before the store -> a new tensor, written whole.
+        tiles: the same over the windows read in place, zeros in the trailing rows and columns that belong to no window.
+        listed (with src.csr): the windows overlap -- one msst_tokenize_at_bwd_input writes the per-window gradients dwin [n, C, N], one
+        msst_scene_fold_at sums them per pixel in its fixed order into a new tensor written whole (zeros where no window lies), or
+        into src.sink's running map: the sink's first fold writes it whole, the later ones accumulate."""
+        src = self._src(src)
+        img = src.img
         self._require_cuda(img)
-        B = img.shape[0]
-        S, N, P = self.S, self.N, self.P
-        dimg = torch.empty(img.shape, dtype=torch.float32, device=img.device)
-        _lib.check(self.lib.msst_tokenize_bwd_input(
-            _p(img), *self._tok_params(), _p(mask_u8), _p(dx0), _p(dtarget), _p(dimg), B, S, N, P,
-            emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_bwd_input")
-        return dimg
-
-    def tokenize_windows_input_bwd(self, img, dx0, emb_drop=(0.0, 0), tiles=False, origins=None, csr=None, out=None, accumulate=False):
-        """the input gradient of tokenize_windows: of a window batch (tokenize_input_bwd, nothing masked), or with tiles=True of the
-        tiles [B, C, Ht, Wt] whose windows it read in place -- one msst_tokenize_scene_bwd_input over all windows, zeros in the
-        trailing rows and columns that belong to no window.
-        origins [n, 3] (int32, on the device) with csr = scene.origins_csr(origins, ...): of the scenes img [Bs, C, Hs, Ws] whose listed
-        windows it read in place.  They overlap: one msst_tokenize_at_bwd_input writes the per-window gradients dwin [n, C, N], one
-        msst_scene_fold_at sums them per pixel in its fixed order into dscene -- a new tensor written whole (zeros where no window
-        lies), or `out` [Bs, C, Hs, Ws] fp32; with accumulate the sums start from out's values (a caller's running map)."""
-        if origins is not None:
-            self._require_cuda(img)
-            Bs, C, Hs, Ws = img.shape
-            s, n = self.enc.num_spatial_patches_sqrt, origins.shape[0]
-            if accumulate and out is None:
-                raise ValueError("accumulate needs the running map: out=")
-            if out is None:
-                out = torch.empty(img.shape, dtype=torch.float32, device=img.device)
-            elif tuple(out.shape) != tuple(img.shape) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != img.device:
+        name, drop_args = _tok_entry(_TOK_INPUT_BWD, "tokenize_input_bwd", src, mask_u8 is not None, emb_drop)
+        if dtarget is not None and src.kind != "batch":
+            raise NotImplementedError(f"tokenize_input_bwd: no entry point for {src.kind} windows with a target gradient")
+        lead, dims = self._src_args(src, 0, src.n)
+        fn, par, st = getattr(self.lib, name), self._tok_params(), _stream()
+        if src.kind != "listed":
+            dimg = torch.empty(img.shape, dtype=torch.float32, device=img.device)
+            mask_args = (_p(mask_u8),) if src.kind == "batch" else ()
+            target_args = (_p(dtarget),) if src.kind == "batch" else ()
+            _lib.check(fn(*lead, *par, *mask_args, _p(dx0), *target_args, _p(dimg), *dims, *drop_args, st), name)
+            return dimg
+        if src.csr is None:
+            raise NotImplementedError("no input gradient through windows at listed origins unless the forward opted in "
+                                      "(forward_at(..., scene_grad=True)): they overlap, so d(scene) is an accumulating fold")
+        sink = src.sink
+        if sink is None:
+            out = torch.empty(img.shape, dtype=torch.float32, device=img.device)
+        else:
+            out = sink.out
+            if tuple(out.shape) != tuple(img.shape) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != img.device:
                 raise ValueError(f"out must be a contiguous fp32 tensor {tuple(img.shape)} on the scene's device")
-            cell_ptr, cell_win = csr
-            dwin = torch.empty(n, C, self.N, dtype=torch.float32, device=img.device)
-            st = _stream()
-            _lib.check(self.lib.msst_tokenize_at_bwd_input(
-                _p(img), _p(origins), *self._tok_params(), _p(dx0), _p(dwin), Bs, Hs, Ws, s, n, self.S, self.P,
-                emb_drop[0], emb_drop[1], st), "msst_tokenize_at_bwd_input")
-            _lib.check(self.lib.msst_scene_fold_at(_p(dwin), _p(cell_ptr), _p(cell_win), _p(out), Bs, C, Hs, Ws, s, n, self.P,
-                                                   int(bool(accumulate)), st), "msst_scene_fold_at")
-            return out
-        if not tiles:
-            return self.tokenize_input_bwd(img, None, dx0, emb_drop=emb_drop)
-        self._require_cuda(img)
-        B, _, Ht, Wt = img.shape
-        s, nr, nq = self.tile_grid(img)
-        dtiles = torch.empty(img.shape, dtype=torch.float32, device=img.device)
-        _lib.check(self.lib.msst_tokenize_scene_bwd_input(
-            _p(img), *self._tok_params(), _p(dx0), _p(dtiles), B, Ht, Wt, s, s, 0, B * nr * nq, self.S, self.P,
-            emb_drop[0], emb_drop[1], _stream()), "msst_tokenize_scene_bwd_input")
-        return dtiles
+        Bs, C, Hs, Ws = img.shape
+        dwin = torch.empty(src.n, C, self.N, dtype=torch.float32, device=img.device)
+        _lib.check(fn(*lead, *par, _p(dx0), _p(dwin), *dims, *drop_args, st), name)
+        _lib.check(self.lib.msst_scene_fold_at(_p(dwin), _p(src.csr[0]), _p(src.csr[1]), _p(out), Bs, C, Hs, Ws, self.enc.num_spatial_patches_sqrt, src.n, self.P,
+                                               int(bool(sink and sink.started)), st), "msst_scene_fold_at")
+        if sink:
+            sink.started = True
+        return out
 
     def head_bwd_target(self, dpred, csr_ptr, csr_pos, gout=None):
         """the SimMIM loss's direct dependence on the input (msst_head_bwd_target): dpred [B, K, P] of head_fwd and the inverse CSR
@@ -1089,52 +1031,31 @@ class Engine:
         cur["ev"].record(torch.cuda.current_stream(dev))
         return out
 
-    def simmim_loss(self, img, bool_mask, idx):
-        """scalar loss attached to autograd (reference SimMIMSpatialSpectral.forward :203-340)"""
+    def simmim_loss(self, src, bool_mask, idx):
+        """scalar loss attached to autograd (reference SimMIMSpatialSpectral.forward :203-340) of src: a batch img [B, C, s, s], or the
+        windows listed in a Windows' origins of resident tiles, read where they lie: no stacked copy.  bool_mask / idx: one row per
+        window.  Listed windows give the loss and, through autograd, every parameter gradient the bits of the stacked batch; the tiles get
+        no gradient (SimMIMSpatialSpectral.forward_at refuses tiles that ask for one)"""
+        src = self._src(src)
+        img = src.img
         self._require_cuda(img)
         self.ensure()
-        dev = img.device
         T = self.S * self.N
-        img = img.contiguous().float()
         from .masking import inverse_csr
         bm = bool_mask.cpu().numpy() if torch.is_tensor(bool_mask) else np.asarray(bool_mask)
         ix = idx.cpu().numpy() if torch.is_tensor(idx) else np.asarray(idx)
         ptr, pos = inverse_csr(ix, T)
-        mask_u8, idx32, csr_ptr, csr_pos = self._upload(dev, bm.astype(np.uint8), ix.astype(np.int32), ptr, pos)
+        mask_u8, idx32, csr_ptr, csr_pos = self._upload(img.device, bm.astype(np.uint8), ix.astype(np.int32), ptr, pos)
         names = [n for n, _ in self.trainable()]
         params = [p for _, p in self.trainable()]
-        if not torch.is_grad_enabled() or not (img.requires_grad or any(p.requires_grad for p in params)):
+        want_img = src.kind == "batch" and img.requires_grad
+        if not torch.is_grad_enabled() or not (want_img or any(p.requires_grad for p in params)):
             self.prep_weights()
-            x0 = self.tokenize(img, mask_u8)
+            x0 = self.tokenize(src, mask_u8)
             acts, _ = self.blocks_fwd(x0, save=False, drop=self.dropout_state())
-            loss, _, _ = self.head_fwd(acts[-1], img, idx32)
+            loss, _, _ = self.head_fwd(acts[-1], src, idx32)
             return loss
-        return _SimMIMLossFn.apply(self, names, self.dropout_state(), img, mask_u8, idx32, csr_ptr, csr_pos, *params)
-
-    def simmim_loss_at(self, tiles, origins, bool_mask, idx):
-        """simmim_loss of the windows listed in origins (int32 [n, 3] on the tiles' device: tile, y0, x0) of the resident tiles
-        [Bs, C, Ht, Wt], read where they lie: no stacked copy.  bool_mask / idx: one row per window, as simmim_loss takes them.  The
-        loss and, through autograd, every parameter gradient have the bits of simmim_loss on the stacked windows; the tiles get no
-        gradient (SimMIMSpatialSpectral.forward_at refuses tiles that ask for one)"""
-        self._require_cuda(tiles)
-        self.ensure()
-        dev = tiles.device
-        T = self.S * self.N
-        tiles = tiles.contiguous()
-        from .masking import inverse_csr
-        bm = bool_mask.cpu().numpy() if torch.is_tensor(bool_mask) else np.asarray(bool_mask)
-        ix = idx.cpu().numpy() if torch.is_tensor(idx) else np.asarray(idx)
-        ptr, pos = inverse_csr(ix, T)
-        mask_u8, idx32, csr_ptr, csr_pos = self._upload(dev, bm.astype(np.uint8), ix.astype(np.int32), ptr, pos)
-        names = [n for n, _ in self.trainable()]
-        params = [p for _, p in self.trainable()]
-        if not torch.is_grad_enabled() or not any(p.requires_grad for p in params):
-            self.prep_weights()
-            x0 = self.tokenize_at_masked(tiles, origins, mask_u8)
-            acts, _ = self.blocks_fwd(x0, save=False, drop=self.dropout_state())
-            loss, _, _ = self.head_fwd(acts[-1], tiles, idx32, origins=origins)
-            return loss
-        return _SimMIMLossAtFn.apply(self, names, self.dropout_state(), tiles, origins, mask_u8, idx32, csr_ptr, csr_pos, *params)
+        return _SimMIMLossFn.apply(self, names, self.dropout_state(), src, img, mask_u8, idx32, csr_ptr, csr_pos, *params)
 
     # ------------------------------------------------------------------ encoder-level API (inference)
     def _block_param_names(self):
@@ -1279,7 +1200,7 @@ class Engine:
         for B = 1, the reference's squeeze)."""
         self._require_cuda(img)
         self.ensure()
-        return self._classify(img.contiguous().float(), img.shape[0], False)
+        return self._classify(Windows("batch", img))
 
     def classify_tiles(self, tiles):
         """classify(stack_image_batch(tiles)) without the stacked copy: logits of every non-overlapping s x s window of tiles
@@ -1292,22 +1213,22 @@ class Engine:
         NotImplementedError (a dropout element is addressed by its place in one launch's output)."""
         self._require_cuda(tiles)
         self.ensure()
-        tiles = tiles.contiguous().float()
-        s, nr, nq = self.tile_grid(tiles)
-        if nr < 1 or nq < 1:
+        s = self.enc.num_spatial_patches_sqrt
+        src = Windows("tiles", tiles, s=s)
+        if min(src.grid) < 1:
             raise ValueError(f"tiles of {tuple(tiles.shape[-2:])} hold no {s} x {s} window")
-        return self._classify(tiles, tiles.shape[0] * nr * nq, True)
+        return self._classify(src)
 
-    def classify_at(self, scene, origins):
-        """classify(the stacked s x s windows of scene [Bs, C, Hs, Ws] at origins [n, 3] = (scene, y0, x0)) without the stacked copy:
-        both tokenizer passes read the listed windows in place (msst_tokenize_at_fwd / _bwd).  origins: int32, contiguous, on the
-        scene's device, every row inside the scene (ViTSpatialSpectral.forward_at checks).  Shapes, regimes, seeds and limits of
+    def classify_at(self, src):
+        """classify(the stacked s x s windows of the scenes src.img [Bs, C, Hs, Ws] at src.origins [n, 3] = (scene, y0, x0)) without the
+        stacked copy: both tokenizer passes read the listed windows in place (msst_tokenize_at_fwd / _bwd).  origins: int32, contiguous,
+        on the scene's device, every row inside the scene (ViTSpatialSpectral.forward_at checks).  Shapes, regimes, seeds and limits of
         classify_tiles; n = 0 is refused."""
-        self._require_cuda(scene)
+        self._require_cuda(src.img)
         self.ensure()
-        if origins.shape[0] < 1:
+        if src.n < 1:
             raise ValueError("origins lists no window")
-        return self._classify(scene.contiguous().float(), origins.shape[0], origins)   # (or a ListedWindows: the scene's gradient too)
+        return self._classify(src)
 
     def window_alignment(self):
         """A: a window's logits and gradients keep their bits when its place in the batch moves by a multiple of A windows.  The block
@@ -1325,36 +1246,32 @@ class Engine:
             b = ts // gcd(self.S, ts)
         return a * b // gcd(a, b)
 
-    def _classify(self, img, B, tiles):
-        """classify / classify_tiles / classify_at: img a batch of B windows, or (tiles is True) the tiles that hold B windows, or
-        (tiles an origins table) the scenes the B listed windows lie in"""
+    def _classify(self, src):
+        """classify / classify_tiles / classify_at on their source"""
+        img, B = src.img, src.n
         p = float(self.enc.dropout_p) if self.enc.training else 0.0
         pe = float(self.enc.emb_dropout_p) if self.enc.training else 0.0
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if (p > 0 or pe > 0) else 0
         drop, emb_drop = (p, seed), (pe, seed ^ 0x5bd1e995)
-        params = [q for _, q in self.trainable()]
-        want = torch.is_grad_enabled() and (img.requires_grad or any(q.requires_grad for q in params))
-        if self.mim is not None or not want:
-            if self.mim is not None and want:
-                raise NotImplementedError("train the classifier through a bare ViTSpatialSpectral (as finetune.py "
-                                          "does), not through an encoder wrapped in SimMIMSpatialSpectral")
-            self.prep_weights()
-            x0 = self.tokenize_windows(img, emb_drop, **_window_kw(tiles))
+        named = self.trainable()
+        want = torch.is_grad_enabled() and (img.requires_grad or any(q.requires_grad for _, q in named))
+        if self.mim is not None and want:
+            raise NotImplementedError("train the classifier through a bare ViTSpatialSpectral (as finetune.py "
+                                      "does), not through an encoder wrapped in SimMIMSpatialSpectral")
+        if want and (img.requires_grad or any(q.requires_grad for n, q in named if not n.startswith("mlp_head."))):
+            out = _ClassifyFn.apply(self, [n for n, _ in named], drop, emb_drop, src, img, *[q for _, q in named])
+            return self._classify_view(out, B)
+        self.prep_weights()
+        x0 = self.tokenize(src, None, emb_drop=emb_drop)
+        if not want:
             acts, _ = self.blocks_fwd(x0, save=False, drop=drop)
             return self._classify_view(self.head_logits(acts[-1]), B)
-        named = self.trainable()
-        if not img.requires_grad and not any(q.requires_grad for n, q in named if not n.startswith("mlp_head.")):
-            # linear evaluation (reference finetune.py:110-136: only mlp_head trains): the body runs as in a no-gradient forward --
-            # module still in training mode, so its dropout stays on -- with nothing saved, and only the head has a backward.  (An
-            # input that requires a gradient needs the full body backward: that call takes the full path below.)
-            self.prep_weights()
-            x0 = self.tokenize_windows(img, emb_drop, **_window_kw(tiles))
-            y = self.blocks_fwd_pingpong(x0, drop=drop)
-            head = [(n, q) for n, q in named if n.startswith("mlp_head.")]
-            out = _HeadOnlyFn.apply(self, [n for n, _ in head], y, *[q for _, q in head])
-            return self._classify_view(out, B)
-        names = [n for n, _ in named]
-        out = _ClassifyFn.apply(self, names, drop, emb_drop, tiles, img, *params)
+        # linear evaluation (reference finetune.py:110-136: only mlp_head trains): the body runs as in a no-gradient forward --
+        # module still in training mode, so its dropout stays on -- with nothing saved, and only the head has a backward.  (An
+        # input that requires a gradient needs the full body backward: that call takes the full path above.)
+        y = self.blocks_fwd_pingpong(x0, drop=drop)
+        head = [(n, q) for n, q in named if n.startswith("mlp_head.")]
+        out = _HeadOnlyFn.apply(self, [n for n, _ in head], y, *[q for _, q in head])
         return self._classify_view(out, B)
 
     # ------------------------------------------------------------------ scene inference (maskedsst_amd/scene.py, msst_scene_assemble)
@@ -1531,68 +1448,38 @@ class Engine:
 
 
 class _SimMIMLossFn(torch.autograd.Function):
-    """loss = SimMIM(img); gradients of every parameter come from the HIP backward kernels and are
-    handed to autograd as views of the flat gradient buffer."""
+    """loss = SimMIM(the windows of src); gradients of every parameter come from the HIP backward kernels and are handed to autograd as
+    views of the flat gradient buffer.  img = src.img, for autograd: a batch receives its gradient, tiles read through listed windows
+    none."""
 
     @staticmethod
-    def forward(ctx, eng, names, drop, img, mask_u8, idx32, csr_ptr, csr_pos, *params):
+    def forward(ctx, eng, names, drop, src, img, mask_u8, idx32, csr_ptr, csr_pos, *params):
         eng.prep_weights()
-        x0 = eng.tokenize(img, mask_u8)
+        x0 = eng.tokenize(src, mask_u8)
         acts, x1s = eng.blocks_fwd(x0, save=True, drop=drop)
         ctx.drop = drop
-        loss, dpred, _ = eng.head_fwd(acts[-1], img, idx32)
+        loss, dpred, _ = eng.head_fwd(acts[-1], src, idx32)
         ctx.eng = eng
         ctx.names = names
-        ctx.stash = (img, mask_u8, csr_ptr, csr_pos, acts, x1s, dpred)
+        ctx.stash = (src, mask_u8, csr_ptr, csr_pos, acts, x1s, dpred)
         return loss
 
     @staticmethod
     def backward(ctx, gout):
         eng = ctx.eng
-        img, mask_u8, csr_ptr, csr_pos, acts, x1s, dpred = ctx.stash
-        ctx.stash = None
-        needs = ctx.needs_input_grad[8:]
-        _refuse_accumulation(eng, ctx.names, needs)
-        gout = gout.contiguous().float()
-        dy = eng.head_bwd(acts[-1], dpred, csr_ptr, csr_pos, gout)
-        dx0 = eng.blocks_bwd(acts, x1s, dy, drop=ctx.drop)
-        dimg = None
-        if ctx.needs_input_grad[3]:   # the input asked for its gradient: two more launches that only read
-            dimg = eng.tokenize_input_bwd(img, mask_u8, dx0, eng.head_bwd_target(dpred, csr_ptr, csr_pos, gout))
-        if any(needs):   # (a fully frozen model: the tokenizer backward writes parameter gradients only, nobody reads them)
-            eng.tokenize_bwd(img, mask_u8, dx0)
-        return (None, None, None, dimg) + (None,) * 4 + _grad_views(eng, ctx.names, needs)
-
-
-class _SimMIMLossAtFn(torch.autograd.Function):
-    """_SimMIMLossFn over windows at listed positions of resident tiles (Engine.simmim_loss_at): the tokenizer and the head read the
-    windows out of the tiles, everything between them is the same sequence.  The tiles receive no gradient."""
-
-    @staticmethod
-    def forward(ctx, eng, names, drop, tiles, origins, mask_u8, idx32, csr_ptr, csr_pos, *params):
-        eng.prep_weights()
-        x0 = eng.tokenize_at_masked(tiles, origins, mask_u8)
-        acts, x1s = eng.blocks_fwd(x0, save=True, drop=drop)
-        ctx.drop = drop
-        loss, dpred, _ = eng.head_fwd(acts[-1], tiles, idx32, origins=origins)
-        ctx.eng = eng
-        ctx.names = names
-        ctx.stash = (tiles, origins, mask_u8, csr_ptr, csr_pos, acts, x1s, dpred)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gout):
-        eng = ctx.eng
-        tiles, origins, mask_u8, csr_ptr, csr_pos, acts, x1s, dpred = ctx.stash
+        src, mask_u8, csr_ptr, csr_pos, acts, x1s, dpred = ctx.stash
         ctx.stash = None
         needs = ctx.needs_input_grad[9:]
         _refuse_accumulation(eng, ctx.names, needs)
         gout = gout.contiguous().float()
         dy = eng.head_bwd(acts[-1], dpred, csr_ptr, csr_pos, gout)
         dx0 = eng.blocks_bwd(acts, x1s, dy, drop=ctx.drop)
+        dimg = None
+        if ctx.needs_input_grad[4] and src.kind == "batch":   # the input asked for its gradient: two more launches that only read
+            dimg = eng.tokenize_input_bwd(src, mask_u8, dx0, eng.head_bwd_target(dpred, csr_ptr, csr_pos, gout))
         if any(needs):   # (a fully frozen model: the tokenizer backward writes parameter gradients only, nobody reads them)
-            eng.tokenize_at_masked_bwd(tiles, origins, mask_u8, dx0)
-        return (None,) * 9 + _grad_views(eng, ctx.names, needs)
+            eng.tokenize_bwd(src, mask_u8, dx0)
+        return (None,) * 4 + (dimg,) + (None,) * 4 + _grad_views(eng, ctx.names, needs)
 
 
 def _refuse_accumulation(eng, names, needs=None):
@@ -1659,8 +1546,7 @@ class _EmbedFn(torch.autograd.Function):
         dtok = dtok.contiguous().float()
         dimg = eng.tokenize_input_bwd(img, None, dtok) if ctx.needs_input_grad[2] else None
         if any(needs):
-            zero_mask = eng._zero_mask_for(img.shape[0] * eng.S * eng.N, img.device)
-            eng.tokenize_bwd(img, zero_mask, dtok, with_pos=False)
+            eng.tokenize_bwd(img, None, dtok, with_pos=False)
         return (None, None, dimg) + _grad_views(eng, ctx.names, needs)
 
 
@@ -1673,63 +1559,36 @@ class SceneGradSink:
         self.out, self.started = out, False
 
 
-class ListedWindows:
-    """the `tiles` slot of _classify / _ClassifyFn for classify_at when the scene's gradient was opted into (forward_at(...,
-    scene_grad=True)): the int32 origins table [n, 3], its inverse index (scene.origins_csr) and optionally the sink the backward
-    folds into.  A bare table in the slot keeps refusing the scene's gradient."""
-
-    def __init__(self, origins, csr, sink=None):
-        self.origins, self.csr, self.sink = origins, csr, sink
-        self.shape = origins.shape
-
-
-def _window_kw(tiles):
-    """the `tiles` slot of _classify / _ClassifyFn as tokenize_windows' keywords: a flag (window batch or tiles), or the int32 origins
-    table [n, 3] of classify_at (the windows listed in it, read out of the scenes; a ListedWindows: its table)"""
-    if isinstance(tiles, ListedWindows):
-        return {"origins": tiles.origins}
-    return {"origins": tiles} if torch.is_tensor(tiles) else {"tiles": tiles}
-
-
 class _ClassifyFn(torch.autograd.Function):
-    """logits = encoder(img) for the classification path; backward through the same HIP kernels.  img: a window batch, or (tiles) tiles
-    whose windows both tokenizer passes read in place (Engine.tokenize_windows) -- the stash holds img as it came.  The tiles slot
-    may hold an origins table instead of a flag (_window_kw): img is then the scenes, and ctx keeps the table for the backward."""
+    """logits = encoder(the windows of src) for the classification path; backward through the same HIP kernels.  Both tokenizer passes
+    read tiles and listed windows in place: the stash holds the source, not the windows.  img = src.img, for autograd."""
 
     @staticmethod
-    def forward(ctx, eng, names, drop, emb_drop, tiles, img, *params):
+    def forward(ctx, eng, names, drop, emb_drop, src, img, *params):
         eng.prep_weights()
-        x0 = eng.tokenize_windows(img, emb_drop, **_window_kw(tiles))
+        x0 = eng.tokenize(src, None, emb_drop=emb_drop)
         acts, x1s = eng.blocks_fwd(x0, save=True, drop=drop)
         logits = eng.head_logits(acts[-1])
-        ctx.eng, ctx.names, ctx.drop, ctx.emb_drop, ctx.tiles = eng, names, drop, emb_drop, tiles
-        ctx.stash = (img, acts, x1s)
+        ctx.eng, ctx.names, ctx.drop, ctx.emb_drop = eng, names, drop, emb_drop
+        ctx.stash = (src, acts, x1s)
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         eng = ctx.eng
-        img, acts, x1s = ctx.stash
+        src, acts, x1s = ctx.stash
         ctx.stash = None
         needs = ctx.needs_input_grad[6:]
         _refuse_accumulation(eng, ctx.names, needs)
         dy = eng.head_logits_bwd(acts[-1], dlogits.contiguous().float())
         dx0 = eng.blocks_bwd(acts, x1s, dy, drop=ctx.drop)
         dimg = None
-        if ctx.needs_input_grad[5]:   # the input (window batch or tiles) asked for its gradient: one more launch that only reads
-            if torch.is_tensor(ctx.tiles):
-                raise NotImplementedError("no input gradient through windows at listed origins unless the forward opted in "
-                                          "(forward_at(..., scene_grad=True)): they overlap, so d(scene) is an accumulating fold")
-            if isinstance(ctx.tiles, ListedWindows):   # two more launches that only read: per-window gradients, then the fold
-                at, sink = ctx.tiles, ctx.tiles.sink
-                dimg = eng.tokenize_windows_input_bwd(img, dx0, emb_drop=ctx.emb_drop, origins=at.origins, csr=at.csr,
-                                                      out=sink.out if sink else None, accumulate=bool(sink and sink.started))
-                if sink:
-                    sink.started, dimg = True, None
-            else:
-                dimg = eng.tokenize_windows_input_bwd(img, dx0, emb_drop=ctx.emb_drop, tiles=ctx.tiles)
+        if ctx.needs_input_grad[5]:   # the input asked for its gradient: launches that only read (listed windows refuse unless opted in)
+            dimg = eng.tokenize_input_bwd(src, None, dx0, emb_drop=ctx.emb_drop)
+            if src.sink is not None:   # the sink holds the fold: autograd gets no gradient for the scene
+                dimg = None
         if any(needs):   # (a fully frozen model: the tokenizer backward writes parameter gradients only, nobody reads them)
-            eng.tokenize_windows_bwd(img, dx0, emb_drop=ctx.emb_drop, **_window_kw(ctx.tiles))
+            eng.tokenize_bwd(src, None, dx0, emb_drop=ctx.emb_drop)
         return (None,) * 5 + (dimg,) + _grad_views(eng, ctx.names, needs)
 
 

@@ -195,12 +195,13 @@ def forward_at(model, scene, origins, check=True, scene_grad=False):
                                   "the scene (parameter gradients are computed)")
     eng = model.engine()
     eng._require_cuda(scene)
+    from .engine import SceneGradSink, Windows
     table = origins.to(device=scene.device, dtype=torch.int32).contiguous()
+    csr = sink = None
     if wants:
-        from .engine import ListedWindows, SceneGradSink
         Bs, _, Hs, Ws = scene.shape
-        table = ListedWindows(table, origins_csr(table, Bs, Hs, Ws), scene_grad if isinstance(scene_grad, SceneGradSink) else None)
-    return eng.classify_at(scene, table)
+        csr, sink = origins_csr(table, Bs, Hs, Ws), scene_grad if isinstance(scene_grad, SceneGradSink) else None
+    return eng.classify_at(Windows("listed", scene, table, csr, sink))
 
 
 def predict_at(model, scene, origins, return_logits=False, max_windows=SCENE_MAX_WINDOWS):

@@ -151,7 +151,8 @@ class SimMIMSpatialSpectral(nn.Module):
             masks = self.draw_masks(n)
         self.last_masks = masks
         table = origins.to(device=tiles.device, dtype=torch.int32).contiguous()
-        return eng.simmim_loss_at(tiles, table, masks[0], masks[1])
+        from .engine import Windows
+        return eng.simmim_loss(Windows("listed", tiles, table), masks[0], masks[1])
 
     def forward_windows(self, tiles, masks=None):
         """forward(stack_image_batch(tiles), masks) without the stacked copy: the loss over every non-overlapping image_size x

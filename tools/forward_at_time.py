@@ -36,6 +36,7 @@ sys.path.insert(0, ROOT)
 
 import finetune  # noqa: E402
 from maskedsst_amd import ViTSpatialSpectral, centre_origins, random_origins, window_labels  # noqa: E402
+from maskedsst_amd.engine import Windows  # noqa: E402
 
 
 def build(args, device, pixelwise):
@@ -92,9 +93,9 @@ def tokenizer_alone(model, tiles, origins, s):
     model.eval()
     with torch.no_grad():
         eng.ensure()
-        stacked = gather(tiles, origins, s)
-        return dict(at=event_ms(lambda: eng.tokenize_windows(tiles, origins=origins)), gather=event_ms(lambda: gather(tiles, origins, s)),
-                    batch=event_ms(lambda: eng.tokenize_windows(stacked)))
+        stacked, listed = gather(tiles, origins, s), Windows("listed", tiles, origins)
+        return dict(at=event_ms(lambda: eng.tokenize(listed)), gather=event_ms(lambda: gather(tiles, origins, s)),
+                    batch=event_ms(lambda: eng.tokenize(stacked)))
 
 
 def shape_row(args, dev, pixelwise, n):

@@ -36,6 +36,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from maskedsst_amd import SimMIMSpatialSpectral, ViTSpatialSpectral  # noqa: E402
 from maskedsst_amd.data import ResidentTileLoader  # noqa: E402
+from maskedsst_amd.engine import Windows  # noqa: E402
 from maskedsst_amd.optim import FusedAdamW  # noqa: E402
 from forward_at_time import event_ms, gather, timed  # noqa: E402
 
@@ -60,11 +61,11 @@ def launches_alone(model, pool, origins, masks, s):
     idx32 = torch.as_tensor(np.asarray(masks[1])).to(device=pool.device, dtype=torch.int32).contiguous()
     with torch.no_grad():
         eng.prep_weights()
-        stacked = gather(pool, origins, s).contiguous()
+        stacked, listed = gather(pool, origins, s).contiguous(), Windows("listed", pool, origins)
         y = eng.tokenize(stacked, mask_u8)
-        tok = dict(at=event_ms(lambda: eng.tokenize_at_masked(pool, origins, mask_u8)), gather=event_ms(lambda: gather(pool, origins, s)),
+        tok = dict(at=event_ms(lambda: eng.tokenize(listed, mask_u8)), gather=event_ms(lambda: gather(pool, origins, s)),
                    batch=event_ms(lambda: eng.tokenize(stacked, mask_u8)))
-        head = dict(at=event_ms(lambda: eng.head_fwd(y, pool, idx32, origins=origins)), batch=event_ms(lambda: eng.head_fwd(y, stacked, idx32)))
+        head = dict(at=event_ms(lambda: eng.head_fwd(y, listed, idx32)), batch=event_ms(lambda: eng.head_fwd(y, stacked, idx32)))
     return tok, head
 
 
