@@ -107,6 +107,11 @@ def build_parser():
                     help="one more line per validation: the three spectral blocks that receive the most rollout attention "
                          "(maskedsst_amd.attention_rollout of model.attention_maps(stack='spectral')) over the first batch of windows "
                          "of the --val-scenes")
+    ap.add_argument("--accumulate", type=int, default=1, metavar="K",
+                    help="sum the gradients of K micro-steps of batch_size // K tiles (--train-at: windows_per_step // K windows) before "
+                         "each optimizer step (maskedsst_amd.GradAccumulator); --steps counts optimizer steps")
+    ap.add_argument("--clip-norm", type=float, default=None, metavar="X",
+                    help="clip the (accumulated) gradient to the global L2 norm X before the optimizer step (clip_grad_norm_, fused)")
     return ap
 
 
@@ -184,6 +189,8 @@ def main():
         for n, p in model.named_parameters():
             p.requires_grad_("mlp_head" in n)
     optimizer = make_optimizer(model, config, args.optimizer)
+    accumulator, micro, micro_windows = make_accumulator(model, args.accumulate, args.clip_norm, config.batch_size, args.windows_per_step,
+                                                         bool(args.train_at))
     if args.train_at == "labelled" and not config.pixelwise:
         raise SystemExit("--train-at labelled draws one class per window: it needs a pixelwise model (--pixelwise)")
     if args.train_at == "random" and config.pixelwise:
@@ -226,11 +233,15 @@ def main():
             weight = inverse_frequency_weights(label, config.n_classes, config.ignored_label)
             print("class weights " + " ".join(f"{v:.4f}" for v in weight.tolist()), flush=True)
             criterion = make_criterion(args.loss, config.ignored_label, weight, args.label_smoothing).to(device)
-        if args.train_at:
-            loss, acc, macro_acc = train_step_at_listed(img.to(device), label, model, config, criterion, optimizer, args.train_at,
-                                                        args.windows_per_step, gen)
-        else:
-            loss, acc, macro_acc = train_step(img, label, model, config, device, criterion, optimizer)
+        # --accumulate K: K micro-steps over K slices of the step's tiles (--train-at: K draws of windows_per_step // K windows from
+        # all of them); the optimizer steps inside the last one, and the step's log line is the last micro-step's
+        for k in range(args.accumulate):
+            if args.train_at:
+                loss, acc, macro_acc = train_step_at_listed(img.to(device), label, model, config, criterion, optimizer, args.train_at,
+                                                            micro_windows, gen, accumulator=accumulator)
+            else:
+                loss, acc, macro_acc = train_step(img[k * micro:(k + 1) * micro], label[k * micro:(k + 1) * micro], model, config, device,
+                                                  criterion, optimizer, accumulator=accumulator)
         if step % config.logging_freq == 0:
             macro = f" macro_acc {float(macro_acc):.3f}" if fused else ""   # (the eager path has no macro accuracy: it repeats acc)
             print(f"step {step} loss {loss.item():.4f} acc {float(acc):.3f}{macro} {step * per_step / (time.time() - t0):.1f} samples/s",
@@ -250,7 +261,25 @@ def main():
                 validate_attention(model, val, step)
 
 
-def train_step_at_listed(scene, label, model, config, criterion, optimizer, mode, n, gen):
+def make_accumulator(model, accumulate, clip_norm, batch_size, windows_per_step, train_at):
+    """--accumulate K / --clip-norm X -> (the GradAccumulator, or None without either flag: the step as it always was; tiles per
+    micro-step; windows per micro-step under --train-at)"""
+    if accumulate < 1:
+        raise SystemExit("--accumulate must be at least 1")
+    if clip_norm is not None and not clip_norm > 0.0:
+        raise SystemExit("--clip-norm must be positive")
+    if train_at and windows_per_step % accumulate:
+        raise SystemExit(f"--windows-per-step {windows_per_step} does not split into --accumulate {accumulate} micro-steps")
+    if not train_at and batch_size % accumulate:
+        raise SystemExit(f"batch size {batch_size} does not split into --accumulate {accumulate} micro-steps")
+    accumulator = None
+    if accumulate > 1 or clip_norm is not None:
+        from maskedsst_amd import GradAccumulator
+        accumulator = GradAccumulator(model, steps=accumulate, max_norm=clip_norm)
+    return accumulator, batch_size // accumulate, windows_per_step // accumulate
+
+
+def train_step_at_listed(scene, label, model, config, criterion, optimizer, mode, n, gen, accumulator=None):
     """--train-at: one step on n windows of the resident tiles scene [B, C, 64, 64] (on the device; label [B, 64, 64] on the host, where
     the table is drawn).  labelled: n of centre_origins' rows, drawn without replacement (all of them when there are fewer), each with
     its centre's class; random: n random_origins that hold a labelled pixel, with their label patches."""
@@ -267,7 +296,7 @@ def train_step_at_listed(scene, label, model, config, criterion, optimizer, mode
         origins = random_origins(label.shape[0], label.shape[1], label.shape[2], s, n, generator=gen, labels=label,
                                  ignore_index=config.ignored_label)
         labels = window_labels(label, origins, s)
-    return train_step_at(scene, labels, origins, model, config, criterion, optimizer)
+    return train_step_at(scene, labels, origins, model, config, criterion, optimizer, accumulator=accumulator)
 
 
 def validate_at(model, val, step, ignored_label, report=False):

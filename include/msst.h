@@ -732,6 +732,41 @@ typedef struct {
 int msst_adam_groups(float* p, const float* g, float* m, float* v, const MsstAdamGroup* groups /*host*/, int ngroups,
                      int group_bytes, double beta1, double beta2, float eps, float gscale, void* stream);
 
+/* Gradient accumulation over micro-batches and the global-norm clip on the flat gradient buffers (additive under MSST_VERSION 109).
+ * Both entry points work over a HOST table of 1 .. MSST_GRAD_MAX_RANGES element ranges [start, end) of the flat buffers, ascending,
+ * disjoint, end > start; range_bytes = sizeof(MsstGradRange).  The table travels by value in the kernel arguments.  Elements outside
+ * every range are neither read nor written in any buffer.  Range ends are arbitrary: the 16-byte aligned interior of a range moves
+ * as dwordx4, its ragged ends (at most 3 + 3 elements) as single floats; buffers that are not 16-byte aligned themselves are walked
+ * float by float.  One launch each, 256 threads per workgroup, a capped grid and a strided loop.  No atomics, nothing to zero
+ * beforehand: two calls on the same input give the same bits in every output, the scratch included.
+ *
+ * The accumulate call, per element of a range:  a = first ? g[i] : acc[i] + g[i] (one fp32 add);  acc[i] = a;  with out != NULL also
+ * out[i] = a * scale (one fp32 multiply; out may be g itself: a lane reads its elements before it writes them; out must not be acc).
+ * With scratch != NULL every workgroup also leaves, in its own slot of scratch, the double sum of (double)a * (double)a over its
+ * elements and the count of its non-finite a, summed in a fixed order; which element belongs to which workgroup depends on the range
+ * table alone.  scratch: msst_grad_accum_scratch_bytes(nranges) bytes of device memory, 8-byte aligned (0 for nranges outside
+ * 1 .. MSST_GRAD_MAX_RANGES).
+ *
+ * The finalize call reads a scratch the accumulate call wrote for the SAME table.  Every workgroup re-reduces the partials in one fixed
+ * order, in double, and forms   total = (float)(scale * sqrt(sum));   coef = max_norm > 0 ? min(1, max_norm / (total + 1e-6f)) : 1
+ * in fp32 -- the operations of torch.nn.utils.clip_grad_norm_ on the gradient acc * scale -- then   g[i] = (acc[i] * scale) * coef,
+ * two fp32 multiplies in that order.  One workgroup writes record[0..3] = {total, coef, (float)(number of non-finite a), 0} on the
+ * device.  g must not be acc.
+ *
+ * Checked before anything is enqueued, in this order: MSST_ERR_BADARG for a null required pointer (acc, g, ranges; finalize also
+ * scratch and record), for nranges < 1 and for a range_bytes of another header revision; MSST_ERR_UNSUPPORTED for nranges >
+ * MSST_GRAD_MAX_RANGES; MSST_ERR_BADARG for a range with start < 0 or end <= start, for ranges that overlap or do not ascend, and for
+ * a scratch that is not 8-byte aligned and for a g or an out that is acc. */
+#define MSST_GRAD_MAX_RANGES 64
+typedef struct {
+    long start, end;       /* element range [start, end) of the flat buffers */
+} MsstGradRange;
+long msst_grad_accum_scratch_bytes(int nranges);
+int msst_grad_accumulate(float* acc, const float* g, const MsstGradRange* ranges /*host*/, int nranges, int range_bytes, int first,
+                         float* out /*optional*/, float scale, void* scratch /*optional*/, void* stream);
+int msst_grad_finalize(const float* acc, float* g, const MsstGradRange* ranges /*host*/, int nranges, int range_bytes, float scale,
+                       float max_norm, const void* scratch, float* record, void* stream);
+
 /* Opt-in per-kernel timing: when enabled every kernel launch of the library is bracketed by a pair
  * of HIP events recorded on the launch stream.  msst_profile_collect synchronises on the recorded
  * events and returns, per kernel id (0 .. msst_profile_kernels()-1), the summed duration in ms and

@@ -10,7 +10,8 @@ Compute runs in hand-written HIP kernels (``maskedsst_amd/csrc``) behind the C-A
 from .vit_spatial_spectral import ViTSpatialSpectral  # noqa: F401
 from .vit_simmim_original import SimMIMSpatialSpectral, BlockwiseToPixels, Reconstruction, SceneReconstruction  # noqa: F401
 from .recon import recon_report, ReconReport, window_masks_to_scene, scene_mask_to_windows  # noqa: F401
-from .masking import MaskGenerator  # noqa: F401
+from .masking import MaskGenerator, micro_masks  # noqa: F401
+from .optim import GradAccumulator  # noqa: F401
 from .scene import SceneEmbedding, centre_origins, random_origins, window_labels  # noqa: F401
 from .saliency import input_gradient, band_importance, integrated_gradients, scene_saliency, band_importance_scene, SceneSaliency  # noqa: F401
 from .attention import AttentionMaps, attention_rollout, attention_received  # noqa: F401
@@ -18,4 +19,5 @@ from .attention import AttentionMaps, attention_rollout, attention_received  # n
 __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "MaskGenerator", "Reconstruction", "recon_report",
            "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows", "SceneEmbedding",
            "input_gradient", "band_importance", "integrated_gradients", "AttentionMaps", "attention_rollout", "attention_received",
-           "centre_origins", "random_origins", "window_labels", "scene_saliency", "band_importance_scene", "SceneSaliency"]
+           "centre_origins", "random_origins", "window_labels", "scene_saliency", "band_importance_scene", "SceneSaliency",
+           "GradAccumulator", "micro_masks"]

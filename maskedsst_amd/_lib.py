@@ -45,8 +45,13 @@ class MsstAdamGroup(Structure):
     _fields_ = [("start", c_long), ("end", c_long), ("lr", c_float), ("weight_decay", c_float), ("step", c_int), ("flags", c_int)]
 
 
+class MsstGradRange(Structure):
+    _fields_ = [("start", c_long), ("end", c_long)]
+
+
 _P = c_void_p
-ADAM_DECOUPLED = 1            # include/msst.h: MSST_ADAM_DECOUPLED
+GRAD_MAX_RANGES = 64          # include/msst.h: MSST_GRAD_MAX_RANGES
+ADAM_DECOUPLED = 1           # include/msst.h: MSST_ADAM_DECOUPLED
 ADAM_MAX_GROUPS = 64          # include/msst.h: MSST_ADAM_MAX_GROUPS
 BWD_DEFER_REDUCE = 512 << 8   # include/msst.h: MSST_BWD_DEFER_REDUCE
 X1_BF16 = 1024 << 8           # include/msst.h: MSST_X1_BF16
@@ -137,6 +142,9 @@ _SIGS = {
                            c_float, c_float, _P]),
     "msst_adam_groups": (c_int, [_P, _P, _P, _P, POINTER(MsstAdamGroup), c_int, c_int, ctypes.c_double, ctypes.c_double,
                                  c_float, c_float, _P]),
+    "msst_grad_accum_scratch_bytes": (c_long, [c_int]),
+    "msst_grad_accumulate": (c_int, [_P, _P, POINTER(MsstGradRange), c_int, c_int, c_int, _P, c_float, _P, _P]),
+    "msst_grad_finalize": (c_int, [_P, _P, POINTER(MsstGradRange), c_int, c_int, c_float, c_float, _P, _P, _P]),
 }
 
 _lib = None

@@ -345,7 +345,7 @@ const char* msst_profile_name(int id) {
     static const char* names[K_COUNT] = {"prep_weights", "tokenize_fwd", "block_fwd", "head_fwd", "loss_reduce",
                                          "head_bwd", "reduce_slabs", "block_bwd_mlp", "block_bwd_attn",
                                          "attn_slab_reduce", "block_bwd_ln1", "tokenize_bwd", "pos_split", "adamw", "block_bwd_ln1mlp", "layernorm", "adam_groups", "cross_entropy", "recon_fwd",
-                                         "tokenize_bwd_input", "head_bwd_target"};
+                                         "tokenize_bwd_input", "head_bwd_target", "grad_accumulate", "grad_finalize"};
     return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 
@@ -1434,6 +1434,81 @@ int msst_adam_groups(float* p, const float* g, float* m, float* v, const MsstAda
     if (!t.nseg) return 0;
     if (!p || !g || !m || !v) return fail(MSST_ERR_BADARG, "msst_adam_groups (null buffer)");
     return fail(launch_adam_groups(p, g, m, v, t, (hipStream_t)stream), "msst_adam_groups");
+}
+
+// ---- gradient accumulation and the global-norm clip (msst_accum.hip) ----
+// the checks both entry points share, in the order include/msst.h states; `have_ptrs`: every required pointer of the caller is non-null
+static int grad_ranges_check(const char* what, bool have_ptrs, const MsstGradRange* ranges, int nranges, int range_bytes) {
+    if (!have_ptrs || !ranges) return fail(MSST_ERR_BADARG, what, " (null argument)");
+    if (nranges < 1) return fail(MSST_ERR_BADARG, what, " (nranges < 1)");
+    if (range_bytes != (int)sizeof(MsstGradRange)) return fail(MSST_ERR_BADARG, what, " (MsstGradRange of another header revision)");
+    if (nranges > MSST_GRAD_MAX_RANGES) return fail(MSST_ERR_UNSUPPORTED, what, " (more than MSST_GRAD_MAX_RANGES ranges)");
+    long prev_end = 0;
+    for (int i = 0; i < nranges; ++i) {
+        if (ranges[i].start < 0 || ranges[i].end <= ranges[i].start) return fail(MSST_ERR_BADARG, what, " (range with end <= start)");
+        if (ranges[i].start < prev_end) return fail(MSST_ERR_BADARG, what, " (ranges overlap or are not ascending)");
+        prev_end = ranges[i].end;
+    }
+    return 0;
+}
+
+// The workgroups of either launch over the table: range i gets one per 256 * GRAD_U float4 pieces of its aligned interior (at least
+// one), scaled down together when that exceeds GRAD_GRID; nblocks <= GRAD_GRID + nranges.  The split depends on the element ranges
+// alone, so the finalize launch knows how many partials the accumulate launch left; buffers that are not 16-byte aligned themselves
+// only empty the interiors (the first workgroup of a range then walks all of it float by float, the others find nothing).
+static void grad_table(GradTable& t, const MsstGradRange* ranges, int nranges, bool aligned) {
+    long need[MSST_GRAD_MAX_RANGES], total = 0;
+    const long per = 256L * GRAD_U, grid_cap = GRAD_GRID;
+    for (int i = 0; i < nranges; ++i) {
+        GradSeg& s = t.s[i];
+        s.start = ranges[i].start; s.end = ranges[i].end;
+        s.a0 = (s.start + 3) & ~3L;
+        s.a1 = s.end & ~3L;
+        if (s.a1 <= s.a0) s.a0 = s.a1 = s.end;
+        need[i] = ((s.a1 - s.a0) / 4 + per - 1) / per;
+        if (need[i] < 1) need[i] = 1;
+        total += need[i];
+        if (!aligned) s.a0 = s.a1 = s.end;
+    }
+    t.nseg = nranges; t.nblocks = 0;
+    for (int i = 0; i < nranges; ++i) {
+        long nb = total <= grid_cap ? need[i] : need[i] * grid_cap / total;
+        if (nb < 1) nb = 1;
+        t.s[i].blk0 = t.nblocks; t.s[i].nblk = (int)nb;
+        t.nblocks += (int)nb;
+    }
+}
+
+long msst_grad_accum_scratch_bytes(int nranges) {
+    if (nranges < 1 || nranges > MSST_GRAD_MAX_RANGES) return 0;
+    return ((long)(GRAD_GRID + nranges) * (long)(sizeof(double) + sizeof(unsigned)) + 15) & ~15L;
+}
+
+int msst_grad_accumulate(float* acc, const float* g, const MsstGradRange* ranges, int nranges, int range_bytes, int first, float* out,
+                         float scale, void* scratch, void* stream) {
+    const int rc = grad_ranges_check("msst_grad_accumulate", acc && g, ranges, nranges, range_bytes);
+    if (rc) return rc;
+    if ((uintptr_t)scratch & 7) return fail(MSST_ERR_BADARG, "msst_grad_accumulate (scratch not 8-byte aligned)");
+    if (out == acc || g == acc) return fail(MSST_ERR_BADARG, "msst_grad_accumulate (g and out must not be acc)");
+    const bool aligned = (((uintptr_t)acc | (uintptr_t)g | (uintptr_t)out) & 15) == 0;
+    GradTable t;
+    grad_table(t, ranges, nranges, aligned);
+    double* part_sum = (double*)scratch;
+    unsigned* part_bad = scratch ? (unsigned*)(part_sum + t.nblocks) : nullptr;
+    return fail(launch_grad_accumulate(acc, g, out, scale, first != 0, part_sum, part_bad, t, (hipStream_t)stream), "msst_grad_accumulate");
+}
+
+int msst_grad_finalize(const float* acc, float* g, const MsstGradRange* ranges, int nranges, int range_bytes, float scale, float max_norm,
+                       const void* scratch, float* record, void* stream) {
+    const int rc = grad_ranges_check("msst_grad_finalize", acc && g && scratch && record, ranges, nranges, range_bytes);
+    if (rc) return rc;
+    if ((uintptr_t)scratch & 7) return fail(MSST_ERR_BADARG, "msst_grad_finalize (scratch not 8-byte aligned)");
+    if ((const void*)acc == (const void*)g) return fail(MSST_ERR_BADARG, "msst_grad_finalize (g must not be acc)");
+    GradTable t;
+    grad_table(t, ranges, nranges, (((uintptr_t)acc | (uintptr_t)g) & 15) == 0);
+    const double* part_sum = (const double*)scratch;   // one slot per workgroup of the accumulate launch: the same split
+    const unsigned* part_bad = (const unsigned*)(part_sum + t.nblocks);
+    return fail(launch_grad_finalize(acc, g, scale, max_norm, part_sum, part_bad, t.nblocks, record, t, (hipStream_t)stream), "msst_grad_finalize");
 }
 
 }  // extern "C"

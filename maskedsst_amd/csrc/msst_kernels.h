@@ -9,6 +9,7 @@
 #define MSST_ERR_UNSUPPORTED (-2)
 #define MSST_ERR_BADARG (-3)
 #define MSST_ADAM_MAX_GROUPS 64
+#define MSST_GRAD_MAX_RANGES 64
 
 namespace msst {
 
@@ -282,7 +283,7 @@ int launch_head_bwd_target(const float* dpred, const int* csr_ptr, const int* cs
 enum KernelId {
     K_PREP = 0, K_TOK_FWD, K_BLOCK_FWD, K_HEAD_FWD, K_LOSS_REDUCE, K_HEAD_BWD, K_REDUCE, K_BWD_MLP, K_BWD_ATTN,
     K_ATTN_REDUCE, K_BWD_LN1, K_TOK_BWD, K_POS_SPLIT, K_ADAMW, K_BWD_LN1MLP, K_LAYERNORM, K_ADAM_GROUPS, K_CE, K_RECON, K_TOK_BWD_INPUT,
-    K_HEAD_BWD_TARGET, K_COUNT
+    K_HEAD_BWD_TARGET, K_GRAD_ACCUM, K_GRAD_FINAL, K_COUNT
 };
 void prof_begin(int id, hipStream_t st);
 void prof_end(hipStream_t st);
@@ -399,6 +400,24 @@ struct AdamTable {
 constexpr int ADAM_QPB = 1024;   // float4 pieces of a range's aligned interior per workgroup (256 threads x 4)
 static_assert(sizeof(AdamTable) <= 4096, "AdamTable travels as a kernel argument");
 int launch_adam_groups(float* p, const float* g, float* m, float* v, const AdamTable& t, hipStream_t st);
+// gradient accumulation / global-norm clip (msst_accum.hip): the range table as the kernels receive it.  A range's 16-byte aligned
+// interior is walked by nblk workgroups in a strided loop (lb, lb + nblk, ... pieces of 256 U float4), its ragged ends by the first.
+struct GradSeg {
+    long start, end;     // element range
+    long a0, a1;         // its 16-byte aligned interior (a0 == a1 == end: none; the whole range then moves float by float)
+    int blk0, nblk;      // first workgroup of the range, workgroups of the range
+};
+struct GradTable {
+    GradSeg s[MSST_GRAD_MAX_RANGES];
+    int nseg, nblocks;
+};
+static_assert(sizeof(GradTable) <= 4096, "GradTable travels as a kernel argument");
+constexpr int GRAD_GRID = 512;             // grid cap of both launches (+ at most one workgroup per range): 2 workgroups per CU ...
+constexpr int GRAD_U = 4;                  // ... that keep four float4 per buffer and lane in flight per trip of the strided loop
+int launch_grad_accumulate(float* acc, const float* g, float* out, float scale, int first, double* part_sum, unsigned* part_bad,
+                           const GradTable& t, hipStream_t st);
+int launch_grad_finalize(const float* acc, float* g, float scale, float max_norm, const double* part_sum, const unsigned* part_bad,
+                         int nparts, float* record, const GradTable& t, hipStream_t st);
 int launch_cu_thief(int nblocks, int us, unsigned* sink, hipStream_t st);   // msst_opt.hip (occupancy probe)
 int launch_box_probe(double* out4, void* scratch, long bytes, hipStream_t st);   // msst_opt.hip (MFMA rate / shader clock / HBM read rate of this box)
 int launch_block_fwd_rs(const BlockArgs& a, int grid, hipStream_t st);   // msst_fwd3.hip (bf16, 8 heads; role split: the default)

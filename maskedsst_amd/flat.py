@@ -35,6 +35,7 @@ class FlatParams:
         self.mim = mim
         self.flat = None
         self.grad = None
+        self.accum = None               # second gradient buffer of GradAccumulator (optim.py): allocated on first use, dropped by a re-flatten
         self.segments = OrderedDict()   # name -> (offset, numel, shape)
         self.buckets = []               # [(name, start, end)] in backward-completion order
         self.n_trainable = 0            # prefix length that receives gradients in pre-training
@@ -114,10 +115,17 @@ class FlatParams:
                     self.buckets.append((bname, start, off))
                     self.n_trainable = off
         self.flat, self.grad = flat, grad
+        self.accum = None
         self.version += 1
         self._ptrs = tuple(p.data_ptr() for p in allp)
         self.total = total
         return self
+
+    def accum_buffer(self):
+        """the accumulation buffer: fp32, the size and device of ``grad``; allocated on first use and again after a re-flatten"""
+        if self.accum is None:
+            self.accum = torch.zeros_like(self.grad)
+        return self.accum
 
     def view(self, name, buf=None):
         off, n, shape = self.segments[name]

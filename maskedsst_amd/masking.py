@@ -107,6 +107,21 @@ def topk_masks(batch, num_patches, num_masked):
     return bm, idx
 
 
+def micro_masks(masks, k, steps):
+    """The masks of micro-batch ``k`` of ``steps``: rows [k m, (k + 1) m), m = B / steps, of the ``(bool_mask, idx)`` pair that
+    ``draw_masks(B)`` gave for the whole batch -- the rule the data-parallel path uses for a rank's rows.  ``steps`` micro-batches
+    then see exactly the masks of the one large batch, the cross-row coupling of the misaligned indices included, and the RNG has
+    advanced once."""
+    bm, idx = masks
+    B = bm.shape[0]
+    if steps < 1 or B % steps or idx.shape[0] != B:
+        raise ValueError(f"{B} mask rows ({idx.shape[0]} index rows) do not split into {steps} equal micro-batches")
+    if not 0 <= k < steps:
+        raise ValueError(f"micro-batch {k} outside 0 .. {steps - 1}")
+    m = B // steps
+    return bm[k * m:(k + 1) * m], idx[k * m:(k + 1) * m]
+
+
 def inverse_csr(idx, num_tokens):
     """For the gather ``enc[b, idx[b, k]]`` build, per row, the token-sorted list of positions:
     ``ptr`` [B, T+1] and ``pos`` [B, K] (int32) such that the positions k with idx[b, k] == t are

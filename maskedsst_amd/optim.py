@@ -12,6 +12,10 @@ outside the updated range.  ``grad_clamp`` applies the reference's per-parameter
 learning rates -- ``lr`` / ``mlp_head_lr`` -- and frozen parameters under ``linear_eval``): its ``step`` turns the parameter groups
 into a table of element ranges of the flat buffer (``adam_ranges``) and updates all of them in ONE launch of ``msst_adam_groups``.
 
+``GradAccumulator`` sums the gradients of several micro-batches in a second flat buffer between backwards and leaves their mean,
+optionally clipped by its global L2 norm (``clip_grad_norm_``), in the flat gradient buffer: one or two launches
+(``msst_grad_accumulate``, ``msst_grad_finalize``) over the range table ``grad_ranges`` builds.
+
 ``BucketReducer`` all-reduces slices of the flat gradient buffer as soon as the backward has
 completed them (buckets are contiguous because the flat layout follows backward order), on the
 process group's own stream (``torch.distributed`` NCCL backend == RCCL on ROCm), overlapping the
@@ -207,6 +211,27 @@ class AdamRange(namedtuple("AdamRange", "start end group step params")):
         return self.start % 4 == 0 and self.end % 4 == 0
 
 
+def _locator(fp, who, where):
+    """locate(p) -> the offset of parameter p in the flat buffers of ``fp``, or None when p is skipped (``requires_grad=False`` or
+    ``grad is None``: torch's rule); raises when p is no view of ``fp.flat`` or its ``.grad`` is not p's own view of ``fp.grad``.
+    who / where: how the two messages name the caller."""
+    base, gbase = fp.flat.data_ptr(), fp.grad.data_ptr()
+    known = {off: n for off, n, _ in fp.segments.values()}
+
+    def locate(p):
+        if not p.requires_grad or p.grad is None:
+            return None
+        off, rem = divmod(p.data_ptr() - base, 4)
+        if rem or known.get(off) != p.numel():
+            raise RuntimeError(f"{who}: a parameter of the optimizer is no view of the model's flat parameter buffer "
+                               "(was the model rebuilt or moved without a forward since?)")
+        if p.grad.data_ptr() != gbase + 4 * off or p.grad.numel() != p.numel() or p.grad.dtype != torch.float32:
+            raise RuntimeError(f"{where}: a gradient is no view of the flat gradient buffer (gradients must be "
+                               "the ones the HIP backward hands to autograd)")
+        return off
+    return locate
+
+
 def adam_ranges(fp, param_groups, step_of=None, max_ranges=64):
     """The range table of one grouped-Adam step over the flat buffers of ``fp`` (a ``FlatParams``; CPU or GPU).
 
@@ -215,21 +240,13 @@ def adam_ranges(fp, param_groups, step_of=None, max_ranges=64):
     parameter's view of ``fp.grad`` raises.  ``step_of(p)``: updates this tensor has received so far (default: none), its range runs
     at that plus one.  Neighbouring segments of one group whose step counters are equal merge into one range.  Returns the
     ``AdamRange`` list sorted by start; more than ``max_ranges`` (the kernel's table size, MSST_ADAM_MAX_GROUPS) raises."""
-    base, gbase = fp.flat.data_ptr(), fp.grad.data_ptr()
-    known = {off: n for off, n, _ in fp.segments.values()}
+    locate = _locator(fp, "FusedAdam", "FusedAdam.step()")
     segs = []
     for gi, group in enumerate(param_groups):
         for p in group["params"]:
-            if not p.requires_grad or p.grad is None:
-                continue
-            off, rem = divmod(p.data_ptr() - base, 4)
-            if rem or known.get(off) != p.numel():
-                raise RuntimeError("FusedAdam: a parameter of the optimizer is no view of the model's flat parameter buffer "
-                                   "(was the model rebuilt or moved without a forward since?)")
-            if p.grad.data_ptr() != gbase + 4 * off or p.grad.numel() != p.numel() or p.grad.dtype != torch.float32:
-                raise RuntimeError("FusedAdam.step(): a gradient is no view of the flat gradient buffer (gradients must be "
-                                   "the ones the HIP backward hands to autograd)")
-            segs.append((off, off + p.numel(), gi, (step_of(p) if step_of is not None else 0) + 1, p))
+            off = locate(p)
+            if off is not None:
+                segs.append((off, off + p.numel(), gi, (step_of(p) if step_of is not None else 0) + 1, p))
     segs.sort(key=lambda t: t[0])
     out = []
     for start, end, gi, step, p in segs:
@@ -345,6 +362,156 @@ class FusedAdam(torch.optim.Optimizer):
         else:
             m.zero_()
             v.zero_()
+
+
+GradRange = namedtuple("GradRange", "start end params")   # elements [start, end) of the flat buffers; params: the tensors covered, in flat order
+
+
+def grad_ranges(fp, params, max_ranges=64):
+    """The range table of one ``GradAccumulator.add()`` over the flat buffers of ``fp`` (a ``FlatParams``; CPU or GPU): every
+    parameter of ``params`` that holds its view of ``fp.grad``, located as ``adam_ranges`` locates them; frozen parameters and
+    parameters without a gradient leave a hole, neighbouring segments merge.  Returns the ``GradRange`` list sorted by start; more
+    than ``max_ranges`` (the kernels' table size, MSST_GRAD_MAX_RANGES) raises."""
+    locate = _locator(fp, "GradAccumulator", "GradAccumulator.add()")
+    segs = sorted(((off, p) for off, p in ((locate(p), p) for p in params) if off is not None), key=lambda t: t[0])
+    out = []
+    for off, p in segs:
+        if out and out[-1].end == off:
+            out[-1] = out[-1]._replace(end=off + p.numel(), params=out[-1].params + [p])
+        else:
+            out.append(GradRange(off, off + p.numel(), [p]))
+    if len(out) > max_ranges:
+        raise ValueError(f"GradAccumulator: the frozen / unfrozen pattern of the parameters splits the flat buffer into {len(out)} "
+                         f"ranges, the kernels' table holds {max_ranges}")
+    return out
+
+
+class GradAccumulator:
+    """Sums the gradients of ``steps`` micro-batches in a second flat buffer and leaves their mean in the flat gradient buffer, clipped
+    by its global L2 norm when ``max_norm`` is set (``torch.nn.utils.clip_grad_norm_``): one or two launches per call instead of one
+    kernel per parameter tensor.
+
+        acc = GradAccumulator(model, steps=K, max_norm=1.0)
+        for k, img in enumerate(micro_batches):
+            model(img, masks=micro_masks(masks, k, K)).backward()
+            ready = acc.add()            # True after the K-th call
+        optimizer.step(); optimizer.zero_grad()
+
+    Calls 1 .. K-1 add the gradients the backward has just written to ``fp.accum`` and drop the parameters' ``.grad`` so that the next
+    backward is accepted.  Call K leaves ``dp_scale / K`` times the sum in ``fp.grad``, where the parameters' ``.grad`` views still
+    point: ``FusedAdamW``, ``FusedAdam`` (``grad_scale`` left at 1) and any ``torch.optim`` optimizer step on it unchanged.  The
+    parameters that take part are those that hold a flat-buffer gradient at the first call of a cycle (frozen ones and ones without a
+    gradient leave holes nobody touches); another pattern later in the cycle raises.  ``steps=1`` is a fused ``clip_grad_norm_``.
+    ``track_norm``: measure the norm without clipping.  ``error_if_nonfinite``: read the record back on the final call and raise when a
+    summed gradient is NaN or infinite, as torch does."""
+
+    def __init__(self, model, steps=1, max_norm=None, track_norm=False, error_if_nonfinite=False):
+        if int(steps) < 1:
+            raise ValueError(f"steps must be >= 1, got {steps}")
+        if max_norm is not None and not float(max_norm) > 0.0:
+            raise ValueError(f"max_norm must be > 0 (None: no clip), got {max_norm}")
+        self.model = model
+        self.steps = int(steps)
+        self.max_norm = None if max_norm is None else float(max_norm)
+        self.track_norm = bool(track_norm)
+        self.error_if_nonfinite = bool(error_if_nonfinite)
+        self.count = 0            # calls of add() in the running cycle
+        self._key = None          # (flat layout version, which parameters hold a gradient) of the running cycle
+        self._table_key = None    # ... the cached range table was built for
+        self._ranges = None
+        self._table = None
+        self._scratch = None
+        self._record = None
+        self._has_record = False
+
+    @property
+    def wants_norm(self):
+        return self.max_norm is not None or self.track_norm or self.error_if_nonfinite
+
+    def reset(self):
+        """abandon the running cycle (the next ``add()`` starts a new sum)"""
+        self.count = 0
+        self._key = None
+
+    @torch.no_grad()
+    def add(self, dp_scale=1.0):
+        """Take in the gradients of the backward that has just run.  dp_scale: what ``BucketReducer.finish()`` returned (1 / world
+        when the all-reduce summed), applied with the 1 / steps of the mean on the final call.  Returns True when that was the final
+        call of the cycle and ``fp.grad`` holds the finished gradient."""
+        from . import _lib
+        eng = self.model.engine()
+        fp = eng.fp
+        if fp.flat is None:
+            raise RuntimeError("GradAccumulator.add(): no backward has run yet (the model has no flat gradient buffer)")
+        # the table is cached on the flat layout and on which parameters hold a gradient (as FusedAdam.ranges: attribute reads only
+        # on the per-call path); a hit re-checks the gradients at both ends of every range against the flat buffer
+        named = eng.trainable()
+        key = (fp.version, tuple(p.requires_grad and p.grad is not None for _, p in named))
+        if key != self._table_key:
+            ranges = grad_ranges(fp, [p for _, p in named], _lib.GRAD_MAX_RANGES)
+            self._ranges = ranges
+            self._table = (_lib.MsstGradRange * max(1, len(ranges)))(*[_lib.MsstGradRange(r.start, r.end) for r in ranges])
+            self._table_key = key
+        else:
+            ranges = self._ranges
+            gbase, base = fp.grad.data_ptr(), fp.flat.data_ptr()
+            for r in ranges:
+                for p in (r.params[0], r.params[-1]):
+                    if p.grad.data_ptr() - gbase != p.data_ptr() - base:
+                        raise RuntimeError("GradAccumulator.add(): a gradient is no view of the flat gradient buffer (gradients must "
+                                           "be the ones the HIP backward hands to autograd)")
+        if not ranges:
+            raise RuntimeError("GradAccumulator.add(): no parameter holds a gradient of the HIP backward (call loss.backward() first)")
+        if self.count == 0:
+            self._key = key
+        elif key != self._key:
+            raise RuntimeError("GradAccumulator.add(): the parameters that hold a gradient changed inside an accumulation cycle "
+                               f"(call {self.count + 1} of {self.steps}): freeze / unfreeze or rebuild between cycles, or reset()")
+        first = self.count == 0
+        final = self.count + 1 == self.steps
+        grad, accum = fp.grad, fp.accum_buffer()
+        n, nbytes = len(ranges), ctypes.sizeof(_lib.MsstGradRange)
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        if not final:
+            _lib.check(eng.lib.msst_grad_accumulate(P(accum), P(grad), self._table, n, nbytes, int(first), None, 1.0, None, stream),
+                       "msst_grad_accumulate")
+            for r in ranges:
+                for p in r.params:
+                    p.grad = None
+            self.count += 1
+            return False
+        scale = float(dp_scale) / self.steps
+        if not self.wants_norm:
+            _lib.check(eng.lib.msst_grad_accumulate(P(accum), P(grad), self._table, n, nbytes, int(first), P(grad), scale, None, stream),
+                       "msst_grad_accumulate")
+        else:
+            if self._scratch is None or self._scratch.device != grad.device:
+                self._scratch = torch.empty(int(eng.lib.msst_grad_accum_scratch_bytes(_lib.GRAD_MAX_RANGES)) // 8, dtype=torch.float64,
+                                            device=grad.device)
+                self._record = torch.zeros(4, dtype=torch.float32, device=grad.device)
+            _lib.check(eng.lib.msst_grad_accumulate(P(accum), P(grad), self._table, n, nbytes, int(first), None, 1.0, P(self._scratch),
+                                                    stream), "msst_grad_accumulate")
+            _lib.check(eng.lib.msst_grad_finalize(P(accum), P(grad), self._table, n, nbytes, scale,
+                                                  0.0 if self.max_norm is None else self.max_norm, P(self._scratch), P(self._record),
+                                                  stream), "msst_grad_finalize")
+            self._has_record = True
+        self.count = 0
+        self._key = None
+        if self.error_if_nonfinite:
+            norm, _, bad = self.record()
+            if bad or norm != norm or norm in (float("inf"), float("-inf")):
+                raise RuntimeError(f"GradAccumulator: the accumulated gradient holds {bad} non-finite values (total norm {norm}); "
+                                   "the flat gradient buffer has been written all the same")
+        return True
+
+    def record(self):
+        """(norm, coef, nonfinite) of the last finished cycle: the L2 norm of the mean gradient before clipping, the factor it was
+        multiplied with (1.0 without ``max_norm`` or below it) and how many summed gradients were NaN or infinite.  One read-back."""
+        if not self._has_record:
+            raise RuntimeError("GradAccumulator.record(): no cycle with max_norm, track_norm or error_if_nonfinite has finished yet")
+        norm, coef, bad, _ = self._record.tolist()
+        return norm, coef, int(bad)
 
 
 def attach_data_parallel(model, group=None, bucket_bytes=4 << 20):

@@ -101,7 +101,7 @@ def stack_windows(t, s):
     return t.permute(0, 1, 3, 2, 4).reshape(lead[0] * nr * nq, s, s)
 
 
-def train_step(img, label, model, config, device, criterion, optimizer, acc_criterion=None):
+def train_step(img, label, model, config, device, criterion, optimizer, acc_criterion=None, accumulator=None):
     """reference src/utils.py:608-663 for the ViTSpatialSpectral method: optional random crop, forward,
     CE(ignore_index) loss, pixel accuracy on valid labels, backward, optimizer step.  With ``config.pixelwise`` a label
     map [B, s, s] is reduced to its centre pixel ``label[:, c, c]``, ``c = (image_size - patch_sub) // 2`` (reference
@@ -111,7 +111,10 @@ def train_step(img, label, model, config, device, criterion, optimizer, acc_crit
     other criterion: the eager path below, unchanged.
     ``config.shifting_window`` (reference :608-613) on 64 x 64 tiles: no crop -- the step trains on every non-overlapping window of
     the tiles at once (``stack_image_batch`` order; 64 windows of 8 x 8 per tile, 81 of 7 x 7 for a pixelwise model), the labels are
-    stacked, the images are not: ``model.forward_windows`` reads the windows out of the tiles on the device."""
+    stacked, the images are not: ``model.forward_windows`` reads the windows out of the tiles on the device.
+    ``accumulator`` (a ``maskedsst_amd.optim.GradAccumulator``; default None: the step as it always was): this call is one micro-step
+    -- its gradients join the accumulator's sum and the optimizer steps, on the mean of the micro-steps' gradients (each the mean over
+    its own valid labels), only when the accumulator's cycle is complete."""
     patch_sub = getattr(config, "patch_sub", 0)
     windows = bool(getattr(config, "shifting_window", False)) and config.image_size != 64 and img.shape[-1] == 64
     if windows:
@@ -130,7 +133,7 @@ def train_step(img, label, model, config, device, criterion, optimizer, acc_crit
     optimizer.zero_grad()
     output = model.forward_windows(img) if windows else model(img)
     if getattr(criterion, "fused_stats", False):
-        return _fused_tail(output, label, criterion, optimizer)
+        return _fused_tail(output, label, criterion, optimizer, accumulator)
     loss = criterion(output, label)
     if torch.isnan(loss):
         raise ValueError("Loss is NaN")
@@ -139,18 +142,18 @@ def train_step(img, label, model, config, device, criterion, optimizer, acc_crit
     acc = (pred[valid] == label[valid]).sum() / max(int(valid.sum()), 1)
     macro_acc = acc_criterion(pred[valid].to(int), label[valid]) if (acc_criterion is not None and valid.any()) else acc
     loss.backward()
-    optimizer.step()
+    _optimizer_step(optimizer, accumulator)
     return loss, acc, macro_acc
 
 
-def train_step_at(scene, labels, origins, model, config, criterion, optimizer, acc_criterion=None):
+def train_step_at(scene, labels, origins, model, config, criterion, optimizer, acc_criterion=None, accumulator=None):
     """train_step on the windows of resident scenes listed in origins [n, 3] = (scene, y0, x0) (the reference's Houston2018 sampling,
     src/data_houston2018.py:303-329): train_step's body with ``model.forward_at(scene, origins)`` in place of crop, stack and
     ``model(img)`` -- no window is copied.  scene [Bs, C, Hs, Ws] is on the device already; labels and origins are moved to it.
     labels: one entry per window -- [n] for a pixelwise model (``centre_origins``' second result), [n, s, s] for the patch heads
     (``window_labels``) -- or the label maps [Bs, Hs, Ws] of the scenes, from which exactly those are gathered here (pixelwise: the
     label at the window's centre, index s // 2 of the window).  Loss, accuracy, backward and optimizer step as in train_step, the
-    fused criterion included."""
+    fused criterion and ``accumulator`` included."""
     from .scene import window_labels
     s = config.image_size - getattr(config, "patch_sub", 0)
     if labels.dim() == 3 and tuple(labels.shape) == (scene.shape[0],) + tuple(scene.shape[-2:]):
@@ -169,7 +172,7 @@ def train_step_at(scene, labels, origins, model, config, criterion, optimizer, a
     optimizer.zero_grad()
     output = model.forward_at(scene, origins)
     if getattr(criterion, "fused_stats", False):
-        return _fused_tail(output, label, criterion, optimizer)
+        return _fused_tail(output, label, criterion, optimizer, accumulator)
     loss = criterion(output, label)
     if torch.isnan(loss):
         raise ValueError("Loss is NaN")
@@ -178,11 +181,18 @@ def train_step_at(scene, labels, origins, model, config, criterion, optimizer, a
     acc = (pred[valid] == label[valid]).sum() / max(int(valid.sum()), 1)
     macro_acc = acc_criterion(pred[valid].to(int), label[valid]) if (acc_criterion is not None and valid.any()) else acc
     loss.backward()
-    optimizer.step()
+    _optimizer_step(optimizer, accumulator)
     return loss, acc, macro_acc
 
 
-def _fused_tail(output, label, criterion, optimizer):
+def _optimizer_step(optimizer, accumulator):
+    """the end of a training step: the optimizer step -- or, with a ``maskedsst_amd.optim.GradAccumulator``, one micro-step of it:
+    the gradients join its sum and the optimizer steps on the (clipped) mean only after the last micro-step of the cycle"""
+    if accumulator is None or accumulator.add():
+        optimizer.step()
+
+
+def _fused_tail(output, label, criterion, optimizer, accumulator=None):
     """train_step from the loss on, for a FusedCrossEntropy: loss + record (two launches), ONE read-back of the record, the
     reference's NaN check on it (before the backward, as there), backward (one launch up to the head's), optimizer step.
     -> (loss: 0-d device tensor, acc, macro_acc: floats; acc = 0 and macro_acc = acc when no label is valid, as on the eager path)"""
@@ -193,6 +203,6 @@ def _fused_tail(output, label, criterion, optimizer):
     if h.bad_labels:
         raise ValueError(f"{h.bad_labels} labels outside [0, {stats.n_classes}) that are not the ignored label")
     loss.backward(criterion.unit_gradient(loss.device))
-    optimizer.step()
+    _optimizer_step(optimizer, accumulator)
     acc = h.n_correct / max(h.n_valid, 1)
     return loss, acc, (h.macro_acc if h.n_valid else acc)

@@ -24,7 +24,7 @@ import time
 import numpy as np
 import torch
 
-from maskedsst_amd import ViTSpatialSpectral, SimMIMSpatialSpectral
+from maskedsst_amd import ViTSpatialSpectral, SimMIMSpatialSpectral, GradAccumulator, micro_masks
 from maskedsst_amd.config import get_pretrain_config
 from maskedsst_amd.data import ResidentTileLoader, SyntheticCubeLoader
 from maskedsst_amd.optim import FusedAdamW, attach_data_parallel, dp_mean
@@ -76,6 +76,12 @@ def build_parser():
                          "of it (no host crop, no per-step copy of the windows); with --crop batch the same losses as the default loader")
     ap.add_argument("--crop", default="batch", choices=["batch", "sample"],
                     help="with --resident-tiles: one window position per batch (the reference's crop) or one per window")
+    ap.add_argument("--accumulate", type=int, default=1, metavar="K",
+                    help="sum the gradients of K micro-batches of batch_size // (world * K) samples before each optimizer step "
+                         "(maskedsst_amd.GradAccumulator); batch_size stays the global batch, its masks are drawn once per step")
+    ap.add_argument("--clip-norm", type=float, default=None, metavar="X",
+                    help="clip the (accumulated, averaged) gradient to the global L2 norm X before the optimizer step "
+                         "(clip_grad_norm_, fused; the config's clip_grad_norm value clamp still applies inside the optimizer)")
     return ap
 
 
@@ -162,6 +168,17 @@ def main():
     else:   # the stepping below tests the same two names: anything else would train at a constant rate without a word
         raise ValueError(f"unknown scheduler {config.scheduler!r} (reference src/utils.py:47-59 knows ReduceLROnPlateau and cosine)")
     reducer = attach_data_parallel(model) if world > 1 else None
+    K = args.accumulate
+    if K < 1 or config.batch_size % (world * K):
+        raise SystemExit(f"--accumulate {K}: the batch of {config.batch_size} does not split into {world} x {K} micro-batches")
+    if args.clip_norm is not None and not args.clip_norm > 0.0:
+        raise SystemExit("--clip-norm must be positive")
+    accumulator = None
+    if K > 1 or args.clip_norm is not None:
+        if args.torch_optim and config.clip_grad_norm:
+            raise SystemExit("--accumulate / --clip-norm work on the flat gradient buffer: with --torch-optim the value clamp's hooks "
+                             "replace the gradients by tensors of their own")
+        accumulator = GradAccumulator(model, steps=K, max_norm=args.clip_norm)
 
     # synthetic standardised tiles [bands, 64, 64] (per-band N(0,1), like StandardizeEnMAP output), cropped per batch
     gen = torch.Generator().manual_seed(SEED + 1000 * rank)
@@ -174,24 +191,35 @@ def main():
     step, losses, t0 = 0, [], time.time()
     for epoch in range(config.epoch):
         model.train()
-        loader_kw = dict(image_size=config.image_size, pool_tiles=args.pool_tiles, steps=steps_per_epoch,
+        # --accumulate K: the loader yields K micro-batches of per_rank // K samples per optimizer step
+        loader_kw = dict(image_size=config.image_size, pool_tiles=args.pool_tiles, steps=steps_per_epoch * K,
                          seed=SEED + 1000 * rank + epoch, device=device)
         if args.resident_tiles:
-            loader = ResidentTileLoader(per_rank, config.n_bands, crop=args.crop, **loader_kw)
+            loader = ResidentTileLoader(per_rank // K, config.n_bands, crop=args.crop, **loader_kw)
         else:
-            loader = SyntheticCubeLoader(per_rank, config.n_bands, **loader_kw)
+            loader = SyntheticCubeLoader(per_rank // K, config.n_bands, **loader_kw)
+        micro, micro_losses, masks = 0, [], None
         for img in loader:
-            optimizer.zero_grad()
+            if micro == 0:
+                optimizer.zero_grad()
+                if K > 1:   # one draw per optimizer step, for the global batch: the micro-batches see the rows of the one large batch
+                    masks = model.draw_masks(per_rank)
+            mk = micro_masks(masks, micro, K) if K > 1 else None
             if args.resident_tiles:
                 tiles, origins = img
-                loss = model.forward_at(tiles, origins, check=False)   # the loader's own table: inside the tiles by construction
+                loss = model.forward_at(tiles, origins, masks=mk, check=False)   # the loader's own table: inside the tiles by construction
             else:
-                loss = model(img)
+                loss = model(img, masks=mk)
             loss.backward()
-            if reducer is not None:
-                s = reducer.finish()
-                if isinstance(optimizer, FusedAdamW):
-                    optimizer.grad_scale = s
+            s = reducer.finish() if reducer is not None else 1.0
+            if accumulator is not None:
+                micro = (micro + 1) % K
+                micro_losses.append(loss.detach())
+                if not accumulator.add(dp_scale=s):   # the 1 / world of the all-reduce and the 1 / K of the mean: on the last micro-batch
+                    continue
+                loss, micro_losses = torch.stack(micro_losses).mean(), []
+            elif reducer is not None and isinstance(optimizer, FusedAdamW):
+                optimizer.grad_scale = s
             optimizer.step()
             step += 1
             losses.append(loss.detach())
