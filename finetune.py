@@ -75,6 +75,12 @@ def build_parser():
                          "Houston2018 sampling): labelled -- windows centred at labelled pixels, one class each (pixelwise models); random "
                          "-- windows at random positions that hold a labelled pixel (patch heads)")
     ap.add_argument("--windows-per-step", type=int, default=512, metavar="N", help="windows drawn per step under --train-at")
+    ap.add_argument("--augment", default=None, choices=["d4"],
+                    help="with --train-at: every listed window is read in a random one of its eight orientations (flips and quarter "
+                         "turns, forward_at(..., orient=)): applied where the kernels form the window's address, no copy")
+    ap.add_argument("--val-tta", action="store_true",
+                    help="with --val-at: test-time augmentation, predict_at(..., tta='d4') -- the mean of the logits over the eight "
+                         "orientations of every window")
     ap.add_argument("--val-at", action="store_true",
                     help="validate with predict_at on the windows centred at the validation tiles' labelled pixels (--val-scenes defaults "
                          "to 2 and --val-every to --steps when they are not given)")
@@ -157,6 +163,10 @@ def make_optimizer(model, config, kind):
 
 def main():
     args = build_parser().parse_args()
+    if args.augment and not args.train_at:
+        raise SystemExit("--augment d4 orients windows at listed positions: it needs --train-at")
+    if args.val_tta and not args.val_at:
+        raise SystemExit("--val-tta averages predict_at over the eight orientations: it needs --val-at")
     random.seed(SEED); np.random.seed(SEED); torch.manual_seed(SEED)
     if not torch.cuda.is_available():
         raise SystemExit("finetune.py needs an MI355X: maskedsst_amd has no CPU fallback")
@@ -238,7 +248,7 @@ def main():
         for k in range(args.accumulate):
             if args.train_at:
                 loss, acc, macro_acc = train_step_at_listed(img.to(device), label, model, config, criterion, optimizer, args.train_at,
-                                                            micro_windows, gen, accumulator=accumulator)
+                                                            micro_windows, gen, accumulator=accumulator, augment=args.augment)
             else:
                 loss, acc, macro_acc = train_step(img[k * micro:(k + 1) * micro], label[k * micro:(k + 1) * micro], model, config, device,
                                                   criterion, optimizer, accumulator=accumulator)
@@ -248,7 +258,7 @@ def main():
                   flush=True)
         if val is not None and step % args.val_every == 0:
             if args.val_at:
-                validate_at(model, val, step, config.ignored_label, report=args.val_report)
+                validate_at(model, val, step, config.ignored_label, report=args.val_report, tta=args.val_tta)
             else:
                 validate(model, val, step, config.ignored_label, fused=fused, report=args.val_report)
             if args.val_embed:
@@ -279,11 +289,12 @@ def make_accumulator(model, accumulate, clip_norm, batch_size, windows_per_step,
     return accumulator, batch_size // accumulate, windows_per_step // accumulate
 
 
-def train_step_at_listed(scene, label, model, config, criterion, optimizer, mode, n, gen, accumulator=None):
+def train_step_at_listed(scene, label, model, config, criterion, optimizer, mode, n, gen, accumulator=None, augment=None):
     """--train-at: one step on n windows of the resident tiles scene [B, C, 64, 64] (on the device; label [B, 64, 64] on the host, where
     the table is drawn).  labelled: n of centre_origins' rows, drawn without replacement (all of them when there are fewer), each with
-    its centre's class; random: n random_origins that hold a labelled pixel, with their label patches."""
-    from maskedsst_amd import centre_origins, random_origins, window_labels
+    its centre's class; random: n random_origins that hold a labelled pixel, with their label patches.  augment="d4": an orientation per
+    window, drawn after the table from the same generator; the label patches are those of the oriented windows."""
+    from maskedsst_amd import centre_origins, random_origins, random_orients, window_labels
     from maskedsst_amd.utils import train_step_at
     s = config.image_size - config.patch_sub
     if mode == "labelled":
@@ -296,10 +307,17 @@ def train_step_at_listed(scene, label, model, config, criterion, optimizer, mode
         origins = random_origins(label.shape[0], label.shape[1], label.shape[2], s, n, generator=gen, labels=label,
                                  ignore_index=config.ignored_label)
         labels = window_labels(label, origins, s)
-    return train_step_at(scene, labels, origins, model, config, criterion, optimizer, accumulator=accumulator)
+    if augment is None:
+        return train_step_at(scene, labels, origins, model, config, criterion, optimizer, accumulator=accumulator)
+    orient = random_orients(origins.shape[0], generator=gen)
+    if mode != "labelled":
+        labels = window_labels(label, origins, s, orient)
+    elif s % 2 == 0:   # an even window's centre index is no fixed point of the orientations: the label under the oriented centre
+        labels = window_labels(label, origins, s, orient)[:, s // 2, s // 2]
+    return train_step_at(scene, labels, origins, model, config, criterion, optimizer, accumulator=accumulator, orient=orient)
 
 
-def validate_at(model, val, step, ignored_label, report=False):
+def validate_at(model, val, step, ignored_label, report=False, tta=False):
     """--val-at: the Houston test protocol -- predictions only where a label exists.  One predict_at pass over the windows centred at
     the validation tiles' labelled pixels (a patch head: the logits at the window's centre), then loss, accuracies and with report
     the confusion-matrix line from one pass of the fused loss over those logits."""
@@ -308,7 +326,7 @@ def validate_at(model, val, step, ignored_label, report=False):
     img, label = val
     w = model.num_spatial_patches_sqrt
     origins, labels = centre_origins(label, w, ignored_label)
-    _, logits = model.predict_at(img, origins, return_logits=True)
+    _, logits = model.predict_at(img, origins, return_logits=True, tta="d4") if tta else model.predict_at(img, origins, return_logits=True)
     if logits.dim() == 4:
         logits = logits[:, :, w // 2, w // 2].contiguous()
     with torch.no_grad():

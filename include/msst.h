@@ -234,6 +234,48 @@ int msst_head_at_fwd(const float* y, const float* scene, const int32_t* origins,
                      const float* b_pix, int per_block, float* dpred, float* pred /*optional*/, float* partial, float* loss, int Bs,
                      int Hs, int Ws, int window, int nwin, int S, int P, int K, void* stream);
 
+/* D4 augmentation of listed windows: flips and quarter turns applied where the window's address is formed (forward_at(..., orient=),
+ * SimMIMSpatialSpectral.forward_at(..., orient=), predict_at(..., tta="d4")).  Additive under MSST_VERSION 109: no struct and no
+ * existing signature changes; the five entry points above launch the kernels they launched before.
+ *
+ * orient is a device table [nwin] of uint8, one orientation code per row of origins: o = k + 4 f, k in 0 .. 3, f in 0 .. 1.  Sample i
+ * of the call is the window w at origins[i] flipped left to right when f, then turned k quarter turns counter-clockwise --
+ * torch.rot90(torch.flip(w, (-1,)) if f else w, k, (-2, -1)); code 0 is the window as it lies.  Pixel (i, j) of the oriented window is
+ * read at origin + start + i * step_i + j * step_j with the steps in {+-1, +-Ws}: no copy, no further launch, the same arithmetic.
+ * Everything else sees the ORIENTED window: token n is its pixel n, so position row, mask byte (window coordinates of the oriented
+ * window), dropout element, dx0 row and idx entry are those of the oriented copy, and every output is bit-identical to the
+ * un-oriented entry point's counterpart (msst_tokenize_fwd / _bwd / msst_head_fwd) on the oriented copies.  THE CALLER GUARANTEES codes
+ * 0 .. 7 as it does the origins' ranges (the kernels look at the low three bits only: another value reads inside the window all the same).
+ *
+ * Each is its namesake without _orient plus the table, after origins; arguments, limits, outputs and the order of the argument checks
+ * (before anything is enqueued) are the namesake's: MSST_ERR_BADARG for a size below 1; MSST_ERR_UNSUPPORTED outside window <= Hs, Ws,
+ * window * window <= 64, P <= 16 (the head: also nwin <= 65535; the forward tokenizers: that for P != 10 or window != 8);
+ * MSST_ERR_BADARG for a null required pointer, a null orient included.  The codes whose steps swap the axes (k odd) read Ws floats
+ * apart along j. */
+int msst_tokenize_at_fwd_orient(const float* scene, const int32_t* origins, const uint8_t* orient, const float* pre_g, const float* pre_b,
+                                const float* w_emb, const float* b_emb, const float* post_g, const float* post_b, const float* pos_a,
+                                const float* pos_b, int pos_split, float* out, int Bs, int Hs, int Ws, int window, int nwin, int S, int P,
+                                float emb_dropout_p, uint32_t seed, void* stream);
+int msst_tokenize_at_bwd_orient(const float* scene, const int32_t* origins, const uint8_t* orient, const float* pre_g, const float* pre_b,
+                                const float* w_emb, const float* b_emb, const float* post_g, const float* post_b, const float* dx0,
+                                float* slab, int nchunk, float* dpre_g, float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g,
+                                float* dpost_b, float* dpos_a, float* dpos_b, int pos_split, int Bs, int Hs, int Ws, int window, int nwin,
+                                int S, int P, float emb_dropout_p, uint32_t seed, void* stream);
+int msst_tokenize_at_fwd_masked_orient(const float* scene, const int32_t* origins, const uint8_t* orient, const float* pre_g,
+                                       const float* pre_b, const float* w_emb, const float* b_emb, const float* post_g,
+                                       const float* post_b, const float* pos_a, const float* pos_b, int pos_split,
+                                       const float* mask_token, const uint8_t* mask, float* out, int Bs, int Hs, int Ws, int window,
+                                       int nwin, int S, int P, void* stream);
+int msst_tokenize_at_bwd_masked_orient(const float* scene, const int32_t* origins, const uint8_t* orient, const float* pre_g,
+                                       const float* pre_b, const float* w_emb, const float* b_emb, const float* post_g,
+                                       const float* post_b, const uint8_t* mask, const float* dx0, float* slab, int nchunk, float* dpre_g,
+                                       float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g, float* dpost_b, float* dpos_a,
+                                       float* dpos_b, int pos_split, float* dmask_token, int Bs, int Hs, int Ws, int window, int nwin,
+                                       int S, int P, void* stream);
+int msst_head_at_fwd_orient(const float* y, const float* scene, const int32_t* origins, const uint8_t* orient, const int32_t* idx,
+                            const float* w_pix, const float* b_pix, int per_block, float* dpred, float* pred /*optional*/, float* partial,
+                            float* loss, int Bs, int Hs, int Ws, int window, int nwin, int S, int P, int K, void* stream);
+
 /* msst_scene_assemble: adds the per-window logits win_logits [nwin][n_classes][window*window] (msst_cls_head_fwd of windows
  * win0 .. win0 + nwin - 1) into the running per-pixel sums logits [Bs][n_classes][Hs][Ws] (fp32).  The calls of one scene batch
  * must cover windows 0, 1, ... in order (any split into calls); logits needs no initialisation.  finalize != 0 (the last call, after

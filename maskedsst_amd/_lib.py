@@ -78,6 +78,12 @@ _SIGS = {
     "msst_tokenize_at_fwd_masked": (c_int, [_P] * 10 + [c_int, _P, _P, _P] + [c_int] * 7 + [_P]),
     "msst_tokenize_at_bwd_masked": (c_int, [_P] * 11 + [c_int] + [_P] * 8 + [c_int, _P] + [c_int] * 7 + [_P]),
     "msst_head_at_fwd": (c_int, [_P] * 6 + [c_int] + [_P] * 4 + [c_int] * 8 + [_P]),
+    # the five above with the orientation table (uint8 [nwin]) after origins
+    "msst_tokenize_at_fwd_orient": (c_int, [_P] * 11 + [c_int, _P] + [c_int] * 7 + [c_float, c_uint32, _P]),
+    "msst_tokenize_at_bwd_orient": (c_int, [_P] * 11 + [c_int] + [_P] * 8 + [c_int] * 8 + [c_float, c_uint32, _P]),
+    "msst_tokenize_at_fwd_masked_orient": (c_int, [_P] * 11 + [c_int, _P, _P, _P] + [c_int] * 7 + [_P]),
+    "msst_tokenize_at_bwd_masked_orient": (c_int, [_P] * 12 + [c_int] + [_P] * 8 + [c_int, _P] + [c_int] * 7 + [_P]),
+    "msst_head_at_fwd_orient": (c_int, [_P] * 7 + [c_int] + [_P] * 4 + [c_int] * 8 + [_P]),
     "msst_tokenize_bwd_input": (c_int, [_P] * 11 + [c_int] * 4 + [c_float, c_uint32, _P]),
     "msst_head_bwd_target": (c_int, [_P] * 5 + [c_int] * 5 + [_P]),
     "msst_tokenize_scene_bwd_input": (c_int, [_P] * 9 + [c_int] * 5 + [c_long, c_int, c_int, c_int, c_float, c_uint32, _P]),

@@ -219,7 +219,16 @@ struct WinSrc {
     const int32_t* origins = nullptr;
     int nq = 1;
     long wps = 1;
+    bool oriented = false;            // listed windows, each in orientation orient[b] (the _orient entry points): the table is required
+    const uint8_t* orient = nullptr;
 };
+// the listed windows of an _orient entry point
+static WinSrc oriented_src(int Bs, int Hs, int Ws, int window, int nwin, const int32_t* origins, const uint8_t* orient) {
+    WinSrc w{Bs, Hs, Ws, window, window, 0, nwin, true, origins};
+    w.oriented = true;
+    w.orient = orient;
+    return w;
+}
 // window grid of a scene: false when the shapes are not a valid (scene, window, stride) triple
 static bool scene_grid(int Bs, int Hs, int Ws, int window, int stride, int* nr, int* nq) {
     if (Bs < 1 || window < 1 || stride < 1 || stride > window || Hs < window || Ws < window) return false;
@@ -228,14 +237,14 @@ static bool scene_grid(int Bs, int Hs, int Ws, int window, int stride, int* nr, 
     return true;
 }
 // the argument check of every training entry point over a window source, in this order: sizes below 1 (BADARG), shapes outside the
-// kernels' limits (UNSUPPORTED), a null required pointer (the caller's `pointers`; a listed source's table counts) or a pos_split outside
+// kernels' limits (UNSUPPORTED), a null required pointer (the caller's `pointers`; a listed source's tables count) or a pos_split outside
 // [0, 96) (BADARG), windows beyond the scenes' grids (BADARG; the value ranges of a listed table are the caller's guarantee).
 // min_nwin: 0 or 1
 static int check_src(WinSrc& w, bool pointers, int min_nwin, int S, int P, int pos_split) {
     if (w.Bs < 1 || w.Hs < 1 || w.Ws < 1 || w.window < 1 || w.stride < 1 || S < 1 || P < 1 || w.nwin < min_nwin || w.win0 < 0)
         return MSST_ERR_BADARG;
     if (w.stride > w.window || w.window > w.Hs || w.window > w.Ws || w.window > 8 || P > 16) return MSST_ERR_UNSUPPORTED;   // 8: at most 64 pixels per window
-    if (!pointers || (w.listed && !w.origins) || pos_split < 0 || pos_split >= 96) return MSST_ERR_BADARG;
+    if (!pointers || (w.listed && !w.origins) || (w.oriented && !w.orient) || pos_split < 0 || pos_split >= 96) return MSST_ERR_BADARG;
     if (w.listed) return 0;
     int nr = 0;
     scene_grid(w.Bs, w.Hs, w.Ws, w.window, w.stride, &nr, &w.nq);
@@ -431,6 +440,10 @@ static int tokenize_src_fwd(const char* what, bool masked, const TokPtrs& p, con
     TokArgs a{};
     fill_tok(a, p, pos_a, pos_b, pos_split, mask_token, mask, out, w.nwin, S, w.window * w.window, P, drop);
     fill_src(a, w);
+    if (w.oriented) {
+        a.orient = w.orient;
+        return fail(launch_tokenize_at_fwd_orient(a, masked, (hipStream_t)stream), what);
+    }
     return fail((!w.listed ? launch_tokenize_scene_fwd : masked ? launch_tokenize_at_fwd_masked : launch_tokenize_at_fwd)(a, (hipStream_t)stream),
                 what);
 }
@@ -460,6 +473,25 @@ int msst_tokenize_at_fwd_masked(const float* scene, const int32_t* origins, cons
     return tokenize_src_fwd("msst_tokenize_at_fwd_masked", true, {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, pos_a, pos_b,
                             pos_split, mask_token, mask, out, WinSrc{Bs, Hs, Ws, window, window, 0, nwin, true, origins}, S, P, make_drop(0.f, 0, 255),
                             stream);
+}
+
+int msst_tokenize_at_fwd_orient(const float* scene, const int32_t* origins, const uint8_t* orient, const float* pre_g, const float* pre_b,
+                                const float* w_emb, const float* b_emb, const float* post_g, const float* post_b, const float* pos_a,
+                                const float* pos_b, int pos_split, float* out, int Bs, int Hs, int Ws, int window, int nwin, int S, int P,
+                                float emb_dropout_p, uint32_t seed, void* stream) {
+    return tokenize_src_fwd("msst_tokenize_at_fwd_orient", false, {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, pos_a, pos_b,
+                            pos_split, nullptr, nullptr, out, oriented_src(Bs, Hs, Ws, window, nwin, origins, orient), S, P,
+                            make_drop(emb_dropout_p, seed, 255), stream);
+}
+
+int msst_tokenize_at_fwd_masked_orient(const float* scene, const int32_t* origins, const uint8_t* orient, const float* pre_g,
+                                       const float* pre_b, const float* w_emb, const float* b_emb, const float* post_g,
+                                       const float* post_b, const float* pos_a, const float* pos_b, int pos_split,
+                                       const float* mask_token, const uint8_t* mask, float* out, int Bs, int Hs, int Ws, int window,
+                                       int nwin, int S, int P, void* stream) {
+    return tokenize_src_fwd("msst_tokenize_at_fwd_masked_orient", true, {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, pos_a, pos_b,
+                            pos_split, mask_token, mask, out, oriented_src(Bs, Hs, Ws, window, nwin, origins, orient), S, P,
+                            make_drop(0.f, 0, 255), stream);
 }
 
 int msst_scene_assemble(const float* win_logits, long win0, int nwin, float* logits, int64_t* classes, int Bs,
@@ -692,23 +724,38 @@ int msst_head_fwd(const float* y, const float* img, const int32_t* idx, const fl
     HeadArgs a;
     a.y = y; a.img = img; a.idx = idx; a.w_pix = w_pix; a.b_pix = b_pix; a.dpred = dpred; a.pred = pred;
     a.partial = partial; a.B = B; a.S = S; a.N = N; a.T = S * N; a.P = P; a.K = K; a.per_block = per_block;
-    a.origins = nullptr; a.Hs = 0; a.Ws = 0; a.win = 0;   // (msst_head_at_fwd's target source: unread here)
+    a.origins = nullptr; a.Hs = 0; a.Ws = 0; a.win = 0; a.orient = nullptr;   // (msst_head_at_fwd's target source: unread here)
     return fail(launch_head_fwd(a, loss, (hipStream_t)stream), "msst_head_fwd");
+}
+
+// msst_head_at_fwd and msst_head_at_fwd_orient (oriented: the orientation table is required too)
+static int head_at_fwd(const char* what, bool oriented, const float* y, const float* scene, const int32_t* origins, const uint8_t* orient,
+                       const int32_t* idx, const float* w_pix, const float* b_pix, int per_block, float* dpred, float* pred, float* partial,
+                       float* loss, int Bs, int Hs, int Ws, int window, int nwin, int S, int P, int K, void* stream) {
+    if (Bs < 1 || Hs < 1 || Ws < 1 || window < 1 || S < 1 || P < 1 || K < 1 || nwin < 1) return fail(MSST_ERR_BADARG, what);
+    if (window > Hs || window > Ws || window > 8 || P > 16 || nwin > 65535)   // 65535: one workgroup row per window (grid y)
+        return fail(MSST_ERR_UNSUPPORTED, what, " (window <= Hs, Ws, window * window <= 64, P <= 16, nwin <= 65535)");
+    if (!y || !scene || !origins || (oriented && !orient) || !idx || !w_pix || !b_pix || !dpred || !partial || !loss || K > S * window * window)
+        return fail(MSST_ERR_BADARG, what);
+    HeadArgs a;
+    a.y = y; a.img = scene; a.idx = idx; a.w_pix = w_pix; a.b_pix = b_pix; a.dpred = dpred; a.pred = pred;
+    a.partial = partial; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P; a.K = K; a.per_block = per_block;
+    a.origins = origins; a.Hs = Hs; a.Ws = Ws; a.win = window; a.orient = orient;
+    return fail((oriented ? launch_head_at_fwd_orient : launch_head_at_fwd)(a, loss, (hipStream_t)stream), what);
 }
 
 int msst_head_at_fwd(const float* y, const float* scene, const int32_t* origins, const int32_t* idx, const float* w_pix,
                      const float* b_pix, int per_block, float* dpred, float* pred, float* partial, float* loss, int Bs, int Hs, int Ws,
                      int window, int nwin, int S, int P, int K, void* stream) {
-    if (Bs < 1 || Hs < 1 || Ws < 1 || window < 1 || S < 1 || P < 1 || K < 1 || nwin < 1) return fail(MSST_ERR_BADARG, "msst_head_at_fwd");
-    if (window > Hs || window > Ws || window > 8 || P > 16 || nwin > 65535)   // 65535: one workgroup row per window (grid y)
-        return fail(MSST_ERR_UNSUPPORTED, "msst_head_at_fwd (window <= Hs, Ws, window * window <= 64, P <= 16, nwin <= 65535)");
-    if (!y || !scene || !origins || !idx || !w_pix || !b_pix || !dpred || !partial || !loss || K > S * window * window)
-        return fail(MSST_ERR_BADARG, "msst_head_at_fwd");
-    HeadArgs a;
-    a.y = y; a.img = scene; a.idx = idx; a.w_pix = w_pix; a.b_pix = b_pix; a.dpred = dpred; a.pred = pred;
-    a.partial = partial; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P; a.K = K; a.per_block = per_block;
-    a.origins = origins; a.Hs = Hs; a.Ws = Ws; a.win = window;
-    return fail(launch_head_at_fwd(a, loss, (hipStream_t)stream), "msst_head_at_fwd");
+    return head_at_fwd("msst_head_at_fwd", false, y, scene, origins, nullptr, idx, w_pix, b_pix, per_block, dpred, pred, partial, loss, Bs,
+                       Hs, Ws, window, nwin, S, P, K, stream);
+}
+
+int msst_head_at_fwd_orient(const float* y, const float* scene, const int32_t* origins, const uint8_t* orient, const int32_t* idx,
+                            const float* w_pix, const float* b_pix, int per_block, float* dpred, float* pred, float* partial, float* loss,
+                            int Bs, int Hs, int Ws, int window, int nwin, int S, int P, int K, void* stream) {
+    return head_at_fwd("msst_head_at_fwd_orient", true, y, scene, origins, orient, idx, w_pix, b_pix, per_block, dpred, pred, partial, loss,
+                       Bs, Hs, Ws, window, nwin, S, P, K, stream);
 }
 
 int msst_head_bwd(const float* y, const float* dpred, const int32_t* csr_ptr, const int32_t* csr_pos,
@@ -986,11 +1033,14 @@ static int tokenize_src_bwd(const char* what, const TokPtrs& p, const uint8_t* m
     }
     if (nchunk < 1) return fail(MSST_ERR_BADARG, what);
     hipStream_t st = (hipStream_t)stream;
-    TokAtBwdArgs a{};   // its bases are the argument blocks of the other two launchers
+    TokAtOrBwdArgs a{};   // its bases are the argument blocks of the other three launchers
     fill_tok_common(a, p, B, S, N, P, drop);
     a.mask = mask; a.dx0 = dx0; a.slab = slab;
     if (w) fill_src(a, *w);
-    if (int rc = !w ? launch_tokenize_bwd(a, nchunk, st) : w->listed ? launch_tokenize_at_bwd(a, nchunk, st) : launch_tokenize_scene_bwd(a, nchunk, st))
+    if (w && w->oriented) {
+        a.orient = w->orient;
+        if (int rc = launch_tokenize_at_bwd_orient(a, nchunk, st)) return fail(rc, what);
+    } else if (int rc = !w ? launch_tokenize_bwd(a, nchunk, st) : w->listed ? launch_tokenize_at_bwd(a, nchunk, st) : launch_tokenize_scene_bwd(a, nchunk, st))
         return fail(rc, what);
     return tokenize_bwd_reduce(slab, nchunk, g, S, N, P, st);
 }
@@ -1037,6 +1087,29 @@ int msst_tokenize_at_bwd_masked(const float* scene, const int32_t* origins, cons
     return tokenize_src_bwd("msst_tokenize_at_bwd_masked", {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, mask, true, dx0, slab,
                             nchunk, {dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, dmask_token}, &w, nwin, S,
                             window * window, P, make_drop(0.f, 0, 255), stream);
+}
+
+int msst_tokenize_at_bwd_orient(const float* scene, const int32_t* origins, const uint8_t* orient, const float* pre_g, const float* pre_b,
+                                const float* w_emb, const float* b_emb, const float* post_g, const float* post_b, const float* dx0,
+                                float* slab, int nchunk, float* dpre_g, float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g,
+                                float* dpost_b, float* dpos_a, float* dpos_b, int pos_split, int Bs, int Hs, int Ws, int window, int nwin,
+                                int S, int P, float emb_dropout_p, uint32_t seed, void* stream) {
+    WinSrc w = oriented_src(Bs, Hs, Ws, window, nwin, origins, orient);
+    return tokenize_src_bwd("msst_tokenize_at_bwd_orient", {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, nullptr, false, dx0, slab,
+                            nchunk, {dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, nullptr}, &w, nwin, S,
+                            window * window, P, make_drop(emb_dropout_p, seed, 255), stream);
+}
+
+int msst_tokenize_at_bwd_masked_orient(const float* scene, const int32_t* origins, const uint8_t* orient, const float* pre_g,
+                                       const float* pre_b, const float* w_emb, const float* b_emb, const float* post_g,
+                                       const float* post_b, const uint8_t* mask, const float* dx0, float* slab, int nchunk, float* dpre_g,
+                                       float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g, float* dpost_b, float* dpos_a,
+                                       float* dpos_b, int pos_split, float* dmask_token, int Bs, int Hs, int Ws, int window, int nwin,
+                                       int S, int P, void* stream) {
+    WinSrc w = oriented_src(Bs, Hs, Ws, window, nwin, origins, orient);
+    return tokenize_src_bwd("msst_tokenize_at_bwd_masked_orient", {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, mask, true, dx0,
+                            slab, nchunk, {dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, dmask_token}, &w,
+                            nwin, S, window * window, P, make_drop(0.f, 0, 255), stream);
 }
 
 // ---- input gradient (msst_input_grad.hip)

@@ -1367,6 +1367,8 @@ __global__ __launch_bounds__(256) void block_bwd_ln1_kernel(Ln1BwdArgs a) {
 // true: sample b is window win0 + b of a scene (TokSceneBwdArgs), or the window at origins[b] (TokAtBwdArgs: scene_window_origin's
 // overload reads the table), nothing masked (the classification path).  The arithmetic
 // and every summation order are the same: equal pixels and equal dx0 give equal bits.
+// TokAtOrBwdArgs (msst_tokenize_at_bwd_orient / _at_bwd_masked_orient): window b is read in orientation a.orient[b] (window_steps,
+// msst_kernels.h) -- sample b is the oriented window, so dx0 row, mask byte and dropout element are its; only the address of the read differs.
 template <int PC, bool SCENE, class Args>
 __global__ __launch_bounds__(256) void tokenize_bwd_kernel(Args a) {
     __shared__ float patch[16][64];
@@ -1402,9 +1404,13 @@ __global__ __launch_bounds__(256) void tokenize_bwd_kernel(Args a) {
         if constexpr (SCENE) {
             const long plane = (long)a.Hs * a.Ws;
             const float* src = scene_window_origin(a, b) + (long)c * P * plane;
+            constexpr bool ORIENT = std::is_same<Args, TokAtOrBwdArgs>::value;
+            WinSteps ws{};   // ORIENT: this window's code, read once
+            if constexpr (ORIENT) ws = window_steps(a.orient[b], a.win, a.Ws);
             for (int i = tid; i < P * N; i += 256) {
                 const int k = i / N, nn = i % N;
-                patch[k][nn] = src[k * plane + (long)(nn / a.win) * a.Ws + nn % a.win];
+                if constexpr (ORIENT) patch[k][nn] = src[k * plane + ws.start + (nn / a.win) * ws.si + (nn % a.win) * ws.sj];
+                else patch[k][nn] = src[k * plane + (long)(nn / a.win) * a.Ws + nn % a.win];
             }
         } else {
             const float* src = a.img + ((long)b * a.S + c) * P * N;
@@ -1613,7 +1619,9 @@ __global__ __launch_bounds__(256, 2) void tokenize_bwd_mfma_kernel(Args a) {
         const int bc = b < a.B ? b : a.B - 1;
         if constexpr (SCENE) {
             const long plane = (long)a.Hs * a.Ws;
-            const float* src = scene_window_origin(a, bc) + (long)c * P * plane + (long)(n / a.win) * a.Ws + n % a.win;
+            const float* src = scene_window_origin(a, bc) + (long)c * P * plane;
+            if constexpr (std::is_same<Args, TokAtOrBwdArgs>::value) src += oriented_pixel(a, bc, n);
+            else src += (long)(n / a.win) * a.Ws + n % a.win;
 #pragma unroll
             for (int ks = 0; ks < 3; ++ks) { const int k = 4 * ks + g; px[ks] = src[(k < P ? k : 0) * plane]; }
 #pragma unroll
@@ -1913,6 +1921,7 @@ static int launch_tokenize_bwd_src(const Args& a, int nchunk, hipStream_t st) {
 int launch_tokenize_bwd(const TokBwdArgs& a, int nchunk, hipStream_t st) { return launch_tokenize_bwd_src(a, nchunk, st); }
 int launch_tokenize_scene_bwd(const TokSceneBwdArgs& a, int nchunk, hipStream_t st) { return launch_tokenize_bwd_src(a, nchunk, st); }
 int launch_tokenize_at_bwd(const TokAtBwdArgs& a, int nchunk, hipStream_t st) { return launch_tokenize_bwd_src(a, nchunk, st); }
+int launch_tokenize_at_bwd_orient(const TokAtOrBwdArgs& a, int nchunk, hipStream_t st) { return launch_tokenize_bwd_src(a, nchunk, st); }
 
 int launch_pos_split(const float* dpos, int S, int N, int split, float* dpe, float* dce, hipStream_t st) {
     const int n = N * split + S * (96 - split);

@@ -28,15 +28,19 @@ namespace msst {
 // table a.origins instead of computed from its number (msst_tokenize_at_fwd);  TOK_AT_MASKED: TOK_AT's pixels with TOK_BATCH's mask, [B][T]
 // in window coordinates (msst_tokenize_at_fwd_masked).  Nothing else differs: the embedding dropout addresses an element by its place
 // in `out` in all five (msst_tokenize_scene_fwd / _fwd_masked / _at_fwd_masked pass p = 0).
-enum { TOK_BATCH = 0, TOK_SCENE = 1, TOK_SCENE_MASKED = 2, TOK_AT = 3, TOK_AT_MASKED = 4 };
+// TOK_AT_OR / TOK_AT_OR_MASKED: TOK_AT / TOK_AT_MASKED with window b read in orientation a.orient[b] (window_steps, msst_kernels.h;
+// msst_tokenize_at_fwd_orient / _at_fwd_masked_orient): token n is pixel n of the ORIENTED window, so position row, mask byte and dropout
+// element are those of the oriented copy -- only the address of the read differs.  One workgroup reads its window's code once.
+enum { TOK_BATCH = 0, TOK_SCENE = 1, TOK_SCENE_MASKED = 2, TOK_AT = 3, TOK_AT_MASKED = 4, TOK_AT_OR = 5, TOK_AT_OR_MASKED = 6 };
 template <int SRC>
 __device__ __forceinline__ const float* tok_window_origin(const TokArgs& a, int b) {
-    if constexpr (SRC == TOK_AT || SRC == TOK_AT_MASKED) return listed_window_origin(a, b);
+    if constexpr (SRC == TOK_AT || SRC == TOK_AT_MASKED || SRC == TOK_AT_OR || SRC == TOK_AT_OR_MASKED) return listed_window_origin(a, b);
     else return scene_window_origin(a, b);
 }
 template <int PC, int SRC>
 __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
-    constexpr bool SCENE = SRC != TOK_BATCH, NOMASK = SRC == TOK_SCENE || SRC == TOK_AT;
+    constexpr bool SCENE = SRC != TOK_BATCH, NOMASK = SRC == TOK_SCENE || SRC == TOK_AT || SRC == TOK_AT_OR;
+    constexpr bool ORIENT = SRC == TOK_AT_OR || SRC == TOK_AT_OR_MASKED;
     __shared__ float patch[16][64];
     __shared__ float W[96][17];
     __shared__ float bias[96];
@@ -45,9 +49,12 @@ __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
     if constexpr (SCENE) {
         const long plane = (long)a.Hs * a.Ws;
         const float* src = tok_window_origin<SRC>(a, b) + (long)c * P * plane;
+        WinSteps ws{};   // ORIENT: the workgroup's window, its code read once
+        if constexpr (ORIENT) ws = window_steps(a.orient[b], a.win, a.Ws);
         for (int i = tid; i < P * N; i += 256) {
             const int k = i / N, n = i % N;
-            patch[k][n] = src[k * plane + (long)(n / a.win) * a.Ws + n % a.win];
+            if constexpr (ORIENT) patch[k][n] = src[k * plane + ws.start + (n / a.win) * ws.si + (n % a.win) * ws.sj];
+            else patch[k][n] = src[k * plane + (long)(n / a.win) * a.Ws + n % a.win];
         }
     } else {
         const float* src = a.img + ((long)b * a.S + c) * P * N;
@@ -130,7 +137,8 @@ __global__ __launch_bounds__(256) void tokenize_fwd_kernel(TokArgs a) { tokenize
 // Position rows, bias, both LayerNorms' vectors and the mask token are tile invariant for a wave: registers / LDS.
 // SRC: the source addressing policy of tokenize_fwd_body (TOK_SCENE: windows of a scene instead of a batch of cubes, no mask;
 // TOK_SCENE_MASKED: with the scene mask; TOK_AT: windows at listed origins, one table row read per window where the next sample's
-// pixels are requested; TOK_AT_MASKED: those, and the mask byte of a batch of cubes).
+// pixels are requested; TOK_AT_MASKED: those, and the mask byte of a batch of cubes; TOK_AT_OR*: the window's orientation code is read
+// with its table row).
 // ------------------------------------------------------------------------------------------
 template <int SRC>
 __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
@@ -138,7 +146,7 @@ __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
     constexpr int P = 10, N = 64;
     __shared__ __attribute__((aligned(16))) float vec[3][96];   // post_g | post_b | mask_token
     const int c = blockIdx.x, tid = threadIdx.x, w = tid >> 6, l = tid & 63, g = l >> 4, j = l & 15;
-    if (tid < 96) { vec[0][tid] = a.post_g[tid]; vec[1][tid] = a.post_b[tid]; vec[2][tid] = (SRC == TOK_SCENE || SRC == TOK_AT) ? 0.f : a.mask_token[tid]; }
+    if (tid < 96) { vec[0][tid] = a.post_g[tid]; vec[1][tid] = a.post_b[tid]; vec[2][tid] = (SRC == TOK_SCENE || SRC == TOK_AT || SRC == TOK_AT_OR) ? 0.f : a.mask_token[tid]; }
     // A fragments of W_c [96][10]: lane (i = l & 15, kq = l >> 4) holds W[16 mt + i][4 ks + kq] (zero beyond k = 9)
     float wf[6][3];
 #pragma unroll
@@ -176,11 +184,13 @@ __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
         const int bc = b < a.B ? b : a.B - 1;
         if constexpr (SCENE) {
             const long plane = (long)a.Hs * a.Ws;
-            const float* src = tok_window_origin<SRC>(a, bc) + (long)c * P * plane + (long)(n / a.win) * a.Ws + n % a.win;
+            const float* src = tok_window_origin<SRC>(a, bc) + (long)c * P * plane;
+            if constexpr (SRC == TOK_AT_OR || SRC == TOK_AT_OR_MASKED) src += oriented_pixel(a, bc, n);
+            else src += (long)(n / a.win) * a.Ws + n % a.win;
 #pragma unroll
             for (int ks = 0; ks < 3; ++ks) { const int k = 4 * ks + g; px[ks] = src[(k < P ? k : 0) * plane]; }
             if constexpr (SRC == TOK_SCENE_MASKED) mk = scene_window_mask(a, bc, c)[(long)(n / a.win) * a.Ws + n % a.win];
-            else if constexpr (SRC == TOK_AT_MASKED) mk = a.mask[(long)bc * a.T + t];
+            else if constexpr (SRC == TOK_AT_MASKED || SRC == TOK_AT_OR_MASKED) mk = a.mask[(long)bc * a.T + t];
             else mk = 0;
         } else {
             const float* src = a.img + ((long)bc * a.S + c) * P * N + n;
@@ -838,8 +848,9 @@ template __global__ void block_fwd_kernel<PBF16>(BlockArgs);
 // dpred = sign(pred - target) for the backward.
 // AT: the target source.  false: the stacked cube img [B][S*P][N]; true: the scene, at the window origins[b] (msst_head_at_fwd: HeadArgs
 // scene fields).  The grid, the thread-to-entry map and every sum are the same: equal pixels give equal bits.
+// ORIENT (with AT; msst_head_at_fwd_orient): token n is pixel n of that window in orientation a.orient[b] (window_steps).
 // ==========================================================================================
-template <bool AT>
+template <bool AT, bool ORIENT = false>
 __global__ __launch_bounds__(256) void head_fwd_kernel(HeadArgs a) {
     __shared__ float red[4];
     const int tid = threadIdx.x, e = tid >> 2, part = tid & 3;
@@ -861,7 +872,8 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadArgs a) {
         // AT: band 0 of the token's patch at its pixel of the window, and the floats from one band of the scene to the next
         const long plane = AT ? (long)a.Hs * a.Ws : 0;
         const float* tsrc = nullptr;
-        if constexpr (AT) tsrc = listed_window_origin(a, b) + (long)c * P * plane + (long)(n / a.win) * a.Ws + n % a.win;
+        if constexpr (ORIENT) tsrc = listed_window_origin(a, b) + (long)c * P * plane + oriented_pixel(a, b, n);
+        else if constexpr (AT) tsrc = listed_window_origin(a, b) + (long)c * P * plane + (long)(n / a.win) * a.Ws + n % a.win;
         for (int p = 0; p < P; ++p) {
             float acc = 0.f;
 #pragma unroll
@@ -931,6 +943,9 @@ int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st) { return launch_
 int launch_tokenize_scene_fwd_masked(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_SCENE_MASKED>(a, st); }
 int launch_tokenize_at_fwd(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_AT>(a, st); }
 int launch_tokenize_at_fwd_masked(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_AT_MASKED>(a, st); }
+int launch_tokenize_at_fwd_orient(const TokArgs& a, bool masked, hipStream_t st) {
+    return masked ? launch_tokenize_fwd_src<TOK_AT_OR_MASKED>(a, st) : launch_tokenize_fwd_src<TOK_AT_OR>(a, st);
+}
 
 template <class P>
 static int launch_block_fwd_t(const BlockArgs& a, int grid, hipStream_t st) {
@@ -998,12 +1013,12 @@ bool block_fwd_writes_xn(const BlockArgs& a, int prec) {
     return prec == MSST_PREC_BF16 && !(a.dbg & 16);   // both tuned bf16 kernels (head-per-wave for 8 heads, 4-wave otherwise) store their LN1 rows
 }
 
-template <bool AT>
+template <bool AT, bool ORIENT = false>
 static int launch_head_fwd_src(const HeadArgs& a, float* loss, hipStream_t st) {
     if (a.P > 16) return MSST_ERR_UNSUPPORTED;
     dim3 grid((a.K + 63) / 64, a.B);
     { ProfScope ps(K_HEAD_FWD, st);
-    hipLaunchKernelGGL(head_fwd_kernel<AT>, grid, dim3(256), 0, st, a); }
+    hipLaunchKernelGGL((head_fwd_kernel<AT, ORIENT>), grid, dim3(256), 0, st, a); }
     const int np = grid.x * grid.y;
     const float scale = 1.0f / ((float)a.B * (float)a.K * (float)a.P) / (float)a.K;
     ProfScope ps(K_LOSS_REDUCE, st);
@@ -1012,6 +1027,7 @@ static int launch_head_fwd_src(const HeadArgs& a, float* loss, hipStream_t st) {
 }
 int launch_head_fwd(const HeadArgs& a, float* loss, hipStream_t st) { return launch_head_fwd_src<false>(a, loss, st); }
 int launch_head_at_fwd(const HeadArgs& a, float* loss, hipStream_t st) { return launch_head_fwd_src<true>(a, loss, st); }
+int launch_head_at_fwd_orient(const HeadArgs& a, float* loss, hipStream_t st) { return launch_head_fwd_src<true, true>(a, loss, st); }
 
 }  // namespace msst
 

@@ -88,6 +88,9 @@ struct TokArgs {
     // origins[b][0] with its top-left pixel at row origins[b][1], column origins[b][2]; of the scene fields only Hs, Ws and win are read.
     // TOK_AT_MASKED: mask is [B][T] in window coordinates, as for a batch of cubes
     const int32_t* origins;  // [B][3]
+    // oriented listed windows (msst_tokenize_at_fwd_orient / _at_fwd_masked_orient, the kernels' TOK_AT_OR* instances only): sample b is that
+    // window in orientation orient[b] (window_steps); position table, mask and dropout see the oriented window.  Unread by the others
+    const uint8_t* orient;   // [B], codes 0 .. 7
 };
 
 // img pointer of sample b's window origin (scene s, band 0, row r * stride, column q * stride); 64-bit: scenes may be large
@@ -106,6 +109,27 @@ __device__ __forceinline__ const float* listed_window_origin(const Args& a, int 
     const int32_t* o = a.origins + 3 * (long)b;
     const long s = o[0];
     return a.img + ((s * a.S * a.P) * a.Hs + (long)o[1]) * a.Ws + (long)o[2];
+}
+
+// An orientation code o = k + 4 f (k in 0 .. 3, f in 0 .. 1) names one of the eight symmetries of a win x win window w: flipped left to
+// right when f, then turned k quarter turns counter-clockwise -- torch.rot90(torch.flip(w, (-1,)) if f else w, k, (-2, -1)).  It is a
+// different affine map for the same read: pixel (i, j) of the oriented window lies start + i * si + j * sj floats from the window's
+// origin, si and sj in {+-1, +-Ws}.  Only the low three bits of the code are looked at, so whatever the byte holds every read stays
+// inside the window.
+struct WinSteps { int start, si, sj; };
+__device__ __forceinline__ WinSteps window_steps(int o, int win, int Ws) {
+    const int k = o & 3, m = win - 1;
+    // the un-flipped source pixel (y, x) = (y0 + yi i + yj j, x0 + xi i + xj j) of quarter turn k: (i, j), (j, m - i), (m - i, m - j), (m - j, i)
+    const int yi = (k == 0) - (k == 2), yj = (k == 1) - (k == 3), y0 = k >= 2 ? m : 0;
+    int xi = (k == 3) - (k == 1), xj = (k == 0) - (k == 2), x0 = (k == 1 || k == 2) ? m : 0;
+    if (o & 4) { x0 = m - x0; xi = -xi; xj = -xj; }   // the flip: x -> m - x
+    return WinSteps{y0 * Ws + x0, yi * Ws + xi, yj * Ws + xj};
+}
+// floats from the origin of sample b's window to pixel n = i * win + j of it in its orientation (Args: orient, win, Ws)
+template <class Args>
+__device__ __forceinline__ long oriented_pixel(const Args& a, int b, int n) {
+    const WinSteps w = window_steps(a.orient[b], a.win, a.Ws);
+    return (long)w.start + (long)(n / a.win) * w.si + (long)(n % a.win) * w.sj;
 }
 
 // mask byte of token (c, n = 0) of sample b's window in a scene mask [Bs][S][Hs][Ws] (TOK_SCENE_MASKED: TokArgs.mask): one byte per
@@ -163,6 +187,8 @@ struct HeadArgs {
     // origins[b] = (scene, y0, x0) (listed_window_origin)
     const int32_t* origins;  // [B][3]
     int Hs, Ws, win;
+    // msst_head_at_fwd_orient (head_fwd_kernel<HEAD_AT_OR> only): the target is that window in orientation orient[b] (window_steps)
+    const uint8_t* orient;   // [B], codes 0 .. 7
 };
 
 struct HeadBwdArgs {
@@ -247,6 +273,12 @@ struct TokAtBwdArgs : TokSceneBwdArgs {
     const int32_t* origins;   // [B][3]
 };
 __device__ __forceinline__ const float* scene_window_origin(const TokAtBwdArgs& a, int b) { return listed_window_origin(a, b); }
+// msst_tokenize_at_bwd_orient / _at_bwd_masked_orient: those windows, each in orientation orient[b] (window_steps); a type of its own, so
+// that its instances of the kernels stand beside the un-oriented ones
+struct TokAtOrBwdArgs : TokAtBwdArgs {
+    const uint8_t* orient;    // [B], codes 0 .. 7
+};
+__device__ __forceinline__ const float* scene_window_origin(const TokAtOrBwdArgs& a, int b) { return listed_window_origin(a, b); }
 
 // msst_input_grad.hip (msst_tokenize_bwd_input, msst_tokenize_scene_bwd_input, msst_tokenize_at_bwd_input): d(loss)/d(img) from dx0
 struct TokInArgs {
@@ -337,6 +369,7 @@ int launch_tokenize_fwd(const TokArgs& a, hipStream_t st);
 int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st);   // the same kernels reading windows of a scene (TokArgs scene fields)
 int launch_tokenize_scene_fwd_masked(const TokArgs& a, hipStream_t st);   // ... with a scene mask (a.mask [Bs][S][Hs][Ws]) and the mask token
 int launch_tokenize_at_fwd(const TokArgs& a, hipStream_t st);      // ... reading the windows listed in a.origins (no mask)
+int launch_tokenize_at_fwd_orient(const TokArgs& a, bool masked, hipStream_t st);   // ... each in orientation a.orient[b] (masked: a.mask [B][T])
 int launch_tokenize_at_fwd_masked(const TokArgs& a, hipStream_t st);   // ... with a per-window token mask (a.mask [B][T]) and the mask token
 int launch_head_bwd(const HeadBwdArgs& a, int nchunk, hipStream_t st);
 // One reduction segment: dst[(i / row_len) * row_stride + i % row_len] = sum_{k < nslab} src[k * slab_stride + i], i < n
@@ -382,6 +415,7 @@ int launch_block_bwd_ln1mlp(const LnMlpArgs& a, int grid, hipStream_t st);   // 
 int launch_tokenize_bwd(const TokBwdArgs& a, int nchunk, hipStream_t st);
 int launch_tokenize_scene_bwd(const TokSceneBwdArgs& a, int nchunk, hipStream_t st);   // the same kernels reading windows of a scene (no mask)
 int launch_tokenize_at_bwd(const TokAtBwdArgs& a, int nchunk, hipStream_t st);   // ... reading the windows listed in a.origins (a.mask optional)
+int launch_tokenize_at_bwd_orient(const TokAtOrBwdArgs& a, int nchunk, hipStream_t st);   // ... each in orientation a.orient[b]
 int launch_pos_split(const float* dpos, int S, int N, int split, float* dpe, float* dce, hipStream_t st);
 int launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                  float wd, int step, float clamp, float gscale, hipStream_t st);
@@ -428,6 +462,7 @@ bool block_fwd_writes_xn(const BlockArgs& a, int prec);   // does the kernel lau
 bool block_fwd_writes_lse(const BlockArgs& a, int prec);  // ... a.lse_out?  (the role-split kernel: bf16, 8 heads, no selection flags)
 int launch_head_fwd(const HeadArgs& a, float* loss, hipStream_t st);
 int launch_head_at_fwd(const HeadArgs& a, float* loss, hipStream_t st);   // the same kernel, targets read from the scene at a.origins
+int launch_head_at_fwd_orient(const HeadArgs& a, float* loss, hipStream_t st);   // ... from the windows in orientation a.orient[b]
 // msst_ln.hip: stand-alone LayerNorm over the last axis (D <= 128; D = 96 vectorised)
 int launch_layernorm_fwd(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd, long rows, int D,
                          float eps, hipStream_t st);

@@ -117,12 +117,19 @@ class ResidentTileLoader:
     same ``draw()`` random stream: with crop="batch" (one position per batch, the contract of the reference's pretrain.py:99-107) the
     listed windows are SyntheticCubeLoader's batches at the same seed.  crop="sample" draws one position per window instead (after the
     tile indices, from the same generator).  SyntheticCubeLoader's x is the row offset (``pool[:, :, x:x+S, y:y+S]``), so an origin row
-    is (tile, x, y).  No worker thread, no pinned staging: the table is 12 bytes per window."""
+    is (tile, x, y).  No worker thread, no pinned staging: the table is 12 bytes per window.
+    augment="d4": a step is (tiles, origins, orient), orient uint8 [B] on the host -- one orientation code 0 .. 7 per window for
+    ``forward_at(..., orient=)`` (``maskedsst_amd.orient_windows``), drawn from a generator of its own (seeded from `seed`), so the
+    origins of a seed are those of the loader without augment."""
 
     def __init__(self, batch_size, bands, image_size=8, tile_size=64, pool_tiles=64, steps=None, seed=5,
-                 device="cuda", prefetch=2, zero_pad_bands=0, crop="batch"):
+                 device="cuda", prefetch=2, zero_pad_bands=0, crop="batch", augment=None):
         if crop not in ("batch", "sample"):
             raise ValueError(f"crop must be 'batch' (one position per batch) or 'sample' (one per window), got {crop!r}")
+        if augment not in (None, "d4"):
+            raise ValueError(f"augment must be None or 'd4' (flips and quarter turns), got {augment!r}")
+        self.augment = augment
+        self.orient_rng = np.random.default_rng([seed, 0xD4])   # its own stream: the origins never see it
         self.B, self.C, self.S, self.TS = batch_size, bands, image_size, tile_size
         self.steps, self.crop = steps, crop
         self.device = torch.device(device)
@@ -154,7 +161,10 @@ class ResidentTileLoader:
             raise StopIteration
         self._n += 1
         idx, (x, y) = self.draw()
-        return self.pool, torch.from_numpy(np.stack((idx, x, y), axis=1).astype(np.int32))
+        origins = torch.from_numpy(np.stack((idx, x, y), axis=1).astype(np.int32))
+        if self.augment is None:
+            return self.pool, origins
+        return self.pool, origins, torch.from_numpy(self.orient_rng.integers(0, 8, size=self.B).astype(np.uint8))
 
     def close(self):
         pass

@@ -48,10 +48,15 @@ class Windows:
               tile, window row, window column; trailing Ht % s rows / Wt % s columns dropped) -- grid = (nr, nq) per tile;
       listed  img [Bs, C, Hs, Ws] and origins int32 [n, 3] = (scene, y0, x0) on its device; csr = scene.origins_csr(origins, ...) opts
               into the scenes' gradient (the windows overlap: it is a fold over that index), sink a SceneGradSink that receives it.
+              orient uint8 [n] on its device: window i is read in orientation orient[i] (scene.orient_windows; the _orient entry
+              points) -- everything downstream sees the oriented window; no scene gradient through it.
     img is held contiguous and fp32; n: the number of windows."""
 
-    def __init__(self, kind, img, origins=None, csr=None, sink=None, s=None):
+    def __init__(self, kind, img, origins=None, csr=None, sink=None, s=None, orient=None):
         self.kind, self.img, self.origins, self.csr, self.sink = kind, img.contiguous().float(), origins, csr, sink
+        self.orient = orient
+        if orient is not None and (kind != "listed" or csr is not None or sink is not None):
+            raise NotImplementedError("orient goes with listed windows only, and without the scenes' gradient")
         if kind == "tiles":
             self.grid = (img.shape[-2] // s, img.shape[-1] // s)
             self.n = img.shape[0] * self.grid[0] * self.grid[1]
@@ -69,10 +74,14 @@ _TOK_INPUT_BWD = {("batch", False): "msst_tokenize_bwd_input", ("batch", True): 
 
 
 def _tok_entry(table, method, src, masked, emb_drop=(0.0, 0)):
-    """(entry point, its dropout arguments) of `method` on src; the masked listed entry points take no embedding dropout"""
+    """(entry point, its dropout arguments) of `method` on src; the masked listed entry points take no embedding dropout; oriented
+    listed windows run their namesake's _orient entry point (the forward and the parameter backward have one)"""
     name = table.get((src.kind, masked))
+    if name is not None and src.orient is not None:
+        name = name + "_orient" if table is not _TOK_INPUT_BWD else None
     if name is None:
-        raise NotImplementedError(f"{method}: no entry point for {src.kind} windows {'with' if masked else 'without'} a token mask")
+        raise NotImplementedError(f"{method}: no entry point for {'oriented ' if src.orient is not None else ''}{src.kind} windows "
+                                  f"{'with' if masked else 'without'} a token mask")
     if masked and src.kind == "listed":
         if emb_drop[0] > 0:
             raise NotImplementedError(f"{method}: no entry point for listed windows with a token mask and embedding dropout")
@@ -444,7 +453,10 @@ class Engine:
         s = self.enc.num_spatial_patches_sqrt
         if src.kind == "tiles":
             return (_p(src.img),), (Bs, Hs, Ws, s, s, win0, n, S, P)
-        return (_p(src.img), _p(src.origins[win0:] if win0 else src.origins)), (Bs, Hs, Ws, s, n, S, P)
+        lead = (_p(src.img), _p(src.origins[win0:] if win0 else src.origins))
+        if src.orient is not None:   # the _orient entry points: the orientation table follows the origins
+            lead += (_p(src.orient[win0:] if win0 else src.orient),)
+        return lead, (Bs, Hs, Ws, s, n, S, P)
 
     def tokenize(self, src, mask_u8=None, with_pos=True, emb_drop=(0.0, 0)):
         """tokens [n, T, 96] (position added, embedding dropout) of the n windows of src, a Windows or a bare batch img [B, C, H, W] fp32
@@ -631,7 +643,7 @@ class Engine:
 
     def head_fwd(self, y, src, idx32, want_pred=False):
         """the masked-L1 head over y [B, T, 96] -> (loss, dpred, pred); the targets come from src: a batch img [B, C, s, s], or listed
-        windows, read where they lie in their scenes (msst_head_at_fwd): the same bits"""
+        windows, read where they lie in their scenes (msst_head_at_fwd; oriented: msst_head_at_fwd_orient): the same bits"""
         src = self._src(src)
         if src.kind == "tiles":
             raise NotImplementedError("head_fwd: no entry point for tiles windows")
@@ -644,7 +656,7 @@ class Engine:
         loss = torch.empty((), dtype=torch.float32, device=dev)
         per_block = 1 if hasattr(self.mim.to_pixels, "layers") else 0
         V = ctypes.c_void_p
-        name = "msst_head_at_fwd" if src.kind == "listed" else "msst_head_fwd"
+        name = "msst_head_fwd" if src.kind != "listed" else "msst_head_at_fwd" if src.orient is None else "msst_head_at_fwd_orient"
         lead, dims = self._src_args(src, 0, B)
         _lib.check(getattr(self.lib, name)(
             _p(y), *lead, _p(idx32), V(self.fp.ptr("to_pixels.w.0")), V(self.fp.ptr("to_pixels.b.0")), per_block,

@@ -22,6 +22,12 @@ every labelled pixel, or windows at random positions -- with the windows read in
 ``window_labels`` build the origin tables and the labels that go with them.  ``forward_at(..., scene_grad=True)`` also gives the scene its
 gradient: listed windows overlap, so the per-window input gradients (``msst_tokenize_at_bwd_input``) are summed per pixel in a fixed order
 (``msst_scene_fold_at``) through the inverse index ``origins_csr`` builds.
+
+D4 augmentation (``forward_at(..., orient=)``, ``predict_at(..., tta="d4")``): every listed window may be read in one of its eight
+orientations, code ``o = k + 4 f`` -- ``torch.rot90(torch.flip(w, (-1,)) if f else w, k, (-2, -1))`` -- where the kernels form the
+window's address (``msst_tokenize_at_fwd_orient`` / ``_bwd_orient``): no oriented copy exists.  ``orient_windows`` is that expression
+over a batch of windows (and its inverse, which maps patch-head logits back), ``random_orients`` draws codes, ``window_labels(...,
+orient=)`` gives the label patches in the oriented frame.
 """
 from collections import namedtuple
 
@@ -104,15 +110,55 @@ def centre_origins(labels, window, ignore_index=-1):
     return origins, centre_labels
 
 
-def window_labels(labels, origins, window):
+def window_labels(labels, origins, window, orient=None):
     """The label patches [n, window, window] (int64) of the windows listed in origins [n, 3] = (scene, y0, x0) out of label maps
-    [Bs, Hs, Ws]: what a patch head trains against (:324).  A gather of labels only, on the labels' device."""
+    [Bs, Hs, Ws]: what a patch head trains against (:324).  A gather of labels only, on the labels' device.  orient [n] (codes 0 .. 7,
+    any device): the patches in the oriented frame, ``orient_windows`` of them -- what ``forward_at(..., orient=orient)`` predicts."""
     window = _check_labels(labels, window)
     o = origins.to(labels.device).long()
     r = torch.arange(window, device=labels.device)
     ys = (o[:, 1, None] + r)[:, :, None]
     xs = (o[:, 2, None] + r)[:, None, :]
-    return labels[o[:, 0, None, None], ys, xs].long()
+    patches = labels[o[:, 0, None, None], ys, xs].long()
+    return patches if orient is None else orient_windows(patches, orient)
+
+
+ORIENT_CODES = 8   # the dihedral group D4: code o = k + 4 f, k quarter turns counter-clockwise after f left-right flips
+
+
+def _orient_index(s, device):
+    """[8, s s] int64: row o holds, for every pixel of the oriented s x s window in row-major order, the row-major index of the pixel
+    of the window as it lies that lands there -- the normative torch expression applied to the indices themselves"""
+    w = torch.arange(s * s, device=device).view(s, s)
+    return torch.stack([torch.rot90(torch.flip(w, (-1,)) if o >> 2 else w, o & 3, (-2, -1)).reshape(-1) for o in range(ORIENT_CODES)])
+
+
+def orient_windows(x, orient, inverse=False):
+    """The windows x [n, ..., s, s] (any dtype; the last two dimensions are the window) each in its orientation orient [n] (integer
+    codes 0 .. 7 on any device): row i becomes ``torch.rot90(torch.flip(x[i], (-1,)) if f else x[i], k, (-2, -1))`` for
+    ``orient[i] = k + 4 f``; code 0 is the identity.  inverse=True undoes it (oriented windows back to the frame of the scene: what
+    maps the logits of a patch head under ``forward_at(..., orient=)`` back onto the window's pixels).  Eager torch -- one gather on
+    x's device --, the restatement of what the kernels do in their addressing; a new tensor."""
+    if not torch.is_tensor(x) or x.dim() < 3 or x.shape[-1] != x.shape[-2]:
+        raise ValueError(f"x must be a tensor [n, ..., s, s] of square windows, got {getattr(x, 'shape', type(x))}")
+    _check_orient(orient, x.shape[0])
+    s = x.shape[-1]
+    idx = _orient_index(s, x.device)
+    if inverse:
+        idx = torch.argsort(idx, dim=1)
+    rows = idx[orient.to(x.device).long()]                                     # [n, s s]
+    rows = rows.view((x.shape[0],) + (1,) * (x.dim() - 3) + (s * s,)).expand(x.shape[:-2] + (s * s,))
+    return x.reshape(x.shape[:-2] + (s * s,)).gather(-1, rows).view(x.shape)
+
+
+def random_orients(n, generator=None, device=None):
+    """n orientation codes, uniform over 0 .. 7 -> uint8 [n], drawn with `generator` on its own device (the CPU without one) and
+    moved to `device` when given"""
+    if isinstance(n, bool) or int(n) != n or int(n) < 0:
+        raise ValueError(f"n must be a non-negative integer, got {n!r}")
+    dev = generator.device if generator is not None else torch.device("cpu")
+    o = torch.randint(0, ORIENT_CODES, (int(n),), generator=generator, device=dev, dtype=torch.uint8)
+    return o if device is None else o.to(device)
 
 
 def random_origins(Bs, Hs, Ws, window, n, generator=None, labels=None, ignore_index=-1):
@@ -146,8 +192,21 @@ def random_origins(Bs, Hs, Ws, window, n, generator=None, labels=None, ignore_in
     return origins.to(torch.int32)
 
 
-def _check_origins(model, scene, origins, check):
-    """forward_at / predict_at: shapes and dtypes (no device needed), then with check the value ranges -- one reduction, one read-back"""
+_INT_DTYPES = (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8)
+
+
+def _check_orient(orient, n):
+    """shape and dtype of an orientation table for n windows (no device needed, no value read)"""
+    if not torch.is_tensor(orient) or orient.dim() != 1 or orient.shape[0] != n:
+        raise ValueError(f"orient must be an integer tensor [{n}] of orientation codes 0 .. 7, one per window, got "
+                         f"{getattr(orient, 'shape', type(orient))}")
+    if orient.dtype not in _INT_DTYPES:
+        raise ValueError(f"orient must be an integer tensor, got {orient.dtype}")
+
+
+def _check_origins(model, scene, origins, check, orient=None):
+    """forward_at / predict_at: shapes and dtypes (no device needed), then with check the value ranges -- one reduction, one read-back;
+    orient (None: no table): its shape and dtype, and its range 0 .. 7 in that same read-back"""
     if not torch.is_tensor(scene) or scene.dim() != 4:
         raise ValueError(f"scene must be a 4-D tensor [scenes, bands, H, W], got {getattr(scene, 'shape', type(scene))}")
     bands = model.num_spectral_patches * model.patch_depth
@@ -158,11 +217,22 @@ def _check_origins(model, scene, origins, check):
         raise ValueError(f"scene {tuple(scene.shape)} is smaller than one {w} x {w} window")
     if not torch.is_tensor(origins) or origins.dim() != 2 or origins.shape[1] != 3:
         raise ValueError(f"origins must be an integer tensor [n, 3] of (scene, y0, x0), got {getattr(origins, 'shape', type(origins))}")
-    if origins.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+    if origins.dtype not in _INT_DTYPES:
         raise ValueError(f"origins must be an integer tensor, got {origins.dtype}")
+    if orient is not None:
+        _check_orient(orient, origins.shape[0])
     if check and origins.shape[0]:
         hi = (scene.shape[0] - 1, scene.shape[2] - w, scene.shape[3] - w)
-        lo_seen, hi_seen = (v.tolist() for v in torch.stack(torch.aminmax(origins, dim=0)).cpu())   # one reduction, the one read-back
+        seen = torch.stack(torch.aminmax(origins, dim=0))
+        if orient is not None:   # the codes' extremes ride along as a fourth column
+            seen = torch.cat((seen.long(), torch.stack(torch.aminmax(orient.to(origins.device))).long()[:, None]), dim=1)
+        lo_seen, hi_seen = (v.tolist() for v in seen.cpu())   # one reduction, the one read-back
+        if orient is not None:
+            lo_o, hi_o = lo_seen.pop(), hi_seen.pop()
+            if lo_o < 0 or hi_o >= ORIENT_CODES:
+                c = orient.cpu().long()   # the error path alone looks at the rows
+                first = int(((c < 0) | (c >= ORIENT_CODES)).int().argmax())
+                raise ValueError(f"orient[{first}] = {int(c[first])} is no orientation code: they are 0 .. {ORIENT_CODES - 1}")
         if min(lo_seen) < 0 or any(a > b for a, b in zip(hi_seen, hi)):
             o = origins.cpu()   # the error path alone looks at the rows
             first = int(((o < 0) | (o > torch.tensor(hi))).any(dim=1).int().argmax())
@@ -184,11 +254,14 @@ def origins_csr(origins, Bs, Hs, Ws):
     return cell_ptr, cell_win
 
 
-def forward_at(model, scene, origins, check=True, scene_grad=False):
+def forward_at(model, scene, origins, check=True, scene_grad=False, orient=None):
     """See ViTSpatialSpectral.forward_at.  scene_grad may also be an ``engine.SceneGradSink`` (``saliency.scene_saliency``): the backward
     then folds into the sink's running map instead of handing autograd a gradient for the scene."""
-    _check_origins(model, scene, origins, check)
+    _check_origins(model, scene, origins, check, orient)
     wants = scene.requires_grad and torch.is_grad_enabled()
+    if orient is not None and (scene_grad or wants):
+        raise NotImplementedError("forward_at gives the scene no gradient through windows read with orient: the fold would need every "
+                                  "window's inverse map -- detach the scene and drop scene_grad (parameter gradients are computed)")
     if wants and not scene_grad:
         raise NotImplementedError("forward_at gives no gradient for the scene unless asked: listed windows overlap, so d(loss)/d(scene) "
                                   "is an accumulating fold of the per-window input gradients -- pass scene_grad=True for it, or detach "
@@ -201,14 +274,32 @@ def forward_at(model, scene, origins, check=True, scene_grad=False):
     if wants:
         Bs, _, Hs, Ws = scene.shape
         csr, sink = origins_csr(table, Bs, Hs, Ws), scene_grad if isinstance(scene_grad, SceneGradSink) else None
-    return eng.classify_at(Windows("listed", scene, table, csr, sink))
+    if orient is not None:
+        orient = orient.to(device=scene.device, dtype=torch.uint8).contiguous()
+    return eng.classify_at(Windows("listed", scene, table, csr, sink, orient=orient))
 
 
-def predict_at(model, scene, origins, return_logits=False, max_windows=SCENE_MAX_WINDOWS):
+def _forward_d4(model, scene, o, pix):
+    """predict_at(tta="d4") on one chunk: the mean of the logits of every window of o over its eight orientations, the patch heads'
+    mapped back onto the window's pixels first; summed in ascending code order"""
+    total = None
+    for code in range(ORIENT_CODES):
+        codes = torch.full((o.shape[0],), code, dtype=torch.uint8, device=scene.device)
+        out = forward_at(model, scene, o, check=False, orient=codes)
+        out = out.reshape((o.shape[0], -1)) if pix else orient_windows(out, codes, inverse=True)
+        total = out if total is None else total + out
+    return total / ORIENT_CODES
+
+
+def predict_at(model, scene, origins, return_logits=False, max_windows=SCENE_MAX_WINDOWS, orient=None, tta=None):
     """See ViTSpatialSpectral.predict_at."""
     if isinstance(max_windows, bool) or int(max_windows) != max_windows or int(max_windows) < 1:
         raise ValueError(f"max_windows must be a positive integer, got {max_windows!r}")
-    _check_origins(model, scene, origins, True)
+    if tta not in (None, "d4"):
+        raise ValueError(f"tta must be None or 'd4', got {tta!r}")
+    if tta is not None and orient is not None:
+        raise ValueError("tta='d4' runs every window in all eight orientations: it takes no orient")
+    _check_origins(model, scene, origins, True, orient)
     n, nc = origins.shape[0], model.num_classes
     w = model.num_spatial_patches_sqrt
     pix = bool(getattr(model, "pixelwise", False))
@@ -221,7 +312,10 @@ def predict_at(model, scene, origins, return_logits=False, max_windows=SCENE_MAX
             parts = []
             for i in range(0, n, step):
                 o = origins[i:i + step]
-                out = forward_at(model, scene, o, check=False)
+                if tta is not None:
+                    out = _forward_d4(model, scene, o, pix)
+                else:
+                    out = forward_at(model, scene, o, check=False, orient=None if orient is None else orient[i:i + step])
                 parts.append(out.reshape((o.shape[0], nc) if pix else (o.shape[0], nc, w, w)))
             if parts:
                 logits = torch.cat(parts) if len(parts) > 1 else parts[0]

@@ -146,22 +146,28 @@ def train_step(img, label, model, config, device, criterion, optimizer, acc_crit
     return loss, acc, macro_acc
 
 
-def train_step_at(scene, labels, origins, model, config, criterion, optimizer, acc_criterion=None, accumulator=None):
+def train_step_at(scene, labels, origins, model, config, criterion, optimizer, acc_criterion=None, accumulator=None, orient=None):
     """train_step on the windows of resident scenes listed in origins [n, 3] = (scene, y0, x0) (the reference's Houston2018 sampling,
     src/data_houston2018.py:303-329): train_step's body with ``model.forward_at(scene, origins)`` in place of crop, stack and
     ``model(img)`` -- no window is copied.  scene [Bs, C, Hs, Ws] is on the device already; labels and origins are moved to it.
     labels: one entry per window -- [n] for a pixelwise model (``centre_origins``' second result), [n, s, s] for the patch heads
     (``window_labels``) -- or the label maps [Bs, Hs, Ws] of the scenes, from which exactly those are gathered here (pixelwise: the
     label at the window's centre, index s // 2 of the window).  Loss, accuracy, backward and optimizer step as in train_step, the
-    fused criterion and ``accumulator`` included."""
+    fused criterion and ``accumulator`` included.
+    orient [n] (D4 augmentation, ``random_orients``): handed to ``forward_at``, and the labels gathered from label maps are those of the
+    oriented windows (``window_labels(..., orient=)``; pixelwise: the label under the oriented window's centre, the same pixel for an
+    odd window).  Labels given per window are taken as they are: in the oriented frame."""
     from .scene import window_labels
     s = config.image_size - getattr(config, "patch_sub", 0)
     if labels.dim() == 3 and tuple(labels.shape) == (scene.shape[0],) + tuple(scene.shape[-2:]):
         if getattr(config, "pixelwise", False):
-            o = origins.to(labels.device).long()
-            label = labels[o[:, 0], o[:, 1] + s // 2, o[:, 2] + s // 2].long()
+            if orient is not None and s % 2 == 0:   # an even window's centre index is no fixed point of the orientations
+                label = window_labels(labels, origins, s, orient)[:, s // 2, s // 2]
+            else:
+                o = origins.to(labels.device).long()
+                label = labels[o[:, 0], o[:, 1] + s // 2, o[:, 2] + s // 2].long()
         else:
-            label = window_labels(labels, origins, s)
+            label = window_labels(labels, origins, s) if orient is None else window_labels(labels, origins, s, orient)
     else:
         label = labels
         if getattr(config, "pixelwise", False) and label.dim() == 3:
@@ -170,7 +176,7 @@ def train_step_at(scene, labels, origins, model, config, criterion, optimizer, a
         raise ValueError(f"{label.shape[0]} labels for {origins.shape[0]} windows")
     label = label.to(scene.device)
     optimizer.zero_grad()
-    output = model.forward_at(scene, origins)
+    output = model.forward_at(scene, origins) if orient is None else model.forward_at(scene, origins, orient=orient)
     if getattr(criterion, "fused_stats", False):
         return _fused_tail(output, label, criterion, optimizer, accumulator)
     loss = criterion(output, label)

@@ -114,7 +114,7 @@ class SimMIMSpatialSpectral(nn.Module):
     # one window per row of the masked-L1 head's grid (msst_head_at_fwd)
     MAX_WINDOWS_AT = 65535
 
-    def forward_at(self, tiles, origins, masks=None, check=True):
+    def forward_at(self, tiles, origins, masks=None, check=True, orient=None):
         """forward(the stacked windows of tiles at origins, masks) without the stacked copy: pre-training on windows read straight out
         of resident tiles -- several windows per tile, or windows at chosen positions (labelled or cloud-free pixels).  tiles
         [Bs, bands, Ht, Wt] fp32 on the device; origins an integer tensor [n, 3] on either device, row i = (tile index, y0, x0) of the
@@ -126,10 +126,14 @@ class SimMIMSpatialSpectral(nn.Module):
         the tiles; check=False skips that read-back: the kernels then trust the table.  Raises ValueError -- before a device is asked
         for -- for tiles of the wrong rank, dtype or band count or smaller than one window, a table of the wrong shape or dtype or
         with no row or with more than 65535 rows, and masks that are not [n, tokens] / [n, masked tokens]; NotImplementedError for
-        tiles that require a gradient (a fold of the tokenizer's input gradient plus the target's: not built)."""
+        tiles that require a gradient (a fold of the tokenizer's input gradient plus the target's: not built).
+        orient (D4 augmentation): an integer tensor [n] on either device, codes 0 .. 7 (``maskedsst_amd.orient_windows``): window i is
+        read in orientation orient[i], by the tokenizer and by the head's target gather alike; masks are in the coordinates of the
+        oriented window.  Loss and gradients have the bits of ``self(orient_windows(stacked windows, orient), masks)``.  Checked with
+        the origins (ValueError for a wrong shape, dtype or value); None: the un-oriented entry points."""
         from .scene import _check_origins
         enc = self.encoder
-        _check_origins(enc, tiles, origins, check)
+        _check_origins(enc, tiles, origins, check, orient)
         if tiles.dtype != torch.float32:
             raise ValueError(f"tiles must be a float32 tensor, got {tiles.dtype}")
         n = origins.shape[0]
@@ -152,7 +156,9 @@ class SimMIMSpatialSpectral(nn.Module):
         self.last_masks = masks
         table = origins.to(device=tiles.device, dtype=torch.int32).contiguous()
         from .engine import Windows
-        return eng.simmim_loss(Windows("listed", tiles, table), masks[0], masks[1])
+        if orient is not None:
+            orient = orient.to(device=tiles.device, dtype=torch.uint8).contiguous()
+        return eng.simmim_loss(Windows("listed", tiles, table, orient=orient), masks[0], masks[1])
 
     def forward_windows(self, tiles, masks=None):
         """forward(stack_image_batch(tiles), masks) without the stacked copy: the loss over every non-overlapping image_size x

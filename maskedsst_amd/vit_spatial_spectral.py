@@ -352,7 +352,7 @@ class ViTSpatialSpectral(nn.Module):
             raise ValueError(f"tiles of {tuple(tiles.shape[2:])} are smaller than one {s} x {s} window")
         return self.engine().classify_tiles(tiles)
 
-    def forward_at(self, scene, origins, check=True, scene_grad=False):
+    def forward_at(self, scene, origins, check=True, scene_grad=False, orient=None):
         """forward(the stacked windows of scene at origins) without the stacked copy: the sampling of a sparsely labelled scene (the
         reference's Houston2018Dataset, src/data_houston2018.py:303-329 -- a window centred at every labelled pixel, or windows at
         random positions).  scene [Bs, channels, Hs, Ws] fp32 on the device; origins an integer tensor [n, 3] on either device, row i
@@ -370,18 +370,30 @@ class ViTSpatialSpectral(nn.Module):
         the stacked windows) summed per pixel over the windows covering it, in the fixed order of msst_scene_fold_at (ascending y0, x0,
         row of the table): no atomics, equal bits on every run; zero where no window lies.  In training (dropout, full finetune,
         linear_eval) and on a frozen eval() model; the two launches only read, so the parameter gradients keep the bits of a run with
-        the scene detached."""
+        the scene detached.
+        orient (D4 augmentation): an integer tensor [n] on either device, one orientation code o = k + 4 f per window; window i is
+        read as ``torch.rot90(torch.flip(w, (-1,)) if f else w, k, (-2, -1))`` of the window w at origins[i] -- where the kernels form
+        its address: no oriented copy, no further launch.  The result and every parameter gradient have the bits of
+        ``forward(maskedsst_amd.orient_windows(stacked windows, orient))``; the logits of a patch head are in the oriented frame
+        (``orient_windows(logits, orient, inverse=True)`` maps them back, ``window_labels(..., orient=)`` gives their labels).  With
+        check its range 0 .. 7 is verified in the origins' read-back; ValueError for a wrong shape, dtype or value;
+        NotImplementedError together with scene_grad or a scene that requires a gradient.  None: the un-oriented entry points."""
         from .scene import forward_at
-        return forward_at(self, scene, origins, check, scene_grad)
+        return forward_at(self, scene, origins, check, scene_grad, orient)
 
-    def predict_at(self, scene, origins, return_logits=False, max_windows=None):
+    def predict_at(self, scene, origins, return_logits=False, max_windows=None, orient=None, tta=None):
         """Classes at listed windows (the Houston test protocol: predictions only where a label exists): forward_at under no_grad as
         an eval() model, whatever the module's mode, which is left unchanged, in chunks of at most max_windows windows (None:
         maskedsst_amd.scene.SCENE_MAX_WINDOWS; the result does not depend on it).  Returns classes = argmax over the class axis ([n, image_size, image_size] int64;
         pixelwise [n]) and, with return_logits, also the logits ([n, num_classes, image_size, image_size]; pixelwise [n, num_classes],
-        never squeezed).  The table's values are always checked."""
+        never squeezed).  The table's values are always checked.
+        orient [n]: forward_at's, passed through chunk by chunk (patch-head logits stay in the oriented frame).  tta="d4": test-time
+        augmentation -- every window runs in all eight orientations, the logits of a patch head are mapped back onto the window's
+        pixels (``orient_windows(..., inverse=True)``; a pixelwise model's need no mapping: the centre of an odd window is a fixed
+        point of every orientation) and summed in ascending code order, then divided by eight: a fixed order, equal bits on every run
+        and for every max_windows.  ValueError for an unknown tta, or tta together with orient."""
         from .scene import predict_at, SCENE_MAX_WINDOWS
-        return predict_at(self, scene, origins, return_logits, SCENE_MAX_WINDOWS if max_windows is None else max_windows)
+        return predict_at(self, scene, origins, return_logits, SCENE_MAX_WINDOWS if max_windows is None else max_windows, orient, tta)
 
     def predict_scene(self, scene, stride=None, return_logits=False, max_windows=None):
         """Classify whole scenes [Bs, channels, Hs, Ws] with sliding windows of image_size (the window loop of the reference's

@@ -76,6 +76,9 @@ def build_parser():
                          "of it (no host crop, no per-step copy of the windows); with --crop batch the same losses as the default loader")
     ap.add_argument("--crop", default="batch", choices=["batch", "sample"],
                     help="with --resident-tiles: one window position per batch (the reference's crop) or one per window")
+    ap.add_argument("--augment", default=None, choices=["d4"],
+                    help="with --resident-tiles: every window is read in a random one of its eight orientations (flips and quarter "
+                         "turns, forward_at(..., orient=)); the positions of a seed stay those of a run without it")
     ap.add_argument("--accumulate", type=int, default=1, metavar="K",
                     help="sum the gradients of K micro-batches of batch_size // (world * K) samples before each optimizer step "
                          "(maskedsst_amd.GradAccumulator); batch_size stays the global batch, its masks are drawn once per step")
@@ -106,6 +109,8 @@ def main():
     args = build_parser().parse_args()
     if args.crop != "batch" and not args.resident_tiles:
         raise SystemExit("--crop sample needs --resident-tiles (the host loader cuts one position per batch)")
+    if args.augment and not args.resident_tiles:
+        raise SystemExit("--augment d4 orients windows read from resident tiles: it needs --resident-tiles")
 
     random.seed(SEED); np.random.seed(SEED); torch.manual_seed(SEED)
     if not torch.cuda.is_available():
@@ -195,7 +200,7 @@ def main():
         loader_kw = dict(image_size=config.image_size, pool_tiles=args.pool_tiles, steps=steps_per_epoch * K,
                          seed=SEED + 1000 * rank + epoch, device=device)
         if args.resident_tiles:
-            loader = ResidentTileLoader(per_rank // K, config.n_bands, crop=args.crop, **loader_kw)
+            loader = ResidentTileLoader(per_rank // K, config.n_bands, crop=args.crop, augment=args.augment, **loader_kw)
         else:
             loader = SyntheticCubeLoader(per_rank // K, config.n_bands, **loader_kw)
         micro, micro_losses, masks = 0, [], None
@@ -206,8 +211,8 @@ def main():
                     masks = model.draw_masks(per_rank)
             mk = micro_masks(masks, micro, K) if K > 1 else None
             if args.resident_tiles:
-                tiles, origins = img
-                loss = model.forward_at(tiles, origins, masks=mk, check=False)   # the loader's own table: inside the tiles by construction
+                tiles, origins, orient = img if args.augment else img + (None,)
+                loss = model.forward_at(tiles, origins, masks=mk, check=False, orient=orient)   # the loader's own tables: in range by construction
             else:
                 loss = model(img, masks=mk)
             loss.backward()
@@ -238,6 +243,9 @@ def main():
                 if args.resident_tiles:   # the checkpoint's "input": the last step's windows, as the host loader would have cut them
                     s_ = config.image_size
                     img = torch.stack([tiles[t, :, x:x + s_, y:y + s_] for t, x, y in origins.tolist()])
+                    if orient is not None:
+                        from maskedsst_amd import orient_windows
+                        img = orient_windows(img, orient)
                 save_checkpoint(args.save_dir, epoch, model, optimizer, config, losses, img)
             if epoch == 10 and config.model_save_freq == 1:
                 config.model_save_freq = 10
