@@ -221,14 +221,8 @@ struct WinSrc {
     long wps = 1;
     bool oriented = false;            // listed windows, each in orientation orient[b] (the _orient entry points): the table is required
     const uint8_t* orient = nullptr;
+    int kind() const { return oriented ? WIN_LISTED_ORIENTED : listed ? WIN_LISTED : WIN_GRID; }   // of the kernels (msst_kernels.h)
 };
-// the listed windows of an _orient entry point
-static WinSrc oriented_src(int Bs, int Hs, int Ws, int window, int nwin, const int32_t* origins, const uint8_t* orient) {
-    WinSrc w{Bs, Hs, Ws, window, window, 0, nwin, true, origins};
-    w.oriented = true;
-    w.orient = orient;
-    return w;
-}
 // window grid of a scene: false when the shapes are not a valid (scene, window, stride) triple
 static bool scene_grid(int Bs, int Hs, int Ws, int window, int stride, int* nr, int* nq) {
     if (Bs < 1 || window < 1 || stride < 1 || stride > window || Hs < window || Ws < window) return false;
@@ -259,11 +253,11 @@ static int fail(int code, const char* what, const char* suffix) {
     return fail(code, buf);
 }
 
-// what TokArgs, TokBwdArgs (and its scene variants) and TokInArgs share: the source, the parameters, the shape, the dropout stream; the
-// blocks come zeroed (no window grid, no origins: fill_src adds them)
+// what TokArgs, TokBwdArgs and TokInArgs share: the source tensor, the parameters, the shape, the dropout stream; the blocks come
+// zeroed (no window grid, no tables: fill_src adds them)
 template <class Args>
 static void fill_tok_common(Args& a, const TokPtrs& p, int B, int S, int N, int P, Drop drop) {
-    a.img = p.img; a.pre_g = p.pre_g; a.pre_b = p.pre_b; a.w_emb = p.w_emb; a.b_emb = p.b_emb; a.post_g = p.post_g; a.post_b = p.post_b;
+    a.src.base = p.img; a.pre_g = p.pre_g; a.pre_b = p.pre_b; a.w_emb = p.w_emb; a.b_emb = p.b_emb; a.post_g = p.post_g; a.post_b = p.post_b;
     a.B = B; a.S = S; a.N = N; a.T = S * N; a.P = P; a.drop = drop;
 }
 static void fill_tok(TokArgs& a, const TokPtrs& p, const float* pos_a, const float* pos_b, int pos_split, const float* mask_token,
@@ -276,11 +270,10 @@ static void fill_tok_in(TokInArgs& a, const TokPtrs& p, const uint8_t* mask, con
     fill_tok_common(a, p, B, S, N, P, drop);
     a.mask = mask; a.dx0 = dx0; a.dtarget = dtarget; a.dimg = dimg;
 }
-// the source fields of any argument block (Args: TokArgs, TokAtBwdArgs, TokInAtArgs)
-template <class Args>
-static void fill_src(Args& a, const WinSrc& w) {
-    a.win0 = w.win0; a.Hs = w.Hs; a.Ws = w.Ws; a.win = w.window; a.stride = w.stride; a.nq = w.nq; a.wps = (int)w.wps;
-    a.origins = w.origins;
+// where the windows lie, into the argument block's source (its base is already set)
+static void fill_src(WinRef& r, const WinSrc& w) {
+    r.win0 = w.win0; r.Hs = w.Hs; r.Ws = w.Ws; r.win = w.window; r.stride = w.stride; r.nq = w.nq; r.wps = (int)w.wps;
+    r.origins = w.origins; r.orient = w.orient;
 }
 
 // the window grid of an assemble call into its argument block
@@ -395,7 +388,7 @@ int msst_tokenize_fwd(const float* img, const float* pre_g, const float* pre_b, 
     TokArgs a{};
     fill_tok(a, {img, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, pos_a, pos_b, pos_split, mask_token, mask, out, B, S, N, P,
              make_drop(emb_dropout_p, seed, 255));
-    return fail(launch_tokenize_fwd(a, (hipStream_t)stream), "msst_tokenize_fwd");
+    return fail(launch_tokenize_fwd(a, WIN_BATCH, MASK_TOKENS, (hipStream_t)stream), "msst_tokenize_fwd");
 }
 
 // the two inference forwards over a scene's window grid (no dropout; masked: the scene mask and the mask token).  Their own precedence:
@@ -411,8 +404,8 @@ static int tokenize_scene_fwd(const char* what, bool masked, const TokPtrs& p, c
     if (w.window > 8) return fail(MSST_ERR_UNSUPPORTED, what, " (more than 64 pixels per window)");
     TokArgs a{};
     fill_tok(a, p, pos_a, pos_b, pos_split, mask_token, scene_mask, out, w.nwin, S, w.window * w.window, P, make_drop(0.f, 0, 255));
-    fill_src(a, w);
-    return fail((masked ? launch_tokenize_scene_fwd_masked : launch_tokenize_scene_fwd)(a, (hipStream_t)stream), what);
+    fill_src(a.src, w);
+    return fail(launch_tokenize_fwd(a, WIN_GRID, masked ? MASK_SCENE : MASK_NONE, (hipStream_t)stream), what);
 }
 
 int msst_tokenize_scene_fwd(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb,
@@ -439,13 +432,8 @@ static int tokenize_src_fwd(const char* what, bool masked, const TokPtrs& p, con
     if (w.listed && (P != 10 || w.window != 8) && w.nwin > 65535) return fail(MSST_ERR_UNSUPPORTED, what, " (more than 65535 windows)");
     TokArgs a{};
     fill_tok(a, p, pos_a, pos_b, pos_split, mask_token, mask, out, w.nwin, S, w.window * w.window, P, drop);
-    fill_src(a, w);
-    if (w.oriented) {
-        a.orient = w.orient;
-        return fail(launch_tokenize_at_fwd_orient(a, masked, (hipStream_t)stream), what);
-    }
-    return fail((!w.listed ? launch_tokenize_scene_fwd : masked ? launch_tokenize_at_fwd_masked : launch_tokenize_at_fwd)(a, (hipStream_t)stream),
-                what);
+    fill_src(a.src, w);
+    return fail(launch_tokenize_fwd(a, w.kind(), masked ? MASK_TOKENS : MASK_NONE, (hipStream_t)stream), what);
 }
 
 int msst_tokenize_scene_fwd_train(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb,
@@ -480,7 +468,7 @@ int msst_tokenize_at_fwd_orient(const float* scene, const int32_t* origins, cons
                                 const float* pos_b, int pos_split, float* out, int Bs, int Hs, int Ws, int window, int nwin, int S, int P,
                                 float emb_dropout_p, uint32_t seed, void* stream) {
     return tokenize_src_fwd("msst_tokenize_at_fwd_orient", false, {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, pos_a, pos_b,
-                            pos_split, nullptr, nullptr, out, oriented_src(Bs, Hs, Ws, window, nwin, origins, orient), S, P,
+                            pos_split, nullptr, nullptr, out, WinSrc{Bs, Hs, Ws, window, window, 0, nwin, true, origins, 1, 1, true, orient}, S, P,
                             make_drop(emb_dropout_p, seed, 255), stream);
 }
 
@@ -490,7 +478,7 @@ int msst_tokenize_at_fwd_masked_orient(const float* scene, const int32_t* origin
                                        const float* mask_token, const uint8_t* mask, float* out, int Bs, int Hs, int Ws, int window,
                                        int nwin, int S, int P, void* stream) {
     return tokenize_src_fwd("msst_tokenize_at_fwd_masked_orient", true, {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, pos_a, pos_b,
-                            pos_split, mask_token, mask, out, oriented_src(Bs, Hs, Ws, window, nwin, origins, orient), S, P,
+                            pos_split, mask_token, mask, out, WinSrc{Bs, Hs, Ws, window, window, 0, nwin, true, origins, 1, 1, true, orient}, S, P,
                             make_drop(0.f, 0, 255), stream);
 }
 
@@ -721,11 +709,10 @@ int msst_block_fwd_stack(const MsstBlockWeights* const* w, int nblk, const float
 int msst_head_fwd(const float* y, const float* img, const int32_t* idx, const float* w_pix,
                   const float* b_pix, int per_block, float* dpred, float* pred, float* partial,
                   float* loss, int B, int S, int N, int P, int K, void* stream) {
-    HeadArgs a;
-    a.y = y; a.img = img; a.idx = idx; a.w_pix = w_pix; a.b_pix = b_pix; a.dpred = dpred; a.pred = pred;
+    HeadArgs a{};   // a batch of cubes: no window tables
+    a.y = y; a.src.base = img; a.idx = idx; a.w_pix = w_pix; a.b_pix = b_pix; a.dpred = dpred; a.pred = pred;
     a.partial = partial; a.B = B; a.S = S; a.N = N; a.T = S * N; a.P = P; a.K = K; a.per_block = per_block;
-    a.origins = nullptr; a.Hs = 0; a.Ws = 0; a.win = 0; a.orient = nullptr;   // (msst_head_at_fwd's target source: unread here)
-    return fail(launch_head_fwd(a, loss, (hipStream_t)stream), "msst_head_fwd");
+    return fail(launch_head_fwd(a, WIN_BATCH, loss, (hipStream_t)stream), "msst_head_fwd");
 }
 
 // msst_head_at_fwd and msst_head_at_fwd_orient (oriented: the orientation table is required too)
@@ -737,11 +724,12 @@ static int head_at_fwd(const char* what, bool oriented, const float* y, const fl
         return fail(MSST_ERR_UNSUPPORTED, what, " (window <= Hs, Ws, window * window <= 64, P <= 16, nwin <= 65535)");
     if (!y || !scene || !origins || (oriented && !orient) || !idx || !w_pix || !b_pix || !dpred || !partial || !loss || K > S * window * window)
         return fail(MSST_ERR_BADARG, what);
-    HeadArgs a;
-    a.y = y; a.img = scene; a.idx = idx; a.w_pix = w_pix; a.b_pix = b_pix; a.dpred = dpred; a.pred = pred;
+    HeadArgs a{};
+    a.y = y; a.src.base = scene; a.idx = idx; a.w_pix = w_pix; a.b_pix = b_pix; a.dpred = dpred; a.pred = pred;
     a.partial = partial; a.B = nwin; a.S = S; a.N = window * window; a.T = S * a.N; a.P = P; a.K = K; a.per_block = per_block;
-    a.origins = origins; a.Hs = Hs; a.Ws = Ws; a.win = window; a.orient = orient;
-    return fail((oriented ? launch_head_at_fwd_orient : launch_head_at_fwd)(a, loss, (hipStream_t)stream), what);
+    const WinSrc w{Bs, Hs, Ws, window, window, 0, nwin, true, origins, 1, 1, oriented, orient};
+    fill_src(a.src, w);
+    return fail(launch_head_fwd(a, w.kind(), loss, (hipStream_t)stream), what);
 }
 
 int msst_head_at_fwd(const float* y, const float* scene, const int32_t* origins, const int32_t* idx, const float* w_pix,
@@ -1033,15 +1021,11 @@ static int tokenize_src_bwd(const char* what, const TokPtrs& p, const uint8_t* m
     }
     if (nchunk < 1) return fail(MSST_ERR_BADARG, what);
     hipStream_t st = (hipStream_t)stream;
-    TokAtOrBwdArgs a{};   // its bases are the argument blocks of the other three launchers
+    TokBwdArgs a{};
     fill_tok_common(a, p, B, S, N, P, drop);
     a.mask = mask; a.dx0 = dx0; a.slab = slab;
-    if (w) fill_src(a, *w);
-    if (w && w->oriented) {
-        a.orient = w->orient;
-        if (int rc = launch_tokenize_at_bwd_orient(a, nchunk, st)) return fail(rc, what);
-    } else if (int rc = !w ? launch_tokenize_bwd(a, nchunk, st) : w->listed ? launch_tokenize_at_bwd(a, nchunk, st) : launch_tokenize_scene_bwd(a, nchunk, st))
-        return fail(rc, what);
+    if (w) fill_src(a.src, *w);
+    if (int rc = launch_tokenize_bwd(a, w ? w->kind() : WIN_BATCH, nchunk, st)) return fail(rc, what);
     return tokenize_bwd_reduce(slab, nchunk, g, S, N, P, st);
 }
 
@@ -1094,7 +1078,7 @@ int msst_tokenize_at_bwd_orient(const float* scene, const int32_t* origins, cons
                                 float* slab, int nchunk, float* dpre_g, float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g,
                                 float* dpost_b, float* dpos_a, float* dpos_b, int pos_split, int Bs, int Hs, int Ws, int window, int nwin,
                                 int S, int P, float emb_dropout_p, uint32_t seed, void* stream) {
-    WinSrc w = oriented_src(Bs, Hs, Ws, window, nwin, origins, orient);
+    WinSrc w = WinSrc{Bs, Hs, Ws, window, window, 0, nwin, true, origins, 1, 1, true, orient};
     return tokenize_src_bwd("msst_tokenize_at_bwd_orient", {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, nullptr, false, dx0, slab,
                             nchunk, {dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, nullptr}, &w, nwin, S,
                             window * window, P, make_drop(emb_dropout_p, seed, 255), stream);
@@ -1106,7 +1090,7 @@ int msst_tokenize_at_bwd_masked_orient(const float* scene, const int32_t* origin
                                        float* dpre_b, float* dw_emb, float* db_emb, float* dpost_g, float* dpost_b, float* dpos_a,
                                        float* dpos_b, int pos_split, float* dmask_token, int Bs, int Hs, int Ws, int window, int nwin,
                                        int S, int P, void* stream) {
-    WinSrc w = oriented_src(Bs, Hs, Ws, window, nwin, origins, orient);
+    WinSrc w = WinSrc{Bs, Hs, Ws, window, window, 0, nwin, true, origins, 1, 1, true, orient};
     return tokenize_src_bwd("msst_tokenize_at_bwd_masked_orient", {scene, pre_g, pre_b, w_emb, b_emb, post_g, post_b}, mask, true, dx0,
                             slab, nchunk, {dpre_g, dpre_b, dw_emb, db_emb, dpost_g, dpost_b, dpos_a, dpos_b, pos_split, dmask_token}, &w,
                             nwin, S, window * window, P, make_drop(0.f, 0, 255), stream);
@@ -1122,7 +1106,7 @@ int msst_tokenize_bwd_input(const float* img, const float* pre_g, const float* p
     if (!p.all_set() || !dx0 || !dimg) return fail(MSST_ERR_BADARG, "msst_tokenize_bwd_input");
     TokInArgs a{};   // a batch of cubes: no window grid
     fill_tok_in(a, p, mask, dx0, dtarget, dimg, B, S, N, P, make_drop(emb_dropout_p, seed, 255));
-    return fail(launch_tokenize_bwd_input(a, (hipStream_t)stream), "msst_tokenize_bwd_input");
+    return fail(launch_tokenize_bwd_input(a, WIN_BATCH, (hipStream_t)stream), "msst_tokenize_bwd_input");
 }
 
 int msst_head_bwd_target(const float* dpred, const int32_t* csr_ptr, const int32_t* csr_pos, const float* gout, float* dtarget,
@@ -1150,10 +1134,10 @@ static int tokenize_src_bwd_input(const char* what, const TokPtrs& p, const floa
                 return fail(rc, what, "(border)");
         }
     }
-    TokInAtArgs a{};   // its base is the argument block of the grid launcher
+    TokInArgs a{};
     fill_tok_in(a, p, nullptr, dx0, nullptr, dimg, w.nwin, S, w.window * w.window, P, drop);
-    fill_src(a, w);
-    return fail(w.listed ? launch_tokenize_at_bwd_input(a, st) : launch_tokenize_scene_bwd_input(a, st), what);
+    fill_src(a.src, w);
+    return fail(launch_tokenize_bwd_input(a, w.kind(), st), what);
 }
 
 int msst_tokenize_scene_bwd_input(const float* scene, const float* pre_g, const float* pre_b, const float* w_emb, const float* b_emb,

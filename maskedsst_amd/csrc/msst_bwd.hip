@@ -1363,14 +1363,10 @@ __global__ __launch_bounds__(256) void block_bwd_ln1_kernel(Ln1BwdArgs a) {
 // slab per (c, chunk): [dpos N*96 | dW 96*P | db 96 | dpost_g 96 | dpost_b 96 | dmask 96 | dpre_g 16 | dpre_b 16]
 // ==========================================================================================
 // PC: pixels per patch as a compile-time constant (10; 0 = run-time value), see tokenize_fwd_kernel
-// SCENE, Args: addressing policy of the source pixels, as in tokenize_fwd_body.  false: a batch of cubes img [B][S*P][N] and its token mask;
-// true: sample b is window win0 + b of a scene (TokSceneBwdArgs), or the window at origins[b] (TokAtBwdArgs: scene_window_origin's
-// overload reads the table), nothing masked (the classification path).  The arithmetic
-// and every summation order are the same: equal pixels and equal dx0 give equal bits.
-// TokAtOrBwdArgs (msst_tokenize_at_bwd_orient / _at_bwd_masked_orient): window b is read in orientation a.orient[b] (window_steps,
-// msst_kernels.h) -- sample b is the oriented window, so dx0 row, mask byte and dropout element are its; only the address of the read differs.
-template <int PC, bool SCENE, class Args>
-__global__ __launch_bounds__(256) void tokenize_bwd_kernel(Args a) {
+// KIND: where the samples lie (WinRef, msst_kernels.h), as in tokenize_fwd_body.  The arithmetic and every summation order are the same:
+// equal pixels and equal dx0 give equal bits.
+template <int PC, int KIND>
+__global__ __launch_bounds__(256) void tokenize_bwd_kernel(TokBwdArgs a) {
     __shared__ float patch[16][64];
     __shared__ float W[96][17];
     __shared__ float de_s[64][97];
@@ -1401,20 +1397,16 @@ __global__ __launch_bounds__(256) void tokenize_bwd_kernel(Args a) {
 
     for (int b = chunk; b < a.B; b += gridDim.y) {
         __syncthreads();
-        if constexpr (SCENE) {
-            const long plane = (long)a.Hs * a.Ws;
-            const float* src = scene_window_origin(a, b) + (long)c * P * plane;
-            constexpr bool ORIENT = std::is_same<Args, TokAtOrBwdArgs>::value;
-            WinSteps ws{};   // ORIENT: this window's code, read once
-            if constexpr (ORIENT) ws = window_steps(a.orient[b], a.win, a.Ws);
+        const float* src = win_origin<KIND>(a.src.base, a.src, b, c, a.S, P, N);
+        if constexpr (KIND == WIN_BATCH) {   // a cube's tile is P * N contiguous floats
+            for (int i = tid; i < P * N; i += 256) patch[i / N][i % N] = src[i];
+        } else {
+            const auto plane = win_plane<KIND>(a.src, N);
+            const WinSteps ws = win_steps<KIND>(a.src, b);   // oriented: this window's code, read once
             for (int i = tid; i < P * N; i += 256) {
                 const int k = i / N, nn = i % N;
-                if constexpr (ORIENT) patch[k][nn] = src[k * plane + ws.start + (nn / a.win) * ws.si + (nn % a.win) * ws.sj];
-                else patch[k][nn] = src[k * plane + (long)(nn / a.win) * a.Ws + nn % a.win];
+                patch[k][nn] = src[win_pixel<KIND>(a.src, ws, nn, k * plane)];
             }
-        } else {
-            const float* src = a.img + ((long)b * a.S + c) * P * N;
-            for (int i = tid; i < P * N; i += 256) patch[i / N][i % N] = src[i];
         }
         __syncthreads();
         // this thread's dx0 slice, requested unconditionally (clamped row) and all six at once: inside `if (active)` every
@@ -1428,9 +1420,9 @@ __global__ __launch_bounds__(256) void tokenize_bwd_kernel(Args a) {
         }
         if (active) {
             const int t = c * N + n;
-            // SCENE: the mask is optional and msst_tokenize_scene_bwd passes none.  It stays a run-time value on purpose: with a constant
-            // "not masked" the compiler vectorises and contracts the arithmetic below differently, and the last bits move
-            const bool masked = (SCENE && !a.mask) ? false : a.mask[(long)b * T + t] != 0;
+            // a window source's mask is optional and msst_tokenize_scene_bwd passes none.  It stays a run-time value on purpose: with a
+            // constant "not masked" the compiler vectorises and contracts the arithmetic below differently, and the last bits move
+            const bool masked = (KIND != WIN_BATCH && !a.mask) ? false : a.mask[(long)b * T + t] != 0;
             float dt[24];
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
@@ -1575,12 +1567,12 @@ __global__ __launch_bounds__(256) void tokenize_bwd_kernel(Args a) {
 //   * dW[d][k] += sum_token de[d][token] xn[token][k]: 24 MFMAs over the wave's 16 tokens, both operands transposed through a
 //     wave-private LDS tile; a column of ones appended to xn makes dW[d][10] the bias gradient.
 // Slab layout as above.  grid (S, nchunk), 256 threads.
-// SCENE: the source addressing policy of tokenize_bwd_kernel (windows of a scene, nothing masked).  Its instance is plain C++
-// throughout: the lane id is laundered by an identity DPP move (a cross-lane operation is not moved out of a loop), where the batch
-// instance uses an empty asm statement, and the LDS wait before the dW MFMAs is the builtin.
+// KIND: as in tokenize_bwd_kernel.  The window instances are plain C++ throughout: the lane id is laundered by an identity DPP move (a
+// cross-lane operation is not moved out of a loop), where the batch instance uses an empty asm statement, and the LDS wait before the
+// dW MFMAs is the builtin.
 // ------------------------------------------------------------------------------------------
-template <bool SCENE, class Args>
-__global__ __launch_bounds__(256, 2) void tokenize_bwd_mfma_kernel(Args a) {
+template <int KIND>
+__global__ __launch_bounds__(256, 2) void tokenize_bwd_mfma_kernel(TokBwdArgs a) {
     constexpr int P = 10, N = 64;
     __shared__ float wA[6][3][64];        // forward A fragments: [mt][ks][lane] = W[16 mt + (lane & 15)][4 ks + (lane >> 4)]
     __shared__ float wT[6][4][64];        // d(xn) A fragments: [mt][r][lane] = W[16 mt + 4 (lane >> 4) + r][lane & 15] (0 for k >= 10)
@@ -1617,26 +1609,15 @@ __global__ __launch_bounds__(256, 2) void tokenize_bwd_mfma_kernel(Args a) {
     unsigned char mk;
     auto request = [&](int b) {
         const int bc = b < a.B ? b : a.B - 1;
-        if constexpr (SCENE) {
-            const long plane = (long)a.Hs * a.Ws;
-            const float* src = scene_window_origin(a, bc) + (long)c * P * plane;
-            if constexpr (std::is_same<Args, TokAtOrBwdArgs>::value) src += oriented_pixel(a, bc, n);
-            else src += (long)(n / a.win) * a.Ws + n % a.win;
+        const auto plane = win_plane<KIND>(a.src, N);
+        const float* src = win_origin<KIND>(a.src.base, a.src, bc, c, a.S, P, N) + win_pixel<KIND>(a.src, bc, n);
 #pragma unroll
-            for (int ks = 0; ks < 3; ++ks) { const int k = 4 * ks + g; px[ks] = src[(k < P ? k : 0) * plane]; }
+        for (int ks = 0; ks < 3; ++ks) { const int k = 4 * ks + g; px[ks] = src[(k < P ? k : 0) * plane]; }
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { const int k = 4 * g + r; px2[r] = src[(k < P ? k : 0) * plane]; }
-            // the mask is optional and msst_tokenize_scene_bwd passes none; it stays a run-time value on purpose: with a constant "not
-            // masked" the compiler vectorises and contracts the walk's arithmetic differently, and the last bits move
-            mk = a.mask ? a.mask[(long)bc * T + t] : 0;
-        } else {
-            const float* src = a.img + ((long)bc * a.S + c) * P * N + n;
-#pragma unroll
-            for (int ks = 0; ks < 3; ++ks) { const int k = 4 * ks + g; px[ks] = src[(k < P ? k : 0) * N]; }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { const int k = 4 * g + r; px2[r] = src[(k < P ? k : 0) * N]; }
-            mk = a.mask[(long)bc * T + t];
-        }
+        for (int r = 0; r < 4; ++r) { const int k = 4 * g + r; px2[r] = src[(k < P ? k : 0) * plane]; }
+        // a window source's mask is optional and msst_tokenize_scene_bwd passes none; it stays a run-time value on purpose: with a constant
+        // "not masked" the compiler vectorises and contracts the walk's arithmetic differently, and the last bits move
+        mk = (KIND != WIN_BATCH && !a.mask) ? 0 : a.mask[(long)bc * T + t];
     };
     // the dx0 rows of the next sample are requested late in the iteration (behind the LayerNorm backward: 24 registers that are
     // free only then), the pixels and the mask byte early
@@ -1652,7 +1633,7 @@ __global__ __launch_bounds__(256, 2) void tokenize_bwd_mfma_kernel(Args a) {
         // lane indices re-derived from a laundered id every iteration: the weight fragments, the bias and post_norm's gamma are
         // loop-invariant LDS reads -- with an invariant address they are hoisted out of the walk (90 registers) and spilled
         int ll = threadIdx.x & 63;
-        if constexpr (SCENE) ll = __builtin_amdgcn_mov_dpp(ll, 0xe4, 0xf, 0xf, true);   // quad_perm [0, 1, 2, 3]: every lane keeps its own value
+        if constexpr (KIND != WIN_BATCH) ll = __builtin_amdgcn_mov_dpp(ll, 0xe4, 0xf, 0xf, true);   // quad_perm [0, 1, 2, 3]: every lane keeps its own value
         else asm volatile("" : "+v"(ll));
         const int gl = ll >> 4, jl = ll & 15;
         float x[3], x2[4];
@@ -1740,7 +1721,7 @@ __global__ __launch_bounds__(256, 2) void tokenize_bwd_mfma_kernel(Args a) {
             dprb[r] += ok ? dxn[r] : 0.f;
         }
         __builtin_amdgcn_wave_barrier();
-        if constexpr (SCENE) __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0), the other counters at their maxima
+        if constexpr (KIND != WIN_BATCH) __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0), the other counters at their maxima
         else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         // dW[d][k] += sum over the wave's 16 tokens: A[i = feature][kk = token], B[j = pixel k][kk = token]
         const float* dea = &de_t[w][jl][gl];
@@ -1904,24 +1885,28 @@ int launch_block_bwd_ln1(const Ln1BwdArgs& a, int grid, int prec, hipStream_t st
     return (int)hipGetLastError();
 }
 
-// The one kernel selection of the tokenizer backward (that of launch_tokenize_fwd_src, msst_fwd.hip), whatever the source.  Args:
-// TokBwdArgs, a batch of cubes; TokSceneBwdArgs / TokAtBwdArgs, the SCENE instances (a.B = windows of the call).  Not uniform, and
-// kept so: a batch of cubes is launched as given, the window sources refuse an empty call and an nchunk no grid holds.
-template <class Args>
-static int launch_tokenize_bwd_src(const Args& a, int nchunk, hipStream_t st) {
-    constexpr bool SCENE = !std::is_same<Args, TokBwdArgs>::value;
+// The one kernel selection of the tokenizer backward (that of launch_tokenize_fwd_src, msst_fwd.hip), whatever the source (a.B = samples
+// = windows of the call).  Not uniform, and kept so: a batch of cubes is launched as given, the window sources refuse an empty call and
+// an nchunk no grid holds.
+template <int KIND>
+static int launch_tokenize_bwd_src(const TokBwdArgs& a, int nchunk, hipStream_t st) {
     if (a.P > 16 || a.N > 64) return MSST_ERR_UNSUPPORTED;
-    if (SCENE && (a.B < 1 || nchunk < 1 || nchunk > 65535)) return MSST_ERR_BADARG;
+    if (KIND != WIN_BATCH && (a.B < 1 || nchunk < 1 || nchunk > 65535)) return MSST_ERR_BADARG;
     ProfScope ps(K_TOK_BWD, st);
-    if (a.P == 10 && a.N == 64) hipLaunchKernelGGL((tokenize_bwd_mfma_kernel<SCENE, Args>), dim3(a.S, nchunk), dim3(256), 0, st, a);
-    else if (a.P == 10) hipLaunchKernelGGL((tokenize_bwd_kernel<10, SCENE, Args>), dim3(a.S, nchunk), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((tokenize_bwd_kernel<0, SCENE, Args>), dim3(a.S, nchunk), dim3(256), 0, st, a);
+    if (a.P == 10 && a.N == 64) hipLaunchKernelGGL(tokenize_bwd_mfma_kernel<KIND>, dim3(a.S, nchunk), dim3(256), 0, st, a);
+    else if (a.P == 10) hipLaunchKernelGGL((tokenize_bwd_kernel<10, KIND>), dim3(a.S, nchunk), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((tokenize_bwd_kernel<0, KIND>), dim3(a.S, nchunk), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
-int launch_tokenize_bwd(const TokBwdArgs& a, int nchunk, hipStream_t st) { return launch_tokenize_bwd_src(a, nchunk, st); }
-int launch_tokenize_scene_bwd(const TokSceneBwdArgs& a, int nchunk, hipStream_t st) { return launch_tokenize_bwd_src(a, nchunk, st); }
-int launch_tokenize_at_bwd(const TokAtBwdArgs& a, int nchunk, hipStream_t st) { return launch_tokenize_bwd_src(a, nchunk, st); }
-int launch_tokenize_at_bwd_orient(const TokAtOrBwdArgs& a, int nchunk, hipStream_t st) { return launch_tokenize_bwd_src(a, nchunk, st); }
+int launch_tokenize_bwd(const TokBwdArgs& a, int kind, int nchunk, hipStream_t st) {
+    switch (kind) {
+    case WIN_BATCH: return launch_tokenize_bwd_src<WIN_BATCH>(a, nchunk, st);
+    case WIN_GRID: return launch_tokenize_bwd_src<WIN_GRID>(a, nchunk, st);
+    case WIN_LISTED: return launch_tokenize_bwd_src<WIN_LISTED>(a, nchunk, st);
+    case WIN_LISTED_ORIENTED: return launch_tokenize_bwd_src<WIN_LISTED_ORIENTED>(a, nchunk, st);
+    }
+    return MSST_ERR_UNSUPPORTED;
+}
 
 int launch_pos_split(const float* dpos, int S, int N, int split, float* dpe, float* dce, hipStream_t st) {
     const int n = N * split + S * (96 - split);

@@ -21,44 +21,25 @@ namespace msst {
 // ==========================================================================================
 // PC: pixels per patch as a compile-time constant (10 = the reference's spectral patch, configs/config.yaml: band_patch_size)
 // so that the small loops over it unroll and their LDS reads are batched; 0 = run-time value (any P <= 16)
-// SRC: addressing policy of the source pixels and of the token mask.  TOK_BATCH: img[b, c P + k, n] of a batch of cubes [B][S*P][N],
-// mask [B][T];  TOK_SCENE: the same pixel of window b of a scene, scene[s, c P + k, y0 + n / win, x0 + n % win] (TokArgs scene fields;
-// no mask);  TOK_SCENE_MASKED: those pixels, and token (c, n) is masked where the scene mask [Bs][S][Hs][Ws] (a.mask) is non-zero at
-// (s, c, y0 + n / win, x0 + n % win) (msst_tokenize_scene_fwd_masked);  TOK_AT: TOK_SCENE with (s, y0, x0) of window b read from the
-// table a.origins instead of computed from its number (msst_tokenize_at_fwd);  TOK_AT_MASKED: TOK_AT's pixels with TOK_BATCH's mask, [B][T]
-// in window coordinates (msst_tokenize_at_fwd_masked).  Nothing else differs: the embedding dropout addresses an element by its place
-// in `out` in all five (msst_tokenize_scene_fwd / _fwd_masked / _at_fwd_masked pass p = 0).
-// TOK_AT_OR / TOK_AT_OR_MASKED: TOK_AT / TOK_AT_MASKED with window b read in orientation a.orient[b] (window_steps, msst_kernels.h;
-// msst_tokenize_at_fwd_orient / _at_fwd_masked_orient): token n is pixel n of the ORIENTED window, so position row, mask byte and dropout
-// element are those of the oriented copy -- only the address of the read differs.  One workgroup reads its window's code once.
-enum { TOK_BATCH = 0, TOK_SCENE = 1, TOK_SCENE_MASKED = 2, TOK_AT = 3, TOK_AT_MASKED = 4, TOK_AT_OR = 5, TOK_AT_OR_MASKED = 6 };
-template <int SRC>
-__device__ __forceinline__ const float* tok_window_origin(const TokArgs& a, int b) {
-    if constexpr (SRC == TOK_AT || SRC == TOK_AT_MASKED || SRC == TOK_AT_OR || SRC == TOK_AT_OR_MASKED) return listed_window_origin(a, b);
-    else return scene_window_origin(a, b);
-}
-template <int PC, int SRC>
+// KIND, MASK: where the samples lie (WinRef, msst_kernels.h) and the mask policy (MASK_*).  Nothing else differs between the instances:
+// the embedding dropout addresses an element by its place in `out` in all of them.
+template <int PC, int KIND, int MASK>
 __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
-    constexpr bool SCENE = SRC != TOK_BATCH, NOMASK = SRC == TOK_SCENE || SRC == TOK_AT || SRC == TOK_AT_OR;
-    constexpr bool ORIENT = SRC == TOK_AT_OR || SRC == TOK_AT_OR_MASKED;
     __shared__ float patch[16][64];
     __shared__ float W[96][17];
     __shared__ float bias[96];
     const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int P = PC ? PC : a.P, N = a.N;
-    if constexpr (SCENE) {
-        const long plane = (long)a.Hs * a.Ws;
-        const float* src = tok_window_origin<SRC>(a, b) + (long)c * P * plane;
-        WinSteps ws{};   // ORIENT: the workgroup's window, its code read once
-        if constexpr (ORIENT) ws = window_steps(a.orient[b], a.win, a.Ws);
+    const float* src = win_origin<KIND>(a.src.base, a.src, b, c, a.S, P, N);
+    if constexpr (KIND == WIN_BATCH) {   // a cube's tile is P * N contiguous floats
+        for (int i = tid; i < P * N; i += 256) patch[i / N][i % N] = src[i];
+    } else {
+        const auto plane = win_plane<KIND>(a.src, N);
+        const WinSteps ws = win_steps<KIND>(a.src, b);   // oriented: the workgroup's window, its code read once
         for (int i = tid; i < P * N; i += 256) {
             const int k = i / N, n = i % N;
-            if constexpr (ORIENT) patch[k][n] = src[k * plane + ws.start + (n / a.win) * ws.si + (n % a.win) * ws.sj];
-            else patch[k][n] = src[k * plane + (long)(n / a.win) * a.Ws + n % a.win];
+            patch[k][n] = src[win_pixel<KIND>(a.src, ws, n, k * plane)];
         }
-    } else {
-        const float* src = a.img + ((long)b * a.S + c) * P * N;
-        for (int i = tid; i < P * N; i += 256) patch[i / N][i % N] = src[i];
     }
     for (int i = tid; i < 96 * P; i += 256) W[i / P][i % P] = a.w_emb[(long)c * 96 * P + i];
     if (tid < 96) bias[tid] = a.b_emb[c * 96 + tid];
@@ -101,8 +82,8 @@ __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
     const float rstd2 = rsqrtf(v2 * (1.f / 96.f) + 1e-5f);
     const int t = c * N + n;
     bool masked;
-    if constexpr (NOMASK) masked = false;
-    else if constexpr (SRC == TOK_SCENE_MASKED) masked = scene_window_mask(a, b, c)[(long)(n / a.win) * a.Ws + n % a.win] != 0;
+    if constexpr (MASK == MASK_NONE) masked = false;
+    else if constexpr (MASK == MASK_SCENE) masked = win_scene_mask<KIND>(a.src, a.mask, b, c, a.S, n) != 0;
     else masked = a.mask[(long)b * a.T + t] != 0;
     float* dst = a.out + ((long)b * a.T + t) * 96 + part * 4;
 #pragma unroll
@@ -112,7 +93,7 @@ __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
         if (a.pos_split) pos = d < a.pos_split ? a.pos_a[n * a.pos_split + d] : a.pos_b[c * (96 - a.pos_split) + d - a.pos_split];
         else pos = a.pos_a[(long)t * 96 + d];
         const float tok = (e[i] - m2) * rstd2 * a.post_g[d] + a.post_b[d];
-        e[i] = (!NOMASK && masked ? a.mask_token[d] : tok) + pos;
+        e[i] = (MASK != MASK_NONE && masked ? a.mask_token[d] : tok) + pos;
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -122,8 +103,8 @@ __device__ __forceinline__ void tokenize_fwd_body(const TokArgs& a) {
     }
 }
 
-template <int PC, int SRC>
-__global__ __launch_bounds__(256) void tokenize_fwd_kernel(TokArgs a) { tokenize_fwd_body<PC, SRC>(a); }
+template <int PC, int KIND, int MASK>
+__global__ __launch_bounds__(256) void tokenize_fwd_kernel(TokArgs a) { tokenize_fwd_body<PC, KIND, MASK>(a); }
 
 // ------------------------------------------------------------------------------------------
 // The same tokenizer for the reference's shapes (P = 10 pixels per patch, N = 64 spatial tokens) on the fp32 matrix cores
@@ -135,18 +116,15 @@ __global__ __launch_bounds__(256) void tokenize_fwd_kernel(TokArgs a) { tokenize
 // layout), and the C layout (4 consecutive features of one token per lane) is the 16-byte store of the token row.
 // grid (S, nchunk), 256 threads: wave w <-> tokens 16 w .. + 15 of spectral block c, samples chunk, chunk + nchunk, ...
 // Position rows, bias, both LayerNorms' vectors and the mask token are tile invariant for a wave: registers / LDS.
-// SRC: the source addressing policy of tokenize_fwd_body (TOK_SCENE: windows of a scene instead of a batch of cubes, no mask;
-// TOK_SCENE_MASKED: with the scene mask; TOK_AT: windows at listed origins, one table row read per window where the next sample's
-// pixels are requested; TOK_AT_MASKED: those, and the mask byte of a batch of cubes; TOK_AT_OR*: the window's orientation code is read
-// with its table row).
+// KIND, MASK: as in tokenize_fwd_body; a listed window's table row and orientation code are read where the next sample's pixels are
+// requested.
 // ------------------------------------------------------------------------------------------
-template <int SRC>
+template <int KIND, int MASK>
 __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
-    constexpr bool SCENE = SRC != TOK_BATCH;
     constexpr int P = 10, N = 64;
     __shared__ __attribute__((aligned(16))) float vec[3][96];   // post_g | post_b | mask_token
     const int c = blockIdx.x, tid = threadIdx.x, w = tid >> 6, l = tid & 63, g = l >> 4, j = l & 15;
-    if (tid < 96) { vec[0][tid] = a.post_g[tid]; vec[1][tid] = a.post_b[tid]; vec[2][tid] = (SRC == TOK_SCENE || SRC == TOK_AT || SRC == TOK_AT_OR) ? 0.f : a.mask_token[tid]; }
+    if (tid < 96) { vec[0][tid] = a.post_g[tid]; vec[1][tid] = a.post_b[tid]; vec[2][tid] = MASK == MASK_NONE ? 0.f : a.mask_token[tid]; }
     // A fragments of W_c [96][10]: lane (i = l & 15, kq = l >> 4) holds W[16 mt + i][4 ks + kq] (zero beyond k = 9)
     float wf[6][3];
 #pragma unroll
@@ -182,22 +160,13 @@ __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
     unsigned char mk;
     auto request = [&](int b) {
         const int bc = b < a.B ? b : a.B - 1;
-        if constexpr (SCENE) {
-            const long plane = (long)a.Hs * a.Ws;
-            const float* src = tok_window_origin<SRC>(a, bc) + (long)c * P * plane;
-            if constexpr (SRC == TOK_AT_OR || SRC == TOK_AT_OR_MASKED) src += oriented_pixel(a, bc, n);
-            else src += (long)(n / a.win) * a.Ws + n % a.win;
+        const auto plane = win_plane<KIND>(a.src, N);
+        const float* src = win_origin<KIND>(a.src.base, a.src, bc, c, a.S, P, N) + win_pixel<KIND>(a.src, bc, n);
 #pragma unroll
-            for (int ks = 0; ks < 3; ++ks) { const int k = 4 * ks + g; px[ks] = src[(k < P ? k : 0) * plane]; }
-            if constexpr (SRC == TOK_SCENE_MASKED) mk = scene_window_mask(a, bc, c)[(long)(n / a.win) * a.Ws + n % a.win];
-            else if constexpr (SRC == TOK_AT_MASKED || SRC == TOK_AT_OR_MASKED) mk = a.mask[(long)bc * a.T + t];
-            else mk = 0;
-        } else {
-            const float* src = a.img + ((long)bc * a.S + c) * P * N + n;
-#pragma unroll
-            for (int ks = 0; ks < 3; ++ks) { const int k = 4 * ks + g; px[ks] = src[(k < P ? k : 0) * N]; }
-            mk = a.mask[(long)bc * a.T + t];
-        }
+        for (int ks = 0; ks < 3; ++ks) { const int k = 4 * ks + g; px[ks] = src[(k < P ? k : 0) * plane]; }
+        if constexpr (MASK == MASK_SCENE) mk = win_scene_mask<KIND>(a.src, a.mask, bc, c, a.S, n);
+        else if constexpr (MASK == MASK_TOKENS) mk = a.mask[(long)bc * a.T + t];
+        else mk = 0;
     };
     request(blockIdx.y);
     for (int b = blockIdx.y; b < a.B; b += nb) {
@@ -248,8 +217,8 @@ __device__ __forceinline__ void tokenize_fwd_mfma_body(const TokArgs& a) {
     }
 }
 
-template <int SRC>
-__global__ __launch_bounds__(256, 2) void tokenize_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<SRC>(a); }
+template <int KIND, int MASK>
+__global__ __launch_bounds__(256, 2) void tokenize_fwd_mfma_kernel(TokArgs a) { tokenize_fwd_mfma_body<KIND, MASK>(a); }
 
 // ==========================================================================================
 // fused transformer block, forward.  Reference vit_spatial_spectral.py:22-29 (PreNorm),
@@ -846,11 +815,10 @@ template __global__ void block_fwd_kernel<PBF16>(BlockArgs);
 // grid (ceil(K/64), B), 256 threads: 4 threads per masked entry, 24 features each.
 // Writes per-workgroup partial |.| sums (deterministic two-stage reduction) and
 // dpred = sign(pred - target) for the backward.
-// AT: the target source.  false: the stacked cube img [B][S*P][N]; true: the scene, at the window origins[b] (msst_head_at_fwd: HeadArgs
-// scene fields).  The grid, the thread-to-entry map and every sum are the same: equal pixels give equal bits.
-// ORIENT (with AT; msst_head_at_fwd_orient): token n is pixel n of that window in orientation a.orient[b] (window_steps).
+// KIND: where the targets lie (WinRef, msst_kernels.h): WIN_BATCH, the stacked cubes; WIN_LISTED / WIN_LISTED_ORIENTED, the scenes
+// themselves.  The grid, the thread-to-entry map and every sum are the same: equal pixels give equal bits.
 // ==========================================================================================
-template <bool AT, bool ORIENT = false>
+template <int KIND>
 __global__ __launch_bounds__(256) void head_fwd_kernel(HeadArgs a) {
     __shared__ float red[4];
     const int tid = threadIdx.x, e = tid >> 2, part = tid & 3;
@@ -869,11 +837,9 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadArgs a) {
         }
         const int wc = a.per_block ? c : 0;
         const float* Wp = a.w_pix + (long)wc * P * 96 + part * 24;
-        // AT: band 0 of the token's patch at its pixel of the window, and the floats from one band of the scene to the next
-        const long plane = AT ? (long)a.Hs * a.Ws : 0;
-        const float* tsrc = nullptr;
-        if constexpr (ORIENT) tsrc = listed_window_origin(a, b) + (long)c * P * plane + oriented_pixel(a, b, n);
-        else if constexpr (AT) tsrc = listed_window_origin(a, b) + (long)c * P * plane + (long)(n / a.win) * a.Ws + n % a.win;
+        // band 0 of the token's patch at its pixel, and the floats from one band to the next
+        const auto plane = win_plane<KIND>(a.src, a.N);
+        const float* tsrc = win_origin<KIND>(a.src.base, a.src, b, c, a.S, P, a.N) + win_pixel<KIND>(a.src, b, n);
         for (int p = 0; p < P; ++p) {
             float acc = 0.f;
 #pragma unroll
@@ -881,10 +847,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(HeadArgs a) {
             acc += __shfl_xor(acc, 1); acc += __shfl_xor(acc, 2);
             if (part == 0) {
                 const float pred = acc + a.b_pix[wc * P + p];
-                float target;
-                if constexpr (AT) target = tsrc[p * plane];
-                else target = a.img[((long)b * a.S * P + (long)c * P + p) * a.N + n];
-                const float d = pred - target;
+                const float d = pred - tsrc[p * plane];
                 lsum += fabsf(d);
                 a.dpred[((long)b * a.K + k) * P + p] = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
                 if (a.pred) a.pred[((long)b * a.K + k) * P + p] = pred;
@@ -916,35 +879,39 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* partial, 
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
-// The one kernel selection of the tokenizer forward, whatever the source (SRC, see tokenize_fwd_body): the fp32 matrix-core kernel,
-// persistent over the batch, for the reference's shapes (P = 10, N = 64), else one workgroup row per sample (grid y) with P = 10
-// unrolled or P at run time.  a.B: samples = windows of the call.  Not uniform, and kept so: a batch of cubes (TOK_BATCH) is launched
-// as given -- no early return for B < 1, no refusal of more than 65535 grid rows (the launch itself fails then) -- while the window
-// sources return at once for an empty call and refuse what the grid cannot hold.
-template <int SRC>
+// The one kernel selection of the tokenizer forward, whatever the source: the fp32 matrix-core kernel, persistent over the batch, for
+// the reference's shapes (P = 10, N = 64), else one workgroup row per sample (grid y) with P = 10 unrolled or P at run time.  Not
+// uniform, and kept so: a batch of cubes (WIN_BATCH) is launched as given -- no early return for B < 1, no refusal of more than 65535
+// grid rows (the launch itself fails then) -- while the window sources return at once for an empty call and refuse what the grid
+// cannot hold.
+template <int KIND, int MASK>
 static int launch_tokenize_fwd_src(const TokArgs& a, hipStream_t st) {
     if (a.P > 16 || a.N > 64) return MSST_ERR_UNSUPPORTED;
-    if (SRC != TOK_BATCH && a.B < 1) return 0;
+    if (KIND != WIN_BATCH && a.B < 1) return 0;
     ProfScope ps(K_TOK_FWD, st);
     if (a.P == 10 && a.N == 64) {
         int nchunk = 1024 / (a.S > 0 ? a.S : 1);
         if (nchunk < 1) nchunk = 1;
         if (nchunk > a.B) nchunk = a.B;
-        hipLaunchKernelGGL(tokenize_fwd_mfma_kernel<SRC>, dim3(a.S, nchunk), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((tokenize_fwd_mfma_kernel<KIND, MASK>), dim3(a.S, nchunk), dim3(256), 0, st, a);
     } else {
-        if (SRC != TOK_BATCH && a.B > 65535) return MSST_ERR_UNSUPPORTED;   // one workgroup row per window (grid y)
-        if (a.P == 10) hipLaunchKernelGGL((tokenize_fwd_kernel<10, SRC>), dim3(a.S, a.B), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((tokenize_fwd_kernel<0, SRC>), dim3(a.S, a.B), dim3(256), 0, st, a);
+        if (KIND != WIN_BATCH && a.B > 65535) return MSST_ERR_UNSUPPORTED;   // one workgroup row per window (grid y)
+        if (a.P == 10) hipLaunchKernelGGL((tokenize_fwd_kernel<10, KIND, MASK>), dim3(a.S, a.B), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((tokenize_fwd_kernel<0, KIND, MASK>), dim3(a.S, a.B), dim3(256), 0, st, a);
     }
     return (int)hipGetLastError();
 }
-int launch_tokenize_fwd(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_BATCH>(a, st); }
-int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_SCENE>(a, st); }
-int launch_tokenize_scene_fwd_masked(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_SCENE_MASKED>(a, st); }
-int launch_tokenize_at_fwd(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_AT>(a, st); }
-int launch_tokenize_at_fwd_masked(const TokArgs& a, hipStream_t st) { return launch_tokenize_fwd_src<TOK_AT_MASKED>(a, st); }
-int launch_tokenize_at_fwd_orient(const TokArgs& a, bool masked, hipStream_t st) {
-    return masked ? launch_tokenize_fwd_src<TOK_AT_OR_MASKED>(a, st) : launch_tokenize_fwd_src<TOK_AT_OR>(a, st);
+int launch_tokenize_fwd(const TokArgs& a, int kind, int mask, hipStream_t st) {
+    switch (kind * 3 + mask) {   // the seven instances
+    case WIN_BATCH * 3 + MASK_TOKENS: return launch_tokenize_fwd_src<WIN_BATCH, MASK_TOKENS>(a, st);
+    case WIN_GRID * 3 + MASK_NONE: return launch_tokenize_fwd_src<WIN_GRID, MASK_NONE>(a, st);
+    case WIN_GRID * 3 + MASK_SCENE: return launch_tokenize_fwd_src<WIN_GRID, MASK_SCENE>(a, st);
+    case WIN_LISTED * 3 + MASK_NONE: return launch_tokenize_fwd_src<WIN_LISTED, MASK_NONE>(a, st);
+    case WIN_LISTED * 3 + MASK_TOKENS: return launch_tokenize_fwd_src<WIN_LISTED, MASK_TOKENS>(a, st);
+    case WIN_LISTED_ORIENTED * 3 + MASK_NONE: return launch_tokenize_fwd_src<WIN_LISTED_ORIENTED, MASK_NONE>(a, st);
+    case WIN_LISTED_ORIENTED * 3 + MASK_TOKENS: return launch_tokenize_fwd_src<WIN_LISTED_ORIENTED, MASK_TOKENS>(a, st);
+    }
+    return MSST_ERR_UNSUPPORTED;   // a pair no entry point asks for: no kernel, no fall-back
 }
 
 template <class P>
@@ -1013,21 +980,26 @@ bool block_fwd_writes_xn(const BlockArgs& a, int prec) {
     return prec == MSST_PREC_BF16 && !(a.dbg & 16);   // both tuned bf16 kernels (head-per-wave for 8 heads, 4-wave otherwise) store their LN1 rows
 }
 
-template <bool AT, bool ORIENT = false>
+template <int KIND>
 static int launch_head_fwd_src(const HeadArgs& a, float* loss, hipStream_t st) {
     if (a.P > 16) return MSST_ERR_UNSUPPORTED;
     dim3 grid((a.K + 63) / 64, a.B);
     { ProfScope ps(K_HEAD_FWD, st);
-    hipLaunchKernelGGL((head_fwd_kernel<AT, ORIENT>), grid, dim3(256), 0, st, a); }
+    hipLaunchKernelGGL(head_fwd_kernel<KIND>, grid, dim3(256), 0, st, a); }
     const int np = grid.x * grid.y;
     const float scale = 1.0f / ((float)a.B * (float)a.K * (float)a.P) / (float)a.K;
     ProfScope ps(K_LOSS_REDUCE, st);
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, st, a.partial, np, scale, loss);
     return (int)hipGetLastError();
 }
-int launch_head_fwd(const HeadArgs& a, float* loss, hipStream_t st) { return launch_head_fwd_src<false>(a, loss, st); }
-int launch_head_at_fwd(const HeadArgs& a, float* loss, hipStream_t st) { return launch_head_fwd_src<true>(a, loss, st); }
-int launch_head_at_fwd_orient(const HeadArgs& a, float* loss, hipStream_t st) { return launch_head_fwd_src<true, true>(a, loss, st); }
+int launch_head_fwd(const HeadArgs& a, int kind, float* loss, hipStream_t st) {
+    switch (kind) {
+    case WIN_BATCH: return launch_head_fwd_src<WIN_BATCH>(a, loss, st);
+    case WIN_LISTED: return launch_head_fwd_src<WIN_LISTED>(a, loss, st);
+    case WIN_LISTED_ORIENTED: return launch_head_fwd_src<WIN_LISTED_ORIENTED>(a, loss, st);
+    }
+    return MSST_ERR_UNSUPPORTED;   // no grid instance: no entry point asks for one
+}
 
 }  // namespace msst
 

@@ -18,26 +18,17 @@
 
 namespace msst {
 
-// offset of sample b's window origin (scene s, band 0, row r * stride, column q * stride) in a scene [Bs][S*P][Hs][Ws]
-__device__ __forceinline__ long scene_window_offset(const TokInArgs& a, int b) {
-    const long i = a.win0 + b;
-    const long s = i / a.wps;
-    const int rem = (int)(i - s * a.wps), r = rem / a.nq, q = rem - r * a.nq;
-    return ((s * a.S * a.P) * a.Hs + (long)r * a.stride) * a.Ws + (long)q * a.stride;
-}
-
 // KC: ceil(P / 4), the 16-byte pieces of a weight row.  The [96][P] weight lies in LDS with rows of 20 floats, zero beyond P: a
 // thread reads a row as KC ds_read_b128 (tokenize_bwd_kernel: P ds_read_b32 per row and use, which is what bound it), the four
 // threads of a token read rows 4 apart = 80 floats = banks 16 apart, the 16 tokens of a wave the same addresses (broadcast).
 // thread <-> (token n = tid / 4, features 16 (i / 4) + 4 part + i % 4, i < 24): the mapping of tokenize_fwd_kernel / tokenize_bwd_kernel,
 // so a dropout group (four consecutive features) is one thread's f32x4 and has their element address.
-// SRC, the source of sample b's pixels and the place of its gradient.  TOKIN_BATCH: cube b of a batch, dimg of the batch's shape.
-// TOKIN_SCENE: window win0 + b of a scene, stored to the window's pixels of dscene (stride == window: every pixel in at most one
-// window, plain stores), no mask, no dtarget.  TOKIN_AT: the window at origins[b] of a scene (listed_window_origin), stored stacked
-// as for a batch -- dwin [B][S*P][N], plain stores; listed windows overlap, scene_fold_at_kernel below sums them; no mask, no dtarget.
-enum { TOKIN_BATCH = 0, TOKIN_SCENE = 1, TOKIN_AT = 2 };
-template <int KC, int SRC, class Args>
-__global__ __launch_bounds__(256) void tokenize_bwd_input_kernel(Args a) {
+// KIND: where sample b's pixels lie (WinRef, msst_kernels.h) and so the place of its gradient.  WIN_BATCH: dimg of the batch's shape.
+// WIN_GRID: stored in place, to the window's pixels of dscene (stride == window: every pixel in at most one window, plain stores), no
+// mask, no dtarget.  WIN_LISTED: stored stacked as for a batch -- dwin [B][S*P][N], plain stores; listed windows overlap,
+// scene_fold_at_kernel below sums them; no mask, no dtarget.
+template <int KC, int KIND>
+__global__ __launch_bounds__(256) void tokenize_bwd_input_kernel(TokInArgs a) {
     constexpr int KP = 4 * KC;
     __shared__ float patch[16][64];
     __shared__ float outp[16][64];
@@ -52,25 +43,15 @@ __global__ __launch_bounds__(256) void tokenize_bwd_input_kernel(Args a) {
     }
     if (tid < 96) { bias[tid] = a.b_emb[c * 96 + tid]; postg[tid] = a.post_g[tid]; }
     if (tid < 16) { preg[tid] = tid < P ? a.pre_g[tid] : 0.f; preb[tid] = tid < P ? a.pre_b[tid] : 0.f; }
-    long org = 0, plane = 0;
-    if constexpr (SRC == TOKIN_SCENE) {
-        plane = (long)a.Hs * a.Ws;
-        org = scene_window_offset(a, b) + (long)c * P * plane;
-        for (int i = tid; i < P * N; i += 256) {
-            const int k = i / N, nn = i - k * N;
-            patch[k][nn] = a.img[org + k * plane + (long)(nn / a.win) * a.Ws + nn % a.win];
-        }
-    } else if constexpr (SRC == TOKIN_AT) {
-        plane = (long)a.Hs * a.Ws;
-        org = ((long)b * a.S + c) * P * N;   // of the stacked store
-        const float* src = listed_window_origin(a, b) + (long)c * P * plane;
-        for (int i = tid; i < P * N; i += 256) {
-            const int k = i / N, nn = i - k * N;
-            patch[k][nn] = src[k * plane + (long)(nn / a.win) * a.Ws + nn % a.win];
-        }
+    const auto plane = win_plane<KIND>(a.src, N);
+    const float* src = win_origin<KIND>(a.src.base, a.src, b, c, a.S, P, N);
+    if constexpr (KIND == WIN_BATCH) {   // a cube's tile is P * N contiguous floats
+        for (int i = tid; i < P * N; i += 256) patch[i / N][i % N] = src[i];
     } else {
-        org = ((long)b * a.S + c) * P * N;
-        for (int i = tid; i < P * N; i += 256) patch[i / N][i % N] = a.img[org + i];
+        for (int i = tid; i < P * N; i += 256) {
+            const int k = i / N, nn = i - k * N;
+            patch[k][nn] = src[k * plane + win_pixel<KIND>(a.src, b, nn)];
+        }
     }
     __syncthreads();
     const int n = tid >> 2, part = tid & 3;
@@ -170,16 +151,19 @@ __global__ __launch_bounds__(256) void tokenize_bwd_input_kernel(Args a) {
         }
     }
     __syncthreads();
-    if constexpr (SRC == TOKIN_SCENE) {
+    if constexpr (KIND == WIN_GRID) {   // in place
+        float* dst = win_origin<KIND>(a.dimg, a.src, b, c, a.S, P, N);
         for (int i = tid; i < P * N; i += 256) {
             const int k = i / N, nn = i - k * N;
-            a.dimg[org + k * plane + (long)(nn / a.win) * a.Ws + nn % a.win] = outp[k][nn];
+            dst[k * plane + win_pixel<KIND>(a.src, b, nn)] = outp[k][nn];
         }
-    } else {
+    } else {   // stacked
+        float* dst = win_origin<WIN_BATCH>(a.dimg, a.src, b, c, a.S, P, N);
+        const long org = dst - a.dimg;
         for (int i = tid; i < P * N; i += 256) {
             float v = outp[i / N][i % N];
             if (a.dtarget) v += a.dtarget[org + i];
-            a.dimg[org + i] = v;
+            dst[i] = v;
         }
     }
 }
@@ -267,23 +251,28 @@ __global__ __launch_bounds__(256) void scene_fold_at_kernel(SceneFoldAtArgs a) {
 }
 
 // one launcher for the three sources (windows of a scene, numbered or listed: an empty call is no launch); KC = ceil(P / 4)
-template <int SRC, class Args>
-static int launch_tokenize_bwd_input_src(const Args& a, hipStream_t st) {
+template <int KIND>
+static int launch_tokenize_bwd_input_src(const TokInArgs& a, hipStream_t st) {
     if (a.P > 16 || a.N > 64 || (long)a.B * a.S > 0x7fffffffL) return MSST_ERR_UNSUPPORTED;
-    if (SRC != TOKIN_BATCH && a.B < 1) return 0;
+    if (KIND != WIN_BATCH && a.B < 1) return 0;
     ProfScope ps(K_TOK_BWD_INPUT, st);
     const dim3 grid((unsigned)((long)a.B * a.S));
     switch ((a.P + 3) / 4) {
-    case 1: hipLaunchKernelGGL((tokenize_bwd_input_kernel<1, SRC, Args>), grid, dim3(256), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((tokenize_bwd_input_kernel<2, SRC, Args>), grid, dim3(256), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((tokenize_bwd_input_kernel<3, SRC, Args>), grid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((tokenize_bwd_input_kernel<4, SRC, Args>), grid, dim3(256), 0, st, a); break;
+    case 1: hipLaunchKernelGGL((tokenize_bwd_input_kernel<1, KIND>), grid, dim3(256), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((tokenize_bwd_input_kernel<2, KIND>), grid, dim3(256), 0, st, a); break;
+    case 3: hipLaunchKernelGGL((tokenize_bwd_input_kernel<3, KIND>), grid, dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((tokenize_bwd_input_kernel<4, KIND>), grid, dim3(256), 0, st, a); break;
     }
     return (int)hipGetLastError();
 }
-int launch_tokenize_bwd_input(const TokInArgs& a, hipStream_t st) { return launch_tokenize_bwd_input_src<TOKIN_BATCH>(a, st); }
-int launch_tokenize_scene_bwd_input(const TokInArgs& a, hipStream_t st) { return launch_tokenize_bwd_input_src<TOKIN_SCENE>(a, st); }
-int launch_tokenize_at_bwd_input(const TokInAtArgs& a, hipStream_t st) { return launch_tokenize_bwd_input_src<TOKIN_AT>(a, st); }
+int launch_tokenize_bwd_input(const TokInArgs& a, int kind, hipStream_t st) {
+    switch (kind) {
+    case WIN_BATCH: return launch_tokenize_bwd_input_src<WIN_BATCH>(a, st);
+    case WIN_GRID: return launch_tokenize_bwd_input_src<WIN_GRID>(a, st);
+    case WIN_LISTED: return launch_tokenize_bwd_input_src<WIN_LISTED>(a, st);
+    }
+    return MSST_ERR_UNSUPPORTED;   // oriented input gradients: no instance
+}
 
 int launch_scene_fold_at(const SceneFoldAtArgs& a, hipStream_t st) {
     const long pixels = (long)a.Bs * a.Hs * a.Ws;

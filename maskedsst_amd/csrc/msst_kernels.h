@@ -67,49 +67,23 @@ struct StackArgs {
 };
 static_assert(sizeof(StackArgs) <= 4096, "StackArgs travels as a kernel argument");
 
-struct TokArgs {
-    const float* img;        // [B][S*P][N]
-    const float* pre_g; const float* pre_b;     // [P]
-    const float* w_emb;      // [S][96][P]
-    const float* b_emb;      // [S][96]
-    const float* post_g; const float* post_b;   // [96]
-    const float* pos_a;      // pos_split == 0: learned table [T][96]; else spatial table [N][pos_split]
-    const float* pos_b;      // pos_split != 0: spectral table [S][96 - pos_split]
-    const float* mask_token; // [96]
-    const uint8_t* mask;     // [B][T] (1 = masked); all-zero for the classification path.  TOK_SCENE_MASKED: the scene mask [Bs][S][Hs][Ws]
-    float* out;              // [B][T][96]
-    int B, S, N, T, P, pos_split;
-    Drop drop;               // embedding dropout on (token + pos) (vit_spatial_spectral.py:530), classification path only
-    // scene windows (msst_tokenize_scene_fwd / _fwd_train / _fwd_masked, the kernels' TOK_SCENE* instances only): img is a scene [Bs][S*P][Hs][Ws] and
-    // sample b is window win0 + b, row-major over (scene, window row, window column), origin (r * stride, q * stride), win x win pixels
+// Where the samples of a tokenizer or SimMIM-head launch lie: THE one description, embedded once in TokArgs, TokBwdArgs, TokInArgs and
+// HeadArgs, filled by fill_src (msst_api.hip) and read only through the win_* accessors below.  A kernel is compiled per kind:
+//   WIN_BATCH            sample b is cube b of a batch [B][C][N]; of the fields only `base` is read
+//   WIN_GRID             base is scenes [Bs][C][Hs][Ws]; sample b is window win0 + b of the grid (win, stride), row-major over (scene, window
+//                        row, window column), origin (r * stride, q * stride), win x win pixels
+//   WIN_LISTED           ... the window of scene origins[b][0] with its top-left pixel at row origins[b][1], column origins[b][2]; of the grid
+//                        fields only Hs, Ws and win are read
+//   WIN_LISTED_ORIENTED  ... that window in orientation orient[b] (window_steps): token n is pixel n of the ORIENTED window, so position row,
+//                        mask byte, dropout element and gradient row are those of the oriented copy -- only the address of the read differs
+enum { WIN_BATCH = 0, WIN_GRID = 1, WIN_LISTED = 2, WIN_LISTED_ORIENTED = 3 };
+struct WinRef {
+    const float* base;       // the batch, or the scenes
     long win0;
     int Hs, Ws, win, stride, nq, wps;   // nq: windows per window row, wps: windows per scene
-    // listed origins (msst_tokenize_at_fwd / _at_fwd_masked, the kernels' TOK_AT* instances only): sample b is the win x win window of scene
-    // origins[b][0] with its top-left pixel at row origins[b][1], column origins[b][2]; of the scene fields only Hs, Ws and win are read.
-    // TOK_AT_MASKED: mask is [B][T] in window coordinates, as for a batch of cubes
     const int32_t* origins;  // [B][3]
-    // oriented listed windows (msst_tokenize_at_fwd_orient / _at_fwd_masked_orient, the kernels' TOK_AT_OR* instances only): sample b is that
-    // window in orientation orient[b] (window_steps); position table, mask and dropout see the oriented window.  Unread by the others
     const uint8_t* orient;   // [B], codes 0 .. 7
 };
-
-// img pointer of sample b's window origin (scene s, band 0, row r * stride, column q * stride); 64-bit: scenes may be large
-// (Args: TokArgs or TokSceneBwdArgs, the same scene fields)
-template <class Args>
-__device__ __forceinline__ const float* scene_window_origin(const Args& a, int b) {
-    const long i = a.win0 + b;
-    const long s = i / a.wps;
-    const int rem = (int)(i - s * a.wps), r = rem / a.nq, q = rem - r * a.nq;
-    return a.img + ((s * a.S * a.P) * a.Hs + (long)r * a.stride) * a.Ws + (long)q * a.stride;
-}
-
-// the same pointer with the origin read from a table [B][3] of (scene, y0, x0) (Args: TokArgs or TokAtBwdArgs); one 12-byte read per call
-template <class Args>
-__device__ __forceinline__ const float* listed_window_origin(const Args& a, int b) {
-    const int32_t* o = a.origins + 3 * (long)b;
-    const long s = o[0];
-    return a.img + ((s * a.S * a.P) * a.Hs + (long)o[1]) * a.Ws + (long)o[2];
-}
 
 // An orientation code o = k + 4 f (k in 0 .. 3, f in 0 .. 1) names one of the eight symmetries of a win x win window w: flipped left to
 // right when f, then turned k quarter turns counter-clockwise -- torch.rot90(torch.flip(w, (-1,)) if f else w, k, (-2, -1)).  It is a
@@ -125,21 +99,77 @@ __device__ __forceinline__ WinSteps window_steps(int o, int win, int Ws) {
     if (o & 4) { x0 = m - x0; xi = -xi; xj = -xj; }   // the flip: x -> m - x
     return WinSteps{y0 * Ws + x0, yi * Ws + xi, yj * Ws + xj};
 }
-// floats from the origin of sample b's window to pixel n = i * win + j of it in its orientation (Args: orient, win, Ws)
-template <class Args>
-__device__ __forceinline__ long oriented_pixel(const Args& a, int b, int n) {
-    const WinSteps w = window_steps(a.orient[b], a.win, a.Ws);
-    return (long)w.start + (long)(n / a.win) * w.si + (long)(n % a.win) * w.sj;
+
+// floats from one plane (band) of a sample to the next; N: pixels per sample (a batch's planes are N floats, and an int)
+template <int KIND>
+__device__ __forceinline__ auto win_plane(const WinRef& w, int N) {
+    if constexpr (KIND == WIN_BATCH) return N;
+    else return (long)w.Hs * w.Ws;
+}
+// the first band of spectral block c of sample b, at its window's first pixel, in a tensor at `base` laid out like the source: S
+// blocks of P bands per cube or scene (the pixels: w.base, S, P; a gradient of their shape; a scene mask [Bs][S][Hs][Ws]: P = 1).
+// 64-bit: scenes may be large.  A listed window costs one 12-byte read of its table row
+template <int KIND, class T>
+__device__ __forceinline__ T* win_origin(T* base, const WinRef& w, int b, int c, int S, int P, int N) {
+    if constexpr (KIND == WIN_BATCH) return base + ((long)b * S + c) * P * N;
+    else {
+        long s, y0, x0;
+        if constexpr (KIND == WIN_GRID) {
+            const long i = w.win0 + b;
+            s = i / w.wps;
+            const int rem = (int)(i - s * w.wps), r = rem / w.nq, q = rem - r * w.nq;
+            y0 = (long)r * w.stride; x0 = (long)q * w.stride;
+        } else {
+            const int32_t* o = w.origins + 3 * (long)b;
+            s = o[0]; y0 = o[1]; x0 = o[2];
+        }
+        return base + (((s * S * P) * w.Hs + y0) * w.Ws + x0) + (long)c * P * win_plane<KIND>(w, N);
+    }
+}
+// the orientation of sample b's window (oriented kind only): a workgroup that stays on one window reads it once
+template <int KIND>
+__device__ __forceinline__ WinSteps win_steps(const WinRef& w, int b) {
+    if constexpr (KIND == WIN_LISTED_ORIENTED) return window_steps(w.orient[b], w.win, w.Ws);
+    else return WinSteps{};
+}
+// `from` plus the floats from the first pixel of a window to its pixel n = i * win + j, for a workgroup that stays on the window and
+// has read its orientation once (ws: win_steps of the window).  Oriented: 32-bit products (at most 8 Ws), added to `from` left to right
+template <int KIND>
+__device__ __forceinline__ long win_pixel(const WinRef& w, const WinSteps& ws, int n, long from = 0) {
+    if constexpr (KIND == WIN_BATCH) return from + n;
+    else if constexpr (KIND == WIN_LISTED_ORIENTED) return from + ws.start + (n / w.win) * ws.si + (n % w.win) * ws.sj;
+    else return from + (long)(n / w.win) * w.Ws + n % w.win;
+}
+// the same for a lane that meets window b once and reads its orientation itself (64-bit products, as these callers always compiled)
+template <int KIND>
+__device__ __forceinline__ long win_pixel(const WinRef& w, int b, int n) {
+    if constexpr (KIND == WIN_LISTED_ORIENTED) {
+        const WinSteps ws = win_steps<KIND>(w, b);
+        return (long)ws.start + (long)(n / w.win) * ws.si + (long)(n % w.win) * ws.sj;
+    } else return win_pixel<KIND>(w, WinSteps{}, n);
+}
+// the byte of token (c, n) of sample b's window in a scene mask [Bs][S][Hs][Ws]: one byte per spectral block and pixel
+template <int KIND>
+__device__ __forceinline__ uint8_t win_scene_mask(const WinRef& w, const uint8_t* mask, int b, int c, int S, int n) {
+    return win_origin<KIND>(mask, w, b, c, S, 1, 0)[win_pixel<KIND>(w, b, n)];
 }
 
-// mask byte of token (c, n = 0) of sample b's window in a scene mask [Bs][S][Hs][Ws] (TOK_SCENE_MASKED: TokArgs.mask): one byte per
-// spectral block and pixel; token (c, n) is (n / win) * Ws + n % win further
-__device__ __forceinline__ const uint8_t* scene_window_mask(const TokArgs& a, int b, int c) {
-    const long i = a.win0 + b;
-    const long s = i / a.wps;
-    const int rem = (int)(i - s * a.wps), r = rem / a.nq, q = rem - r * a.nq;
-    return a.mask + (((s * a.S + c) * a.Hs) + (long)r * a.stride) * a.Ws + (long)q * a.stride;
-}
+// mask policy of the tokenizer forward: nothing masked; a.mask [B][T] in sample coordinates; a.mask a scene mask [Bs][S][Hs][Ws]
+enum { MASK_NONE = 0, MASK_TOKENS = 1, MASK_SCENE = 2 };
+struct TokArgs {
+    WinRef src;              // the pixels: [B][S*P][N], or windows of scenes
+    const float* pre_g; const float* pre_b;     // [P]
+    const float* w_emb;      // [S][96][P]
+    const float* b_emb;      // [S][96]
+    const float* post_g; const float* post_b;   // [96]
+    const float* pos_a;      // pos_split == 0: learned table [T][96]; else spatial table [N][pos_split]
+    const float* pos_b;      // pos_split != 0: spectral table [S][96 - pos_split]
+    const float* mask_token; // [96]
+    const uint8_t* mask;     // MASK_TOKENS: [B][T] (1 = masked), all-zero for the classification path; MASK_SCENE: [Bs][S][Hs][Ws]
+    float* out;              // [B][T][96]
+    int B, S, N, T, P, pos_split;   // B: samples = windows of the call
+    Drop drop;               // embedding dropout on (token + pos) (vit_spatial_spectral.py:530), classification path only
+};
 
 // the windows covering pixel (y, x) of a scene: window rows rlo .. rhi and columns qlo .. qhi of the grid (Args: win, stride, nr, nq);
 // false when no window covers it
@@ -174,8 +204,8 @@ struct SceneArgs : SceneGrid {
 int launch_scene_finalize(const SceneArgs& a, hipStream_t st);
 
 struct HeadArgs {
+    WinRef src;          // the targets: [B][S*P][N], or listed windows of scenes (plain or oriented)
     const float* y;      // [B][T][96] encoder output
-    const float* img;    // [B][S*P][N]
     const int* idx;      // [B][K] masked token indices
     const float* w_pix;  // [S or 1][P][96]
     const float* b_pix;  // [S or 1][P]
@@ -183,12 +213,6 @@ struct HeadArgs {
     float* pred;         // optional [B][K][P]
     float* partial;      // [B * ceil(K/64)]
     int B, S, N, T, P, K, per_block;
-    // msst_head_at_fwd (head_fwd_kernel<true> only): img is a scene [Bs][S*P][Hs][Ws] and sample b's target the win x win window at
-    // origins[b] = (scene, y0, x0) (listed_window_origin)
-    const int32_t* origins;  // [B][3]
-    int Hs, Ws, win;
-    // msst_head_at_fwd_orient (head_fwd_kernel<HEAD_AT_OR> only): the target is that window in orientation orient[b] (window_steps)
-    const uint8_t* orient;   // [B], codes 0 .. 7
 };
 
 struct HeadBwdArgs {
@@ -257,45 +281,26 @@ struct LnMlpArgs {
 };
 
 struct TokBwdArgs {
-    const float* img; const float* pre_g; const float* pre_b; const float* w_emb; const float* b_emb;
-    const float* post_g; const float* post_b; const uint8_t* mask; const float* dx0; float* slab;
+    WinRef src;
+    const float* pre_g; const float* pre_b; const float* w_emb; const float* b_emb;
+    const float* post_g; const float* post_b;
+    const uint8_t* mask;     // [B][T] in sample coordinates; a window source may pass none (nothing masked)
+    const float* dx0; float* slab;
     int B, S, N, T, P;
     Drop drop;
 };
-// msst_tokenize_scene_bwd (the kernels' SCENE = true instances): img is a scene, sample b its window win0 + b -- the scene fields of TokArgs
-struct TokSceneBwdArgs : TokBwdArgs {
-    long win0;
-    int Hs, Ws, win, stride, nq, wps;
-};
-// msst_tokenize_at_bwd / _at_bwd_masked (SCENE = true instances over this type): sample b is the window at origins[b] = (scene, y0, x0),
-// TokArgs.origins; mask null (nothing masked) or [B][T] in window coordinates
-struct TokAtBwdArgs : TokSceneBwdArgs {
-    const int32_t* origins;   // [B][3]
-};
-__device__ __forceinline__ const float* scene_window_origin(const TokAtBwdArgs& a, int b) { return listed_window_origin(a, b); }
-// msst_tokenize_at_bwd_orient / _at_bwd_masked_orient: those windows, each in orientation orient[b] (window_steps); a type of its own, so
-// that its instances of the kernels stand beside the un-oriented ones
-struct TokAtOrBwdArgs : TokAtBwdArgs {
-    const uint8_t* orient;    // [B], codes 0 .. 7
-};
-__device__ __forceinline__ const float* scene_window_origin(const TokAtOrBwdArgs& a, int b) { return listed_window_origin(a, b); }
 
-// msst_input_grad.hip (msst_tokenize_bwd_input, msst_tokenize_scene_bwd_input, msst_tokenize_at_bwd_input): d(loss)/d(img) from dx0
+// msst_input_grad.hip: d(loss)/d(img) from dx0
 struct TokInArgs {
-    const float* img; const float* pre_g; const float* pre_b; const float* w_emb; const float* b_emb;
+    WinRef src;
+    const float* pre_g; const float* pre_b; const float* w_emb; const float* b_emb;
     const float* post_g; const float* post_b;
     const uint8_t* mask;     // optional [B][T] (1 = masked)
     const float* dx0;        // [B][T][96]
     const float* dtarget;    // optional [B][S*P][N], added before the store
-    float* dimg;             // [B][S*P][N]; the scene instances: dscene [Bs][S*P][Hs][Ws]
+    float* dimg;             // [B][S*P][N], stacked (WIN_BATCH, WIN_LISTED); WIN_GRID: dscene [Bs][S*P][Hs][Ws], stored in place
     int B, S, N, T, P;
     Drop drop;
-    long win0;               // scene instances: the scene fields of TokArgs (img is the scene, sample b its window win0 + b)
-    int Hs, Ws, win, stride, nq, wps;
-};
-// msst_tokenize_at_bwd_input: sample b is the window at origins[b] = (scene, y0, x0) (TokArgs.origins); dimg is dwin [B][S*P][N], stacked
-struct TokInAtArgs : TokInArgs {
-    const int32_t* origins;   // [B][3]
 };
 // msst_scene_fold_at: dwin [nwin][C][win * win] of windows at listed origins, summed per pixel into dscene [Bs][C][Hs][Ws] through the
 // inverse index cell_ptr [Bs Hs Ws + 1] / cell_win [nwin] over origin cells (scene_fold_at_kernel, msst_input_grad.hip)
@@ -303,9 +308,7 @@ struct SceneFoldAtArgs {
     const float* dwin; const int32_t* cell_ptr; const int32_t* cell_win; float* dscene;
     int Bs, C, Hs, Ws, win, nwin, group, accumulate;
 };
-int launch_tokenize_bwd_input(const TokInArgs& a, hipStream_t st);
-int launch_tokenize_scene_bwd_input(const TokInArgs& a, hipStream_t st);
-int launch_tokenize_at_bwd_input(const TokInAtArgs& a, hipStream_t st);
+int launch_tokenize_bwd_input(const TokInArgs& a, int kind, hipStream_t st);   // kind: WIN_BATCH, WIN_GRID or WIN_LISTED
 int launch_scene_fold_at(const SceneFoldAtArgs& a, hipStream_t st);
 int launch_scene_border_zero(float* dscene, long rows, int Hs, int Ws, int rows_in, int cols_in, hipStream_t st);
 int launch_head_bwd_target(const float* dpred, const int* csr_ptr, const int* csr_pos, const float* gout, float gscale, float* dtarget,
@@ -365,12 +368,8 @@ int launch_pix_head_bwd(const PixHeadArgs& a, hipStream_t st);
 int launch_scene_centre_scatter(const SceneArgs& a, hipStream_t st);   // SceneArgs.win_logits: [nwin][NC]
 int launch_scene_centre_fill(const SceneArgs& a, hipStream_t st);
 
-int launch_tokenize_fwd(const TokArgs& a, hipStream_t st);
-int launch_tokenize_scene_fwd(const TokArgs& a, hipStream_t st);   // the same kernels reading windows of a scene (TokArgs scene fields)
-int launch_tokenize_scene_fwd_masked(const TokArgs& a, hipStream_t st);   // ... with a scene mask (a.mask [Bs][S][Hs][Ws]) and the mask token
-int launch_tokenize_at_fwd(const TokArgs& a, hipStream_t st);      // ... reading the windows listed in a.origins (no mask)
-int launch_tokenize_at_fwd_orient(const TokArgs& a, bool masked, hipStream_t st);   // ... each in orientation a.orient[b] (masked: a.mask [B][T])
-int launch_tokenize_at_fwd_masked(const TokArgs& a, hipStream_t st);   // ... with a per-window token mask (a.mask [B][T]) and the mask token
+// the seven (kind, mask) pairs that exist: (WIN_BATCH, MASK_TOKENS), (WIN_GRID, MASK_NONE / MASK_SCENE), (WIN_LISTED*, MASK_NONE / MASK_TOKENS)
+int launch_tokenize_fwd(const TokArgs& a, int kind, int mask, hipStream_t st);
 int launch_head_bwd(const HeadBwdArgs& a, int nchunk, hipStream_t st);
 // One reduction segment: dst[(i / row_len) * row_stride + i % row_len] = sum_{k < nslab} src[k * slab_stride + i], i < n
 struct RSeg {
@@ -412,10 +411,7 @@ int launch_block_bwd_attn_r3(const AttnBwdArgs& a, int nchunk, hipStream_t st); 
 int launch_block_bwd_attn_r4(const AttnBwdArgs& a, int nchunk, hipStream_t st);     // msst_bwd4.hip (the same, two heads per workgroup half a tile apart)
 int launch_block_bwd_ln1(const Ln1BwdArgs& a, int grid, int prec, hipStream_t st);
 int launch_block_bwd_ln1mlp(const LnMlpArgs& a, int grid, hipStream_t st);   // msst_bwd5.hip (bf16: LN1 backward of block i + MLP backward of block i - 1)
-int launch_tokenize_bwd(const TokBwdArgs& a, int nchunk, hipStream_t st);
-int launch_tokenize_scene_bwd(const TokSceneBwdArgs& a, int nchunk, hipStream_t st);   // the same kernels reading windows of a scene (no mask)
-int launch_tokenize_at_bwd(const TokAtBwdArgs& a, int nchunk, hipStream_t st);   // ... reading the windows listed in a.origins (a.mask optional)
-int launch_tokenize_at_bwd_orient(const TokAtOrBwdArgs& a, int nchunk, hipStream_t st);   // ... each in orientation a.orient[b]
+int launch_tokenize_bwd(const TokBwdArgs& a, int kind, int nchunk, hipStream_t st);
 int launch_pos_split(const float* dpos, int S, int N, int split, float* dpe, float* dce, hipStream_t st);
 int launch_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                  float wd, int step, float clamp, float gscale, hipStream_t st);
@@ -460,9 +456,7 @@ int block_fwd_stack_max_steps();
 int launch_block_fwd(const BlockArgs& a, int prec, hipStream_t st);
 bool block_fwd_writes_xn(const BlockArgs& a, int prec);   // does the kernel launch_block_fwd selects honour a.xn_out?
 bool block_fwd_writes_lse(const BlockArgs& a, int prec);  // ... a.lse_out?  (the role-split kernel: bf16, 8 heads, no selection flags)
-int launch_head_fwd(const HeadArgs& a, float* loss, hipStream_t st);
-int launch_head_at_fwd(const HeadArgs& a, float* loss, hipStream_t st);   // the same kernel, targets read from the scene at a.origins
-int launch_head_at_fwd_orient(const HeadArgs& a, float* loss, hipStream_t st);   // ... from the windows in orientation a.orient[b]
+int launch_head_fwd(const HeadArgs& a, int kind, float* loss, hipStream_t st);   // kind: WIN_BATCH, WIN_LISTED or WIN_LISTED_ORIENTED
 // msst_ln.hip: stand-alone LayerNorm over the last axis (D <= 128; D = 96 vectorised)
 int launch_layernorm_fwd(const float* x, const float* g, const float* b, float* y, float* mean, float* rstd, long rows, int D,
                          float eps, hipStream_t st);
