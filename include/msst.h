@@ -75,8 +75,8 @@ typedef struct MsstPrepJob {
     const float* src; /* [rows][cols] fp32 master weight          */
     void* dst;        /* [rows][cols] or [cols][rows] (transpose) */
     int32_t rows, cols, transpose;
-    int32_t pack;     /* bf16 only: 0 = 16-row x 32-k operand fragments (16x16x32 MFMA), 1 = 32-row x 16-k fragments (32x32x16 MFMA;
-                         destination rows % 32 == 0 and k % 16 == 0); + MSST_PREP_HALF (256, MSST_VERSION 104): the destination
+    int32_t pack;     /* bf16 only: 0 = 16-row x 32-k operand fragments (16x16x32 MFMA; destination rows % 16 == 0 and k % 32 == 0),
+                         1 = 32-row x 16-k fragments (32x32x16 MFMA; destination rows % 32 == 0 and k % 16 == 0); + MSST_PREP_HALF (256, MSST_VERSION 104): the destination
                          elements are IEEE half instead of bf16 (same fragment layout; the fp16-operand forward, MSST_FWD_HALF).
                          Any other value: the job is skipped. */
     int32_t scale_rows; /* the first scale_rows SOURCE rows are multiplied by `scale` (0: none).  The round-3 attention backward   */
@@ -87,9 +87,10 @@ typedef struct MsstPrepJob {
 /* Converts / transposes all matrices of the model into operand layout in ONE launch.
  * `jobs` is a DEVICE array. max_elems = max(rows*cols) over jobs.  job_bytes = sizeof(MsstPrepJob) of the CALLER's header: a
  * table laid out by another revision is refused (MSST_ERR_BADARG) instead of being read mis-strided.  err_flag (optional, one
- * zeroed int32 in device memory): the kernel ORs in 1 for a job with a bad pack / shape and 2 for a pack = 1 job that is not
- * whole fragments -- such jobs are skipped, their destinations stay unwritten; the host cannot see the table, so a caller
- * that builds it should read the word back once after its first call. */
+ * zeroed int32 in device memory): the kernel ORs in 1 for a job with a bad pack / shape and 2 for a bf16 / half job whose
+ * destination is not whole fragments (pack = 0: destination rows % 16 == 0 and k % 32 == 0; pack = 1: rows % 32 == 0 and
+ * k % 16 == 0; fp32 destinations take any shape) -- such jobs are skipped, their destinations stay unwritten; the host cannot
+ * see the table, so a caller that builds it should read the word back once after its first call. */
 int msst_prep_weights(const MsstPrepJob* jobs, int njobs, int job_bytes, int max_elems, int prec, int32_t* err_flag, void* stream);
 
 /* Operand-layout weights of one transformer block (device pointers).

@@ -26,14 +26,17 @@ template <class E>
 __global__ __launch_bounds__(256) void prep_weights_kernel(const MsstPrepJob* jobs, int* err_flag) {
     const MsstPrepJob j = jobs[blockIdx.y];
     // malformed jobs are skipped (the job table lives in device memory: the host entry point cannot validate it) and reported
-    // through the caller's error word: bit 0 = bad pack / shape, bit 1 = pack 1 on a shape that is not whole 32 x 16 fragments
+    // through the caller's error word: 1 = bad pack / shape, 2 = a 2-byte destination that is not whole fragments (16 x 32 for
+    // pack 0, 32 x 16 for pack 1)
     const bool half = sizeof(E) == 2 && (j.pack & MSST_PREP_HALF);   // destination elements IEEE half instead of bf16 (the fp16-operand forward)
     if (j.pack < 0 || (j.pack & ~MSST_PREP_HALF) > 1 || (sizeof(E) != 2 && (j.pack & MSST_PREP_HALF)) || j.rows < 1 || j.cols < 1) {
         if (err_flag && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(err_flag, 1);
         return;
     }
     const int pack = j.pack & 1;
-    if (sizeof(E) == 2 && pack == 1 && (((j.transpose ? j.cols : j.rows) & 31) || ((j.transpose ? j.rows : j.cols) & 15))) {
+    const int R = j.transpose ? j.cols : j.rows, K = j.transpose ? j.rows : j.cols;   // logical [R][K] destination
+    const int RB = pack ? 32 : 16, KB = pack ? 16 : 32;                               // fragment = RB rows x KB k, lane = (k / 8) * RB + row
+    if (sizeof(E) == 2 && ((R % RB) || (K % KB))) {
         if (err_flag && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(err_flag, 2);
         return;
     }
@@ -42,55 +45,34 @@ __global__ __launch_bounds__(256) void prep_weights_kernel(const MsstPrepJob* jo
     if constexpr (sizeof(E) == 2) {
         // bf16: a thread writes the 8 consecutive k of one lane of one fragment -- 16 bytes of the fragment-packed destination
         // (see PBF16::ld_w; round 4: one 16-byte store instead of eight 2-byte ones, 55 -> see DESIGN us for the launch)
-        const int R = j.transpose ? j.cols : j.rows, K = j.transpose ? j.rows : j.cols;   // logical [R][K] destination
-        if ((K & 7) == 0) {
-            const int RB = pack ? 32 : 16, KB = pack ? 16 : 32;   // fragment = RB rows x KB k, lane = (k / 8) * RB + row
-            if ((R % RB) == 0 && (K % KB) == 0) {
-                for (int i8 = blockIdx.x * 256 + threadIdx.x; i8 < n / 8; i8 += gridDim.x * 256) {
-                    const int f = i8 / 64, lane = i8 - f * 64;
-                    const int fr = f / (K / KB), fk = f - fr * (K / KB);
-                    const int r = fr * RB + (lane % RB), c0 = fk * KB + (lane / RB) * 8;
-                    s16x8 o;
+        for (int i8 = blockIdx.x * 256 + threadIdx.x; i8 < n / 8; i8 += gridDim.x * 256) {
+            const int f = i8 / 64, lane = i8 - f * 64;
+            const int fr = f / (K / KB), fk = f - fr * (K / KB);
+            const int r = fr * RB + (lane % RB), c0 = fk * KB + (lane / RB) * 8;
+            s16x8 o;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const int c = c0 + e;
-                        const int src_i = j.transpose ? c * j.cols + r : r * j.cols + c;   // dst[r][c] = src[c][r] when transposed
-                        float v = j.src[src_i];
-                        if (src_i / j.cols < j.scale_rows) v *= j.scale;
-                        o[e] = (short)(half ? f2h(v) : f2bf(v));
-                    }
-                    *reinterpret_cast<s16x8*>(dst + (long)i8 * 8) = o;
-                }
-                return;
+            for (int e = 0; e < 8; ++e) {
+                const int c = c0 + e;
+                const int src_i = j.transpose ? c * j.cols + r : r * j.cols + c;   // dst[r][c] = src[c][r] when transposed
+                float v = j.src[src_i];
+                // to_qkv^T for the round-3 attention backward: the q and k blocks (the first scale_rows source rows) carry the softmax
+                // scale dim_head^-0.5 = 2^-3, exact in bf16 -- that kernel keeps dq / dk unscaled (reference vit_spatial_spectral.py:54,71)
+                if (src_i / j.cols < j.scale_rows) v *= j.scale;
+                o[e] = (short)(half ? f2h(v) : f2bf(v));
             }
+            *reinterpret_cast<s16x8*>(dst + (long)i8 * 8) = o;
         }
-    }
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        // i indexes the destination (coalesced writes)
-        int src_i = i;
-        if (j.transpose) {
-            const int c = i / j.rows, r = i - c * j.rows;  // dst[c][r] = src[r][c]
-            src_i = r * j.cols + c;
-        }
-        float v = j.src[src_i];
-        // to_qkv^T for the round-3 attention backward: the q and k blocks (the first scale_rows source rows) carry the softmax scale
-        // dim_head^-0.5 = 2^-3, exact in bf16 -- that kernel keeps dq / dk unscaled (reference vit_spatial_spectral.py:54,71)
-        if (src_i / j.cols < j.scale_rows) v *= j.scale;
-        if constexpr (sizeof(E) == 4) {
+    } else {
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+            // i indexes the destination (coalesced writes)
+            int src_i = i;
+            if (j.transpose) {
+                const int c = i / j.rows, r = i - c * j.rows;  // dst[c][r] = src[r][c]
+                src_i = r * j.cols + c;
+            }
+            float v = j.src[src_i];
+            if (src_i / j.cols < j.scale_rows) v *= j.scale;
             dst[i] = v;
-        } else {
-            // fragment-packed destination (see PBF16::ld_w): logical (r, c) of the [R][K] destination matrix
-            const int K = j.transpose ? j.rows : j.cols;
-            const int r = i / K, c = i - r * K;
-            if (pack >= 1) {   // 32 rows x 16 k per fragment (v_mfma_f32_32x32x16_bf16 operand: lane = row % 32 + 32 (k % 16 / 8))
-                const int f = (r >> 5) * (K >> 4) + (c >> 4);
-                const int lane = ((c & 15) >> 3) * 32 + (r & 31);
-                dst[((long)f * 64 + lane) * 8 + (c & 7)] = half ? f2h(v) : f2bf(v);
-            } else {
-                const int f = (r >> 4) * (K >> 5) + (c >> 5);
-                const int lane = ((c & 31) >> 3) * 16 + (r & 15);
-                dst[((long)f * 64 + lane) * 8 + (c & 7)] = half ? f2h(v) : f2bf(v);
-            }
         }
     }
 }

@@ -391,7 +391,7 @@ __global__ __launch_bounds__(256, 2) void block_bwd_attn_r3_kernel(AttnBwdArgs a
                 }
                 delta = colgroup_sum(delta);
                 // dS WITHOUT the softmax scale (dim_head^-0.5 = 2^-3, exact in bf16): it is folded into the q / k blocks of the
-                // phase-4 weights (msst_prep_weights, pack = 2) and into the dWq / dWk slabs at the end of the kernel
+                // phase-4 weights (msst_prep_weights: MsstPrepJob.scale_rows / scale of wqkvT32) and into the dWq / dWk slabs at the end of the kernel
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     if (!on(t)) { lds_w64(sm, R3_DS + (L8 ^ (t << 5)), s16x4{0, 0, 0, 0}); continue; }

@@ -613,7 +613,7 @@ __global__ __launch_bounds__(512, 1) void block_bwd_attn_r4_kernel(AttnBwdArgs a
                 }
                 float delta = -colgroup_sum((dsum[0] + dsum[1]) + (dsum[2] + dsum[3]));
                 // dS WITHOUT the softmax scale (dim_head^-0.5 = 2^-3, exact in bf16): it is folded into the q / k blocks of the
-                // phase-4 weights (msst_prep_weights, pack = 2) and into the dWq / dWk slabs at the end of the kernel
+                // phase-4 weights (msst_prep_weights: MsstPrepJob.scale_rows / scale of wqkvT32) and into the dWq / dWk slabs at the end of the kernel
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     if (!on(t)) { lds_w64(sm, R3_DS + (L8 ^ (t << 5)), s16x4{0, 0, 0, 0}); continue; }
