@@ -78,41 +78,43 @@ def qkv_scale_of(L):
     return 4 if (L // 2) % 2 else 1        # decorrelated from the parity of L (which picks N) -- half the lengths peaky
 
 
-def pick_B(per_b, L, tokens_per_b, partial=True, min_tokens=256):
-    """batch: at least two tiles, >= min_tokens tokens and (partial) the last tile partly filled whenever a tile holds more than one
-    sequence"""
+def pick_B(per_b, L, tokens_per_b, partial=True, min_tokens=256, min_tiles=2):
+    """batch: at least min_tiles attention tiles (64 // L whole sequences each) and min_tiles 64-row tiles of the row-local kernels,
+    >= min_tokens tokens and (partial) the last attention tile partly filled whenever a tile holds more than one sequence.  (The
+    defaults ask for two attention tiles; their 256 tokens are four row tiles.)"""
     TS = 64 // L
     assert not (partial and TS > 1 and per_b % TS == 0), (per_b, L)   # every batch would fill its last tile
     B = 1
-    while not (B * per_b > TS and (not partial or TS == 1 or (B * per_b) % TS) and B * tokens_per_b >= min_tokens):
+    while not (-(-(B * per_b) // TS) >= min_tiles and -(-(B * tokens_per_b) // 64) >= min_tiles
+               and (not partial or TS == 1 or (B * per_b) % TS) and B * tokens_per_b >= min_tokens):
         B += 1
     return B
 
 
-def spectral_cfg(S, heads, partial=True):
+def spectral_cfg(S, heads, partial=True, **size):
     """N = 4 (sequence bases by shift) for even S, N = 9 (by division) for odd S -- unless N sequences fill whole tiles
-    (TS = 2: no power of two can end partly filled; TS = 3, 4, 9): then the other one"""
+    (TS = 2: no power of two can end partly filled; TS = 3, 4, 9): then the other one.  size: pick_B's min_tokens / min_tiles"""
     P = OTHER_P.get(S, 10)
     TS = 64 // S
     N = 4 if S % 2 == 0 else 9
     if partial and TS > 1 and N % TS == 0:
         N = 13 - N
     side = int(round(N ** 0.5))
-    B = pick_B(N, S, S * N, partial)
+    B = pick_B(N, S, S * N, partial, **size)
     return dict(bands=P * S, spectral_patch=P, image_size=side, depth=1, B=B, heads=heads, mask_patch_size=1,
                 qkv_scale=qkv_scale_of(S))
 
 
-def spatial_cfg(side, heads):
+def spatial_cfg(side, heads, **size):
     """peaky rows at the odd sides (1, 3, 5, 7), plain ones at the even sides"""
     N = side * side
-    B = pick_B(SPATIAL_S, N, SPATIAL_S * N)
+    B = pick_B(SPATIAL_S, N, SPATIAL_S * N, **size)
     return dict(bands=10 * SPATIAL_S, spectral_patch=10, image_size=side, depth=1, B=B, heads=heads, mask_patch_size=1,
                 qkv_scale=4 if side % 2 else 1)
 
 
-def case_cfg(mode, L, heads, partial=True):
-    return spatial_cfg(int(round(L ** 0.5)), heads) if mode == 0 else spectral_cfg(L, heads, partial)
+def case_cfg(mode, L, heads, partial=True, **size):
+    return spatial_cfg(int(round(L ** 0.5)), heads, **size) if mode == 0 else spectral_cfg(L, heads, partial, **size)
 
 
 def tokens_with_offsets(B, S, N, mode, seed):
@@ -167,19 +169,39 @@ def check_saved_statistics(eng, params, x, x1, i, mode, B, S, N, qkv_scale):
     return e_lse, e_rstd
 
 
-def run_block(model, params, eng, cfg, i, prec, drop=None, stats=False):
-    """block i of the depth-1 model: kernels vs float64 autograd on the same x and dy -> dict of errors"""
+def block_inputs(cfg, S, N, i):
+    """block i's input x (offsets per sequence of its mode) and output gradient dy, on the host"""
+    x = tokens_with_offsets(cfg["B"], S, N, 0 if i == 0 else 1, seed=1000 + i)
+    dy = torch.randn(x.shape, generator=torch.Generator().manual_seed(2000 + i))
+    return x, dy
+
+
+def block_reference(params, cfg, S, N, i, x, dy, drop=None):
+    """oracle.model.block on float64 copies of block i's parameters, with the kernels' dropout masks -> the increment y - x, dx - dy
+    (token order of x) and the parameter gradients by name"""
     import oracle.model as om
     from dropout import block_masks
     B, H = cfg["B"], cfg["heads"]
-    S, N = eng.S, eng.N
     mode = 0 if i == 0 else 1
     drop = drop or (0.0, 0)
-    x = tokens_with_offsets(B, S, N, mode, seed=1000 + i)
-    dy = torch.randn(x.shape, generator=torch.Generator().manual_seed(2000 + i))
+    pre = block_prefix(i)
+    p64 = {k: v.double().requires_grad_(True) for k, v in params.items() if k.startswith(pre)}
+    xs = to_seq(x.double(), mode, B, S, N).requires_grad_(True)
+    masks = None
+    if drop[0]:
+        masks = {k: v.double() for k, v in block_masks(drop[0], drop[1], i, mode, B, S, N, H).items()}
+    y = om.block(xs, p64, pre, H, masks)
+    y.backward(to_seq(dy.double(), mode, B, S, N))
+    return dict(inc=from_seq(y.detach(), mode, B, S, N) - x.double(), dxi=from_seq(xs.grad, mode, B, S, N) - dy.double(),
+                grads={k: v.grad for k, v in p64.items()})
+
+
+def block_kernels(eng, cfg, i, prec, xc, dyc, drop=None, ws=None):
+    """block i's forward (_fwd_block, saving) and backward (block_bwd_single, its parameter gradients into the zeroed flat buffer)
+    on device tensors -> (y, x1, dx); asserts that the family's kernels ran"""
+    drop = drop or (0.0, 0)
     bf = prec == "bf16"
-    role_split = bf and H == 8
-    xc = x.cuda()
+    role_split = bf and cfg["heads"] == 8
     acts, x1s = [xc], []
     eng._fwd_block(acts, x1s, i, True, drop, role_split, role_split, 0)
     x1 = x1s[0]
@@ -192,30 +214,38 @@ def run_block(model, params, eng, cfg, i, prec, drop=None, stats=False):
     else:
         assert x1._msst_xn is None and x1._msst_lse is None
     eng.fp.grad.zero_()
-    dx = eng.block_bwd_single(i, xc, x1, dy.cuda().contiguous(), drop=drop)
+    dx = eng.block_bwd_single(i, xc, x1, dyc, drop=drop, ws=ws)
     torch.cuda.synchronize()
+    return acts[1], x1, dx
+
+
+def block_errors(model, eng, i, prec, x, dy, ref, y, dx):
+    """the kernels' y, dx and flat-buffer gradients of block i against block_reference's -> dict of errors"""
     pre = block_prefix(i)
-    p64 = {k: v.double().requires_grad_(True) for k, v in params.items() if k.startswith(pre)}
-    xs = to_seq(x.double(), mode, B, S, N).requires_grad_(True)
-    masks = None
-    if drop[0]:
-        masks = {k: v.double() for k, v in block_masks(drop[0], drop[1], i, mode, B, S, N, H).items()}
-    y = om.block(xs, p64, pre, H, masks)
-    y.backward(to_seq(dy.double(), mode, B, S, N))
-    inc_ref = from_seq(y.detach(), mode, B, S, N) - x.double()
-    dxi_ref = from_seq(xs.grad, mode, B, S, N) - dy.double()
-    err = rel_l2 if bf else relerr
-    out = dict(inc_err=err(acts[1].double().cpu() - x.double(), inc_ref), dx=err(dx.double().cpu() - dy.double(), dxi_ref))
+    err = rel_l2 if prec == "bf16" else relerr
+    out = dict(inc_err=err(y.double().cpu() - x.double(), ref["inc"]), dx=err(dx.double().cpu() - dy.double(), ref["dxi"]))
     flat = {id(p): n for n, p in eng.trainable()}
     worst, worst_name = 0.0, ""
     for pname, p in model.named_parameters():
         if pname.startswith(pre):
-            e = err(eng.fp.view(flat[id(p)], eng.fp.grad), p64[pname].grad)
+            e = err(eng.fp.view(flat[id(p)], eng.fp.grad), ref["grads"][pname])
             if e > worst:
                 worst, worst_name = e, pname[len(pre):]
     out.update(worst_grad=worst, worst_grad_name=worst_name)
+    return out
+
+
+def run_block(model, params, eng, cfg, i, prec, drop=None, stats=False):
+    """block i of the depth-1 model: kernels vs float64 autograd on the same x and dy -> dict of errors"""
+    S, N = eng.S, eng.N
+    x, dy = block_inputs(cfg, S, N, i)
+    xc = x.cuda()
+    y, x1, dx = block_kernels(eng, cfg, i, prec, xc, dy.cuda().contiguous(), drop=drop)
+    ref = block_reference(params, cfg, S, N, i, x, dy, drop=drop)
+    out = block_errors(model, eng, i, prec, x, dy, ref, y, dx)
     if stats:
-        out["lse_abs_err"], out["rstd_err"] = check_saved_statistics(eng, params, xc, x1, i, mode, B, S, N, cfg["qkv_scale"])
+        out["lse_abs_err"], out["rstd_err"] = check_saved_statistics(eng, params, xc, x1, i, 0 if i == 0 else 1, cfg["B"], S, N,
+                                                                     cfg["qkv_scale"])
     return out
 
 
