@@ -810,6 +810,34 @@ int msst_grad_accumulate(float* acc, const float* g, const MsstGradRange* ranges
 int msst_grad_finalize(const float* acc, float* g, const MsstGradRange* ranges /*host*/, int nranges, int range_bytes, float scale,
                        float max_norm, const void* scratch, float* record, void* stream);
 
+/* SimMIM masks drawn on the device (additive under MSST_VERSION 109): for the rows row0 .. row0 + rows - 1 of a conceptually unbounded
+ * global batch, the four arrays a SimMIM step consumes, in ONE launch (one workgroup per row), all device memory:
+ *   mask    uint8 [rows][T]     1 = masked: what msst_tokenize_fwd takes            (T = S * N)
+ *   idx     int32 [rows][K]     the masked-token gather: what msst_head_fwd takes   (K = int(masking_ratio * T), computed by the caller)
+ *   csr_ptr int32 [rows][T + 1] } the token-CSR of that gather, exactly what msst_head_bwd takes: the positions k with idx[k] == t are
+ *   csr_pos int32 [rows][K]     } csr_pos[csr_ptr[t] .. csr_ptr[t + 1] - 1], ascending
+ * Keys are 32 bits of a stateless counter hash of (seed, mode, global row, spectral block, element); a row has the same bits whether it
+ * is drawn alone or inside any batch, whatever row0, rows and the launch geometry are.  Selection is always "the m elements with the
+ * smallest (key, index) pairs".
+ *   MSST_MASK_TOPK   T keys per row, the K smallest are masked.  idx = the masked tokens ascending, csr_pos[k] = k, csr_ptr[t] = the
+ *                    number of masked tokens below t.  rand_size, scale and mask_count are ignored.
+ *   MSST_MASK_BLOCK  per (row, spectral block) rand_size^2 cell keys; the mask_count smallest cells are masked, each covering scale x
+ *                    scale positions of the side x side position grid (side = rand_size * scale, side * side = N).
+ *   MSST_MASK_TUBE   as MSST_MASK_BLOCK with one draw per row repeated over the S blocks.
+ * In the last two modes every row holds R = S * mask_count * scale^2 trues and idx is the row-major list of the true columns of the
+ * global mask cut into chunks of K: entry k of row g is the true of rank (K g + k) % R in mask row (K g + k) / R (a row <= g; the
+ * kernel regenerates it).  Duplicates inside an index row occur and are legal.
+ * No atomics, nothing to zero beforehand, every output element is written and nothing beyond; two calls give the same bits.
+ * Checked before anything is enqueued, in this order: MSST_ERR_BADARG for rows, S, N or K below 1, for a negative row0 or one above
+ * 2^48, and for a mode outside the three; MSST_ERR_UNSUPPORTED for N > 64 or S > 64; MSST_ERR_BADARG for K > T; in the block and tube
+ * modes MSST_ERR_BADARG for rand_size or scale below 1 or (rand_size * scale)^2 != N, for mask_count outside 1 .. rand_size^2 and for
+ * R < K; MSST_ERR_BADARG for a null pointer. */
+#define MSST_MASK_TOPK 0
+#define MSST_MASK_BLOCK 1
+#define MSST_MASK_TUBE 2
+int msst_draw_masks(uint8_t* mask, int32_t* idx, int32_t* csr_ptr, int32_t* csr_pos, uint32_t seed, long row0, int rows, int S, int N,
+                    int K, int mode, int rand_size, int scale, int mask_count, void* stream);
+
 /* Opt-in per-kernel timing: when enabled every kernel launch of the library is bracketed by a pair
  * of HIP events recorded on the launch stream.  msst_profile_collect synchronises on the recorded
  * events and returns, per kernel id (0 .. msst_profile_kernels()-1), the summed duration in ms and

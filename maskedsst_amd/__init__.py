@@ -10,7 +10,7 @@ Compute runs in hand-written HIP kernels (``maskedsst_amd/csrc``) behind the C-A
 from .vit_spatial_spectral import ViTSpatialSpectral  # noqa: F401
 from .vit_simmim_original import SimMIMSpatialSpectral, BlockwiseToPixels, Reconstruction, SceneReconstruction  # noqa: F401
 from .recon import recon_report, ReconReport, window_masks_to_scene, scene_mask_to_windows  # noqa: F401
-from .masking import MaskGenerator, micro_masks  # noqa: F401
+from .masking import MaskGenerator, micro_masks, DeviceMasks  # noqa: F401
 from .optim import GradAccumulator  # noqa: F401
 from .scene import SceneEmbedding, centre_origins, random_origins, window_labels, orient_windows, random_orients  # noqa: F401
 from .saliency import input_gradient, band_importance, integrated_gradients, scene_saliency, band_importance_scene, SceneSaliency  # noqa: F401
@@ -20,4 +20,4 @@ __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "
            "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows", "SceneEmbedding",
            "input_gradient", "band_importance", "integrated_gradients", "AttentionMaps", "attention_rollout", "attention_received",
            "centre_origins", "random_origins", "window_labels", "orient_windows", "random_orients", "scene_saliency", "band_importance_scene", "SceneSaliency",
-           "GradAccumulator", "micro_masks"]
+           "GradAccumulator", "micro_masks", "DeviceMasks"]

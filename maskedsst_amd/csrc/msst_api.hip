@@ -513,6 +513,29 @@ int msst_pool_spectral_fwd(const float* y, float* out, int B, int S, int N, void
     return fail(launch_pool_spectral(y, out, B, S, N, (hipStream_t)stream), "msst_pool_spectral_fwd");
 }
 
+int msst_draw_masks(uint8_t* mask, int32_t* idx, int32_t* csr_ptr, int32_t* csr_pos, uint32_t seed, long row0, int rows, int S, int N,
+                    int K, int mode, int rand_size, int scale, int mask_count, void* stream) {
+    if (rows < 1 || S < 1 || N < 1 || K < 1 || row0 < 0 || row0 > (1L << 48)) return fail(MSST_ERR_BADARG, "msst_draw_masks");
+    if (mode != MSST_MASK_TOPK && mode != MSST_MASK_BLOCK && mode != MSST_MASK_TUBE)
+        return fail(MSST_ERR_BADARG, "msst_draw_masks (mode outside {0, 1, 2})");
+    if (N > 64 || S > 64) return fail(MSST_ERR_UNSUPPORTED, "msst_draw_masks (N <= 64, S <= 64)");
+    if (K > S * N) return fail(MSST_ERR_BADARG, "msst_draw_masks (K > S * N)");
+    MaskDrawArgs a;
+    a.side = a.rand_size = a.scale = a.mask_count = 0;
+    if (mode != MSST_MASK_TOPK) {
+        if (rand_size < 1 || scale < 1 || rand_size > 8 || scale > 8 || rand_size * scale * rand_size * scale != N)
+            return fail(MSST_ERR_BADARG, "msst_draw_masks ((rand_size * scale)^2 is not N)");
+        if (mask_count < 1 || mask_count > rand_size * rand_size)
+            return fail(MSST_ERR_BADARG, "msst_draw_masks (mask_count outside 1 .. rand_size^2)");
+        if (S * mask_count * scale * scale < K) return fail(MSST_ERR_BADARG, "msst_draw_masks (fewer than K trues per row)");
+        a.side = rand_size * scale; a.rand_size = rand_size; a.scale = scale; a.mask_count = mask_count;
+    }
+    if (!mask || !idx || !csr_ptr || !csr_pos) return fail(MSST_ERR_BADARG, "msst_draw_masks (null argument)");
+    a.mask = mask; a.idx = idx; a.csr_ptr = csr_ptr; a.csr_pos = csr_pos; a.seed = seed; a.row0 = row0;
+    a.rows = rows; a.S = S; a.N = N; a.K = K; a.mode = mode;
+    return fail(launch_draw_masks(a, (hipStream_t)stream), "msst_draw_masks");
+}
+
 int msst_attn_maps(const float* x, const float* ln_g, const float* ln_b, const float* wqkv, float* maps, long sample_stride, int mode,
                    int B, int S, int N, int heads, int reduce, void* stream) {
     if (B < 1 || S < 1 || N < 1 || heads < 1) return fail(MSST_ERR_BADARG, "msst_attn_maps");

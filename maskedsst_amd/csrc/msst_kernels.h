@@ -10,6 +10,9 @@
 #define MSST_ERR_BADARG (-3)
 #define MSST_ADAM_MAX_GROUPS 64
 #define MSST_GRAD_MAX_RANGES 64
+#define MSST_MASK_TOPK 0
+#define MSST_MASK_BLOCK 1
+#define MSST_MASK_TUBE 2
 
 namespace msst {
 
@@ -536,5 +539,19 @@ int launch_scene_embed_finalize(const SceneEmbedArgs& a, hipStream_t st);
 // sample's sequences; one workgroup per (sample, head)
 int launch_attn_maps(const float* x, const float* ln_g, const float* ln_b, const float* wqkv, float* maps, long sample_stride,
                      int mode, int B, int S, int N, int heads, int reduce, hipStream_t st);
+
+// msst_mask.hip (msst_draw_masks): the SimMIM token mask, gather indices and the gather's token-CSR of global rows row0 .. row0 + rows - 1
+// from a counter hash; one workgroup per row
+struct MaskDrawArgs {
+    uint8_t* mask;       // [rows][S N] (1 = masked)
+    int32_t* idx;        // [rows][K]
+    int32_t* csr_ptr;    // [rows][S N + 1]
+    int32_t* csr_pos;    // [rows][K]
+    unsigned seed;
+    long row0;
+    int rows, S, N, K, mode;
+    int side, rand_size, scale, mask_count;   // MSST_MASK_BLOCK / MSST_MASK_TUBE: side = rand_size * scale, side * side = N
+};
+int launch_draw_masks(const MaskDrawArgs& a, hipStream_t st);
 
 }  // namespace msst

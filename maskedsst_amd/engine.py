@@ -1043,21 +1043,32 @@ class Engine:
         cur["ev"].record(torch.cuda.current_stream(dev))
         return out
 
-    def simmim_loss(self, src, bool_mask, idx):
+    def simmim_loss(self, src, bool_mask, idx=None):
         """scalar loss attached to autograd (reference SimMIMSpatialSpectral.forward :203-340) of src: a batch img [B, C, s, s], or the
         windows listed in a Windows' origins of resident tiles, read where they lie: no stacked copy.  bool_mask / idx: one row per
-        window.  Listed windows give the loss and, through autograd, every parameter gradient the bits of the stacked batch; the tiles get
+        window; or bool_mask a ``DeviceMasks`` alone (masks drawn on the device: its four tensors reach the kernels as they lie).
+        Listed windows give the loss and, through autograd, every parameter gradient the bits of the stacked batch; the tiles get
         no gradient (SimMIMSpatialSpectral.forward_at refuses tiles that ask for one)"""
         src = self._src(src)
         img = src.img
         self._require_cuda(img)
         self.ensure()
         T = self.S * self.N
-        from .masking import inverse_csr
-        bm = bool_mask.cpu().numpy() if torch.is_tensor(bool_mask) else np.asarray(bool_mask)
-        ix = idx.cpu().numpy() if torch.is_tensor(idx) else np.asarray(idx)
-        ptr, pos = inverse_csr(ix, T)
-        mask_u8, idx32, csr_ptr, csr_pos = self._upload(img.device, bm.astype(np.uint8), ix.astype(np.int32), ptr, pos)
+        from . import masking
+        if isinstance(bool_mask, masking.DeviceMasks):
+            # drawn on the device (msst_draw_masks): the four tensors reach the kernels as they lie -- no numpy, no inverse_csr, no upload
+            dm = bool_mask
+            if idx is not None:
+                raise ValueError("a DeviceMasks carries its own indices: pass it alone")
+            masking.check_device_masks(dm, src.n, T, dm.idx.shape[1] if torch.is_tensor(dm.idx) and dm.idx.dim() == 2 else 0)
+            if dm.bool_mask.device != img.device:
+                raise ValueError(f"DeviceMasks on {dm.bool_mask.device}, input on {img.device}")
+            mask_u8, idx32, csr_ptr, csr_pos = dm.bool_mask.view(torch.uint8), dm.idx, dm.csr_ptr, dm.csr_pos
+        else:
+            bm = bool_mask.cpu().numpy() if torch.is_tensor(bool_mask) else np.asarray(bool_mask)
+            ix = idx.cpu().numpy() if torch.is_tensor(idx) else np.asarray(idx)
+            ptr, pos = masking.inverse_csr(ix, T)   # (looked up on the module at call time)
+            mask_u8, idx32, csr_ptr, csr_pos = self._upload(img.device, bm.astype(np.uint8), ix.astype(np.int32), ptr, pos)
         names = [n for n, _ in self.trainable()]
         params = [p for _, p in self.trainable()]
         want_img = src.kind == "batch" and img.requires_grad

@@ -11,8 +11,28 @@ Data-parallel runs: every rank seeds identically, generates the masks of the GLO
 slices its own rows, which reproduces the single-process reference on the global batch including
 the cross-row coupling of ``bool_mask_to_indices``.
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
+
+# Masks drawn on the device (SimMIMSpatialSpectral.draw_masks_device, msst_draw_masks): bool_mask [B, T] torch.bool, idx [B, K] int32,
+# csr_ptr [B, T + 1] int32 and csr_pos [B, K] int32 device tensors -- the four arrays a SimMIM step's kernels consume, as the kernel
+# wrote them -- and the (seed, row0) they are a pure function of: row i is global row row0 + i of the seed's stream.  Field 0 is the
+# token mask, as in the host pair.
+DeviceMasks = namedtuple("DeviceMasks", ["bool_mask", "idx", "csr_ptr", "csr_pos", "seed", "row0"])
+
+
+def check_device_masks(dm, rows, T, K):
+    """ValueError unless dm is a DeviceMasks of `rows` rows for T tokens and K masked ones: dtypes, shapes, one device, contiguous
+    (the kernels read the tensors where they lie).  Reads no element: no device is asked for."""
+    want = (("bool_mask", torch.bool, (rows, T)), ("idx", torch.int32, (rows, K)), ("csr_ptr", torch.int32, (rows, T + 1)),
+            ("csr_pos", torch.int32, (rows, K)))
+    for name, dtype, shape in want:
+        t = getattr(dm, name)
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dm.bool_mask.device:
+            raise ValueError(f"DeviceMasks.{name} must be a contiguous {dtype} {list(shape)} tensor on the mask's device, got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
 
 
 class MaskGenerator:
@@ -111,7 +131,15 @@ def micro_masks(masks, k, steps):
     """The masks of micro-batch ``k`` of ``steps``: rows [k m, (k + 1) m), m = B / steps, of the ``(bool_mask, idx)`` pair that
     ``draw_masks(B)`` gave for the whole batch -- the rule the data-parallel path uses for a rank's rows.  ``steps`` micro-batches
     then see exactly the masks of the one large batch, the cross-row coupling of the misaligned indices included, and the RNG has
-    advanced once."""
+    advanced once.  A ``DeviceMasks`` gives a ``DeviceMasks`` of row views (no copy), its row0 moved to the first row it holds."""
+    if isinstance(masks, DeviceMasks):
+        B = masks.bool_mask.shape[0]
+        if steps < 1 or B % steps or any(t.shape[0] != B for t in masks[1:4]):
+            raise ValueError(f"{B} mask rows ({[t.shape[0] for t in masks[1:4]]} index / CSR rows) do not split into {steps} equal micro-batches")
+        if not 0 <= k < steps:
+            raise ValueError(f"micro-batch {k} outside 0 .. {steps - 1}")
+        m = B // steps
+        return DeviceMasks(*(t[k * m:(k + 1) * m] for t in masks[:4]), masks.seed, masks.row0 + k * m)
     bm, idx = masks
     B = bm.shape[0]
     if steps < 1 or B % steps or idx.shape[0] != B:

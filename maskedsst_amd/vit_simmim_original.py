@@ -3,7 +3,8 @@
 Mirrors reference ``src/vit_simmim_original.py:139-340`` (constructor, attributes, ``state_dict``
 keys ``mask_token`` / ``encoder.*`` / ``to_pixels.*``, ``forward(img) -> scalar loss``).  The
 forward/backward arithmetic runs in the HIP kernels of ``libmsst.so``; mask generation stays on the
-host and is bit-exact with the reference (``maskedsst_amd/masking.py``).
+host by default and is bit-exact with the reference (``maskedsst_amd/masking.py``); ``mask_source = "device"`` draws the
+masks in one HIP launch instead (``draw_masks_device``).
 """
 import weakref
 from collections import namedtuple
@@ -103,12 +104,83 @@ class SimMIMSpatialSpectral(nn.Module):
         lo = self.dp_rank * batch
         return bm[lo:lo + batch], idx[lo:lo + batch]
 
+    # ------------------------------------------------------------------ device-side masks (msst_draw_masks)
+    @property
+    def mask_source(self):
+        """where masks come from when a caller passes none: "host" (default; ``draw_masks``, bit-exact with the reference's numpy and
+        torch RNG streams) or "device" (``draw_masks_device``: one HIP launch, no host RNG beyond a seed, no upload)"""
+        return self.__dict__.get("_mask_source", "host")
+
+    @mask_source.setter
+    def mask_source(self, value):
+        if value not in ("host", "device"):
+            raise ValueError(f'mask_source must be "host" or "device", got {value!r}')
+        self.__dict__["_mask_source"] = value
+
+    def _mask_draw_args(self):
+        """(mode, rand_size, scale, mask_count, K) of msst_draw_masks for this model (reference :252-282's three branches)"""
+        from . import _lib
+        K = int(self.masking_ratio * self.encoder.num_patches)
+        if self.mask_patch_size == 1:
+            return _lib.MASK_TOPK, 0, 0, 0, K
+        g = self.mask_generator
+        return (_lib.MASK_TUBE if self.tube_masking else _lib.MASK_BLOCK), g.rand_size, g.scale, g.mask_count, K
+
+    def draw_masks_device(self, batch, seed=None, device=None):
+        """``DeviceMasks`` for ``batch`` local samples, drawn on the device in one launch: the token mask, the gather indices and the
+        gather's token-CSR, rows [dp_rank batch, (dp_rank + 1) batch) of the seed's stream (a stateless counter hash: a row has the
+        same bits in any batch, on any rank; nothing of the other ranks' rows is generated).  seed: an integer in [0, 2^32); None
+        draws a 31-bit one from torch's CPU generator, the way the dropout seed is drawn, so that identically seeded ranks agree and
+        ``torch.manual_seed`` reproduces a run.  device: default the model's.  The masks are NOT those of the host generator (no
+        device reproduces its mt19937 streams): same distribution, other bits; index rows list their tokens ascending.
+        ValueError -- before a device is asked for -- for a batch below 1 and a seed outside [0, 2^32)."""
+        from . import _lib
+        from .masking import DeviceMasks
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
+            raise ValueError(f"batch must be a positive integer, got {batch!r}")
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 32):
+            raise ValueError(f"seed must be an integer in [0, 2^32), got {seed!r}")
+        enc = self.encoder
+        S, N, T = enc.num_spectral_patches, enc.num_spatial_patches, enc.num_patches
+        mode, rand_size, scale, mask_count, K = self._mask_draw_args()
+        if K < 1:
+            raise ValueError(f"masking_ratio {self.masking_ratio} masks no token of {T}")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        dev = torch.device(device) if device is not None else self.mask_token.device
+        if dev.type != "cuda":
+            raise RuntimeError("maskedsst_amd runs on an MI355X only (device masks asked for on %s); there is no CPU fallback" % dev)
+        batch, row0 = int(batch), int(self.dp_rank) * int(batch)
+        bm = torch.empty((batch, T), dtype=torch.bool, device=dev)
+        idx = torch.empty((batch, K), dtype=torch.int32, device=dev)
+        ptr = torch.empty((batch, T + 1), dtype=torch.int32, device=dev)
+        pos = torch.empty((batch, K), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.load().msst_draw_masks(bm.data_ptr(), idx.data_ptr(), ptr.data_ptr(), pos.data_ptr(), int(seed), row0, batch,
+                                                   S, N, K, mode, rand_size, scale, mask_count, st), "msst_draw_masks")
+        return DeviceMasks(bm, idx, ptr, pos, int(seed), row0)
+
+    def _draw(self, batch, device=None):
+        """the masks of a call that was handed none: the configured source's"""
+        return self.draw_masks_device(batch, device=device) if self.mask_source == "device" else self.draw_masks(batch)
+
+    def _check_device_masks(self, dm, rows):
+        from .masking import check_device_masks
+        check_device_masks(dm, rows, self.encoder.num_patches, int(self.masking_ratio * self.encoder.num_patches))
+
     def forward(self, img, masks=None):
-        """img [B, bands, H, W] -> scalar reconstruction loss (mean |pred - target| / num_masked)."""
+        """img [B, bands, H, W] -> scalar reconstruction loss (mean |pred - target| / num_masked).  masks: None draws them from
+        ``mask_source``; or the (bool_mask, idx) host pair; or a ``DeviceMasks``, which reaches the kernels as it is."""
+        from .masking import DeviceMasks
         eng = self.engine()
+        if isinstance(masks, DeviceMasks):
+            self._check_device_masks(masks, img.shape[0])
         if masks is None:
-            masks = self.draw_masks(img.shape[0])
+            masks = self._draw(img.shape[0], getattr(img, "device", None))
         self.last_masks = masks
+        if isinstance(masks, DeviceMasks):
+            return eng.simmim_loss(img, masks)
         return eng.simmim_loss(img, masks[0], masks[1])
 
     # one window per row of the masked-L1 head's grid (msst_head_at_fwd)
@@ -139,7 +211,10 @@ class SimMIMSpatialSpectral(nn.Module):
         n = origins.shape[0]
         if n < 1 or n > self.MAX_WINDOWS_AT:
             raise ValueError(f"origins lists {n} windows: one call takes 1 to {self.MAX_WINDOWS_AT} (one row of the head's grid each)")
-        if masks is not None:
+        from .masking import DeviceMasks
+        if isinstance(masks, DeviceMasks):   # shapes and dtypes only: nothing is read back
+            self._check_device_masks(masks, n)
+        elif masks is not None:
             T, K = enc.num_patches, int(self.masking_ratio * enc.num_patches)
             pair = [np.asarray(m.cpu() if torch.is_tensor(m) else m) for m in masks] if isinstance(masks, (tuple, list)) else []
             if len(pair) != 2 or pair[0].dtype != np.bool_ or pair[0].shape != (n, T) or pair[1].dtype.kind not in "iu" or pair[1].shape != (n, K):
@@ -152,13 +227,14 @@ class SimMIMSpatialSpectral(nn.Module):
         eng = self.engine()
         eng._require_cuda(tiles)
         if masks is None:
-            masks = self.draw_masks(n)
+            masks = self._draw(n, tiles.device)
         self.last_masks = masks
         table = origins.to(device=tiles.device, dtype=torch.int32).contiguous()
         from .engine import Windows
         if orient is not None:
             orient = orient.to(device=tiles.device, dtype=torch.uint8).contiguous()
-        return eng.simmim_loss(Windows("listed", tiles, table, orient=orient), masks[0], masks[1])
+        src = Windows("listed", tiles, table, orient=orient)
+        return eng.simmim_loss(src, masks) if isinstance(masks, DeviceMasks) else eng.simmim_loss(src, masks[0], masks[1])
 
     def forward_windows(self, tiles, masks=None):
         """forward(stack_image_batch(tiles), masks) without the stacked copy: the loss over every non-overlapping image_size x
@@ -177,11 +253,19 @@ class SimMIMSpatialSpectral(nn.Module):
     def _token_mask(self, masks, B):
         """the bool [B, T] token mask of `masks`: the (bool_mask, idx) pair forward takes, or the bool mask alone"""
         T = self.encoder.num_patches
-        bm = masks[0] if isinstance(masks, (tuple, list)) else masks
+        bm = masks[0] if isinstance(masks, (tuple, list)) else masks   # (a DeviceMasks is a tuple: field 0 is the mask)
         bm = bm if torch.is_tensor(bm) else torch.from_numpy(np.asarray(bm))
         if bm.dtype != torch.bool or tuple(bm.shape) != (B, T):
             raise ValueError(f"mask must be a bool [{B}, {T}] tensor (batch, tokens), got {bm.dtype} {tuple(bm.shape)}")
         return bm
+
+    @staticmethod
+    def _mask_u8(bm, device):
+        """the contiguous uint8 view the kernels read of a bool token mask: a bool mask already on the device is reinterpreted where
+        it lies (a kernel-written DeviceMasks: no copy), anything else is converted and moved"""
+        if bm.device == torch.device(device) and bm.is_contiguous():
+            return bm.view(torch.uint8)
+        return bm.to(device=device, dtype=torch.uint8).contiguous()
 
     def reconstruct(self, img, masks=None, blend=True):
         """What the model reconstructs: img [B, bands, H, W] -> Reconstruction(cube, mask, band_err, band_cnt).
@@ -201,13 +285,13 @@ class SimMIMSpatialSpectral(nn.Module):
             raise ValueError(f"img {tuple(img.shape)} is not [batch, {C}, {s}, {s}] (the model's bands and image size)")
         B = img.shape[0]
         if masks is None:
-            masks = self.draw_masks(B)
+            masks = self._draw(B, img.device)
             self.last_masks = masks
         bm = self._token_mask(masks, B)
         eng = self.engine()
         eng._require_cuda(img)
         S, N, P = enc.num_spectral_patches, enc.num_spatial_patches, enc.pixels_per_patch
-        mask_u8 = bm.to(device=img.device, dtype=torch.uint8).contiguous()
+        mask_u8 = self._mask_u8(bm, img.device)
         recon, err, cnt = eng.reconstruct(img, mask_u8, blend)   # passes no dropout and saves nothing, whatever self.training
         mask = mask_u8.bool().view(B, S, 1, s, s).expand(B, S, P, s, s).reshape(B, C, s, s)
         return Reconstruction(recon.view(B, C, s, s), mask, err, cnt)
@@ -237,7 +321,7 @@ class SimMIMSpatialSpectral(nn.Module):
                 raise ValueError(f"mask=None draws one random mask per window, which needs non-overlapping windows: stride must be "
                                  f"{w} (the window size), got {stride}")
             nr, nq = (Hs - w) // w + 1, (Ws - w) // w + 1
-            masks = self.draw_masks(Bs * nr * nq)
+            masks = self._draw(Bs * nr * nq, scene.device)
             self.last_masks = masks
             mask = window_masks_to_scene(self._token_mask(masks, Bs * nr * nq), Bs, S, Hs, Ws, w)
         elif not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (Bs, S, Hs, Ws):
@@ -260,5 +344,5 @@ class SimMIMSpatialSpectral(nn.Module):
         if masks is not None:
             if not torch.is_tensor(img) or img.dim() != 4:
                 raise ValueError(f"img must be a 4-D tensor [batch, bands, H, W], got {getattr(img, 'shape', type(img))}")
-            mask_u8 = self._token_mask(masks, img.shape[0]).to(device=img.device, dtype=torch.uint8).contiguous()
+            mask_u8 = self._mask_u8(self._token_mask(masks, img.shape[0]), img.device)
         return _attention_maps(self.encoder, img, mask_u8, stack, reduce, blocks)

@@ -14,7 +14,8 @@ Differences from the reference script, all opt-in or forced by the environment:
   * ``--dp``: one process per GPU under ``python -m torch.distributed.run`` (RCCL gradient all-reduce);
   * optimizer: fused AdamW over the flat parameter buffer (``--torch-optim`` keeps torch.optim.AdamW
     with the reference's clamp hooks);
-  * dropout: the four transformer dropout sites are fused into the kernels (stateless counter-based masks).
+  * dropout: the four transformer dropout sites are fused into the kernels (stateless counter-based masks);
+  * ``--device-masks``: the SimMIM masks are drawn by a HIP kernel from a counter hash instead of the host RNG streams.
 """
 import argparse
 import os
@@ -85,6 +86,9 @@ def build_parser():
     ap.add_argument("--clip-norm", type=float, default=None, metavar="X",
                     help="clip the (accumulated, averaged) gradient to the global L2 norm X before the optimizer step "
                          "(clip_grad_norm_, fused; the config's clip_grad_norm value clamp still applies inside the optimizer)")
+    ap.add_argument("--device-masks", action="store_true",
+                    help="draw the SimMIM masks on the device (model.mask_source = \"device\": one HIP launch per step, each rank only "
+                         "its own rows; no host RNG beyond one seed, no upload); the default host generator keeps the reference's RNG streams")
     return ap
 
 
@@ -151,6 +155,8 @@ def main():
         to_pixels_per_spectral_block=config.to_pixels_per_spectral_block,
         tube_masking=config.tube_masking).to(device)
     config.model_params = sum(p.numel() for p in model.parameters())
+    if args.device_masks:
+        model.mask_source = "device"
 
     if args.torch_optim and world > 1:
         # torch.optim.AdamW reads p.grad; with the clamp hooks those are fresh tensors, not views of the flat buffer the
@@ -208,7 +214,7 @@ def main():
             if micro == 0:
                 optimizer.zero_grad()
                 if K > 1:   # one draw per optimizer step, for the global batch: the micro-batches see the rows of the one large batch
-                    masks = model.draw_masks(per_rank)
+                    masks = model.draw_masks_device(per_rank) if args.device_masks else model.draw_masks(per_rank)
             mk = micro_masks(masks, micro, K) if K > 1 else None
             if args.resident_tiles:
                 tiles, origins, orient = img if args.augment else img + (None,)
