@@ -598,7 +598,8 @@ def test_ln1_from_saved_rows_guard(monkeypatch):
 
 def test_bf16_x1_rows_with_a_large_row_offset(monkeypatch):
     """bf16 x1 rows are the default, and the backward recomputes the LN2 statistics from them; a residual stream with
-    |row mean| >> row std (a trained or deep model: the parity tests elsewhere run at random initialisation, |x| ~ std) would lose
+    |row mean| >> row std (a trained or deep model: the parity tests here run at random initialisation, |x| ~ std; tests/test_gpu_trained_state.py holds such
+    a stream against float64) would lose
     them to the rounding -- 2^-9 |x| / std -- if the rows were rounded as they are.  They are saved CENTRED (msst_fwd3.hip, ln2()),
     so the offset does not matter: tokens + 30 (|mean| / std ~ 30) give the same agreement with the fp32-row backward as tokens."""
     cfg, drop = dict(bands=50, depth=2, B=4), (0.1, 777)

@@ -136,12 +136,15 @@ def from_seq(t, mode, B, S, N):
     return t.reshape(B, S * N, 96) if mode == 0 else t.reshape(B, N, S, 96).transpose(1, 2).reshape(B, S * N, 96)
 
 
-def make_model(cfg, prec):
+def make_model(cfg, prec, edit=None):
+    """edit(model, params): changes the parameters (the model's and the oracle's copies alike) before the engine exists"""
     from maskedsst_amd.engine import _kernel_flags
     # the families here are chosen by precision and head count alone: a kernel-selection override (MSST_DBG) would swap the
     # kernels under test for others -- refuse to run rather than check the wrong path
     assert _kernel_flags() == 0, "MSST_DBG selects kernels other than the families these tests name"
     model, params, _ = build_product(cfg, precision=prec, device="cuda")
+    if edit is not None:
+        edit(model, params)
     eng = model.engine()
     eng.prep_weights()
     return model, params, eng
@@ -176,43 +179,48 @@ def block_inputs(cfg, S, N, i):
     return x, dy
 
 
-def block_reference(params, cfg, S, N, i, x, dy, drop=None):
+def block_reference(params, cfg, S, N, i, x, dy, drop=None, dtype=torch.float64):
     """oracle.model.block on float64 copies of block i's parameters, with the kernels' dropout masks -> the increment y - x, dx - dy
-    (token order of x) and the parameter gradients by name"""
+    (token order of x) and the parameter gradients by name.  dtype: the arithmetic of the oracle (float32: tests/test_trained_state_host.py)"""
     import oracle.model as om
     from dropout import block_masks
     B, H = cfg["B"], cfg["heads"]
     mode = 0 if i == 0 else 1
     drop = drop or (0.0, 0)
     pre = block_prefix(i)
-    p64 = {k: v.double().requires_grad_(True) for k, v in params.items() if k.startswith(pre)}
-    xs = to_seq(x.double(), mode, B, S, N).requires_grad_(True)
+    p64 = {k: v.to(dtype).requires_grad_(True) for k, v in params.items() if k.startswith(pre)}
+    xs = to_seq(x.to(dtype), mode, B, S, N).requires_grad_(True)
     masks = None
     if drop[0]:
-        masks = {k: v.double() for k, v in block_masks(drop[0], drop[1], i, mode, B, S, N, H).items()}
+        masks = {k: v.to(dtype) for k, v in block_masks(drop[0], drop[1], i, mode, B, S, N, H).items()}
     y = om.block(xs, p64, pre, H, masks)
-    y.backward(to_seq(dy.double(), mode, B, S, N))
-    return dict(inc=from_seq(y.detach(), mode, B, S, N) - x.double(), dxi=from_seq(xs.grad, mode, B, S, N) - dy.double(),
+    y.backward(to_seq(dy.to(dtype), mode, B, S, N))
+    return dict(inc=from_seq(y.detach(), mode, B, S, N) - x.to(dtype), dxi=from_seq(xs.grad, mode, B, S, N) - dy.to(dtype),
                 grads={k: v.grad for k, v in p64.items()})
 
 
-def block_kernels(eng, cfg, i, prec, xc, dyc, drop=None, ws=None):
+def block_kernels(eng, cfg, i, prec, xc, dyc, drop=None, ws=None, flags=0, x1_bf16=None, want_lse=None, half=True):
     """block i's forward (_fwd_block, saving) and backward (block_bwd_single, its parameter gradients into the zeroed flat buffer)
-    on device tensors -> (y, x1, dx); asserts that the family's kernels ran"""
+    on device tensors -> (y, x1, dx); asserts that the family's kernels ran.  flags: the forward's kernel-selection flags
+    (engine._kernel_flags(); the backward reads MSST_DBG itself); x1_bf16 / want_lse: what the role-split forward saves (default:
+    bf16 x1 rows and the statistics, as blocks_fwd asks for); half: whether its operands are expected to be IEEE half"""
     drop = drop or (0.0, 0)
     bf = prec == "bf16"
-    role_split = bf and cfg["heads"] == 8
+    role_split = bf and cfg["heads"] == 8 and flags == 0
+    x1_bf16 = role_split if x1_bf16 is None else (role_split and x1_bf16)
+    want_lse = role_split if want_lse is None else (role_split and want_lse)
     acts, x1s = [xc], []
-    eng._fwd_block(acts, x1s, i, True, drop, role_split, role_split, 0)
+    eng._fwd_block(acts, x1s, i, True, drop, x1_bf16, want_lse, flags)
     x1 = x1s[0]
     # the path under test ran: role-split forward (bf16 x1 rows, saved statistics, half operands), 4-wave forward (saved LN1 rows,
-    # no statistics), fp32 template forward (neither)
+    # no statistics), template forward (fp32, or bf16 under MSST_KERNEL_GENERIC: neither)
     if role_split:
-        assert x1.dtype == torch.bfloat16 and x1._msst_lse is not None and eng.fwd_half
-    elif bf:
-        assert x1._msst_xn is not None and x1._msst_lse is None
+        assert x1.dtype == (torch.bfloat16 if x1_bf16 else torch.float32) and (x1._msst_lse is not None) == want_lse
+        assert x1._msst_xn is not None and bool(eng.fwd_half) == half
+    elif bf and not flags & (16 << 8):
+        assert x1.dtype == torch.float32 and x1._msst_xn is not None and x1._msst_lse is None
     else:
-        assert x1._msst_xn is None and x1._msst_lse is None
+        assert x1.dtype == torch.float32 and x1._msst_xn is None and x1._msst_lse is None
     eng.fp.grad.zero_()
     dx = eng.block_bwd_single(i, xc, x1, dyc, drop=drop, ws=ws)
     torch.cuda.synchronize()

@@ -75,16 +75,17 @@ def ln1_rows_as_used(x, ln_g, ln_b, x1, half):
     return x1._msst_xn.float().reshape(-1, 96), torch.bfloat16
 
 
-def lse_restatement(xn, wqkv, heads, low):
+def lse_restatement(xn, wqkv, heads, low, scores=False):
     """xn [sequences, L, 96]: LN1 rows as used (ln1_rows_as_used, in sequence layout); wqkv [3 heads 64, 96] fp32 -> [sequences, heads, L]
     lse = log2 of every query's softmax denominator in the kernels' exponent domain (s = q k * dim_head^-0.5 * log2 e), q and k
-    rounded to `low` as the forward rounds them, the rest in float64"""
+    rounded to `low` as the forward rounds them, the rest in float64.  scores=True: -> (lse, the largest |s|)"""
     wq = wqkv.to(low).float()
     qkv = (xn @ wq.t()).to(low).double()
     n, L = xn.shape[0], xn.shape[1]
     q, k = qkv[..., :heads * 64].reshape(n, L, heads, 64), qkv[..., heads * 64:2 * heads * 64].reshape(n, L, heads, 64)
     s = torch.einsum("bnhd,bmhd->bhnm", q, k) * (0.125 * 1.4426950408889634)
-    return torch.logsumexp(s * 0.6931471805599453, dim=-1) * 1.4426950408889634
+    lse = torch.logsumexp(s * 0.6931471805599453, dim=-1) * 1.4426950408889634
+    return (lse, float(s.abs().max())) if scores else lse
 
 
 def saved_lse_rows(lse, heads, L, nseq):
