@@ -102,6 +102,10 @@ def build_parser():
     ap.add_argument("--val-embed", action="store_true",
                     help="one more line per validation: nearest-class-mean accuracy on the frozen per-pixel features of "
                          "encode_scene(normalize=True); class means from the first half of the --val-scenes, scored on the second half")
+    ap.add_argument("--val-knn", type=int, default=0, metavar="K",
+                    help="one more line per validation: accuracy of the weighted K-nearest-neighbour classifier (maskedsst_amd.knn_classify, "
+                         "temperature 0.07) on the same frozen features and the same split as --val-embed: the bank is the first half of "
+                         "the --val-scenes, scored on the second half; needs --val-scenes and --val-every")
     ap.add_argument("--val-saliency", action="store_true",
                     help="one more line per validation: the five bands with the largest mean |gradient x input| attribution "
                          "(maskedsst_amd.band_importance, argmax class) over the windows of the --val-scenes")
@@ -212,6 +216,7 @@ def main():
         args.val_every = args.val_every or args.steps
     if args.val_saliency_scene and args.val_scenes < 1:
         raise SystemExit("--val-saliency-scene attributes the validation scenes: it needs --val-scenes")
+    check_val_knn(args)
     if not 0.0 <= args.label_smoothing < 1.0:
         raise SystemExit("--label-smoothing must lie in [0, 1)")
     # --class-weights inverse: the weights come from the first step's labels, so the criterion is made there
@@ -263,6 +268,8 @@ def main():
                 validate(model, val, step, config.ignored_label, fused=fused, report=args.val_report)
             if args.val_embed:
                 validate_embedding(model, val, step, config.n_classes, config.ignored_label)
+            if args.val_knn:
+                validate_knn(model, val, step, args.val_knn, config.n_classes, config.ignored_label)
             if args.val_saliency:
                 validate_saliency(model, val, step)
             if args.val_saliency_scene:
@@ -379,6 +386,34 @@ def validate_embedding(model, val, step, n_classes, ignored_label):
         present = int((count > 0).sum())
     print(f"val-embed step {step} ncm_acc {acc:.3f} classes {present} train_pixels {len(ltr)} test_pixels {len(lte)} "
           f"scenes {img.shape[0]}", flush=True)
+
+
+def check_val_knn(args):
+    if not args.val_knn:
+        return
+    if not 1 <= args.val_knn <= 64:
+        raise SystemExit("--val-knn K must lie in [1, 64]")
+    if args.val_scenes < 1 or args.val_every < 1:
+        raise SystemExit("--val-knn scores the validation scenes: it needs --val-scenes and --val-every")
+
+
+def validate_knn(model, val, step, k, n_classes, ignored_label, temperature=0.07):
+    """--val-knn K: the weighted K-nearest-neighbour accuracy of the frozen features (Wu et al. 2018), the split of --val-embed: the
+    labelled covered pixels of the first half of the scenes are the bank (maskedsst_amd.KnnBank), those of the second half the
+    queries; two HIP launches (msst_knn_topk, msst_knn_vote), no score matrix.  nan when either half has no such pixel."""
+    from maskedsst_amd import KnnBank, knn_classify
+    img, label = val
+    emb = model.encode_scene(img, normalize=True)
+    f = emb.features.permute(0, 2, 3, 1)                      # [Bs, Hs, Ws, 96]
+    ok = (emb.cover > 0) & (label != ignored_label)
+    half = img.shape[0] // 2
+    ftr, ltr = f[:half][ok[:half]], label[:half][ok[:half]]
+    fte, lte = f[half:][ok[half:]], label[half:][ok[half:]]
+    acc = float("nan")
+    if half > 0 and len(ltr) and len(lte):
+        res = knn_classify(KnnBank(ftr.contiguous(), ltr, n_classes), fte.contiguous(), k=k, temperature=temperature)
+        acc = float((res.classes == lte).double().mean())
+    print(f"val-knn step {step} k {k} knn_acc {acc:.3f} bank_pixels {len(ltr)} test_pixels {len(lte)} scenes {img.shape[0]}", flush=True)
 
 
 def validate_saliency(model, val, step, batch=256, top=5):

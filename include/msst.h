@@ -375,6 +375,43 @@ int msst_scene_embed_assemble(const float* win_feat, long win0, int nwin, float*
 int msst_attn_maps(const float* x, const float* ln_g, const float* ln_b, const float* wqkv, float* maps, long sample_stride, int mode,
                    int B, int S, int N, int heads, int reduce, void* stream);
 
+/* kNN evaluation of frozen features (maskedsst_amd/knn.py: knn_classify, ViTSpatialSpectral.knn_predict_scene).  Additive under
+ * MSST_VERSION 109: no struct and no existing signature changes.  The weighted k-nearest-neighbour classifier over a bank of
+ * labelled features (Wu et al. 2018), two launches: msst_knn_topk finds every query's neighbours, msst_knn_vote turns them into votes.
+ *
+ * msst_knn_topk.  Similarity s(q, m) = sum over d = 0 .. 95 of query[d] * bank[m][d] on v_mfma_f32_16x16x4_f32, d ascending from a
+ * zero accumulator: the fp32 fmaf chain in that order, the same bits wherever the pair lands in a tile, a workgroup or a bank slice.
+ * dim is the feature width and must be 96 (the encoder's).  bank [M][96] row-major, 16-byte aligned.  Queries:
+ *   q_layout = 0: rows [Q][96];
+ *   q_layout = 1: the encode_scene map [Q / plane][96][plane] read in place -- query b plane + p reads queries[(b 96 + d) plane + p].
+ * The neighbours of a query are the first k bank rows under ONE total order -- similarity descending, then bank index ascending --
+ * stored in that order: nbr_idx [Q][k] (int32), nbr_sim [Q][k].  With M < k the tail holds index -1 and similarity -inf; a query
+ * with a NaN in any channel (an uncovered pixel of encode_scene) holds that in every slot.  The bank is walked in `splits` slices of
+ * whole 64-row tiles by different workgroups (splits = 0: chosen from (Q, M) only; more slices than tiles: one per tile); with more
+ * than one slice the partial lists go to scratch (msst_knn_scratch_bytes(Q, M, k, splits) bytes, 16-byte aligned; 0 bytes and a null
+ * pointer for splits = 1) and are merged under the same order.  The order is total and the similarities do not depend on the slice,
+ * so every output has the same bits for every splits, in every call, and for a query whatever batch it sits in.  No atomics; no
+ * output needs initialising.  Queries run in chunks of 32,768 inside the call, which re-use the scratch in stream order.
+ * msst_knn_scratch_bytes is monotone in every argument for splits >= 1; for splits = 0 it bounds what the automatic choice needs.
+ *
+ * msst_knn_vote.  w_j = exp((s_j - s_1) / temperature) relative to the query's best neighbour (w_1 = 1, nothing overflows, the
+ * argmax does not depend on the feature scale); temperature = 0: w_j = 1.  votes[q][c] = sum of w_j over the neighbours with
+ * bank_labels[index] == c, added in fp32 in rank order j = 1 .. k (a label outside [0, n_classes) votes for nothing);
+ * classes[q] (int64) = the argmax, ties to the lowest class, -1 for a query without neighbours (index -1 in slot 0), whose votes are
+ * all 0.  vote_layout = 0: votes [Q][n_classes];  vote_layout = 1: votes [Q / plane][n_classes][plane], a scene's vote map in the
+ * layout of predict_scene's logits.  plane is read in layout 1 only.
+ *
+ * Checked before anything is enqueued, in this order: MSST_ERR_BADARG for a size below 1 (M, dim, n_classes; Q < 0; splits < 0 --
+ * Q = 0 is allowed and launches nothing); MSST_ERR_UNSUPPORTED outside dim == 96, 1 <= k <= 64, n_classes <= 128, splits <= 64, and
+ * Q, M <= 2^31 - 1; MSST_ERR_BADARG for a layout outside {0, 1}, in layout 1 a plane below 1 or not dividing Q, a negative (or NaN)
+ * temperature, a null or misaligned pointer (bank and scratch 16 bytes, classes 8, the others 4), a scratch_bytes below
+ * msst_knn_scratch_bytes. */
+long msst_knn_scratch_bytes(long Q, long M, int k, int splits);
+int msst_knn_topk(const float* bank, long M, int dim, const float* queries, int q_layout, long Q, long plane, int k, int splits,
+                  int32_t* nbr_idx, float* nbr_sim, void* scratch, long scratch_bytes, void* stream);
+int msst_knn_vote(const int32_t* nbr_idx, const float* nbr_sim, const int32_t* bank_labels, long Q, int k, int n_classes,
+                  float temperature, float* votes, int vote_layout, long plane, int64_t* classes, void* stream);
+
 /* a7-a10: one fused pre-norm transformer block (PreNorm+Attention+FeedForward+residuals,
  * vit_spatial_spectral.py:22-104) over all B*S*N tokens; mode selects the spatial or spectral
  * sequence grouping of vit_spatial_spectral.py:410-431 (no transposes are materialised).

@@ -95,6 +95,9 @@ _SIGS = {
     "msst_pool_spectral_fwd": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "msst_scene_embed_assemble": (c_int, [_P, c_long, c_int, _P, _P] + [c_int] * 8 + [_P]),
     "msst_attn_maps": (c_int, [_P, _P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "msst_knn_scratch_bytes": (c_long, [c_long, c_long, c_int, c_int]),
+    "msst_knn_topk": (c_int, [_P, c_long, c_int, _P, c_int, c_long, c_long, c_int, c_int, _P, _P, _P, c_long, _P]),
+    "msst_knn_vote": (c_int, [_P, _P, _P, c_long, c_int, c_int, c_float, _P, c_int, c_long, _P, _P]),
     "msst_draw_masks": (c_int, [_P, _P, _P, _P, c_uint32, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "msst_scene_assemble": (c_int, [_P, c_long, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "msst_cls_head_fwd": (c_int, [_P] * 6 + [c_int, c_int, c_int, c_int, _P]),

@@ -551,6 +551,45 @@ int msst_attn_maps(const float* x, const float* ln_g, const float* ln_b, const f
                 "msst_attn_maps");
 }
 
+long msst_knn_scratch_bytes(long Q, long M, int k, int splits) {
+    if (Q < 1 || M < 1 || k < 1 || splits < 0) return 0;
+    return knn_scratch_bytes(Q, M, k, splits);
+}
+
+int msst_knn_topk(const float* bank, long M, int dim, const float* queries, int q_layout, long Q, long plane, int k, int splits,
+                  int32_t* nbr_idx, float* nbr_sim, void* scratch, long scratch_bytes, void* stream) {
+    if (M < 1 || dim < 1 || Q < 0 || splits < 0) return fail(MSST_ERR_BADARG, "msst_knn_topk");
+    if (dim != 96 || k < 1 || k > 64 || splits > 64 || M > 2147483647L || Q > 2147483647L)
+        return fail(MSST_ERR_UNSUPPORTED, "msst_knn_topk (dim == 96, 1 <= k <= 64, splits <= 64, Q and M <= 2^31 - 1)");
+    if (q_layout != 0 && q_layout != 1) return fail(MSST_ERR_BADARG, "msst_knn_topk (q_layout outside {0, 1})");
+    if (q_layout == 1 && (plane < 1 || Q % plane)) return fail(MSST_ERR_BADARG, "msst_knn_topk (plane does not divide Q)");
+    if (Q == 0) return 0;
+    if (!bank || !queries || !nbr_idx || !nbr_sim || ((uintptr_t)bank & 15) || ((uintptr_t)queries & 3) || ((uintptr_t)nbr_idx & 3) ||
+        ((uintptr_t)nbr_sim & 3))
+        return fail(MSST_ERR_BADARG, "msst_knn_topk (null or misaligned argument)");
+    const long need = knn_scratch_bytes(Q, M, k, splits);
+    if (scratch_bytes < need || (need > 0 && (!scratch || ((uintptr_t)scratch & 15))))
+        return fail(MSST_ERR_BADARG, "msst_knn_topk (scratch null, misaligned or smaller than msst_knn_scratch_bytes)");
+    return fail(launch_knn_topk(bank, M, queries, q_layout, Q, plane, k, splits, nbr_idx, nbr_sim, scratch, (hipStream_t)stream),
+                "msst_knn_topk");
+}
+
+int msst_knn_vote(const int32_t* nbr_idx, const float* nbr_sim, const int32_t* bank_labels, long Q, int k, int n_classes,
+                  float temperature, float* votes, int vote_layout, long plane, int64_t* classes, void* stream) {
+    if (Q < 0 || n_classes < 1) return fail(MSST_ERR_BADARG, "msst_knn_vote");
+    if (k < 1 || k > 64 || n_classes > 128 || Q > 2147483647L)
+        return fail(MSST_ERR_UNSUPPORTED, "msst_knn_vote (1 <= k <= 64, n_classes <= 128, Q <= 2^31 - 1)");
+    if (vote_layout != 0 && vote_layout != 1) return fail(MSST_ERR_BADARG, "msst_knn_vote (vote_layout outside {0, 1})");
+    if (vote_layout == 1 && (plane < 1 || Q % plane)) return fail(MSST_ERR_BADARG, "msst_knn_vote (plane does not divide Q)");
+    if (!(temperature >= 0.f)) return fail(MSST_ERR_BADARG, "msst_knn_vote (negative temperature)");
+    if (Q == 0) return 0;
+    if (!nbr_idx || !nbr_sim || !bank_labels || !votes || !classes || ((uintptr_t)nbr_idx & 3) || ((uintptr_t)nbr_sim & 3) ||
+        ((uintptr_t)bank_labels & 3) || ((uintptr_t)votes & 3) || ((uintptr_t)classes & 7))
+        return fail(MSST_ERR_BADARG, "msst_knn_vote (null or misaligned argument)");
+    return fail(launch_knn_vote(nbr_idx, nbr_sim, bank_labels, Q, k, n_classes, temperature, votes, vote_layout, plane, classes,
+                                (hipStream_t)stream), "msst_knn_vote");
+}
+
 int msst_scene_embed_assemble(const float* win_feat, long win0, int nwin, float* feat, int32_t* cover, int Bs, int D, int Hs, int Ws,
                               int window, int stride, int finalize, int l2norm, void* stream) {
     if (Bs < 1 || D < 1 || Hs < 1 || Ws < 1 || window < 1 || stride < 1 || nwin < 0 || win0 < 0)

@@ -540,6 +540,14 @@ int launch_scene_embed_finalize(const SceneEmbedArgs& a, hipStream_t st);
 int launch_attn_maps(const float* x, const float* ln_g, const float* ln_b, const float* wqkv, float* maps, long sample_stride,
                      int mode, int B, int S, int N, int heads, int reduce, hipStream_t st);
 
+// msst_knn.hip (msst_knn_topk, msst_knn_vote): the k most similar bank rows of every query under a total order (fp32 MFMA similarity
+// with the selection fused behind it, bank slices merged without atomics) and the weighted vote of their labels
+long knn_scratch_bytes(long Q, long M, int k, int splits);
+int launch_knn_topk(const float* bank, long M, const float* queries, int q_layout, long Q, long plane, int k, int splits,
+                    int32_t* nbr_idx, float* nbr_sim, void* scratch, hipStream_t st);
+int launch_knn_vote(const int32_t* nbr_idx, const float* nbr_sim, const int32_t* labels, long Q, int k, int n_classes,
+                    float temperature, float* votes, int vote_layout, long plane, int64_t* classes, hipStream_t st);
+
 // msst_mask.hip (msst_draw_masks): the SimMIM token mask, gather indices and the gather's token-CSR of global rows row0 .. row0 + rows - 1
 // from a counter hash; one workgroup per row
 struct MaskDrawArgs {

@@ -424,6 +424,22 @@ class ViTSpatialSpectral(nn.Module):
         from .scene import encode_scene, SCENE_MAX_WINDOWS
         return encode_scene(self, scene, stride, normalize, SCENE_MAX_WINDOWS if max_windows is None else max_windows)
 
+    def knn_predict_scene(self, scene, bank, k=20, temperature=0.07, stride=None, max_windows=None):
+        """Classify every pixel of whole scenes [Bs, channels, Hs, Ws] by the weighted vote of its k nearest neighbours in a bank of
+        labelled features (maskedsst_amd.KnnBank, e.g. from maskedsst_amd.feature_bank): encode_scene(normalize=True), then
+        msst_knn_topk and msst_knn_vote on the returned map in place -- no permuted copy and no score matrix.  Returns
+        KnnScene(classes, votes, cover):
+          classes [Bs, Hs, Ws] int64, -1 where no window covers the pixel;
+          votes [Bs, n_classes, Hs, Ws] fp32 (the layout of predict_scene's logits): the sum of exp((s_j - s_1) / temperature) over
+            the neighbours of each class, s_1 the best similarity (temperature = 0: the neighbour counts); 0 where uncovered;
+          cover [Bs, Hs, Ws] int32 as from encode_scene.
+        Neighbours are ranked by similarity descending, ties by bank index ascending, so the maps have the same bits in every call.
+        stride, max_windows: encode_scene's.  No head runs: a bare encoder and the encoder of a SimMIMSpatialSpectral work.  The
+        module's mode is left unchanged.  ValueError, before any device work, for a bank that is no KnnBank, k outside [1, 64], a
+        negative temperature or a scene encode_scene refuses."""
+        from .knn import knn_predict_scene
+        return knn_predict_scene(self, scene, bank, k, temperature, stride, max_windows)
+
     def attention_maps(self, img, stack="both", reduce="mean", blocks=None):
         """The attention probabilities of the transformer blocks for img [B, channels, image_size, image_size] (fp32, on the device):
         AttentionMaps(spatial, spectral), fp32 on the device; the stack not asked for is None.
