@@ -106,6 +106,11 @@ def build_parser():
                     help="one more line per validation: accuracy of the weighted K-nearest-neighbour classifier (maskedsst_amd.knn_classify, "
                          "temperature 0.07) on the same frozen features and the same split as --val-embed: the bank is the first half of "
                          "the --val-scenes, scored on the second half; needs --val-scenes and --val-every")
+    ap.add_argument("--val-probe", type=int, default=0, metavar="STEPS",
+                    help="one more line per validation: accuracy of a linear probe (maskedsst_amd.fit_linear_probe: LayerNorm -> Linear "
+                         "trained for STEPS full-batch Adam steps at lr 1e-2 on cached features) on the raw frozen features and the split "
+                         "of --val-embed: the bank is the first half of the --val-scenes, scored on the second half; needs --val-scenes "
+                         "and --val-every")
     ap.add_argument("--val-saliency", action="store_true",
                     help="one more line per validation: the five bands with the largest mean |gradient x input| attribution "
                          "(maskedsst_amd.band_importance, argmax class) over the windows of the --val-scenes")
@@ -217,6 +222,7 @@ def main():
     if args.val_saliency_scene and args.val_scenes < 1:
         raise SystemExit("--val-saliency-scene attributes the validation scenes: it needs --val-scenes")
     check_val_knn(args)
+    check_val_probe(args)
     if not 0.0 <= args.label_smoothing < 1.0:
         raise SystemExit("--label-smoothing must lie in [0, 1)")
     # --class-weights inverse: the weights come from the first step's labels, so the criterion is made there
@@ -270,6 +276,8 @@ def main():
                 validate_embedding(model, val, step, config.n_classes, config.ignored_label)
             if args.val_knn:
                 validate_knn(model, val, step, args.val_knn, config.n_classes, config.ignored_label)
+            if args.val_probe:
+                validate_probe(model, val, step, args.val_probe, config.n_classes, config.ignored_label)
             if args.val_saliency:
                 validate_saliency(model, val, step)
             if args.val_saliency_scene:
@@ -414,6 +422,37 @@ def validate_knn(model, val, step, k, n_classes, ignored_label, temperature=0.07
         res = knn_classify(KnnBank(ftr.contiguous(), ltr, n_classes), fte.contiguous(), k=k, temperature=temperature)
         acc = float((res.classes == lte).double().mean())
     print(f"val-knn step {step} k {k} knn_acc {acc:.3f} bank_pixels {len(ltr)} test_pixels {len(lte)} scenes {img.shape[0]}", flush=True)
+
+
+def check_val_probe(args):
+    if not args.val_probe:
+        return
+    if args.val_probe < 1:
+        raise SystemExit("--val-probe STEPS must be at least 1")
+    if args.val_scenes < 1 or args.val_every < 1:
+        raise SystemExit("--val-probe scores the validation scenes: it needs --val-scenes and --val-every")
+
+
+def validate_probe(model, val, step, steps, n_classes, ignored_label, lr=1e-2):
+    """--val-probe STEPS: the linear-probe accuracy of the frozen features, the split of --val-embed on the RAW features
+    (encode_scene(normalize=False): what mlp_head of the patch-head model consumes): a fresh LayerNorm -> Linear is trained on the
+    labelled covered pixels of the first half of the scenes for STEPS full-batch Adam steps (maskedsst_amd.fit_linear_probe: two HIP
+    launches per step on the cached rows, the body never runs again) and scored on those of the second half.  The model's own head
+    is not touched.  nan when either half has no such pixel."""
+    from maskedsst_amd import KnnBank, fit_linear_probe
+    img, label = val
+    emb = model.encode_scene(img, normalize=False)
+    f = emb.features.permute(0, 2, 3, 1)                      # [Bs, Hs, Ws, 96]
+    ok = (emb.cover > 0) & (label != ignored_label)
+    half = img.shape[0] // 2
+    ftr, ltr = f[:half][ok[:half]], label[:half][ok[:half]]
+    fte, lte = f[half:][ok[half:]], label[half:][ok[half:]]
+    acc = float("nan")
+    if half > 0 and len(ltr) and len(lte):
+        probe = fit_linear_probe(KnnBank(ftr.contiguous(), ltr, n_classes), steps=steps, lr=lr)
+        acc = float((probe.classify(fte.contiguous()) == lte).double().mean())
+    print(f"val-probe step {step} steps {steps} probe_acc {acc:.3f} bank_pixels {len(ltr)} test_pixels {len(lte)} scenes {img.shape[0]}",
+          flush=True)
 
 
 def validate_saliency(model, val, step, batch=256, top=5):

@@ -412,6 +412,45 @@ int msst_knn_topk(const float* bank, long M, int dim, const float* queries, int 
 int msst_knn_vote(const int32_t* nbr_idx, const float* nbr_sim, const int32_t* bank_labels, long Q, int k, int n_classes,
                   float temperature, float* votes, int vote_layout, long plane, int64_t* classes, void* stream);
 
+/* The linear probe on cached features (maskedsst_amd/probe.py: fit_linear_probe, ViTSpatialSpectral.probe_predict_scene).  Additive
+ * under MSST_VERSION 109.  Multinomial logistic regression through a trainable LayerNorm(96, eps 1e-5) with torch.optim.Adam on a bank
+ * x [M][96] of frozen features (encode_scene(normalize=False) rows).  theta = [gamma 96 | beta 96 | W nc x 96 | b nc] fp32: the layout
+ * of the mlp_head segment of the flat parameter buffer, so a probe can train a model's head where it lies.  A step is two launches
+ * and no host synchronisation; nothing uses atomics and every output has the same bits in every call.
+ *
+ * msst_probe_grad.  Rows [row0, row0 + rows) of x (16-byte aligned) with labels [M] (int32; a label outside [0, nc) weighs nothing)
+ * and class_w [nc] (null: all 1).  Per row: two-pass fp32 LayerNorm statistics, logits on v_mfma_f32_16x16x4_f32, softmax,
+ * dl = w_y (p - onehot).  Every workgroup walks whole 64-row tiles -- the partition is a function of (rows, nc) only -- and writes
+ * one slab row [dgamma 96 | dbeta 96 | dW nc x 96 | db nc | sum of w_y nll, sum of w_y, rows whose argmax (ties to the lowest class)
+ * equals the label, 0]: msst_probe_scratch_floats(rows, nc) floats in all (0 for arguments the calls refuse).
+ *
+ * msst_probe_update.  Sums the slab rows in a fixed order and divides by the weight sum -- torch's CrossEntropyLoss(weight=),
+ * reduction "mean" -- writes that mean gradient to grad_out [192 + 97 nc] when it is not null, and history_row [4] = {loss, weight
+ * sum, hits, rows} of the parameters as they were.  apply != 0: torch.optim.Adam semantics on theta, m, v (coupled L2: g += weight_decay
+ * theta; bias correction; eps outside the square root) with the step count kept on the device: step, int32 [MSST_PROBE_STEP_INTS], zero
+ * before the first step; step[0] is the number of steps applied (every workgroup keeps a copy of its own, so none reads what another
+ * writes).  A launch whose weight sum is 0 is skipped whole: theta, m, v and step stay, its loss (and grad_out) is NaN.  apply = 0
+ * only reduces: theta, m, v, step may be null.  lr is an argument, so a schedule costs nothing.
+ *
+ * msst_probe_fwd.  logits and classes (int64 argmax, ties to the lowest class) of Q rows:
+ *   x_layout = 0: rows [Q][96] (16-byte aligned);  x_layout = 1: the encode_scene map [Q / plane][96][plane] read in place;
+ *   out_layout = 0: logits [Q][nc];                out_layout = 1: [Q / plane][nc][plane], the layout of predict_scene's logits.
+ * A row with a NaN (or infinite) channel -- a pixel no window covers -- gets NaN logits and class -1.  plane is read in layout 1 only.
+ *
+ * Checked before any HIP call, in this order: MSST_ERR_BADARG for a size below 1 (M, dim, rows / Q, nc), row0 < 0 or row0 + rows > M;
+ * MSST_ERR_UNSUPPORTED outside dim == 96, nc <= 128 and M, Q <= 2^31 - 1; MSST_ERR_BADARG for a negative (or NaN) lr, eps or
+ * weight_decay, a beta outside [0, 1), a layout outside {0, 1}, in layout 1 a plane below 1 or not dividing Q, a null or misaligned
+ * pointer, a slab smaller than msst_probe_scratch_floats.  msst_last_error names the call. */
+#define MSST_PROBE_STEP_INTS 512
+long msst_probe_scratch_floats(long rows, int nc);
+int msst_probe_grad(const float* x, const int32_t* labels, const float* class_w, const float* theta, long M, int dim, long row0, long rows,
+                    int nc, float* slab, long slab_floats, void* stream);
+int msst_probe_update(const float* slab, long slab_floats, long rows, int dim, int nc, float* theta, float* m, float* v, int32_t* step,
+                      double lr, double beta1, double beta2, double eps, double weight_decay, float* history_row, float* grad_out,
+                      int apply, void* stream);
+int msst_probe_fwd(const float* x, int x_layout, long Q, long plane, const float* theta, int dim, int nc, float* logits, int out_layout,
+                   int64_t* classes, void* stream);
+
 /* a7-a10: one fused pre-norm transformer block (PreNorm+Attention+FeedForward+residuals,
  * vit_spatial_spectral.py:22-104) over all B*S*N tokens; mode selects the spatial or spectral
  * sequence grouping of vit_spatial_spectral.py:410-431 (no transposes are materialised).

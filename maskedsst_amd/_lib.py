@@ -64,6 +64,7 @@ CE_LOSS_SUM, CE_N_VALID, CE_N_CORRECT, CE_BAD_LABELS, CE_NONFINITE, CE_SUPPORT =
 CE_EXT_LOSS_SUM, CE_EXT_WEIGHT_SUM = range(2)   # include/msst.h: MSST_CE_EXT_* slots of the double sums of msst_ce_ext_fwd
 CE_CONFUSION_MAX_CLASSES = 128                  # include/msst.h: MSST_CE_CONFUSION_MAX_CLASSES
 ATTN_PER_SEQ, ATTN_MEAN_SEQ = 0, 1              # include/msst.h: MSST_ATTN_PER_SEQ, MSST_ATTN_MEAN_SEQ
+PROBE_STEP_INTS = 512                           # include/msst.h: MSST_PROBE_STEP_INTS
 MASK_TOPK, MASK_BLOCK, MASK_TUBE = 0, 1, 2      # include/msst.h: MSST_MASK_TOPK, MSST_MASK_BLOCK, MSST_MASK_TUBE
 _SIGS = {
     "msst_version": (c_int, []),
@@ -98,6 +99,10 @@ _SIGS = {
     "msst_knn_scratch_bytes": (c_long, [c_long, c_long, c_int, c_int]),
     "msst_knn_topk": (c_int, [_P, c_long, c_int, _P, c_int, c_long, c_long, c_int, c_int, _P, _P, _P, c_long, _P]),
     "msst_knn_vote": (c_int, [_P, _P, _P, c_long, c_int, c_int, c_float, _P, c_int, c_long, _P, _P]),
+    "msst_probe_scratch_floats": (c_long, [c_long, c_int]),
+    "msst_probe_grad": (c_int, [_P, _P, _P, _P, c_long, c_int, c_long, c_long, c_int, _P, c_long, _P]),
+    "msst_probe_update": (c_int, [_P, c_long, c_long, c_int, c_int, _P, _P, _P, _P] + [ctypes.c_double] * 5 + [_P, _P, c_int, _P]),
+    "msst_probe_fwd": (c_int, [_P, c_int, c_long, c_long, _P, c_int, c_int, _P, c_int, _P, _P]),
     "msst_draw_masks": (c_int, [_P, _P, _P, _P, c_uint32, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "msst_scene_assemble": (c_int, [_P, c_long, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "msst_cls_head_fwd": (c_int, [_P] * 6 + [c_int, c_int, c_int, c_int, _P]),

@@ -590,6 +590,56 @@ int msst_knn_vote(const int32_t* nbr_idx, const float* nbr_sim, const int32_t* b
                                 (hipStream_t)stream), "msst_knn_vote");
 }
 
+long msst_probe_scratch_floats(long rows, int nc) {
+    if (rows < 1 || nc < 1 || nc > 128) return 0;
+    return probe_scratch_floats(rows, nc);
+}
+
+// sizes first (MSST_ERR_BADARG), then what the kernels do not take (MSST_ERR_UNSUPPORTED); pointers are the caller's next check
+static int probe_shape(long M, int dim, long row0, long rows, int nc) {
+    if (M < 1 || dim < 1 || rows < 1 || row0 < 0 || row0 > M || rows > M - row0 || nc < 1) return MSST_ERR_BADARG;
+    if (dim != 96 || nc > 128 || M > 2147483647L) return MSST_ERR_UNSUPPORTED;
+    return 0;
+}
+
+int msst_probe_grad(const float* x, const int32_t* labels, const float* class_w, const float* theta, long M, int dim, long row0, long rows,
+                    int nc, float* slab, long slab_floats, void* stream) {
+    if (int rc = probe_shape(M, dim, row0, rows, nc))
+        return fail(rc, rc == MSST_ERR_BADARG ? "msst_probe_grad (a size below 1 or rows outside [0, M))" : "msst_probe_grad (dim == 96, nc <= 128, M <= 2^31 - 1)");
+    if (!x || !labels || !theta || !slab || ((uintptr_t)x & 15) || ((uintptr_t)labels & 3) || ((uintptr_t)class_w & 3) ||
+        ((uintptr_t)theta & 3) || ((uintptr_t)slab & 3))
+        return fail(MSST_ERR_BADARG, "msst_probe_grad (null or misaligned argument)");
+    if (slab_floats < probe_scratch_floats(rows, nc)) return fail(MSST_ERR_BADARG, "msst_probe_grad (slab smaller than msst_probe_scratch_floats)");
+    return fail(launch_probe_grad(x, labels, class_w, theta, row0, rows, nc, slab, (hipStream_t)stream), "msst_probe_grad");
+}
+
+int msst_probe_update(const float* slab, long slab_floats, long rows, int dim, int nc, float* theta, float* m, float* v, int32_t* step,
+                      double lr, double beta1, double beta2, double eps, double weight_decay, float* history_row, float* grad_out,
+                      int apply, void* stream) {
+    if (int rc = probe_shape(rows, dim, 0, rows, nc))
+        return fail(rc, rc == MSST_ERR_BADARG ? "msst_probe_update (a size below 1)" : "msst_probe_update (dim == 96, nc <= 128, rows <= 2^31 - 1)");
+    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0))
+        return fail(MSST_ERR_BADARG, "msst_probe_update (lr, eps, weight_decay >= 0 and betas in [0, 1))");
+    if (!slab || !history_row || ((uintptr_t)slab & 3) || ((uintptr_t)history_row & 3) || ((uintptr_t)grad_out & 3) ||
+        (apply && (!theta || !m || !v || !step)) || ((uintptr_t)theta & 3) || ((uintptr_t)m & 3) || ((uintptr_t)v & 3) || ((uintptr_t)step & 3))
+        return fail(MSST_ERR_BADARG, "msst_probe_update (null or misaligned argument)");
+    if (slab_floats < probe_scratch_floats(rows, nc)) return fail(MSST_ERR_BADARG, "msst_probe_update (slab smaller than msst_probe_scratch_floats)");
+    return fail(launch_probe_update(slab, rows, nc, theta, m, v, step, lr, beta1, beta2, eps, weight_decay, history_row, grad_out,
+                                    apply ? 1 : 0, (hipStream_t)stream), "msst_probe_update");
+}
+
+int msst_probe_fwd(const float* x, int x_layout, long Q, long plane, const float* theta, int dim, int nc, float* logits, int out_layout,
+                   int64_t* classes, void* stream) {
+    if (int rc = probe_shape(Q, dim, 0, Q, nc))
+        return fail(rc, rc == MSST_ERR_BADARG ? "msst_probe_fwd (a size below 1)" : "msst_probe_fwd (dim == 96, nc <= 128, Q <= 2^31 - 1)");
+    if ((x_layout != 0 && x_layout != 1) || (out_layout != 0 && out_layout != 1)) return fail(MSST_ERR_BADARG, "msst_probe_fwd (layout outside {0, 1})");
+    if ((x_layout == 1 || out_layout == 1) && (plane < 1 || Q % plane)) return fail(MSST_ERR_BADARG, "msst_probe_fwd (plane does not divide Q)");
+    if (!x || !theta || !logits || !classes || ((uintptr_t)x & (x_layout == 0 ? 15 : 3)) || ((uintptr_t)theta & 3) || ((uintptr_t)logits & 3) ||
+        ((uintptr_t)classes & 7))
+        return fail(MSST_ERR_BADARG, "msst_probe_fwd (null or misaligned argument)");
+    return fail(launch_probe_fwd(x, x_layout, Q, plane, theta, nc, logits, out_layout, classes, (hipStream_t)stream), "msst_probe_fwd");
+}
+
 int msst_scene_embed_assemble(const float* win_feat, long win0, int nwin, float* feat, int32_t* cover, int Bs, int D, int Hs, int Ws,
                               int window, int stride, int finalize, int l2norm, void* stream) {
     if (Bs < 1 || D < 1 || Hs < 1 || Ws < 1 || window < 1 || stride < 1 || nwin < 0 || win0 < 0)

@@ -548,6 +548,16 @@ int launch_knn_topk(const float* bank, long M, const float* queries, int q_layou
 int launch_knn_vote(const int32_t* nbr_idx, const float* nbr_sim, const int32_t* labels, long Q, int k, int n_classes,
                     float temperature, float* votes, int vote_layout, long plane, int64_t* classes, hipStream_t st);
 
+// msst_probe.hip (msst_probe_grad, msst_probe_update, msst_probe_fwd): the linear probe on cached features -- LayerNorm(96) -> Linear
+// -> weighted cross entropy, per-workgroup gradient partials without atomics, torch.optim.Adam on the device, and the forward
+long probe_scratch_floats(long rows, int nc);
+int launch_probe_grad(const float* x, const int32_t* labels, const float* class_w, const float* theta, long row0, long rows, int nc,
+                      float* slab, hipStream_t st);
+int launch_probe_update(const float* slab, long rows, int nc, float* theta, float* m, float* v, int32_t* step, double lr, double beta1,
+                        double beta2, double eps, double weight_decay, float* history_row, float* grad_out, int apply, hipStream_t st);
+int launch_probe_fwd(const float* x, int x_layout, long Q, long plane, const float* theta, int nc, float* logits, int out_layout,
+                     int64_t* classes, hipStream_t st);
+
 // msst_mask.hip (msst_draw_masks): the SimMIM token mask, gather indices and the gather's token-CSR of global rows row0 .. row0 + rows - 1
 // from a counter hash; one workgroup per row
 struct MaskDrawArgs {

@@ -160,6 +160,11 @@ def feature_bank(model, scenes, labels, stride=None, ignored_label=-1, per_class
     per_class: at most that many rows per class, a random subset drawn with `generator` (a CPU torch.Generator; None: the global
     one), rows kept in pixel order.  n_classes is the model's num_classes.  ValueError for labels of the wrong shape or dtype, or
     when no pixel is left."""
+    return _bank_from_scenes(model, scenes, labels, stride, ignored_label, per_class, generator, True)
+
+
+def _bank_from_scenes(model, scenes, labels, stride, ignored_label, per_class, generator, normalize):
+    """feature_bank (normalize=True) and maskedsst_amd.probe_bank (normalize=False: the raw features the head consumes)"""
     if not torch.is_tensor(scenes) or scenes.dim() != 4:
         raise ValueError(f"scenes must be a 4-D tensor [scenes, bands, H, W], got {getattr(scenes, 'shape', type(scenes))}")
     if not torch.is_tensor(labels) or labels.dim() != 3 or labels.shape != (scenes.shape[0],) + tuple(scenes.shape[2:]):
@@ -168,7 +173,7 @@ def feature_bank(model, scenes, labels, stride=None, ignored_label=-1, per_class
         raise ValueError(f"labels must be integers, got {labels.dtype}")
     if per_class is not None and (not _is_int(per_class) or per_class < 1):
         raise ValueError(f"per_class must be None or a positive integer, got {per_class!r}")
-    emb = model.encode_scene(scenes, stride=stride, normalize=True)
+    emb = model.encode_scene(scenes, stride=stride, normalize=normalize)
     labels = labels.to(emb.features.device)
     ok = (emb.cover > 0) & (labels != ignored_label)
     feats = emb.features.permute(0, 2, 3, 1)[ok].contiguous()

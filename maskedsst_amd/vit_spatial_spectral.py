@@ -440,6 +440,22 @@ class ViTSpatialSpectral(nn.Module):
         from .knn import knn_predict_scene
         return knn_predict_scene(self, scene, bank, k, temperature, stride, max_windows)
 
+    def probe_predict_scene(self, scene, probe, stride=None, max_windows=None):
+        """Classify every pixel of whole scenes [Bs, channels, Hs, Ws] with a linear probe (maskedsst_amd.LinearProbe, e.g. from
+        maskedsst_amd.fit_linear_probe): encode_scene(normalize=False), then msst_probe_fwd -- LayerNorm(96) -> Linear -- on the
+        returned map in place, no permuted copy.  Returns ProbeScene(classes, logits, cover):
+          classes [Bs, Hs, Ws] int64: the argmax, ties to the lowest class; -1 where no window covers the pixel;
+          logits [Bs, n_classes, Hs, Ws] fp32 (the layout of predict_scene's logits); NaN where uncovered;
+          cover [Bs, Hs, Ws] int32 as from encode_scene.
+        With overlapping windows (stride < image_size) this differs from probe.load_into(model) followed by predict_scene: here the
+        FEATURES of the windows covering a pixel are averaged before the LayerNorm; predict_scene runs the head per window and
+        averages the LOGITS.  At the default non-overlapping stride the two agree up to rounding.
+        stride, max_windows: encode_scene's.  No head of the model runs, so every head kind and a bare encoder work.  The module's
+        mode is left unchanged.  ValueError, before any device work, for a probe that is no LinearProbe or a scene encode_scene
+        refuses."""
+        from .probe import probe_predict_scene
+        return probe_predict_scene(self, scene, probe, stride, max_windows)
+
     def attention_maps(self, img, stack="both", reduce="mean", blocks=None):
         """The attention probabilities of the transformer blocks for img [B, channels, image_size, image_size] (fp32, on the device):
         AttentionMaps(spatial, spectral), fp32 on the device; the stack not asked for is None.
