@@ -111,6 +111,11 @@ def build_parser():
                          "trained for STEPS full-batch Adam steps at lr 1e-2 on cached features) on the raw frozen features and the split "
                          "of --val-embed: the bank is the first half of the --val-scenes, scored on the second half; needs --val-scenes "
                          "and --val-every")
+    ap.add_argument("--val-cluster", type=int, default=0, metavar="K",
+                    help="one more line per validation: the clustering score of the frozen features, no label used for the fit: k-means "
+                         "(maskedsst_amd.fit_kmeans, K clusters, cosine, k-means++) on the covered pixels of the first half of the "
+                         "--val-scenes, the second half assigned and matched to the classes (Hungarian accuracy, purity, NMI); the split "
+                         "of --val-embed; needs --val-scenes and --val-every")
     ap.add_argument("--val-saliency", action="store_true",
                     help="one more line per validation: the five bands with the largest mean |gradient x input| attribution "
                          "(maskedsst_amd.band_importance, argmax class) over the windows of the --val-scenes")
@@ -223,6 +228,7 @@ def main():
         raise SystemExit("--val-saliency-scene attributes the validation scenes: it needs --val-scenes")
     check_val_knn(args)
     check_val_probe(args)
+    check_val_cluster(args)
     if not 0.0 <= args.label_smoothing < 1.0:
         raise SystemExit("--label-smoothing must lie in [0, 1)")
     # --class-weights inverse: the weights come from the first step's labels, so the criterion is made there
@@ -278,6 +284,8 @@ def main():
                 validate_knn(model, val, step, args.val_knn, config.n_classes, config.ignored_label)
             if args.val_probe:
                 validate_probe(model, val, step, args.val_probe, config.n_classes, config.ignored_label)
+            if args.val_cluster:
+                validate_cluster(model, val, step, args.val_cluster, config.n_classes, config.ignored_label)
             if args.val_saliency:
                 validate_saliency(model, val, step)
             if args.val_saliency_scene:
@@ -453,6 +461,38 @@ def validate_probe(model, val, step, steps, n_classes, ignored_label, lr=1e-2):
         acc = float((probe.classify(fte.contiguous()) == lte).double().mean())
     print(f"val-probe step {step} steps {steps} probe_acc {acc:.3f} bank_pixels {len(ltr)} test_pixels {len(lte)} scenes {img.shape[0]}",
           flush=True)
+
+
+def check_val_cluster(args):
+    if not args.val_cluster:
+        return
+    if not 1 <= args.val_cluster <= 128:
+        raise SystemExit("--val-cluster K must lie in [1, 128]")
+    if args.val_scenes < 1 or args.val_every < 1:
+        raise SystemExit("--val-cluster scores the validation scenes: it needs --val-scenes and --val-every")
+
+
+def validate_cluster(model, val, step, k, n_classes, ignored_label, iters=50):
+    """--val-cluster K: the clustering score of the frozen features, the split of --val-embed: k-means (maskedsst_amd.fit_kmeans: two
+    HIP launches per iteration, cosine, k-means++ with seed 0) is fitted on ALL covered pixels of the first half of the scenes --
+    no label is read -- and the labelled covered pixels of the second half are assigned and matched to the classes
+    (maskedsst_amd.match_clusters: Hungarian accuracy, purity, NMI).  nan when a half has no such pixel or fewer than K."""
+    from maskedsst_amd import contingency, fit_kmeans, match_clusters
+    img, label = val
+    emb = model.encode_scene(img, normalize=True)
+    f = emb.features.permute(0, 2, 3, 1)                      # [Bs, Hs, Ws, 96]
+    covered = emb.cover > 0
+    ok = covered & (label != ignored_label)
+    half = img.shape[0] // 2
+    ftr = f[:half][covered[:half]]
+    fte, lte = f[half:][ok[half:]], label[half:][ok[half:]]
+    acc = purity = nmi = inertia = float("nan")
+    if half > 0 and len(ftr) >= k and len(lte):
+        km = fit_kmeans(ftr.contiguous(), k=k, iters=iters, metric="cosine", init="kmeans++", seed=0, check_every=10)
+        m = match_clusters(contingency(km.assign(fte.contiguous())[0], lte, k, n_classes, ignored_label))
+        acc, purity, nmi, inertia = m.accuracy, m.purity, m.nmi, km.inertia
+    print(f"val-cluster step {step} k {k} cluster_acc {acc:.3f} purity {purity:.3f} nmi {nmi:.3f} inertia {inertia:.4g} "
+          f"test_pixels {len(lte)} train_pixels {len(ftr)} scenes {img.shape[0]}", flush=True)
 
 
 def validate_saliency(model, val, step, batch=256, top=5):

@@ -451,6 +451,50 @@ int msst_probe_update(const float* slab, long slab_floats, long rows, int dim, i
 int msst_probe_fwd(const float* x, int x_layout, long Q, long plane, const float* theta, int dim, int nc, float* logits, int out_layout,
                    int64_t* classes, void* stream);
 
+/* k-means clustering of frozen features (maskedsst_amd/cluster.py: fit_kmeans, ViTSpatialSpectral.cluster_scene).  Additive under
+ * MSST_VERSION 109: no struct and no existing signature changes.  Lloyd's iteration is two launches, msst_kmeans_assign and
+ * msst_kmeans_update; the k-means++ seeding is msst_kmeans_assign against the centres chosen so far and one msst_kmeans_pick per new
+ * centre.  dim == 96, 1 <= k <= 128, fp32; nothing uses atomics and every output has the same bits in every call.
+ *
+ * Scores.  Every row gets s_c = x . c + bias_c per centroid: the dot product is the fp32 fmaf chain over the 96 channels in order
+ * (v_mfma_f32_16x16x4_f32), the bias is added behind it.  MSST_KMEANS_COSINE: bias 0, unit centroids (and unit rows, if the
+ * distance is to mean anything); MSST_KMEANS_EUCLIDEAN: bias_c = -0.5 |c|^2, so argmax_c s_c = argmin_c |x - c|^2.  ONE total order:
+ * score descending, then cluster index ascending.  distance = max(0, 2 (1 - s)) (cosine) or max(0, |x|^2 - 2 s) (euclidean).  A row
+ * whose |x|^2 is not finite (a NaN channel: a pixel no window covers) gets assignment -1 and distance NaN and contributes to no sum.
+ *
+ * msst_kmeans_assign.  x_layout = 0: rows [rows][96] (16-byte aligned); x_layout = 1: the encode_scene map [rows / plane][96][plane]
+ * read in place.  Writes assign [rows] (int32), dist [rows] and, when not null, classes [rows] (int64: in layout 1 that is the map
+ * [rows / plane][plane]).  Fit mode (slab not null): it also reads the previous contents of assign and writes one slab row per
+ * workgroup, [sums k x 96 | counts k | sum of the distances | rows whose assignment changed]; a cluster's sum is one more product
+ * onehot^T x on the same MFMA.  The workgroups own whole 64-row tiles and the partition depends on `rows` alone:
+ * msst_kmeans_scratch_floats(rows, k) floats in all (0 for arguments the calls refuse).
+ *
+ * msst_kmeans_update.  Sums the slab rows in a fixed order and writes, per cluster, the new centroid (euclidean: sum / count, an IEEE
+ * division; cosine: sum / |sum|; a cluster without rows, or a cosine sum of norm 0, keeps its centroid), its bias, counts [k] (int32)
+ * and shift [k], the L2 displacement of the centroid; history_row [2] = {sum of the distances, rows whose assignment changed}.  The
+ * number of empty clusters and the largest displacement follow from counts and shift.  After an iteration that moved no row the next
+ * one reproduces every output bit for bit.
+ *
+ * msst_kmeans_pick.  Centre j of the k-means++ seeding, from the dist array and the slab that msst_kmeans_assign (fit mode, k = j)
+ * left: total = the workgroups' distance sums in workgroup order; u = (h >> 8) 2^-24 with h the stateless counter hash of (seed, j);
+ * t = u total; the chosen row is the first whose inclusive prefix sum of dist (workgroup blocks first, then rows ascending) exceeds t.
+ * Rows chosen before do not count.  total == 0: the lowest row not chosen yet.  j == 0: row floor(u rows) (dist and slab are not
+ * read).  The row is copied into centroid j (divided by its norm for cosine), bias[j] is set and seed_rows[j] = the row.
+ *
+ * Checked before any HIP call, in this order: MSST_ERR_BADARG for a size below 1 (rows, dim, k) or j outside [0, k);
+ * MSST_ERR_UNSUPPORTED outside dim == 96, k <= 128, rows <= 2^31 - 1; MSST_ERR_BADARG for a metric or layout outside {0, 1}, in
+ * layout 1 a plane below 1 or not dividing rows, a null or misaligned pointer, a slab smaller than msst_kmeans_scratch_floats.
+ * msst_last_error names the call. */
+#define MSST_KMEANS_COSINE 0
+#define MSST_KMEANS_EUCLIDEAN 1
+long msst_kmeans_scratch_floats(long rows, int k);
+int msst_kmeans_assign(const float* x, int x_layout, long rows, long plane, int dim, const float* centroids, const float* bias, int k,
+                       int metric, int32_t* assign, float* dist, int64_t* classes, float* slab, long slab_floats, void* stream);
+int msst_kmeans_update(const float* slab, long slab_floats, long rows, int dim, int k, int metric, float* centroids, float* bias,
+                       int32_t* counts, float* shift, float* history_row, void* stream);
+int msst_kmeans_pick(const float* x, long rows, int dim, const float* dist, const float* slab, long slab_floats, int j, int k, int metric,
+                     uint32_t seed, float* centroids, float* bias, int32_t* seed_rows, void* stream);
+
 /* a7-a10: one fused pre-norm transformer block (PreNorm+Attention+FeedForward+residuals,
  * vit_spatial_spectral.py:22-104) over all B*S*N tokens; mode selects the spatial or spectral
  * sequence grouping of vit_spatial_spectral.py:410-431 (no transposes are materialised).

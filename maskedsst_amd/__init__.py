@@ -17,6 +17,7 @@ from .saliency import input_gradient, band_importance, integrated_gradients, sce
 from .attention import AttentionMaps, attention_rollout, attention_received  # noqa: F401
 from .knn import KnnBank, KnnResult, KnnScene, feature_bank, knn_classify, knn_predict_scene  # noqa: F401
 from .probe import LinearProbe, ProbeScene, fit_linear_probe, probe_bank, probe_gradient, probe_predict_scene  # noqa: F401
+from .cluster import KMeans, ClusterScene, ClusterMatch, fit_kmeans, cluster_scene, contingency, match_clusters  # noqa: F401
 
 __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "MaskGenerator", "Reconstruction", "recon_report",
            "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows", "SceneEmbedding",
@@ -24,4 +25,5 @@ __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "
            "centre_origins", "random_origins", "window_labels", "orient_windows", "random_orients", "scene_saliency", "band_importance_scene", "SceneSaliency",
            "GradAccumulator", "micro_masks", "DeviceMasks",
            "KnnBank", "KnnResult", "KnnScene", "feature_bank", "knn_classify", "knn_predict_scene",
-           "LinearProbe", "ProbeScene", "fit_linear_probe", "probe_bank", "probe_gradient", "probe_predict_scene"]
+           "LinearProbe", "ProbeScene", "fit_linear_probe", "probe_bank", "probe_gradient", "probe_predict_scene",
+           "KMeans", "ClusterScene", "ClusterMatch", "fit_kmeans", "cluster_scene", "contingency", "match_clusters"]

@@ -640,6 +640,60 @@ int msst_probe_fwd(const float* x, int x_layout, long Q, long plane, const float
     return fail(launch_probe_fwd(x, x_layout, Q, plane, theta, nc, logits, out_layout, classes, (hipStream_t)stream), "msst_probe_fwd");
 }
 
+long msst_kmeans_scratch_floats(long rows, int k) {
+    if (rows < 1 || rows > 2147483647L || k < 1 || k > 128) return 0;
+    return kmeans_scratch_floats(rows, k);
+}
+
+// sizes first (MSST_ERR_BADARG), then what the kernels do not take (MSST_ERR_UNSUPPORTED), then the metric
+static int kmeans_shape(long rows, int dim, int k, int metric) {
+    if (rows < 1 || dim < 1 || k < 1) return MSST_ERR_BADARG;
+    if (dim != 96 || k > 128 || rows > 2147483647L) return MSST_ERR_UNSUPPORTED;
+    if (metric != MSST_KMEANS_COSINE && metric != MSST_KMEANS_EUCLIDEAN) return MSST_ERR_BADARG;
+    return 0;
+}
+
+int msst_kmeans_assign(const float* x, int x_layout, long rows, long plane, int dim, const float* centroids, const float* bias, int k,
+                       int metric, int32_t* assign, float* dist, int64_t* classes, float* slab, long slab_floats, void* stream) {
+    if (int rc = kmeans_shape(rows, dim, k, metric))
+        return fail(rc, rc == MSST_ERR_BADARG ? "msst_kmeans_assign (a size below 1, or a metric outside {0, 1})"
+                                              : "msst_kmeans_assign (dim == 96, k <= 128, rows <= 2^31 - 1)");
+    if (x_layout != 0 && x_layout != 1) return fail(MSST_ERR_BADARG, "msst_kmeans_assign (x_layout outside {0, 1})");
+    if (x_layout == 1 && (plane < 1 || rows % plane)) return fail(MSST_ERR_BADARG, "msst_kmeans_assign (plane does not divide rows)");
+    if (!x || !centroids || !bias || !assign || !dist || ((uintptr_t)x & (x_layout == 0 ? 15 : 3)) || ((uintptr_t)centroids & 3) ||
+        ((uintptr_t)bias & 3) || ((uintptr_t)assign & 3) || ((uintptr_t)dist & 3) || ((uintptr_t)classes & 7) || ((uintptr_t)slab & 3))
+        return fail(MSST_ERR_BADARG, "msst_kmeans_assign (null or misaligned argument)");
+    if (slab && slab_floats < kmeans_scratch_floats(rows, k))
+        return fail(MSST_ERR_BADARG, "msst_kmeans_assign (slab smaller than msst_kmeans_scratch_floats)");
+    return fail(launch_kmeans_assign(x, x_layout, rows, plane, centroids, bias, k, metric, assign, dist, classes, slab, (hipStream_t)stream),
+                "msst_kmeans_assign");
+}
+
+int msst_kmeans_update(const float* slab, long slab_floats, long rows, int dim, int k, int metric, float* centroids, float* bias,
+                       int32_t* counts, float* shift, float* history_row, void* stream) {
+    if (int rc = kmeans_shape(rows, dim, k, metric))
+        return fail(rc, rc == MSST_ERR_BADARG ? "msst_kmeans_update (a size below 1, or a metric outside {0, 1})"
+                                              : "msst_kmeans_update (dim == 96, k <= 128, rows <= 2^31 - 1)");
+    if (!slab || !centroids || !bias || !counts || !shift || !history_row || ((uintptr_t)slab & 3) || ((uintptr_t)centroids & 3) ||
+        ((uintptr_t)bias & 3) || ((uintptr_t)counts & 3) || ((uintptr_t)shift & 3) || ((uintptr_t)history_row & 3))
+        return fail(MSST_ERR_BADARG, "msst_kmeans_update (null or misaligned argument)");
+    if (slab_floats < kmeans_scratch_floats(rows, k)) return fail(MSST_ERR_BADARG, "msst_kmeans_update (slab smaller than msst_kmeans_scratch_floats)");
+    return fail(launch_kmeans_update(slab, rows, k, metric, centroids, bias, counts, shift, history_row, (hipStream_t)stream), "msst_kmeans_update");
+}
+
+int msst_kmeans_pick(const float* x, long rows, int dim, const float* dist, const float* slab, long slab_floats, int j, int k, int metric,
+                     uint32_t seed, float* centroids, float* bias, int32_t* seed_rows, void* stream) {
+    if (j < 0 || (k >= 1 && j >= k) || (rows >= 1 && j >= rows)) return fail(MSST_ERR_BADARG, "msst_kmeans_pick (j outside [0, k), or no row left)");
+    if (int rc = kmeans_shape(rows, dim, k, metric))
+        return fail(rc, rc == MSST_ERR_BADARG ? "msst_kmeans_pick (a size below 1, or a metric outside {0, 1})"
+                                              : "msst_kmeans_pick (dim == 96, k <= 128, rows <= 2^31 - 1)");
+    if (!x || !centroids || !bias || !seed_rows || (j > 0 && (!dist || !slab)) || ((uintptr_t)x & 3) || ((uintptr_t)dist & 3) ||
+        ((uintptr_t)slab & 3) || ((uintptr_t)centroids & 3) || ((uintptr_t)bias & 3) || ((uintptr_t)seed_rows & 3))
+        return fail(MSST_ERR_BADARG, "msst_kmeans_pick (null or misaligned argument)");
+    if (j > 0 && slab_floats < kmeans_scratch_floats(rows, j)) return fail(MSST_ERR_BADARG, "msst_kmeans_pick (slab smaller than msst_kmeans_scratch_floats(rows, j))");
+    return fail(launch_kmeans_pick(x, rows, dist, slab, j, metric, seed, centroids, bias, seed_rows, (hipStream_t)stream), "msst_kmeans_pick");
+}
+
 int msst_scene_embed_assemble(const float* win_feat, long win0, int nwin, float* feat, int32_t* cover, int Bs, int D, int Hs, int Ws,
                               int window, int stride, int finalize, int l2norm, void* stream) {
     if (Bs < 1 || D < 1 || Hs < 1 || Ws < 1 || window < 1 || stride < 1 || nwin < 0 || win0 < 0)

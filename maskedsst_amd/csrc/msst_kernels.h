@@ -558,6 +558,16 @@ int launch_probe_update(const float* slab, long rows, int nc, float* theta, floa
 int launch_probe_fwd(const float* x, int x_layout, long Q, long plane, const float* theta, int nc, float* logits, int out_layout,
                      int64_t* classes, hipStream_t st);
 
+// msst_kmeans.hip (msst_kmeans_assign, msst_kmeans_update, msst_kmeans_pick): k-means on frozen features -- scores and per-cluster sums
+// on the fp32 MFMA, per-workgroup partials without atomics, the centroid update, and the k-means++ draw
+long kmeans_scratch_floats(long rows, int k);
+int launch_kmeans_assign(const float* x, int x_layout, long rows, long plane, const float* centroids, const float* bias, int k, int metric,
+                         int32_t* assign, float* dist, int64_t* classes, float* slab, hipStream_t st);
+int launch_kmeans_update(const float* slab, long rows, int k, int metric, float* centroids, float* bias, int32_t* counts, float* shift,
+                         float* history_row, hipStream_t st);
+int launch_kmeans_pick(const float* x, long rows, const float* dist, const float* slab, int j, int metric, unsigned seed, float* centroids,
+                       float* bias, int32_t* seed_rows, hipStream_t st);
+
 // msst_mask.hip (msst_draw_masks): the SimMIM token mask, gather indices and the gather's token-CSR of global rows row0 .. row0 + rows - 1
 // from a counter hash; one workgroup per row
 struct MaskDrawArgs {

@@ -456,6 +456,20 @@ class ViTSpatialSpectral(nn.Module):
         from .probe import probe_predict_scene
         return probe_predict_scene(self, scene, probe, stride, max_windows)
 
+    def cluster_scene(self, scene, km, stride=None, max_windows=None):
+        """Segment whole scenes [Bs, channels, Hs, Ws] without labels: every pixel goes to the nearest centroid of a k-means clustering
+        (maskedsst_amd.KMeans, e.g. from maskedsst_amd.fit_kmeans on the features of other scenes): encode_scene(normalize = (km.metric ==
+        "cosine")), then msst_kmeans_assign on the returned map in place, no permuted copy and no distance matrix.  Returns
+        ClusterScene(classes, distance, cover):
+          classes [Bs, Hs, Ws] int64: the cluster of the largest score, ties to the lowest index; -1 where no window covers the pixel;
+          distance [Bs, Hs, Ws] fp32: 2 (1 - x . c) (cosine) or |x - c|^2 (euclidean) to that centroid; NaN where uncovered;
+          cover [Bs, Hs, Ws] int32 as from encode_scene.
+        The maps have the same bits in every call and equal km.assign on the permuted map.  stride, max_windows: encode_scene's.  No
+        head runs: a bare encoder and the encoder of a SimMIMSpatialSpectral work.  The module's mode is left unchanged.  ValueError,
+        before any device work, for a km that is no KMeans or a scene encode_scene refuses."""
+        from .cluster import cluster_scene
+        return cluster_scene(self, scene, km, stride, max_windows)
+
     def attention_maps(self, img, stack="both", reduce="mean", blocks=None):
         """The attention probabilities of the transformer blocks for img [B, channels, image_size, image_size] (fp32, on the device):
         AttentionMaps(spatial, spectral), fp32 on the device; the stack not asked for is None.
