@@ -379,21 +379,30 @@ def validate(model, val, step, ignored_label, fused=False, report=False):
               f"pixels {r.total}", flush=True)
 
 
+def frozen_split(model, val, ignored_label, normalize, all_covered=False):
+    """The split --val-embed, --val-knn, --val-probe and --val-cluster share, from one encode_scene pass (windows of image_size, eval
+    forward, the module's mode untouched): (ftr, ltr, fte, lte), the per-pixel 96-vectors and labels of the labelled covered pixels
+    of the first half of the scenes (the bank or train rows) and of the second half (the test rows).  all_covered: the first half
+    keeps ALL covered pixels, labelled or not.  A half without such a pixel (fewer than two scenes) comes back empty."""
+    img, label = val
+    emb = model.encode_scene(img, normalize=normalize)
+    f = emb.features.permute(0, 2, 3, 1)                      # [Bs, Hs, Ws, 96]
+    covered = emb.cover > 0
+    ok = covered & (label != ignored_label)
+    half = img.shape[0] // 2
+    tr = (covered if all_covered else ok)[:half]
+    return f[:half][tr], label[:half][tr], f[half:][ok[half:]], label[half:][ok[half:]]
+
+
 def validate_embedding(model, val, step, n_classes, ignored_label):
     """--val-embed: how separable the classes are in the encoder's own representation, without the head.  One encode_scene pass
     (windows of image_size, eval forward, the module's mode untouched, unit-length 96-vectors per pixel); the class means of the
     labelled covered pixels of the first half of the scenes classify those of the second half by the nearest mean (plain torch on
     the returned map).  nan when either half has no such pixel (fewer than two scenes)."""
-    img, label = val
-    emb = model.encode_scene(img, normalize=True)
-    f = emb.features.permute(0, 2, 3, 1)                      # [Bs, Hs, Ws, 96]
-    ok = (emb.cover > 0) & (label != ignored_label)
-    half = img.shape[0] // 2
-    ftr, ltr = f[:half][ok[:half]], label[:half][ok[:half]]
-    fte, lte = f[half:][ok[half:]], label[half:][ok[half:]]
+    ftr, ltr, fte, lte = frozen_split(model, val, ignored_label, True)
     acc, present = float("nan"), 0
-    if half > 0 and len(ltr) and len(lte):
-        sums = torch.zeros(n_classes, f.shape[-1], device=f.device).index_add_(0, ltr, ftr)
+    if len(ltr) and len(lte):
+        sums = torch.zeros(n_classes, ftr.shape[-1], device=ftr.device).index_add_(0, ltr, ftr)
         count = torch.bincount(ltr, minlength=n_classes)
         means = sums / count.clamp(min=1).unsqueeze(1)
         dist = torch.cdist(fte, means)
@@ -401,7 +410,7 @@ def validate_embedding(model, val, step, n_classes, ignored_label):
         acc = float((dist.argmin(dim=1) == lte).double().mean())
         present = int((count > 0).sum())
     print(f"val-embed step {step} ncm_acc {acc:.3f} classes {present} train_pixels {len(ltr)} test_pixels {len(lte)} "
-          f"scenes {img.shape[0]}", flush=True)
+          f"scenes {val[0].shape[0]}", flush=True)
 
 
 def check_val_knn(args):
@@ -418,18 +427,12 @@ def validate_knn(model, val, step, k, n_classes, ignored_label, temperature=0.07
     labelled covered pixels of the first half of the scenes are the bank (maskedsst_amd.KnnBank), those of the second half the
     queries; two HIP launches (msst_knn_topk, msst_knn_vote), no score matrix.  nan when either half has no such pixel."""
     from maskedsst_amd import KnnBank, knn_classify
-    img, label = val
-    emb = model.encode_scene(img, normalize=True)
-    f = emb.features.permute(0, 2, 3, 1)                      # [Bs, Hs, Ws, 96]
-    ok = (emb.cover > 0) & (label != ignored_label)
-    half = img.shape[0] // 2
-    ftr, ltr = f[:half][ok[:half]], label[:half][ok[:half]]
-    fte, lte = f[half:][ok[half:]], label[half:][ok[half:]]
+    ftr, ltr, fte, lte = frozen_split(model, val, ignored_label, True)
     acc = float("nan")
-    if half > 0 and len(ltr) and len(lte):
+    if len(ltr) and len(lte):
         res = knn_classify(KnnBank(ftr.contiguous(), ltr, n_classes), fte.contiguous(), k=k, temperature=temperature)
         acc = float((res.classes == lte).double().mean())
-    print(f"val-knn step {step} k {k} knn_acc {acc:.3f} bank_pixels {len(ltr)} test_pixels {len(lte)} scenes {img.shape[0]}", flush=True)
+    print(f"val-knn step {step} k {k} knn_acc {acc:.3f} bank_pixels {len(ltr)} test_pixels {len(lte)} scenes {val[0].shape[0]}", flush=True)
 
 
 def check_val_probe(args):
@@ -448,18 +451,12 @@ def validate_probe(model, val, step, steps, n_classes, ignored_label, lr=1e-2):
     launches per step on the cached rows, the body never runs again) and scored on those of the second half.  The model's own head
     is not touched.  nan when either half has no such pixel."""
     from maskedsst_amd import KnnBank, fit_linear_probe
-    img, label = val
-    emb = model.encode_scene(img, normalize=False)
-    f = emb.features.permute(0, 2, 3, 1)                      # [Bs, Hs, Ws, 96]
-    ok = (emb.cover > 0) & (label != ignored_label)
-    half = img.shape[0] // 2
-    ftr, ltr = f[:half][ok[:half]], label[:half][ok[:half]]
-    fte, lte = f[half:][ok[half:]], label[half:][ok[half:]]
+    ftr, ltr, fte, lte = frozen_split(model, val, ignored_label, False)
     acc = float("nan")
-    if half > 0 and len(ltr) and len(lte):
+    if len(ltr) and len(lte):
         probe = fit_linear_probe(KnnBank(ftr.contiguous(), ltr, n_classes), steps=steps, lr=lr)
         acc = float((probe.classify(fte.contiguous()) == lte).double().mean())
-    print(f"val-probe step {step} steps {steps} probe_acc {acc:.3f} bank_pixels {len(ltr)} test_pixels {len(lte)} scenes {img.shape[0]}",
+    print(f"val-probe step {step} steps {steps} probe_acc {acc:.3f} bank_pixels {len(ltr)} test_pixels {len(lte)} scenes {val[0].shape[0]}",
           flush=True)
 
 
@@ -478,21 +475,14 @@ def validate_cluster(model, val, step, k, n_classes, ignored_label, iters=50):
     no label is read -- and the labelled covered pixels of the second half are assigned and matched to the classes
     (maskedsst_amd.match_clusters: Hungarian accuracy, purity, NMI).  nan when a half has no such pixel or fewer than K."""
     from maskedsst_amd import contingency, fit_kmeans, match_clusters
-    img, label = val
-    emb = model.encode_scene(img, normalize=True)
-    f = emb.features.permute(0, 2, 3, 1)                      # [Bs, Hs, Ws, 96]
-    covered = emb.cover > 0
-    ok = covered & (label != ignored_label)
-    half = img.shape[0] // 2
-    ftr = f[:half][covered[:half]]
-    fte, lte = f[half:][ok[half:]], label[half:][ok[half:]]
+    ftr, _, fte, lte = frozen_split(model, val, ignored_label, True, all_covered=True)
     acc = purity = nmi = inertia = float("nan")
-    if half > 0 and len(ftr) >= k and len(lte):
+    if len(ftr) >= k and len(lte):
         km = fit_kmeans(ftr.contiguous(), k=k, iters=iters, metric="cosine", init="kmeans++", seed=0, check_every=10)
         m = match_clusters(contingency(km.assign(fte.contiguous())[0], lte, k, n_classes, ignored_label))
         acc, purity, nmi, inertia = m.accuracy, m.purity, m.nmi, km.inertia
     print(f"val-cluster step {step} k {k} cluster_acc {acc:.3f} purity {purity:.3f} nmi {nmi:.3f} inertia {inertia:.4g} "
-          f"test_pixels {len(lte)} train_pixels {len(ftr)} scenes {img.shape[0]}", flush=True)
+          f"test_pixels {len(lte)} train_pixels {len(ftr)} scenes {val[0].shape[0]}", flush=True)
 
 
 def validate_saliency(model, val, step, batch=256, top=5):

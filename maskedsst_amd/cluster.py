@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .knn import KnnBank, DIM, _require_cuda, _p, _stream, _is_int
+from .features import DIM, KnnBank, _is_int, _p, _stream, _require_cuda, check_rows, on_scene_map
 
 MAX_K = 128        # include/msst.h: msst_kmeans_assign
 METRICS = {"cosine": 0, "euclidean": 1}     # include/msst.h: MSST_KMEANS_COSINE, MSST_KMEANS_EUCLIDEAN
@@ -35,17 +35,6 @@ HISTORY = ("inertia", "moved", "empty", "shift")   # the columns of KMeans.histo
 ClusterScene = namedtuple("ClusterScene", ["classes", "distance", "cover"])
 # mapping [k] (the class matched to every cluster, -1 for a cluster left without one), accuracy, purity, nmi
 ClusterMatch = namedtuple("ClusterMatch", ["mapping", "accuracy", "purity", "nmi"])
-
-
-def _check_rows(features, what):
-    if not torch.is_tensor(features) or features.dim() != 2 or features.shape[1] != DIM:
-        raise ValueError(f"{what} must be a 2-D tensor [M, {DIM}], got {getattr(features, 'shape', type(features))}")
-    if features.dtype != torch.float32:
-        raise ValueError(f"{what} must be float32, got {features.dtype}")
-    if features.shape[0] < 1:
-        raise ValueError(f"{what} needs at least one row")
-    if not features.is_contiguous():
-        raise ValueError(f"{what} must be contiguous")
 
 
 def _bias(centroids, metric):
@@ -90,7 +79,7 @@ class KMeans:
         """(labels [Q] int64, distance [Q] fp32) of rows [Q, 96] (fp32, contiguous, on the device): the cluster of the largest score,
         ties to the lowest index, and max(0, 2 (1 - s)) (cosine) or max(0, |x|^2 - 2 s) (euclidean); a row with a NaN channel gets
         -1 and NaN.  A row has the same bits whatever batch it sits in."""
-        _check_rows(features, "features")
+        check_rows(features, "features", 1, few="features needs at least one row")
         _require_cuda(features, "features")
         _require_cuda(self.centroids, "the centroids")
         Q = features.shape[0]
@@ -112,7 +101,7 @@ def kmeans_assign(km, x, x_layout, rows, plane, classes, dist, assign=None):
 
 def _check_fit(features, k, iters, metric, init, seed, n_init, check_every):
     x = features.features if isinstance(features, KnnBank) else features
-    _check_rows(x, "features")
+    check_rows(x, "features", 1, few="features needs at least one row")
     if not _is_int(k) or not 1 <= k <= MAX_K:
         raise ValueError(f"k must be an integer in [1, {MAX_K}], got {k!r}")
     if not _is_int(iters) or iters < 1:
@@ -252,17 +241,18 @@ def fit_kmeans(features, k=16, iters=50, metric="cosine", init="kmeans++", seed=
 
 def cluster_scene(model, scene, km, stride=None, max_windows=None):
     """See ViTSpatialSpectral.cluster_scene."""
-    from .scene import encode_scene, SCENE_MAX_WINDOWS
     if not isinstance(km, KMeans):
         raise ValueError(f"km must be a KMeans, got {type(km).__name__}")
-    emb = encode_scene(model, scene, stride, km.metric == "cosine", SCENE_MAX_WINDOWS if max_windows is None else max_windows)
-    _require_cuda(km.centroids, "the centroids")
-    Bs, _, Hs, Ws = emb.features.shape
-    dev = emb.features.device
-    classes = torch.empty(Bs, Hs, Ws, dtype=torch.int64, device=dev)
-    dist = torch.empty(Bs, Hs, Ws, dtype=torch.float32, device=dev)
-    kmeans_assign(km, emb.features, 1, Bs * Hs * Ws, Hs * Ws, classes, dist)
-    return ClusterScene(classes, dist, emb.cover)
+
+    def launch(emb, Bs, Hs, Ws):
+        _require_cuda(km.centroids, "the centroids")
+        dev = emb.features.device
+        classes = torch.empty(Bs, Hs, Ws, dtype=torch.int64, device=dev)
+        dist = torch.empty(Bs, Hs, Ws, dtype=torch.float32, device=dev)
+        kmeans_assign(km, emb.features, 1, Bs * Hs * Ws, Hs * Ws, classes, dist)
+        return ClusterScene(classes, dist, emb.cover)
+
+    return on_scene_map(model, scene, stride, km.metric == "cosine", max_windows, launch)
 
 
 def contingency(labels, truth, k, n_classes, ignored_label=-1):

@@ -551,6 +551,36 @@ int msst_attn_maps(const float* x, const float* ln_g, const float* ln_b, const f
                 "msst_attn_maps");
 }
 
+// ---- the entry points on frozen per-pixel features (msst_knn.hip, msst_probe.hip, msst_kmeans.hip) share two checks.
+// The sizes of a call on rows [row0, row0 + rows) of M feature rows with n classes or clusters: sizes first (MSST_ERR_BADARG), then what
+// the kernels do not take (MSST_ERR_UNSUPPORTED), then the metric (k-means only); pointers are the caller's next check.  `sizes` is the
+// text of the first and last refusal, `n_name` and `rows_name` are what the entry point calls n and M.
+static int feat_shape(const char* what, const char* sizes, const char* n_name, const char* rows_name, long M, int dim, long row0, long rows,
+                      int n, int metric = MSST_KMEANS_COSINE) {
+    char buf[96];
+    int rc = 0;
+    if (M < 1 || dim < 1 || rows < 1 || row0 < 0 || row0 > M || rows > M - row0 || n < 1) rc = MSST_ERR_BADARG;
+    else if (dim != 96 || n > 128 || M > 2147483647L) rc = MSST_ERR_UNSUPPORTED;
+    else if (metric != MSST_KMEANS_COSINE && metric != MSST_KMEANS_EUCLIDEAN) rc = MSST_ERR_BADARG;
+    if (rc == MSST_ERR_BADARG) snprintf(buf, sizeof(buf), " (%s)", sizes);
+    else snprintf(buf, sizeof(buf), " (dim == 96, %s <= 128, %s <= 2^31 - 1)", n_name, rows_name);
+    return rc ? fail(rc, what, buf) : 0;
+}
+
+// A layout is 0 (rows) or 1 (an encode_scene map, whose plane must divide the row count); `arg` and `rows_name` are the entry point's names
+static int feat_layout(const char* what, const char* arg, const char* rows_name, long rows, long plane, int layout, int layout2 = 0) {
+    char buf[64];
+    if ((layout != 0 && layout != 1) || (layout2 != 0 && layout2 != 1)) {
+        snprintf(buf, sizeof(buf), " (%s outside {0, 1})", arg);
+        return fail(MSST_ERR_BADARG, what, buf);
+    }
+    if ((layout == 1 || layout2 == 1) && (plane < 1 || rows % plane)) {
+        snprintf(buf, sizeof(buf), " (plane does not divide %s)", rows_name);
+        return fail(MSST_ERR_BADARG, what, buf);
+    }
+    return 0;
+}
+
 long msst_knn_scratch_bytes(long Q, long M, int k, int splits) {
     if (Q < 1 || M < 1 || k < 1 || splits < 0) return 0;
     return knn_scratch_bytes(Q, M, k, splits);
@@ -561,8 +591,7 @@ int msst_knn_topk(const float* bank, long M, int dim, const float* queries, int 
     if (M < 1 || dim < 1 || Q < 0 || splits < 0) return fail(MSST_ERR_BADARG, "msst_knn_topk");
     if (dim != 96 || k < 1 || k > 64 || splits > 64 || M > 2147483647L || Q > 2147483647L)
         return fail(MSST_ERR_UNSUPPORTED, "msst_knn_topk (dim == 96, 1 <= k <= 64, splits <= 64, Q and M <= 2^31 - 1)");
-    if (q_layout != 0 && q_layout != 1) return fail(MSST_ERR_BADARG, "msst_knn_topk (q_layout outside {0, 1})");
-    if (q_layout == 1 && (plane < 1 || Q % plane)) return fail(MSST_ERR_BADARG, "msst_knn_topk (plane does not divide Q)");
+    if (int rc = feat_layout("msst_knn_topk", "q_layout", "Q", Q, plane, q_layout)) return rc;
     if (Q == 0) return 0;
     if (!bank || !queries || !nbr_idx || !nbr_sim || ((uintptr_t)bank & 15) || ((uintptr_t)queries & 3) || ((uintptr_t)nbr_idx & 3) ||
         ((uintptr_t)nbr_sim & 3))
@@ -579,8 +608,7 @@ int msst_knn_vote(const int32_t* nbr_idx, const float* nbr_sim, const int32_t* b
     if (Q < 0 || n_classes < 1) return fail(MSST_ERR_BADARG, "msst_knn_vote");
     if (k < 1 || k > 64 || n_classes > 128 || Q > 2147483647L)
         return fail(MSST_ERR_UNSUPPORTED, "msst_knn_vote (1 <= k <= 64, n_classes <= 128, Q <= 2^31 - 1)");
-    if (vote_layout != 0 && vote_layout != 1) return fail(MSST_ERR_BADARG, "msst_knn_vote (vote_layout outside {0, 1})");
-    if (vote_layout == 1 && (plane < 1 || Q % plane)) return fail(MSST_ERR_BADARG, "msst_knn_vote (plane does not divide Q)");
+    if (int rc = feat_layout("msst_knn_vote", "vote_layout", "Q", Q, plane, vote_layout)) return rc;
     if (!(temperature >= 0.f)) return fail(MSST_ERR_BADARG, "msst_knn_vote (negative temperature)");
     if (Q == 0) return 0;
     if (!nbr_idx || !nbr_sim || !bank_labels || !votes || !classes || ((uintptr_t)nbr_idx & 3) || ((uintptr_t)nbr_sim & 3) ||
@@ -595,17 +623,9 @@ long msst_probe_scratch_floats(long rows, int nc) {
     return probe_scratch_floats(rows, nc);
 }
 
-// sizes first (MSST_ERR_BADARG), then what the kernels do not take (MSST_ERR_UNSUPPORTED); pointers are the caller's next check
-static int probe_shape(long M, int dim, long row0, long rows, int nc) {
-    if (M < 1 || dim < 1 || rows < 1 || row0 < 0 || row0 > M || rows > M - row0 || nc < 1) return MSST_ERR_BADARG;
-    if (dim != 96 || nc > 128 || M > 2147483647L) return MSST_ERR_UNSUPPORTED;
-    return 0;
-}
-
 int msst_probe_grad(const float* x, const int32_t* labels, const float* class_w, const float* theta, long M, int dim, long row0, long rows,
                     int nc, float* slab, long slab_floats, void* stream) {
-    if (int rc = probe_shape(M, dim, row0, rows, nc))
-        return fail(rc, rc == MSST_ERR_BADARG ? "msst_probe_grad (a size below 1 or rows outside [0, M))" : "msst_probe_grad (dim == 96, nc <= 128, M <= 2^31 - 1)");
+    if (int rc = feat_shape("msst_probe_grad", "a size below 1 or rows outside [0, M)", "nc", "M", M, dim, row0, rows, nc)) return rc;
     if (!x || !labels || !theta || !slab || ((uintptr_t)x & 15) || ((uintptr_t)labels & 3) || ((uintptr_t)class_w & 3) ||
         ((uintptr_t)theta & 3) || ((uintptr_t)slab & 3))
         return fail(MSST_ERR_BADARG, "msst_probe_grad (null or misaligned argument)");
@@ -616,8 +636,7 @@ int msst_probe_grad(const float* x, const int32_t* labels, const float* class_w,
 int msst_probe_update(const float* slab, long slab_floats, long rows, int dim, int nc, float* theta, float* m, float* v, int32_t* step,
                       double lr, double beta1, double beta2, double eps, double weight_decay, float* history_row, float* grad_out,
                       int apply, void* stream) {
-    if (int rc = probe_shape(rows, dim, 0, rows, nc))
-        return fail(rc, rc == MSST_ERR_BADARG ? "msst_probe_update (a size below 1)" : "msst_probe_update (dim == 96, nc <= 128, rows <= 2^31 - 1)");
+    if (int rc = feat_shape("msst_probe_update", "a size below 1", "nc", "rows", rows, dim, 0, rows, nc)) return rc;
     if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0))
         return fail(MSST_ERR_BADARG, "msst_probe_update (lr, eps, weight_decay >= 0 and betas in [0, 1))");
     if (!slab || !history_row || ((uintptr_t)slab & 3) || ((uintptr_t)history_row & 3) || ((uintptr_t)grad_out & 3) ||
@@ -630,10 +649,8 @@ int msst_probe_update(const float* slab, long slab_floats, long rows, int dim, i
 
 int msst_probe_fwd(const float* x, int x_layout, long Q, long plane, const float* theta, int dim, int nc, float* logits, int out_layout,
                    int64_t* classes, void* stream) {
-    if (int rc = probe_shape(Q, dim, 0, Q, nc))
-        return fail(rc, rc == MSST_ERR_BADARG ? "msst_probe_fwd (a size below 1)" : "msst_probe_fwd (dim == 96, nc <= 128, Q <= 2^31 - 1)");
-    if ((x_layout != 0 && x_layout != 1) || (out_layout != 0 && out_layout != 1)) return fail(MSST_ERR_BADARG, "msst_probe_fwd (layout outside {0, 1})");
-    if ((x_layout == 1 || out_layout == 1) && (plane < 1 || Q % plane)) return fail(MSST_ERR_BADARG, "msst_probe_fwd (plane does not divide Q)");
+    if (int rc = feat_shape("msst_probe_fwd", "a size below 1", "nc", "Q", Q, dim, 0, Q, nc)) return rc;
+    if (int rc = feat_layout("msst_probe_fwd", "layout", "Q", Q, plane, x_layout, out_layout)) return rc;
     if (!x || !theta || !logits || !classes || ((uintptr_t)x & (x_layout == 0 ? 15 : 3)) || ((uintptr_t)theta & 3) || ((uintptr_t)logits & 3) ||
         ((uintptr_t)classes & 7))
         return fail(MSST_ERR_BADARG, "msst_probe_fwd (null or misaligned argument)");
@@ -645,21 +662,12 @@ long msst_kmeans_scratch_floats(long rows, int k) {
     return kmeans_scratch_floats(rows, k);
 }
 
-// sizes first (MSST_ERR_BADARG), then what the kernels do not take (MSST_ERR_UNSUPPORTED), then the metric
-static int kmeans_shape(long rows, int dim, int k, int metric) {
-    if (rows < 1 || dim < 1 || k < 1) return MSST_ERR_BADARG;
-    if (dim != 96 || k > 128 || rows > 2147483647L) return MSST_ERR_UNSUPPORTED;
-    if (metric != MSST_KMEANS_COSINE && metric != MSST_KMEANS_EUCLIDEAN) return MSST_ERR_BADARG;
-    return 0;
-}
+static const char KMEANS_SIZES[] = "a size below 1, or a metric outside {0, 1}";
 
 int msst_kmeans_assign(const float* x, int x_layout, long rows, long plane, int dim, const float* centroids, const float* bias, int k,
                        int metric, int32_t* assign, float* dist, int64_t* classes, float* slab, long slab_floats, void* stream) {
-    if (int rc = kmeans_shape(rows, dim, k, metric))
-        return fail(rc, rc == MSST_ERR_BADARG ? "msst_kmeans_assign (a size below 1, or a metric outside {0, 1})"
-                                              : "msst_kmeans_assign (dim == 96, k <= 128, rows <= 2^31 - 1)");
-    if (x_layout != 0 && x_layout != 1) return fail(MSST_ERR_BADARG, "msst_kmeans_assign (x_layout outside {0, 1})");
-    if (x_layout == 1 && (plane < 1 || rows % plane)) return fail(MSST_ERR_BADARG, "msst_kmeans_assign (plane does not divide rows)");
+    if (int rc = feat_shape("msst_kmeans_assign", KMEANS_SIZES, "k", "rows", rows, dim, 0, rows, k, metric)) return rc;
+    if (int rc = feat_layout("msst_kmeans_assign", "x_layout", "rows", rows, plane, x_layout)) return rc;
     if (!x || !centroids || !bias || !assign || !dist || ((uintptr_t)x & (x_layout == 0 ? 15 : 3)) || ((uintptr_t)centroids & 3) ||
         ((uintptr_t)bias & 3) || ((uintptr_t)assign & 3) || ((uintptr_t)dist & 3) || ((uintptr_t)classes & 7) || ((uintptr_t)slab & 3))
         return fail(MSST_ERR_BADARG, "msst_kmeans_assign (null or misaligned argument)");
@@ -671,9 +679,7 @@ int msst_kmeans_assign(const float* x, int x_layout, long rows, long plane, int 
 
 int msst_kmeans_update(const float* slab, long slab_floats, long rows, int dim, int k, int metric, float* centroids, float* bias,
                        int32_t* counts, float* shift, float* history_row, void* stream) {
-    if (int rc = kmeans_shape(rows, dim, k, metric))
-        return fail(rc, rc == MSST_ERR_BADARG ? "msst_kmeans_update (a size below 1, or a metric outside {0, 1})"
-                                              : "msst_kmeans_update (dim == 96, k <= 128, rows <= 2^31 - 1)");
+    if (int rc = feat_shape("msst_kmeans_update", KMEANS_SIZES, "k", "rows", rows, dim, 0, rows, k, metric)) return rc;
     if (!slab || !centroids || !bias || !counts || !shift || !history_row || ((uintptr_t)slab & 3) || ((uintptr_t)centroids & 3) ||
         ((uintptr_t)bias & 3) || ((uintptr_t)counts & 3) || ((uintptr_t)shift & 3) || ((uintptr_t)history_row & 3))
         return fail(MSST_ERR_BADARG, "msst_kmeans_update (null or misaligned argument)");
@@ -684,9 +690,7 @@ int msst_kmeans_update(const float* slab, long slab_floats, long rows, int dim, 
 int msst_kmeans_pick(const float* x, long rows, int dim, const float* dist, const float* slab, long slab_floats, int j, int k, int metric,
                      uint32_t seed, float* centroids, float* bias, int32_t* seed_rows, void* stream) {
     if (j < 0 || (k >= 1 && j >= k) || (rows >= 1 && j >= rows)) return fail(MSST_ERR_BADARG, "msst_kmeans_pick (j outside [0, k), or no row left)");
-    if (int rc = kmeans_shape(rows, dim, k, metric))
-        return fail(rc, rc == MSST_ERR_BADARG ? "msst_kmeans_pick (a size below 1, or a metric outside {0, 1})"
-                                              : "msst_kmeans_pick (dim == 96, k <= 128, rows <= 2^31 - 1)");
+    if (int rc = feat_shape("msst_kmeans_pick", KMEANS_SIZES, "k", "rows", rows, dim, 0, rows, k, metric)) return rc;
     if (!x || !centroids || !bias || !seed_rows || (j > 0 && (!dist || !slab)) || ((uintptr_t)x & 3) || ((uintptr_t)dist & 3) ||
         ((uintptr_t)slab & 3) || ((uintptr_t)centroids & 3) || ((uintptr_t)bias & 3) || ((uintptr_t)seed_rows & 3))
         return fail(MSST_ERR_BADARG, "msst_kmeans_pick (null or misaligned argument)");

@@ -4,26 +4,21 @@
 // (an iteration that moves no row) reproduces itself bit for bit.
 //
 // Every row gets one score per centroid, s_c = x . c + bias_c: the dot product is the fp32 fmaf chain over d = 0 .. 95 in order from a
-// zero accumulator (v_mfma_f32_16x16x4_f32, as msst_knn_topk forms its similarities), the bias is added behind it.  cosine: bias 0 and
+// zero accumulator (msst_feat.h: scores), the bias is added behind it.  cosine: bias 0 and
 // unit centroids; euclidean: bias = -0.5 |c|^2, so that argmax_c s_c = argmin_c |x - c|^2.  ONE total order: score descending, then
 // cluster index ascending.  distance = max(0, 2 (1 - s)) (cosine) or max(0, |x|^2 - 2 s) (euclidean).  A row whose |x|^2 is not finite
 // (a NaN channel) gets assignment -1 and distance NaN and contributes to no sum.
 //
-// kmeans_assign  grid = workgroups of whole 64-row tiles (the partition depends on the row count only: km_partition), 256 threads = 4
-//             waves, LDS (kp = k rounded up to 16, 32, 64 or 128): centroids [kp][98] | x tile [64][98] | bias [kp] | |x|^2 [64] |
-//             assignment [64] | 16 x 2 row sums: 75 KB at kp = 128, two workgroups per CU.  The cluster-tile count and the layout are
-//             template parameters.
-//   tile      layout 0: 16-byte global loads one tile ahead in registers (as msst_knn.hip), stored at pitch 98 (the 32 lanes of a
-//             one-dword operand read on 32 banks); layout 1: thread = (row tid & 63, channels 4 i + (tid >> 6)), the 64 lanes of a wave on
-//             64 adjacent pixels of one channel plane.  Rows past the end are zero rows, masked by index.
+// The tile loaders of both layouts, the scores loop, the order, the pairs and the partition are msst_feat.h's.
+// kmeans_assign  grid = workgroups of whole 64-row tiles (feat_partition), 256 threads = 4 waves, LDS (kp = k rounded up to 16, 32, 64 or
+//             128, KmAssignLds): centroids [kp][98] | x tile [64][98] | bias [kp] | |x|^2 [64] | assignment [64] | 16 x 2 row sums: 75 KB
+//             at kp = 128, two workgroups per CU.  The cluster-tile count and the layout are template parameters.
+//   tile      one tile ahead in registers, stored at pitch 98.  Rows past the end are zero rows, masked by index.
 //   |x|^2     four threads per row, channels 4 i + q by fmaf, then (q0 + q1) + (q2 + q3); a row that is not finite is zeroed in LDS (0 x NaN
 //             would poison the sums below) and flagged by a NaN in the |x|^2 table.
-//   scores    wave w owns rows 16 w .. 16 w + 15: A = x[row l & 15][4 ks + (l >> 4)], B = c[cluster 16 jt + (l & 15)][4 ks + (l >> 4)], 24
-//             k-steps; lane l then holds rows 4 (l >> 4) + r, clusters 16 jt + (l & 15).  The best (score, index) of a row: over the lane's
-//             own clusters ascending, then over the 16 lanes of the group (xor 1, 2, 4, 8) under the total order.
-//   sums      (fit mode: slab != null) one more product onehot^T x on the same MFMA, as msst_probe_grad forms dl^T xhat: the (cluster
-//             tile, channel tile) pairs are dealt round-robin to the 4 waves, each accumulates its pairs over ALL tiles of the workgroup
-//             in registers: A = (assignment[row 4 ks + (l >> 4)] == cluster) ? 1 : 0, B = x[row 4 ks + (l >> 4)][channel]; the k-step loop
+//   scores    the best (score, index) of a row: over the lane's own clusters ascending, then over the 16 lanes of the group.
+//   sums      (fit mode: slab != null) one more product onehot^T x on the same MFMA: each wave accumulates its (cluster tile, channel
+//             tile) pairs over ALL tiles of the workgroup in registers: A = (assignment[row 4 ks + (l >> 4)] == cluster) ? 1 : 0, B = x[row 4 ks + (l >> 4)][channel]; the k-step loop
 //             is outermost, so a wave's up to 12 accumulators are independent and one assignment read serves all its pairs.  fma(0, x, acc)
 //             = acc, so a cluster's sum is the fmaf chain of its member rows in row order.  Counts: thread c counts the tile's rows of
 //             cluster c, in integers.
@@ -41,29 +36,26 @@
 //             Centre 0: row (h >> 8) M >> 24 = floor(u M).
 // No inline assembly.
 #include "../../include/msst.h"
-#include "msst_dev.h"
+#include "msst_feat.h"
 #include "msst_kernels.h"
-
-#include <atomic>
 
 namespace msst {
 
 namespace {
 
-constexpr int KM_D = 96;
-constexpr int KM_P = 98;               // LDS pitch of a centroid row and of a feature row (msst_knn.hip)
-constexpr int KM_MAX_WGS = 512;        // 256 CUs x 2
+constexpr int KM_P = 98;               // LDS pitch of a centroid row and of a feature row
 
-__host__ __device__ constexpr int km_pairs_per_wave(int nct) { return (nct * 6 + 3) / 4; }
-
-int km_nct(int k) { return k <= 16 ? 1 : k <= 32 ? 2 : k <= 64 ? 4 : 8; }
-
-void km_partition(long rows, long* tiles_per_wg, int* nwg) {
-    const long tiles = (rows + 63) / 64;
-    const long per = (tiles + KM_MAX_WGS - 1) / KM_MAX_WGS;
-    *tiles_per_wg = per;
-    *nwg = (int)((tiles + per - 1) / per);
-}
+// the LDS of kmeans_assign_kernel<NCT, .>, offsets in floats
+template <int NCT>
+struct KmAssignLds {
+    static constexpr int cent = 0;                       // [16 NCT][KM_P]
+    static constexpr int x = cent + 16 * NCT * KM_P;     // [64][KM_P]
+    static constexpr int bias = x + 64 * KM_P;           // [16 NCT]
+    static constexpr int x2 = bias + 16 * NCT;           // [64]  NaN: the row is not finite
+    static constexpr int asg = x2 + 64;                  // [64] int
+    static constexpr int red = asg + 64;                 // [16][2]
+    static constexpr size_t bytes = (size_t)4 * (red + 32);
+};
 
 __device__ __forceinline__ unsigned km_mix(unsigned x) {   // the finaliser of msst_mask.hip
     x *= 0x9E3779B1U; x ^= x >> 15;
@@ -87,22 +79,20 @@ struct KmAssignArgs {
 
 template <int NCT, int LAYOUT>
 __global__ __launch_bounds__(256, NCT <= 2 ? 3 : NCT == 4 ? 2 : 1) void kmeans_assign_kernel(KmAssignArgs a) {
-    constexpr int KP = 16 * NCT, NPAIR = NCT * 6, PPW = km_pairs_per_wave(NCT);
+    constexpr int KP = 16 * NCT, PPW = feat_pairs_per_wave(NCT);
+    using L = KmAssignLds<NCT>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float* sc = reinterpret_cast<float*>(smem_raw);    // [KP][KM_P]
-    float* xs = sc + KP * KM_P;                        // [64][KM_P]
-    float* sbias = xs + 64 * KM_P;                     // [KP]
-    float* sx2 = sbias + KP;                           // [64]  NaN: the row is not finite
-    int* sasg = reinterpret_cast<int*>(sx2 + 64);      // [64]
-    float* sred = reinterpret_cast<float*>(sasg + 64); // [16][2]
+    float* smem = reinterpret_cast<float*>(smem_raw);
+    float *sc = smem + L::cent, *xs = smem + L::x, *sbias = smem + L::bias, *sx2 = smem + L::x2, *sred = smem + L::red;
+    int* sasg = reinterpret_cast<int*>(smem + L::asg);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cg = lane >> 4, cc = lane & 15;
     const int k = a.k;
     const bool fit = a.slab != nullptr;
     const bool cosine = a.metric == MSST_KMEANS_COSINE;
 
-    for (int e = tid; e < KP * KM_D; e += 256) {
-        const int j = e / KM_D, d = e - j * KM_D;
+    for (int e = tid; e < KP * FEAT_D; e += 256) {
+        const int j = e / FEAT_D, d = e - j * FEAT_D;
         sc[j * KM_P + d] = j < k ? a.cent[e] : 0.f;
     }
     for (int j = tid; j < KP; j += 256) sbias[j] = j < k ? a.bias[j] : 0.f;
@@ -113,22 +103,8 @@ __global__ __launch_bounds__(256, NCT <= 2 ? 3 : NCT == 4 ? 2 : 1) void kmeans_a
 
     f32x4 pre[6];
     auto load_tile = [&](long r0) {
-        if (LAYOUT == 0) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const int e = tid + 256 * i;
-                const int row = e / 24, c4 = e - row * 24;
-                const long r = r0 + row;
-                pre[i] = r < rend ? *reinterpret_cast<const f32x4*>(a.x + r * KM_D + 4 * c4) : zero4();
-            }
-        } else {
-            const long q = r0 + lane;
-            const bool in = q < rend;
-            const long b = in ? q / a.plane : 0, p = in ? q - b * a.plane : 0;
-            const float* src = a.x + b * KM_D * a.plane + p;
-#pragma unroll
-            for (int i = 0; i < 24; ++i) pre[i >> 2][i & 3] = in ? src[(long)(4 * i + wave) * a.plane] : 0.f;
-        }
+        if (LAYOUT == 0) feat_rows_prefetch(pre, a.x, r0, rend, tid);
+        else feat_map_prefetch(pre, a.x, a.plane, r0, rend, tid);
     };
     if (ntiles > 0) load_tile(rbeg);
 
@@ -141,19 +117,8 @@ __global__ __launch_bounds__(256, NCT <= 2 ? 3 : NCT == 4 ? 2 : 1) void kmeans_a
     for (long t = 0; t < ntiles; ++t) {
         const long r0 = rbeg + t * 64;
         __syncthreads();   // the previous tile's operand reads (and, first, the centroids) are done
-        if (LAYOUT == 0) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const int e = tid + 256 * i;
-                const int row = e / 24, c4 = e - row * 24;
-                float* d = xs + row * KM_P + 4 * c4;   // rows of pitch 98 floats start on 8 bytes
-                *reinterpret_cast<float2*>(d) = make_float2(pre[i][0], pre[i][1]);
-                *reinterpret_cast<float2*>(d + 2) = make_float2(pre[i][2], pre[i][3]);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 24; ++i) xs[lane * KM_P + 4 * i + wave] = pre[i >> 2][i & 3];
-        }
+        if (LAYOUT == 0) feat_rows_store<KM_P>(xs, pre, tid);
+        else feat_map_store<KM_P>(xs, pre, tid);
         __syncthreads();
         if (t + 1 < ntiles) load_tile(r0 + 64);
         {   // ---- |x|^2, four threads per row
@@ -175,16 +140,7 @@ __global__ __launch_bounds__(256, NCT <= 2 ? 3 : NCT == 4 ? 2 : 1) void kmeans_a
         f32x4 c[NCT];
 #pragma unroll
         for (int jt = 0; jt < NCT; ++jt) c[jt] = zero4();
-        {
-            const float* xa = xs + (16 * wave + cc) * KM_P + cg;
-            const float* cb = sc + cc * KM_P + cg;
-#pragma unroll
-            for (int ks = 0; ks < 24; ++ks) {
-                const float av = xa[4 * ks];
-#pragma unroll
-                for (int jt = 0; jt < NCT; ++jt) c[jt] = PF32::mma(av, cb[16 * jt * KM_P + 4 * ks], c[jt]);
-            }
-        }
+        feat_scores<NCT, KM_P, KM_P>(xs, sc, wave, cc, cg, c);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int rl = 16 * wave + 4 * cg + r;
@@ -198,12 +154,7 @@ __global__ __launch_bounds__(256, NCT <= 2 ? 3 : NCT == 4 ? 2 : 1) void kmeans_a
                 const float s = c[jt][r] + sbias[cls];
                 if (cls < k && s > bv) { bv = s; bi = cls; }
             }
-#pragma unroll
-            for (int m = 1; m < 16; m <<= 1) {
-                const float ov = __shfl_xor(bv, m);
-                const int oi = __shfl_xor(bi, m);
-                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-            }
+            feat_group_argmax(bv, bi);
             const float x2 = sx2[rl];
             const int asg = (x2 != x2 || bi == 0x7fffffff) ? -1 : bi;
             const float draw = cosine ? 2.0f * (1.0f - bv) : x2 - 2.0f * bv;
@@ -230,9 +181,8 @@ __global__ __launch_bounds__(256, NCT <= 2 ? 3 : NCT == 4 ? 2 : 1) void kmeans_a
             const float* xrow = xs + (4 * ks + cg) * KM_P + cc;
 #pragma unroll
             for (int i = 0; i < PPW; ++i) {
-                const int p = wave + 4 * i;
-                const int it = p / 6, jt = p - it * 6;
-                if (p < NPAIR && 16 * it < k) acc[i] = PF32::mma(sa == 16 * it + cc ? 1.0f : 0.f, xrow[16 * jt], acc[i]);
+                int it, jt;
+                if (feat_wave_pair<NCT>(wave, i, it, jt) && 16 * it < k) acc[i] = PF32::mma(sa == 16 * it + cc ? 1.0f : 0.f, xrow[16 * jt], acc[i]);
             }
         }
         if (tid < k) {
@@ -252,19 +202,8 @@ __global__ __launch_bounds__(256, NCT <= 2 ? 3 : NCT == 4 ? 2 : 1) void kmeans_a
         sred[(4 * wave + cg) * 2 + 1] = moved_acc;
     }
     float* out = a.slab + (long)blockIdx.x * (97 * k + 2);
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-        const int p = wave + 4 * i;
-        const int it = p / 6, jt = p - it * 6;
-        if (p < NPAIR) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int cls = 16 * it + 4 * cg + r;
-                if (cls < k) out[cls * KM_D + 16 * jt + cc] = acc[i][r];
-            }
-        }
-    }
-    if (tid < k) out[k * KM_D + tid] = (float)cnt;
+    feat_store_pairs<NCT, FEAT_D>(out, acc, k, wave, cc, cg);
+    if (tid < k) out[k * FEAT_D + tid] = (float)cnt;
     __syncthreads();
     if (tid == 0) {
         float ds = 0.f, mv = 0.f;
@@ -285,24 +224,24 @@ struct KmUpdateArgs {
 };
 
 __global__ __launch_bounds__(384) void kmeans_update_kernel(KmUpdateArgs a) {
-    __shared__ float spart[4][KM_D];
-    __shared__ float snew[KM_D];
-    __shared__ float sold[KM_D];
-    __shared__ float swg[2][KM_MAX_WGS];
+    __shared__ float spart[4][FEAT_D];
+    __shared__ float snew[FEAT_D];
+    __shared__ float sold[FEAT_D];
+    __shared__ float swg[2][FEAT_MAX_WGS];
     __shared__ long long scnt;
     const int tid = threadIdx.x;
     const int c = blockIdx.x, k = a.k;
     const int P = 97 * k + 2;
-    const int d = tid % KM_D, slice = tid / KM_D;
+    const int d = tid % FEAT_D, slice = tid / FEAT_D;
     float part = 0.f;
 #pragma unroll 8
-    for (int g = slice; g < a.nwg; g += 4) part += a.slab[(long)g * P + c * KM_D + d];   // the loads of eight rows in flight, the additions in order
+    for (int g = slice; g < a.nwg; g += 4) part += a.slab[(long)g * P + c * FEAT_D + d];   // the loads of eight rows in flight, the additions in order
     spart[slice][d] = part;
     for (int g = tid; g < a.nwg; g += 384) {
-        swg[0][g] = a.slab[(long)g * P + k * KM_D + c];
+        swg[0][g] = a.slab[(long)g * P + k * FEAT_D + c];
         if (c == 0) swg[1][g] = a.slab[(long)g * P + 97 * k];
     }
-    if (tid < KM_D) sold[tid] = a.cent[c * KM_D + tid];
+    if (tid < FEAT_D) sold[tid] = a.cent[c * FEAT_D + tid];
     __syncthreads();
     if (tid == 0) {
         long long n = 0;
@@ -314,7 +253,7 @@ __global__ __launch_bounds__(384) void kmeans_update_kernel(KmUpdateArgs a) {
             a.hist[0] = inertia;
         }
     }
-    if (tid < KM_D) snew[tid] = (spart[0][tid] + spart[1][tid]) + (spart[2][tid] + spart[3][tid]);
+    if (tid < FEAT_D) snew[tid] = (spart[0][tid] + spart[1][tid]) + (spart[2][tid] + spart[3][tid]);
     __syncthreads();
     if (c == 0) {   // moved: the second pass over the table's second row
         for (int g = tid; g < a.nwg; g += 384) swg[1][g] = a.slab[(long)g * P + 97 * k + 1];
@@ -322,20 +261,20 @@ __global__ __launch_bounds__(384) void kmeans_update_kernel(KmUpdateArgs a) {
     const long long n = scnt;
     float norm2 = 0.f;
     if (a.metric == MSST_KMEANS_COSINE) {
-        for (int i = 0; i < KM_D; ++i) norm2 = fmaf(snew[i], snew[i], norm2);   // every thread the same chain
+        for (int i = 0; i < FEAT_D; ++i) norm2 = fmaf(snew[i], snew[i], norm2);   // every thread the same chain
     }
     const bool keep = n == 0 || (a.metric == MSST_KMEANS_COSINE && !(norm2 > 0.f));
     __syncthreads();
-    if (tid < KM_D) {
+    if (tid < FEAT_D) {
         float v = sold[tid];
         if (!keep) v = a.metric == MSST_KMEANS_COSINE ? snew[tid] / sqrtf(norm2) : snew[tid] / (float)n;
         snew[tid] = v;
-        a.cent[c * KM_D + tid] = v;
+        a.cent[c * FEAT_D + tid] = v;
     }
     __syncthreads();
     if (tid == 0) {
         float c2 = 0.f, s2 = 0.f;
-        for (int i = 0; i < KM_D; ++i) {
+        for (int i = 0; i < FEAT_D; ++i) {
             c2 = fmaf(snew[i], snew[i], c2);
             const float df = snew[i] - sold[i];
             s2 = fmaf(df, df, s2);
@@ -365,7 +304,7 @@ struct KmPickArgs {
 
 __global__ __launch_bounds__(256) void kmeans_pick_kernel(KmPickArgs a) {
     __shared__ float sd[256];
-    __shared__ float sx[KM_D];
+    __shared__ float sx[FEAT_D];
     __shared__ int stab[128];
     __shared__ double st;          // t = u total, exact in double (24 x 24 bits)
     __shared__ float sbefore;      // the prefix of the blocks before
@@ -444,30 +383,22 @@ __global__ __launch_bounds__(256) void kmeans_pick_kernel(KmPickArgs a) {
     }
     __syncthreads();
     const long row = (long)sl[1];
-    if (tid < KM_D) sx[tid] = a.x[row * KM_D + tid];
+    if (tid < FEAT_D) sx[tid] = a.x[row * FEAT_D + tid];
     __syncthreads();
     float n2 = 0.f;
-    for (int i = 0; i < KM_D; ++i) n2 = fmaf(sx[i], sx[i], n2);   // every thread the same chain
+    for (int i = 0; i < FEAT_D; ++i) n2 = fmaf(sx[i], sx[i], n2);   // every thread the same chain
     const bool cosine = a.metric == MSST_KMEANS_COSINE;
-    if (tid < KM_D) a.cent[j * KM_D + tid] = (cosine && n2 > 0.f) ? sx[tid] / sqrtf(n2) : sx[tid];
+    if (tid < FEAT_D) a.cent[j * FEAT_D + tid] = (cosine && n2 > 0.f) ? sx[tid] / sqrtf(n2) : sx[tid];
     if (tid == 0) {
         a.bias[j] = cosine ? 0.f : -0.5f * n2;
         a.seed_rows[j] = (int32_t)row;
     }
 }
 
-size_t km_assign_lds(int nct) { return (size_t)4 * (16 * nct * KM_P + 64 * KM_P + 16 * nct + 64 + 64 + 32); }
-
 template <int NCT, int LAYOUT>
 int km_assign_launch(const KmAssignArgs& a, int nwg, hipStream_t st) {
-    static std::atomic<bool> done{false};
-    const size_t lds = km_assign_lds(NCT);
-    if (!done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&kmeans_assign_kernel<NCT, LAYOUT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) return (int)e;
-        done = true;
-    }
+    constexpr size_t lds = KmAssignLds<NCT>::bytes;
+    if (int e = feat_allow_lds<&kmeans_assign_kernel<NCT, LAYOUT>>(lds)) return e;
     hipLaunchKernelGGL((kmeans_assign_kernel<NCT, LAYOUT>), dim3((unsigned)nwg), dim3(256), lds, st, a);
     return (int)hipGetLastError();
 }
@@ -477,7 +408,7 @@ int km_assign_launch(const KmAssignArgs& a, int nwg, hipStream_t st) {
 long kmeans_scratch_floats(long rows, int k) {
     long per;
     int nwg;
-    km_partition(rows, &per, &nwg);
+    feat_partition(rows, &per, &nwg);
     return (long)nwg * (97 * k + 2);
 }
 
@@ -485,23 +416,21 @@ int launch_kmeans_assign(const float* x, int x_layout, long rows, long plane, co
                          int32_t* assign, float* dist, int64_t* classes, float* slab, hipStream_t st) {
     KmAssignArgs a;
     int nwg;
-    km_partition(rows, &a.tiles_per_wg, &nwg);
+    feat_partition(rows, &a.tiles_per_wg, &nwg);
     a.x = x; a.cent = centroids; a.bias = bias; a.assign = assign; a.dist = dist; a.classes = classes; a.slab = slab;
     a.rows = rows; a.plane = plane; a.k = k; a.metric = metric;
     const bool rows_layout = x_layout == 0;
-    switch (km_nct(k)) {
-        case 1: return rows_layout ? km_assign_launch<1, 0>(a, nwg, st) : km_assign_launch<1, 1>(a, nwg, st);
-        case 2: return rows_layout ? km_assign_launch<2, 0>(a, nwg, st) : km_assign_launch<2, 1>(a, nwg, st);
-        case 4: return rows_layout ? km_assign_launch<4, 0>(a, nwg, st) : km_assign_launch<4, 1>(a, nwg, st);
-        default: return rows_layout ? km_assign_launch<8, 0>(a, nwg, st) : km_assign_launch<8, 1>(a, nwg, st);
-    }
+    return feat_dispatch_nct(k, [&](auto n) {
+        constexpr int NCT = decltype(n)::value;
+        return rows_layout ? km_assign_launch<NCT, 0>(a, nwg, st) : km_assign_launch<NCT, 1>(a, nwg, st);
+    });
 }
 
 int launch_kmeans_update(const float* slab, long rows, int k, int metric, float* centroids, float* bias, int32_t* counts, float* shift,
                          float* history_row, hipStream_t st) {
     KmUpdateArgs a;
     long per;
-    km_partition(rows, &per, &a.nwg);
+    feat_partition(rows, &per, &a.nwg);
     a.slab = slab; a.cent = centroids; a.bias = bias; a.counts = counts; a.shift = shift; a.hist = history_row; a.k = k; a.metric = metric;
     hipLaunchKernelGGL(kmeans_update_kernel, dim3((unsigned)k), dim3(384), 0, st, a);
     return (int)hipGetLastError();
@@ -510,7 +439,7 @@ int launch_kmeans_update(const float* slab, long rows, int k, int metric, float*
 int launch_kmeans_pick(const float* x, long rows, const float* dist, const float* slab, int j, int metric, unsigned seed, float* centroids,
                        float* bias, int32_t* seed_rows, hipStream_t st) {
     KmPickArgs a;
-    km_partition(rows, &a.tiles_per_wg, &a.nwg);
+    feat_partition(rows, &a.tiles_per_wg, &a.nwg);
     a.x = x; a.dist = dist; a.slab = slab; a.cent = centroids; a.bias = bias; a.seed_rows = seed_rows; a.rows = rows; a.seed = seed;
     a.j = j; a.metric = metric;
     hipLaunchKernelGGL(kmeans_pick_kernel, dim3(1), dim3(256), 0, st, a);

@@ -10,9 +10,8 @@
 //             q[l & 15][4 ks + (l >> 4)] for the 24 k-steps in 24 registers, loaded once -- layout 0 from rows [Q][96], layout 1
 //             straight from the map [Bs][96][plane] (query b plane + p reads (b 96 + d) plane + p: the 16 lanes of a k-slice
 //             read 16 adjacent pixels).  Rows past Q read as zero and are never stored.
-//   bank      the slice is walked in tiles of 64 rows: 16-byte global loads into registers one tile ahead (issued before the
-//             MFMA loop, stored to LDS [64][98] after it; pitch 98 = 2 mod 32 puts the 32 lanes of a one-dword operand read on
-//             32 banks, see msst_attn_maps.hip), rows past the slice's end are zero and masked by index below.
+//   bank      the slice is walked in tiles of 64 rows with the rows-layout tile loader of msst_feat.h (one tile ahead in registers,
+//             LDS [64][98]); rows past the slice's end are zero and masked by index below.
 //   scores    per tile 24 k-steps x 4 column tiles: c[jt] = mma(q_ks, bank[16 jt + (l & 15)][4 ks + (l >> 4)], c[jt]), ks
 //             ascending from a zero accumulator, so s(q, m) is the fp32 fmaf chain over d = 0 .. 95 in order whatever tile,
 //             wave, workgroup or slice the pair lands in.  Lane l then holds s for queries 4 (l >> 4) + r, bank rows 16 jt + (l & 15).
@@ -25,26 +24,32 @@
 //   output    splits == 1: the lists are the result.  Otherwise slice s writes its list to scratch [s][query][k] and
 // knn_merge   one thread per (query, slice, entry) counts the entries of all slices ahead of its own under the same order
 //             (absent entries rank last, by slice and place) and stores it at that rank if below k: every output slot is written
-//             exactly once, nothing is initialised.
+//             exactly once, nothing is initialised.  The order is msst_feat.h's feat_ahead.
 // knn_vote    64 queries per workgroup, one thread per query: votes in LDS [64][n_classes + 1], w_j = exp((s_j - s_1) / temperature)
 //             (temperature 0: 1) added in rank order j = 1 .. k in fp32, argmax with ties to the lowest class (-1 without
-//             neighbours); the table is stored by all threads, rows [Q][n_classes] or the map [Bs][n_classes][plane].
+//             neighbours); the table is stored by all threads, rows [Q][n_classes] or the map [Bs][n_classes][plane] (msst_feat.h).
 // Queries are processed in chunks of 32,768 inside the call (grids stay small, the scratch is one chunk's).
 // No inline assembly.
 #include "../../include/msst.h"
-#include "msst_dev.h"
+#include "msst_feat.h"
 #include "msst_kernels.h"
 
 namespace msst {
 
 namespace {
 
-constexpr int KNN_D = 96;
 constexpr int KNN_BP = 98;             // LDS pitch of a bank row
 constexpr long KNN_QCHUNK = 32768;     // queries per launch
 constexpr int KNN_MAX_SPLITS = 64;
 constexpr int KNN_AUTO_MAX_SPLITS = 32;
-constexpr int KNN_TARGET_WGS = 512;    // 256 CUs x 2
+
+// the LDS of knn_topk_kernel, offsets in floats
+struct KnnTopkLds {
+    static constexpr int bank = 0;                                             // [64][KNN_BP]
+    static constexpr int sim = bank + 64 * KNN_BP;                             // [64][k]
+    __host__ __device__ static constexpr int idx(int k) { return sim + 64 * k; }   // [64][k] int
+    static constexpr size_t bytes(int k) { return (size_t)4 * (idx(k) + 64 * k); }
+};
 
 struct KnnTopkArgs {
     const float* bank;
@@ -55,15 +60,11 @@ struct KnnTopkArgs {
     int nq, k, q_layout;
 };
 
-__device__ __forceinline__ bool knn_ahead(float s, int i, float es, int ei) {   // (s, i) ranks before (es, ei)
-    return s > es || (s == es && i < ei);
-}
-
 __global__ __launch_bounds__(256) void knn_topk_kernel(KnnTopkArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float* sbank = reinterpret_cast<float*>(smem_raw);               // [64][KNN_BP]
-    float* lsim = sbank + 64 * KNN_BP;                               // [64][k]
-    int* lidx = reinterpret_cast<int*>(lsim + 64 * a.k);             // [64][k]
+    float* smem = reinterpret_cast<float*>(smem_raw);
+    float *sbank = smem + KnnTopkLds::bank, *lsim = smem + KnnTopkLds::sim;
+    int* lidx = reinterpret_cast<int*>(smem + KnnTopkLds::idx(a.k));
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cg = lane >> 4, cc = lane & 15;
     const int k = a.k;
@@ -81,11 +82,11 @@ __global__ __launch_bounds__(256) void knn_topk_kernel(KnnTopkArgs a) {
         const float* src;
         long kstride;
         if (a.q_layout == 0) {
-            src = a.queries + q * KNN_D;
+            src = a.queries + q * FEAT_D;
             kstride = 1;
         } else {
             const long b = q / a.plane, p = q - b * a.plane;
-            src = a.queries + b * KNN_D * a.plane + p;
+            src = a.queries + b * FEAT_D * a.plane + p;
             kstride = a.plane;
         }
 #pragma unroll
@@ -101,32 +102,15 @@ __global__ __launch_bounds__(256) void knn_topk_kernel(KnnTopkArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) { thr_s[r] = -INFINITY; thr_i[r] = -1; }
 
-    // ---- bank tile loads: element e = tid + 256 i of the tile's 64 x 24 16-byte pieces
     f32x4 pre[6];
-    auto load_tile = [&](long m0) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int e = tid + 256 * i;
-            const int row = e / 24, c4 = e - row * 24;
-            const long m = m0 + row;
-            pre[i] = m < mend ? *reinterpret_cast<const f32x4*>(a.bank + m * KNN_D + 4 * c4) : zero4();
-        }
-    };
-    if (ntiles > 0) load_tile(mbeg);
+    if (ntiles > 0) feat_rows_prefetch(pre, a.bank, mbeg, mend, tid);
 
     for (long t = 0; t < ntiles; ++t) {
         const long m0 = mbeg + t * 64;
         __syncthreads();   // the previous tile's operand reads are done
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int e = tid + 256 * i;
-            const int row = e / 24, c4 = e - row * 24;
-            float* d = sbank + row * KNN_BP + 4 * c4;   // rows of pitch 98 floats start on 8 bytes
-            *reinterpret_cast<float2*>(d) = make_float2(pre[i][0], pre[i][1]);
-            *reinterpret_cast<float2*>(d + 2) = make_float2(pre[i][2], pre[i][3]);
-        }
+        feat_rows_store<KNN_BP>(sbank, pre, tid);
         __syncthreads();
-        if (t + 1 < ntiles) load_tile(m0 + 64);
+        if (t + 1 < ntiles) feat_rows_prefetch(pre, a.bank, m0 + 64, mend, tid);
         // ---- scores of 16 queries x 64 bank rows
         f32x4 c[4];
 #pragma unroll
@@ -145,7 +129,7 @@ __global__ __launch_bounds__(256) void knn_topk_kernel(KnnTopkArgs a) {
             for (int jt = 0; jt < 4; ++jt) {
                 const float s = c[jt][r];
                 const long m = m0 + 16 * jt + cc;
-                const bool pass = m < mend && knn_ahead(s, (int)m, thr_s[r], thr_i[r]);
+                const bool pass = m < mend && feat_ahead(s, (int)m, thr_s[r], thr_i[r]);
                 unsigned long long b = __ballot(pass);
                 while (b) {   // wave-uniform
                     const int leader = __ffsll(b) - 1;
@@ -158,7 +142,7 @@ __global__ __launch_bounds__(256) void knn_topk_kernel(KnnTopkArgs a) {
                     const bool mine = lane < k;
                     const float es = mine ? ls[lane] : 0.f;
                     const int ei = mine ? li[lane] : 0;
-                    const int pos = __popcll(__ballot(mine && !knn_ahead(cs, ci, es, ei)));   // entries ahead: a prefix of the sorted list
+                    const int pos = __popcll(__ballot(mine && !feat_ahead(cs, ci, es, ei)));   // entries ahead: a prefix of the sorted list
                     if (pos >= k) continue;
                     const float ps = __shfl_up(es, 1);
                     const int pi = __shfl_up(ei, 1);
@@ -218,7 +202,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(KnnMergeArgs a) {
             const int e2 = s2 * a.k + j2;
             bool ahead;
             if (ei < 0) ahead = i < 0 && e2 < e;       // absent entries rank last, by slice and place
-            else ahead = i < 0 || knn_ahead(es, ei, s, i);
+            else ahead = i < 0 || feat_ahead(es, ei, s, i);
             rank += ahead ? 1 : 0;
         }
     }
@@ -271,15 +255,7 @@ __global__ __launch_bounds__(64) void knn_vote_kernel(KnnVoteArgs a) {
     }
     __syncthreads();
     const long nq = min((long)64, a.Q - q0);
-    if (a.vote_layout == 0) {
-        for (long e = tid; e < nq * nc; e += 64) {
-            const int ql = (int)(e / nc), c = (int)(e - (long)ql * nc);
-            a.votes[q0 * nc + e] = sv[ql * pitch + c];
-        }
-    } else if (q < a.Q) {
-        const long b = q / a.plane, p = q - b * a.plane;
-        for (int c = 0; c < nc; ++c) a.votes[(b * nc + c) * a.plane + p] = v[c];
-    }
+    feat_store_table<64>(sv, pitch, a.votes, a.vote_layout, q0, nq, nc, a.plane, tid);
 }
 
 int knn_splits_for(long nq, long M, int splits) {
@@ -287,7 +263,7 @@ int knn_splits_for(long nq, long M, int splits) {
     long s = splits;
     if (s <= 0) {
         const long qtiles = (nq + 63) / 64;
-        s = (KNN_TARGET_WGS + qtiles - 1) / qtiles;
+        s = (FEAT_MAX_WGS + qtiles - 1) / qtiles;
         if (s > KNN_AUTO_MAX_SPLITS) s = KNN_AUTO_MAX_SPLITS;
     }
     if (s > mtiles) s = mtiles;   // a slice is whole tiles; more slices than tiles would be empty ones
@@ -301,13 +277,13 @@ long knn_scratch_bytes(long Q, long M, int k, int splits) {
     const long nq = Q < KNN_QCHUNK ? Q : KNN_QCHUNK;
     if (splits == 1) return 0;
     // splits = 0: the automatic choice takes at most ceil(512 / ceil(nq / 64)) <= 512 * 64 / nq + 1 slices, so nq + 32768 rows hold it
-    const long rows = splits > 0 ? nq * splits : nq + KNN_TARGET_WGS * 64;
+    const long rows = splits > 0 ? nq * splits : nq + FEAT_MAX_WGS * 64;
     return rows * k * 8;
 }
 
 int launch_knn_topk(const float* bank, long M, const float* queries, int q_layout, long Q, long plane, int k, int splits,
                     int32_t* nbr_idx, float* nbr_sim, void* scratch, hipStream_t st) {
-    const size_t lds = (size_t)64 * KNN_BP * 4 + (size_t)64 * k * 8;
+    const size_t lds = KnnTopkLds::bytes(k);
     for (long q0 = 0; q0 < Q; q0 += KNN_QCHUNK) {
         const int nq = (int)(Q - q0 < KNN_QCHUNK ? Q - q0 : KNN_QCHUNK);
         const int sp = knn_splits_for(nq, M, splits);

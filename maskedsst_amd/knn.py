@@ -13,16 +13,14 @@ exists, and ``knn_predict_scene`` reads the ``encode_scene`` map [Bs, 96, Hs, Ws
 similarity descending and then bank index ascending, so ties have a fixed answer and every output has the same bits in every
 call, for every ``splits`` and for a query whatever batch it sits in.  There is no CPU or eager fallback.
 """
-import ctypes
 from collections import namedtuple
 
 import torch
 
 from . import _lib
+from .features import DIM, MAX_CLASSES, KnnBank, _bank_from_scenes, _is_int, _p, _stream, _require_cuda, check_rows, on_scene_map  # noqa: F401
 
-DIM = 96          # the encoder's feature width: the only one msst_knn_topk takes
 MAX_K = 64        # include/msst.h: msst_knn_topk
-MAX_CLASSES = 128
 MAX_SPLITS = 64
 
 # classes [Q] int64 (-1: a query without neighbours, i.e. one with a NaN channel), votes [Q, n_classes] fp32,
@@ -30,58 +28,6 @@ MAX_SPLITS = 64
 KnnResult = namedtuple("KnnResult", ["classes", "votes", "index", "sim"])
 # classes [Bs, Hs, Ws] int64 (-1 where no window covers the pixel), votes [Bs, n_classes, Hs, Ws] fp32, cover [Bs, Hs, Ws] int32
 KnnScene = namedtuple("KnnScene", ["classes", "votes", "cover"])
-
-
-def _require_cuda(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"maskedsst_amd runs on an MI355X only ({what} is on {t.device}); there is no CPU fallback")
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(0)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _is_int(v):
-    return not isinstance(v, bool) and isinstance(v, int)
-
-
-class KnnBank:
-    """A bank of labelled features: features [M, 96] fp32 contiguous on the device (unit length for cosine similarity; the
-    kernels take any finite values), labels [M] integers in [0, n_classes).  One check at construction, with one read-back:
-    ValueError for a label outside the range or a feature that is not finite.  CPU tensors raise RuntimeError."""
-
-    def __init__(self, features, labels, n_classes):
-        if not torch.is_tensor(features) or features.dim() != 2 or features.shape[1] != DIM:
-            raise ValueError(f"features must be a 2-D tensor [M, {DIM}], got {getattr(features, 'shape', type(features))}")
-        if features.dtype != torch.float32:
-            raise ValueError(f"features must be float32, got {features.dtype}")
-        if features.shape[0] < 1:
-            raise ValueError("the bank needs at least one row")
-        if not torch.is_tensor(labels) or labels.dim() != 1 or labels.shape[0] != features.shape[0]:
-            raise ValueError(f"labels must be a 1-D tensor [{features.shape[0]}], got {getattr(labels, 'shape', type(labels))}")
-        if labels.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
-            raise ValueError(f"labels must be integers, got {labels.dtype}")
-        if not _is_int(n_classes) or not 1 <= n_classes <= MAX_CLASSES:
-            raise ValueError(f"n_classes must be an integer in [1, {MAX_CLASSES}], got {n_classes!r}")
-        if not features.is_contiguous():
-            raise ValueError("features must be contiguous")
-        _require_cuda(features, "the bank's features")
-        _require_cuda(labels, "the bank's labels")
-        bad = torch.stack([((labels < 0) | (labels >= n_classes)).any(), ~torch.isfinite(features).all()]).tolist()
-        if bad[0]:
-            raise ValueError(f"labels must lie in [0, {n_classes})")
-        if bad[1]:
-            raise ValueError("features must be finite (drop the uncovered pixels of encode_scene: cover == 0)")
-        self.features = features
-        self.labels = labels.to(torch.int32).contiguous()
-        self.n_classes = n_classes
-
-    def __len__(self):
-        return self.features.shape[0]
 
 
 def _check_bank(bank):
@@ -125,12 +71,7 @@ def knn_classify(bank, queries, k=20, temperature=0.07, splits=None):
     the same bits for every value.  ValueError, before any device work, for a wrong rank, width, dtype, k, temperature or splits;
     RuntimeError for CPU tensors."""
     _check_bank(bank)
-    if not torch.is_tensor(queries) or queries.dim() != 2 or queries.shape[1] != DIM:
-        raise ValueError(f"queries must be a 2-D tensor [Q, {DIM}], got {getattr(queries, 'shape', type(queries))}")
-    if queries.dtype != torch.float32:
-        raise ValueError(f"queries must be float32, got {queries.dtype}")
-    if not queries.is_contiguous():
-        raise ValueError("queries must be contiguous")
+    check_rows(queries, "queries", shape=f"[Q, {DIM}]")
     _check_k(k, temperature, splits)
     _require_cuda(queries, "queries")
     Q = queries.shape[0]
@@ -142,16 +83,17 @@ def knn_classify(bank, queries, k=20, temperature=0.07, splits=None):
 
 def knn_predict_scene(model, scene, bank, k=20, temperature=0.07, stride=None, max_windows=None):
     """See ViTSpatialSpectral.knn_predict_scene."""
-    from .scene import encode_scene, SCENE_MAX_WINDOWS
     _check_bank(bank)
     _check_k(k, temperature, None)
-    emb = encode_scene(model, scene, stride, True, SCENE_MAX_WINDOWS if max_windows is None else max_windows)
-    Bs, _, Hs, Ws = emb.features.shape
-    dev = emb.features.device
-    votes = torch.empty(Bs, bank.n_classes, Hs, Ws, dtype=torch.float32, device=dev)
-    classes = torch.empty(Bs, Hs, Ws, dtype=torch.int64, device=dev)
-    knn_launch(bank, emb.features, 1, Bs * Hs * Ws, Hs * Ws, k, temperature, None, votes, 1, classes)
-    return KnnScene(classes, votes, emb.cover)
+
+    def launch(emb, Bs, Hs, Ws):
+        dev = emb.features.device
+        votes = torch.empty(Bs, bank.n_classes, Hs, Ws, dtype=torch.float32, device=dev)
+        classes = torch.empty(Bs, Hs, Ws, dtype=torch.int64, device=dev)
+        knn_launch(bank, emb.features, 1, Bs * Hs * Ws, Hs * Ws, k, temperature, None, votes, 1, classes)
+        return KnnScene(classes, votes, emb.cover)
+
+    return on_scene_map(model, scene, stride, True, max_windows, launch)
 
 
 def feature_bank(model, scenes, labels, stride=None, ignored_label=-1, per_class=None, generator=None):
@@ -161,33 +103,3 @@ def feature_bank(model, scenes, labels, stride=None, ignored_label=-1, per_class
     one), rows kept in pixel order.  n_classes is the model's num_classes.  ValueError for labels of the wrong shape or dtype, or
     when no pixel is left."""
     return _bank_from_scenes(model, scenes, labels, stride, ignored_label, per_class, generator, True)
-
-
-def _bank_from_scenes(model, scenes, labels, stride, ignored_label, per_class, generator, normalize):
-    """feature_bank (normalize=True) and maskedsst_amd.probe_bank (normalize=False: the raw features the head consumes)"""
-    if not torch.is_tensor(scenes) or scenes.dim() != 4:
-        raise ValueError(f"scenes must be a 4-D tensor [scenes, bands, H, W], got {getattr(scenes, 'shape', type(scenes))}")
-    if not torch.is_tensor(labels) or labels.dim() != 3 or labels.shape != (scenes.shape[0],) + tuple(scenes.shape[2:]):
-        raise ValueError(f"labels must be a 3-D tensor [scenes, H, W] matching the scenes, got {getattr(labels, 'shape', type(labels))}")
-    if labels.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
-        raise ValueError(f"labels must be integers, got {labels.dtype}")
-    if per_class is not None and (not _is_int(per_class) or per_class < 1):
-        raise ValueError(f"per_class must be None or a positive integer, got {per_class!r}")
-    emb = model.encode_scene(scenes, stride=stride, normalize=normalize)
-    labels = labels.to(emb.features.device)
-    ok = (emb.cover > 0) & (labels != ignored_label)
-    feats = emb.features.permute(0, 2, 3, 1)[ok].contiguous()
-    labs = labels[ok].long()
-    if per_class is not None and len(labs):
-        lab_cpu = labs.cpu()
-        keep = torch.zeros(len(lab_cpu), dtype=torch.bool)
-        for c in torch.unique(lab_cpu).tolist():
-            rows = torch.nonzero(lab_cpu == c).reshape(-1)
-            if len(rows) > per_class:
-                rows = rows[torch.randperm(len(rows), generator=generator)[:per_class]]
-            keep[rows] = True
-        keep = keep.to(feats.device)
-        feats, labs = feats[keep].contiguous(), labs[keep]
-    if len(labs) == 0:
-        raise ValueError("no covered, labelled pixel to put into the bank")
-    return KnnBank(feats, labs, int(model.num_classes))

@@ -25,7 +25,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from .knn import KnnBank, DIM, MAX_CLASSES, _require_cuda, _p, _stream, _is_int, _bank_from_scenes
+from .features import DIM, MAX_CLASSES, KnnBank, _bank_from_scenes, _is_int, _p, _stream, _require_cuda, check_rows, on_scene_map
 
 # classes [Bs, Hs, Ws] int64 (-1 where no window covers the pixel), logits [Bs, n_classes, Hs, Ws] fp32 (NaN there), cover [Bs, Hs, Ws] int32
 ProbeScene = namedtuple("ProbeScene", ["classes", "logits", "cover"])
@@ -111,12 +111,7 @@ class LinearProbe:
         return LinearProbe(self.theta.clone(), self.n_classes, self.m.clone(), self.v.clone(), self.step.clone(), self.history)
 
     def _forward(self, features):
-        if not torch.is_tensor(features) or features.dim() != 2 or features.shape[1] != DIM or features.shape[0] < 1:
-            raise ValueError(f"features must be a 2-D tensor [Q, {DIM}] with Q >= 1, got {getattr(features, 'shape', type(features))}")
-        if features.dtype != torch.float32:
-            raise ValueError(f"features must be float32, got {features.dtype}")
-        if not features.is_contiguous():
-            raise ValueError("features must be contiguous")
+        check_rows(features, "features", 1, shape=f"[Q, {DIM}] with Q >= 1")
         _require_cuda(features, "features")
         _require_cuda(self.theta, "the probe")
         Q = features.shape[0]
@@ -327,14 +322,15 @@ def probe_bank(model, scenes, labels, stride=None, ignored_label=-1, per_class=N
 
 def probe_predict_scene(model, scene, probe, stride=None, max_windows=None):
     """See ViTSpatialSpectral.probe_predict_scene."""
-    from .scene import encode_scene, SCENE_MAX_WINDOWS
     if not isinstance(probe, LinearProbe):
         raise ValueError(f"probe must be a LinearProbe, got {type(probe).__name__}")
-    emb = encode_scene(model, scene, stride, False, SCENE_MAX_WINDOWS if max_windows is None else max_windows)
-    _require_cuda(probe.theta, "the probe")
-    Bs, _, Hs, Ws = emb.features.shape
-    dev = emb.features.device
-    logits = torch.empty(Bs, probe.n_classes, Hs, Ws, dtype=torch.float32, device=dev)
-    classes = torch.empty(Bs, Hs, Ws, dtype=torch.int64, device=dev)
-    probe_forward(probe, emb.features, 1, Bs * Hs * Ws, Hs * Ws, logits, 1, classes)
-    return ProbeScene(classes, logits, emb.cover)
+
+    def launch(emb, Bs, Hs, Ws):
+        _require_cuda(probe.theta, "the probe")
+        dev = emb.features.device
+        logits = torch.empty(Bs, probe.n_classes, Hs, Ws, dtype=torch.float32, device=dev)
+        classes = torch.empty(Bs, Hs, Ws, dtype=torch.int64, device=dev)
+        probe_forward(probe, emb.features, 1, Bs * Hs * Ws, Hs * Ws, logits, 1, classes)
+        return ProbeScene(classes, logits, emb.cover)
+
+    return on_scene_map(model, scene, stride, False, max_windows, launch)

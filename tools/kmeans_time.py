@@ -27,7 +27,7 @@ sys.path.insert(0, ROOT)
 
 from maskedsst_amd import _lib, fit_kmeans  # noqa: E402
 from maskedsst_amd import cluster  # noqa: E402
-from maskedsst_amd.knn import _p, _stream  # noqa: E402
+from maskedsst_amd.features import _p, _stream  # noqa: E402
 
 SEED = 5
 CHUNK = 65536

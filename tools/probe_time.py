@@ -29,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from maskedsst_amd import KnnBank, LinearProbe, ViTSpatialSpectral, _lib, fit_linear_probe  # noqa: E402
-from maskedsst_amd.knn import _p, _stream  # noqa: E402
+from maskedsst_amd.features import _p, _stream  # noqa: E402
 
 SEED = 5
 
