@@ -116,6 +116,11 @@ def build_parser():
                          "(maskedsst_amd.fit_kmeans, K clusters, cosine, k-means++) on the covered pixels of the first half of the "
                          "--val-scenes, the second half assigned and matched to the classes (Hungarian accuracy, purity, NMI); the split "
                          "of --val-embed; needs --val-scenes and --val-every")
+    ap.add_argument("--val-pca", type=int, default=0, metavar="R",
+                    help="one more line per validation: the spectrum of the frozen features' covariance, no label read: "
+                         "maskedsst_amd.fit_pca on the covered pixels of the first half of the --val-scenes (the R leading "
+                         "explained-variance ratios and the effective rank), then the mean and largest RX anomaly score of the second "
+                         "half under that fit; needs --val-scenes and --val-every")
     ap.add_argument("--val-saliency", action="store_true",
                     help="one more line per validation: the five bands with the largest mean |gradient x input| attribution "
                          "(maskedsst_amd.band_importance, argmax class) over the windows of the --val-scenes")
@@ -229,6 +234,7 @@ def main():
     check_val_knn(args)
     check_val_probe(args)
     check_val_cluster(args)
+    check_val_pca(args)
     if not 0.0 <= args.label_smoothing < 1.0:
         raise SystemExit("--label-smoothing must lie in [0, 1)")
     # --class-weights inverse: the weights come from the first step's labels, so the criterion is made there
@@ -286,6 +292,8 @@ def main():
                 validate_probe(model, val, step, args.val_probe, config.n_classes, config.ignored_label)
             if args.val_cluster:
                 validate_cluster(model, val, step, args.val_cluster, config.n_classes, config.ignored_label)
+            if args.val_pca:
+                validate_pca(model, val, step, args.val_pca)
             if args.val_saliency:
                 validate_saliency(model, val, step)
             if args.val_saliency_scene:
@@ -483,6 +491,38 @@ def validate_cluster(model, val, step, k, n_classes, ignored_label, iters=50):
         acc, purity, nmi, inertia = m.accuracy, m.purity, m.nmi, km.inertia
     print(f"val-cluster step {step} k {k} cluster_acc {acc:.3f} purity {purity:.3f} nmi {nmi:.3f} inertia {inertia:.4g} "
           f"test_pixels {len(lte)} train_pixels {len(ftr)} scenes {val[0].shape[0]}", flush=True)
+
+
+def check_val_pca(args):
+    if not args.val_pca:
+        return
+    if not 1 <= args.val_pca <= 96:
+        raise SystemExit("--val-pca R must lie in [1, 96]")
+    if args.val_scenes < 1 or args.val_every < 1:
+        raise SystemExit("--val-pca reads the validation scenes: it needs --val-scenes and --val-every")
+
+
+def validate_pca(model, val, step, r):
+    """--val-pca R: the label-free health check of the frozen features.  One encode_scene pass (raw features, eval forward, the
+    module's mode untouched); maskedsst_amd.fit_pca reads the map of the first half of the scenes in place (uncovered pixels skipped,
+    no label read): the R leading explained-variance ratios and the effective rank (exp of the entropy of the normalised eigenvalues:
+    1 for a collapsed encoder, 96 for an isotropic one).  The second half is scored under that fit by the RX detector
+    (FeaturePCA.mahalanobis on its map): the mean and the largest score over its covered pixels.  nan with fewer than two scenes or
+    fewer than two covered pixels in the first half."""
+    from maskedsst_amd import fit_pca
+    emb = model.encode_scene(val[0], normalize=False)
+    half = val[0].shape[0] // 2
+    rows, evr, erank, rx_mean, rx_max = 0, [float("nan")] * r, float("nan"), float("nan"), float("nan")
+    if half >= 1 and int((emb.cover[:half] > 0).sum()) >= 2:
+        pca = fit_pca(emb.features[:half].contiguous())
+        rows, evr, erank = pca.count, pca.explained_variance_ratio[:r].tolist(), pca.effective_rank
+        if pca.rank >= 1:
+            score = pca.mahalanobis(emb.features[half:].contiguous())
+            score = score[emb.cover[half:] > 0]
+            if len(score):
+                rx_mean, rx_max = float(score.double().mean()), float(score.max())
+    print(f"val-pca step {step} rows {rows} evr {' '.join(f'{v:.4f}' for v in evr)} effective_rank {erank:.3f} rx_mean {rx_mean:.4g} "
+          f"rx_max {rx_max:.4g} scenes {val[0].shape[0]}", flush=True)
 
 
 def validate_saliency(model, val, step, batch=256, top=5):

@@ -495,6 +495,42 @@ int msst_kmeans_update(const float* slab, long slab_floats, long rows, int dim, 
 int msst_kmeans_pick(const float* x, long rows, int dim, const float* dist, const float* slab, long slab_floats, int j, int k, int metric,
                      uint32_t seed, float* centroids, float* bias, int32_t* seed_rows, void* stream);
 
+/* Second-order statistics of frozen features (maskedsst_amd/pca.py: fit_pca, FeaturePCA, ViTSpatialSpectral.pca_scene and
+ * anomaly_scene).  Additive under MSST_VERSION 109: no struct and no existing signature changes.  dim == 96, fp32; nothing uses atomics
+ * and every output has the same bits in every call.  x_layout = 0: rows [rows][96] (16-byte aligned); x_layout = 1: the encode_scene
+ * map [rows / plane][96][plane] read in place.
+ *
+ * msst_feat_moments.  One pass over x.  c = x - centre (centre [96]; null: zeros) is formed in fp32; a row with a channel that is
+ * not finite (a pixel no window covers) is skipped and not counted.  Every workgroup writes one slab row [n (int32 bits) | s1 96 |
+ * s2 96 x 96]: the number of counted rows, s1[d] = sum c[d] and s2[i][j] = sum c[i] c[j], the latter on v_mfma_f32_16x16x4_f32 with the
+ * row as the k index, so an entry is the fp32 fmaf chain of its rows in row order; s2 is symmetric bit for bit.  The workgroups own
+ * whole 64-row tiles and the partition depends on `rows` alone: msst_feat_moments_scratch_floats(rows) floats in all (0 for
+ * arguments the calls refuse).
+ *
+ * msst_feat_moments_finish.  Sums the slab rows in workgroup order in double and writes count [1] (int64), mean[d] = centre[d] +
+ * s1[d] / n, and, when not null, cov [96][96] = (s2[i][j] - s1[i] s1[j] / n) / (n - ddof), evaluated in double and rounded once, and
+ * raw [96 + 96 x 96] = [s1 | s2] rounded to fp32.  `centre` is the pointer the moments call was given.  n - ddof <= 0: cov is NaN;
+ * n == 0: the mean is NaN.  The centred two-pass covariance is four launches: moments (null centre), finish (the mean), moments
+ * (centre = that mean), finish (cov; the residual s1 of the second pass is the correction term, not assumed zero).
+ *
+ * msst_feat_project.  out[q][j] = sum_d (x[q][d] - mean[d]) components[j][d], components [r][96], 1 <= r <= 96: the subtraction in
+ * fp32, the sum the fmaf chain over d = 0 .. 95 in order from a zero accumulator.  out (null: not wanted) is rows [rows][r]
+ * (out_layout 0) or a map [rows / plane][r][plane] (out_layout 1); sumsq [rows] (null: not wanted) = sum_j out[q][j]^2 in an order
+ * that depends on r alone.  A row with a channel that is not finite gets NaN in every output; a row's outputs have the same bits
+ * whatever batch or layout it sits in.
+ *
+ * Checked before any HIP call, in this order: MSST_ERR_BADARG for rows or dim below 1 or a negative ddof; MSST_ERR_UNSUPPORTED
+ * outside dim == 96, 1 <= r <= 96, rows <= 2^31 - 1; MSST_ERR_BADARG for a layout outside {0, 1}, in layout 1 a plane below 1 or not
+ * dividing rows, a null or misaligned required pointer, both outputs null, a slab smaller than msst_feat_moments_scratch_floats.
+ * msst_last_error names the call. */
+long msst_feat_moments_scratch_floats(long rows);
+int msst_feat_moments(const float* x, int x_layout, long rows, long plane, int dim, const float* centre, float* slab, long slab_floats,
+                      void* stream);
+int msst_feat_moments_finish(const float* slab, long slab_floats, long rows, int dim, const float* centre, int ddof, int64_t* count,
+                             float* mean, float* cov, float* raw, void* stream);
+int msst_feat_project(const float* x, int x_layout, long rows, long plane, int dim, const float* mean, const float* components, int r,
+                      float* out, int out_layout, float* sumsq, void* stream);
+
 /* a7-a10: one fused pre-norm transformer block (PreNorm+Attention+FeedForward+residuals,
  * vit_spatial_spectral.py:22-104) over all B*S*N tokens; mode selects the spatial or spectral
  * sequence grouping of vit_spatial_spectral.py:410-431 (no transposes are materialised).

@@ -18,6 +18,7 @@ from .attention import AttentionMaps, attention_rollout, attention_received  # n
 from .knn import KnnBank, KnnResult, KnnScene, feature_bank, knn_classify, knn_predict_scene  # noqa: F401
 from .probe import LinearProbe, ProbeScene, fit_linear_probe, probe_bank, probe_gradient, probe_predict_scene  # noqa: F401
 from .cluster import KMeans, ClusterScene, ClusterMatch, fit_kmeans, cluster_scene, contingency, match_clusters  # noqa: F401
+from .pca import FeaturePCA, PcaScene, AnomalyScene, fit_pca, pca_scene, anomaly_scene  # noqa: F401
 
 __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "MaskGenerator", "Reconstruction", "recon_report",
            "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows", "SceneEmbedding",
@@ -26,4 +27,5 @@ __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "
            "GradAccumulator", "micro_masks", "DeviceMasks",
            "KnnBank", "KnnResult", "KnnScene", "feature_bank", "knn_classify", "knn_predict_scene",
            "LinearProbe", "ProbeScene", "fit_linear_probe", "probe_bank", "probe_gradient", "probe_predict_scene",
-           "KMeans", "ClusterScene", "ClusterMatch", "fit_kmeans", "cluster_scene", "contingency", "match_clusters"]
+           "KMeans", "ClusterScene", "ClusterMatch", "fit_kmeans", "cluster_scene", "contingency", "match_clusters",
+           "FeaturePCA", "PcaScene", "AnomalyScene", "fit_pca", "pca_scene", "anomaly_scene"]

@@ -698,6 +698,52 @@ int msst_kmeans_pick(const float* x, long rows, int dim, const float* dist, cons
     return fail(launch_kmeans_pick(x, rows, dist, slab, j, metric, seed, centroids, bias, seed_rows, (hipStream_t)stream), "msst_kmeans_pick");
 }
 
+long msst_feat_moments_scratch_floats(long rows) {
+    if (rows < 1 || rows > 2147483647L) return 0;
+    return feat_moments_scratch_floats(rows);
+}
+
+// the sizes of the three calls on the moments and projections of frozen features: r is 1 where the call has none
+static int pca_shape(const char* what, long rows, int dim, int r, int ddof = 0) {
+    if (rows < 1 || dim < 1 || ddof < 0) return fail(MSST_ERR_BADARG, what, " (rows or dim below 1, or a negative ddof)");
+    if (dim != 96 || r < 1 || r > 96 || rows > 2147483647L) return fail(MSST_ERR_UNSUPPORTED, what, " (dim == 96, 1 <= r <= 96, rows <= 2^31 - 1)");
+    return 0;
+}
+
+int msst_feat_moments(const float* x, int x_layout, long rows, long plane, int dim, const float* centre, float* slab, long slab_floats,
+                      void* stream) {
+    if (int rc = pca_shape("msst_feat_moments", rows, dim, 1)) return rc;
+    if (int rc = feat_layout("msst_feat_moments", "x_layout", "rows", rows, plane, x_layout)) return rc;
+    if (!x || !slab || ((uintptr_t)x & (x_layout == 0 ? 15 : 3)) || ((uintptr_t)centre & 3) || ((uintptr_t)slab & 3))
+        return fail(MSST_ERR_BADARG, "msst_feat_moments (null or misaligned argument)");
+    if (slab_floats < feat_moments_scratch_floats(rows))
+        return fail(MSST_ERR_BADARG, "msst_feat_moments (slab smaller than msst_feat_moments_scratch_floats)");
+    return fail(launch_feat_moments(x, x_layout, rows, plane, centre, slab, (hipStream_t)stream), "msst_feat_moments");
+}
+
+int msst_feat_moments_finish(const float* slab, long slab_floats, long rows, int dim, const float* centre, int ddof, int64_t* count,
+                             float* mean, float* cov, float* raw, void* stream) {
+    if (int rc = pca_shape("msst_feat_moments_finish", rows, dim, 1, ddof)) return rc;
+    if (!slab || !count || !mean || ((uintptr_t)slab & 3) || ((uintptr_t)centre & 3) || ((uintptr_t)count & 7) || ((uintptr_t)mean & 3) ||
+        ((uintptr_t)cov & 3) || ((uintptr_t)raw & 3))
+        return fail(MSST_ERR_BADARG, "msst_feat_moments_finish (null or misaligned argument)");
+    if (slab_floats < feat_moments_scratch_floats(rows))
+        return fail(MSST_ERR_BADARG, "msst_feat_moments_finish (slab smaller than msst_feat_moments_scratch_floats)");
+    return fail(launch_feat_moments_finish(slab, rows, centre, ddof, count, mean, cov, raw, (hipStream_t)stream), "msst_feat_moments_finish");
+}
+
+int msst_feat_project(const float* x, int x_layout, long rows, long plane, int dim, const float* mean, const float* components, int r,
+                      float* out, int out_layout, float* sumsq, void* stream) {
+    if (int rc = pca_shape("msst_feat_project", rows, dim, r)) return rc;
+    if (int rc = feat_layout("msst_feat_project", "layout", "rows", rows, plane, x_layout, out_layout)) return rc;
+    if (!x || !mean || !components || ((uintptr_t)x & (x_layout == 0 ? 15 : 3)) || ((uintptr_t)mean & 3) || ((uintptr_t)components & 3) ||
+        ((uintptr_t)out & 3) || ((uintptr_t)sumsq & 3))
+        return fail(MSST_ERR_BADARG, "msst_feat_project (null or misaligned argument)");
+    if (!out && !sumsq) return fail(MSST_ERR_BADARG, "msst_feat_project (both outputs null)");
+    return fail(launch_feat_project(x, x_layout, rows, plane, mean, components, r, out, out_layout, sumsq, (hipStream_t)stream),
+                "msst_feat_project");
+}
+
 int msst_scene_embed_assemble(const float* win_feat, long win0, int nwin, float* feat, int32_t* cover, int Bs, int D, int Hs, int Ws,
                               int window, int stride, int finalize, int l2norm, void* stream) {
     if (Bs < 1 || D < 1 || Hs < 1 || Ws < 1 || window < 1 || stride < 1 || nwin < 0 || win0 < 0)

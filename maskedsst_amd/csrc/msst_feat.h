@@ -1,6 +1,6 @@
-// What the kernels on frozen per-pixel features share (msst_knn.hip, msst_probe.hip, msst_kmeans.hip): rows x [M][96] fp32, or an
+// What the kernels on frozen per-pixel features share (msst_knn.hip, msst_probe.hip, msst_kmeans.hip, msst_pca.hip): rows x [M][96] fp32, or an
 // encode_scene map [Bs][96][plane] read in place, walked in tiles of 64 rows by workgroups of 256 threads = 4 waves, with one score per
-// (row, class) on v_mfma_f32_16x16x4_f32.  Every rule that the three files must agree on to keep their bits lives here, once:
+// (row, class) on v_mfma_f32_16x16x4_f32.  Every rule that these files must agree on to keep their bits lives here, once:
 //   zero rows   a row past the end of the walk is loaded as zeros (never as garbage) and masked by index by the caller.
 //   tile        rows layout: piece e = tid + 256 i of the tile's 64 x 24 16-byte pieces, row e / 24, channels 4 (e % 24) ..; one 16-byte
 //               global load per piece, held in registers (f32x4 pre[6]) so that a tile is fetched while the one before is computed on.
@@ -13,8 +13,8 @@
 //   order       ONE total order: value descending, then index ascending.
 //   pairs       the NCT x 6 (class tile, channel tile) accumulators of a [class][channel] product are dealt round-robin to the 4 waves.
 //   partition   rows over workgroups of whole tiles, from the row count alone.
-// What differs between the three (kNN's query fragments and top-k lists, the probe's LayerNorm and softmax, the two accumulation
-// loops) stays in its own file.  No helper takes a flag that says which caller it serves.  No inline assembly.
+// What differs between them (kNN's query fragments and top-k lists, the probe's LayerNorm and softmax, the accumulation loops, the
+// centring and the 21 symmetric pairs of msst_pca.hip) stays in its own file.  No helper takes a flag that says which caller it serves.  No inline assembly.
 #pragma once
 #include "msst_dev.h"
 

@@ -568,6 +568,16 @@ int launch_kmeans_update(const float* slab, long rows, int k, int metric, float*
 int launch_kmeans_pick(const float* x, long rows, const float* dist, const float* slab, int j, int metric, unsigned seed, float* centroids,
                        float* bias, int32_t* seed_rows, hipStream_t st);
 
+// msst_pca.hip (msst_feat_moments, msst_feat_moments_finish, msst_feat_project): mean and covariance of frozen features -- x^T x on the
+// fp32 MFMA with the row as the k index, per-workgroup partials without atomics, summed in double -- and the projection of rows or a
+// map onto given directions with the squared norm of the result
+long feat_moments_scratch_floats(long rows);
+int launch_feat_moments(const float* x, int x_layout, long rows, long plane, const float* centre, float* slab, hipStream_t st);
+int launch_feat_moments_finish(const float* slab, long rows, const float* centre, int ddof, int64_t* count, float* mean, float* cov,
+                               float* raw, hipStream_t st);
+int launch_feat_project(const float* x, int x_layout, long rows, long plane, const float* mean, const float* components, int r, float* out,
+                        int out_layout, float* sumsq, hipStream_t st);
+
 // msst_mask.hip (msst_draw_masks): the SimMIM token mask, gather indices and the gather's token-CSR of global rows row0 .. row0 + rows - 1
 // from a counter hash; one workgroup per row
 struct MaskDrawArgs {

@@ -470,6 +470,31 @@ class ViTSpatialSpectral(nn.Module):
         from .cluster import cluster_scene
         return cluster_scene(self, scene, km, stride, max_windows)
 
+    def pca_scene(self, scene, pca, stride=None, whiten=False, max_windows=None):
+        """The principal-component maps of whole scenes [Bs, channels, Hs, Ws] under a maskedsst_amd.FeaturePCA (e.g. from
+        maskedsst_amd.fit_pca on the features of other scenes; the first three maps are the usual false-colour picture of an
+        embedding): encode_scene(normalize=False), then msst_feat_project on the returned map in place, no permuted copy.  Returns
+        PcaScene(components, cover):
+          components [Bs, r, Hs, Ws] fp32: (x - mean) . component_j per pixel; whiten=True: divided by sqrt(lambda_j), the maps from
+                     pca.rank on dropped; NaN where no window covers the pixel;
+          cover [Bs, Hs, Ws] int32 as from encode_scene.
+        The maps have the same bits in every call and equal pca.transform on the permuted map.  stride, max_windows: encode_scene's.
+        No head runs; the module's mode is left unchanged.  ValueError, before any device work, for a pca that is no FeaturePCA or a
+        scene encode_scene refuses."""
+        from .pca import pca_scene
+        return pca_scene(self, scene, pca, stride, whiten, max_windows)
+
+    def anomaly_scene(self, scene, pca=None, stride=None, max_windows=None):
+        """The RX anomaly score of whole scenes [Bs, channels, Hs, Ws] on the frozen features: per pixel the squared Mahalanobis
+        distance to the mean of a maskedsst_amd.FeaturePCA under its covariance (pca.mahalanobis: one whitening projection and a row
+        norm, msst_feat_project on the encode_scene map in place).  pca=None: fitted on the scenes' own covered pixels (global RX;
+        maskedsst_amd.fit_pca on the map, uncovered pixels skipped).  Returns AnomalyScene(score, cover, pca): score [Bs, Hs, Ws] fp32,
+        NaN where no window covers the pixel; cover as from encode_scene; pca the FeaturePCA used.  stride, max_windows:
+        encode_scene's.  No head runs; the module's mode is left unchanged.  ValueError for a pca that is neither None nor a
+        FeaturePCA, one that keeps fewer than its `rank` components, or a scene encode_scene refuses."""
+        from .pca import anomaly_scene
+        return anomaly_scene(self, scene, pca, stride, max_windows)
+
     def attention_maps(self, img, stack="both", reduce="mean", blocks=None):
         """The attention probabilities of the transformer blocks for img [B, channels, image_size, image_size] (fp32, on the device):
         AttentionMaps(spatial, spectral), fp32 on the device; the stack not asked for is None.
