@@ -121,6 +121,11 @@ def build_parser():
                          "maskedsst_amd.fit_pca on the covered pixels of the first half of the --val-scenes (the R leading "
                          "explained-variance ratios and the effective rank), then the mean and largest RX anomaly score of the second "
                          "half under that fit; needs --val-scenes and --val-every")
+    ap.add_argument("--val-gauss", default=None, choices=["full", "tied"], metavar="{full,tied}",
+                    help="one more line per validation: accuracy of the class-conditional Gaussian classifier (maskedsst_amd.fit_gaussian: "
+                         "full covariances = QDA, a tied one = LDA) on the raw frozen features and the split of --val-knn: the bank is the "
+                         "first half of the --val-scenes, scored on the second half, with the mean distance to the predicted class and the "
+                         "share of pixels farther than the bank's 0.99 quantile; needs --val-scenes and --val-every")
     ap.add_argument("--val-saliency", action="store_true",
                     help="one more line per validation: the five bands with the largest mean |gradient x input| attribution "
                          "(maskedsst_amd.band_importance, argmax class) over the windows of the --val-scenes")
@@ -235,6 +240,7 @@ def main():
     check_val_probe(args)
     check_val_cluster(args)
     check_val_pca(args)
+    check_val_gauss(args)
     if not 0.0 <= args.label_smoothing < 1.0:
         raise SystemExit("--label-smoothing must lie in [0, 1)")
     # --class-weights inverse: the weights come from the first step's labels, so the criterion is made there
@@ -294,6 +300,8 @@ def main():
                 validate_cluster(model, val, step, args.val_cluster, config.n_classes, config.ignored_label)
             if args.val_pca:
                 validate_pca(model, val, step, args.val_pca)
+            if args.val_gauss:
+                validate_gauss(model, val, step, args.val_gauss, config.n_classes, config.ignored_label)
             if args.val_saliency:
                 validate_saliency(model, val, step)
             if args.val_saliency_scene:
@@ -523,6 +531,43 @@ def validate_pca(model, val, step, r):
                 rx_mean, rx_max = float(score.double().mean()), float(score.max())
     print(f"val-pca step {step} rows {rows} evr {' '.join(f'{v:.4f}' for v in evr)} effective_rank {erank:.3f} rx_mean {rx_mean:.4g} "
           f"rx_max {rx_max:.4g} scenes {val[0].shape[0]}", flush=True)
+
+
+def check_val_gauss(args):
+    if not args.val_gauss:
+        return
+    if args.val_gauss not in ("full", "tied"):
+        raise SystemExit("--val-gauss must be full or tied")
+    if args.val_scenes < 1 or args.val_every < 1:
+        raise SystemExit("--val-gauss scores the validation scenes: it needs --val-scenes and --val-every")
+
+
+def validate_gauss(model, val, step, covariance, n_classes, ignored_label):
+    """--val-gauss {full,tied}: maximum-likelihood classification of the frozen features, the split of --val-knn on the RAW features:
+    class-conditional Gaussians (maskedsst_amd.fit_gaussian: the moments kernels on every class's rows, the eigendecompositions on
+    the host) are fitted on the labelled covered pixels of the first half of the scenes and those of the second half are scored in
+    one HIP launch (msst_gauss_score).  gauss_acc: the accuracy; mean_d2: the mean squared Mahalanobis distance to the predicted
+    class; rejected: the share of test pixels farther from their predicted class than 99 % of the bank's pixels are from their own
+    (clf.threshold(bank, 0.99): the open-set rule).  nan when either half has no such pixel or a class has too few rows for its
+    covariance."""
+    from maskedsst_amd import KnnBank, fit_gaussian
+    ftr, ltr, fte, lte = frozen_split(model, val, ignored_label, False)
+    acc = mean_d2 = rejected = float("nan")
+    if len(ltr) and len(lte):
+        bank = KnnBank(ftr.contiguous(), ltr, n_classes)
+        try:
+            clf = fit_gaussian(bank, covariance=covariance)
+        except ValueError as e:
+            print(f"val-gauss not fitted at step {step}: {e}", flush=True)
+            clf = None
+        if clf is not None:
+            res = clf.classify(fte.contiguous(), scores=False)
+            limit = clf.threshold(bank, 0.99)
+            acc = float((res.classes == lte).double().mean())
+            mean_d2 = float(res.distance.double().mean())
+            rejected = float((res.distance > limit).double().mean())
+    print(f"val-gauss step {step} cov {covariance} gauss_acc {acc:.3f} mean_d2 {mean_d2:.4g} rejected {rejected:.3f} bank_pixels {len(ltr)} "
+          f"test_pixels {len(lte)} scenes {val[0].shape[0]}", flush=True)
 
 
 def validate_saliency(model, val, step, batch=256, top=5):

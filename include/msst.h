@@ -531,6 +531,28 @@ int msst_feat_moments_finish(const float* slab, long slab_floats, long rows, int
 int msst_feat_project(const float* x, int x_layout, long rows, long plane, int dim, const float* mean, const float* components, int r,
                       float* out, int out_layout, float* sumsq, void* stream);
 
+/* Class-conditional Gaussian scores of frozen features (maskedsst_amd/gaussian.py: fit_gaussian, GaussianClassifier,
+ * ViTSpatialSpectral.gaussian_predict_scene).  Additive under MSST_VERSION 109.  dim == 96, 1 <= nc <= 128, fp32, no atomics.  x and
+ * x_layout as in msst_feat_project.  One table form serves full and tied covariances: n_tables <= nc tables, table t a centre
+ * centres[t][96] and a matrix tables[t][96][96] (16-byte aligned); class c has a table id class_table[c] -- a HOST array [nc], read
+ * and checked here, before the launch -- an offset offsets[c][96] in its table's whitened coordinates and a constant consts[c].
+ *   z = A_t (x - centre_t): the subtraction in fp32, then the fmaf chain over d = 0 .. 95 from zero;
+ *   d2_c = max((|z|^2 + |m_c|^2) - 2 z . m_c, 0) = |A_t (x - centre_t) - m_c|^2, every sum in an order that depends on 96 alone;
+ *   score_c = fmaf(-0.5, d2_c, consts[c]).
+ * classes [rows] (int32) is the argmax of the score under the total order (score descending, then class ascending), distance [rows]
+ * the d2 of that class; a row with a channel that is not finite gets class -1 and NaN everywhere; a row whose distance exceeds max_d2
+ * (+inf: none) gets class -2, its scores and distance still written.  scores (null: not wanted) is rows [rows][nc] (out_layout 0) or
+ * a map [rows / plane][nc][plane] (out_layout 1).  A row's outputs have the same bits whatever batch or layout it sits in, with or
+ * without scores.
+ *
+ * Checked before any HIP call, in this order: MSST_ERR_BADARG for negative rows, dim or nc below 1, n_tables outside [1, nc];
+ * MSST_ERR_UNSUPPORTED outside dim == 96, nc <= 128, rows <= 2^31 - 1; MSST_ERR_BADARG for a layout outside {0, 1}, with a map on
+ * either side a plane below 1 or not dividing rows, max_d2 negative or NaN; rows == 0 returns 0 here; then MSST_ERR_BADARG for a null
+ * or misaligned pointer and for a table id outside [0, n_tables).  msst_last_error names the call. */
+int msst_gauss_score(const float* x, int x_layout, long rows, long plane, int dim, const float* centres, const float* tables, int n_tables,
+                     const int32_t* class_table, const float* offsets, const float* consts, int nc, float max_d2, int32_t* classes,
+                     float* distance, float* scores, int out_layout, void* stream);
+
 /* a7-a10: one fused pre-norm transformer block (PreNorm+Attention+FeedForward+residuals,
  * vit_spatial_spectral.py:22-104) over all B*S*N tokens; mode selects the spatial or spectral
  * sequence grouping of vit_spatial_spectral.py:410-431 (no transposes are materialised).

@@ -19,6 +19,7 @@ from .knn import KnnBank, KnnResult, KnnScene, feature_bank, knn_classify, knn_p
 from .probe import LinearProbe, ProbeScene, fit_linear_probe, probe_bank, probe_gradient, probe_predict_scene  # noqa: F401
 from .cluster import KMeans, ClusterScene, ClusterMatch, fit_kmeans, cluster_scene, contingency, match_clusters  # noqa: F401
 from .pca import FeaturePCA, PcaScene, AnomalyScene, fit_pca, pca_scene, anomaly_scene  # noqa: F401
+from .gaussian import GaussianClassifier, GaussianResult, GaussianScene, fit_gaussian, gaussian_predict_scene  # noqa: F401
 
 __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "MaskGenerator", "Reconstruction", "recon_report",
            "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows", "SceneEmbedding",
@@ -28,4 +29,5 @@ __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "
            "KnnBank", "KnnResult", "KnnScene", "feature_bank", "knn_classify", "knn_predict_scene",
            "LinearProbe", "ProbeScene", "fit_linear_probe", "probe_bank", "probe_gradient", "probe_predict_scene",
            "KMeans", "ClusterScene", "ClusterMatch", "fit_kmeans", "cluster_scene", "contingency", "match_clusters",
-           "FeaturePCA", "PcaScene", "AnomalyScene", "fit_pca", "pca_scene", "anomaly_scene"]
+           "FeaturePCA", "PcaScene", "AnomalyScene", "fit_pca", "pca_scene", "anomaly_scene",
+           "GaussianClassifier", "GaussianResult", "GaussianScene", "fit_gaussian", "gaussian_predict_scene"]

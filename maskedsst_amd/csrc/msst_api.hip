@@ -744,6 +744,26 @@ int msst_feat_project(const float* x, int x_layout, long rows, long plane, int d
                 "msst_feat_project");
 }
 
+int msst_gauss_score(const float* x, int x_layout, long rows, long plane, int dim, const float* centres, const float* tables, int n_tables,
+                     const int32_t* class_table, const float* offsets, const float* consts, int nc, float max_d2, int32_t* classes,
+                     float* distance, float* scores, int out_layout, void* stream) {
+    if (rows < 0 || dim < 1 || nc < 1 || n_tables < 1 || n_tables > nc)
+        return fail(MSST_ERR_BADARG, "msst_gauss_score (negative rows, dim or nc below 1, or n_tables outside [1, nc])");
+    if (dim != 96 || nc > 128 || rows > 2147483647L) return fail(MSST_ERR_UNSUPPORTED, "msst_gauss_score (dim == 96, nc <= 128, rows <= 2^31 - 1)");
+    if (int rc = feat_layout("msst_gauss_score", "layout", "rows", rows, plane, x_layout, out_layout)) return rc;
+    if (!(max_d2 >= 0.f)) return fail(MSST_ERR_BADARG, "msst_gauss_score (max_d2 negative or NaN)");
+    if (rows == 0) return 0;
+    if (!x || !centres || !tables || !class_table || !offsets || !consts || !classes || !distance || ((uintptr_t)x & (x_layout == 0 ? 15 : 3)) ||
+        ((uintptr_t)centres & 3) || ((uintptr_t)tables & 15) || ((uintptr_t)class_table & 3) || ((uintptr_t)offsets & 3) ||
+        ((uintptr_t)consts & 3) || ((uintptr_t)classes & 3) || ((uintptr_t)distance & 3) || ((uintptr_t)scores & 3))
+        return fail(MSST_ERR_BADARG, "msst_gauss_score (null or misaligned argument)");
+    for (int c = 0; c < nc; ++c) {   // class_table is the caller's host copy
+        if (class_table[c] < 0 || class_table[c] >= n_tables) return fail(MSST_ERR_BADARG, "msst_gauss_score (a table id outside [0, n_tables))");
+    }
+    return fail(launch_gauss_score(x, x_layout, rows, plane, centres, tables, n_tables, class_table, offsets, consts, nc, max_d2, classes,
+                                   distance, scores, out_layout, (hipStream_t)stream), "msst_gauss_score");
+}
+
 int msst_scene_embed_assemble(const float* win_feat, long win0, int nwin, float* feat, int32_t* cover, int Bs, int D, int Hs, int Ws,
                               int window, int stride, int finalize, int l2norm, void* stream) {
     if (Bs < 1 || D < 1 || Hs < 1 || Ws < 1 || window < 1 || stride < 1 || nwin < 0 || win0 < 0)

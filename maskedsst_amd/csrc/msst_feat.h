@@ -1,4 +1,4 @@
-// What the kernels on frozen per-pixel features share (msst_knn.hip, msst_probe.hip, msst_kmeans.hip, msst_pca.hip): rows x [M][96] fp32, or an
+// What the kernels on frozen per-pixel features share (msst_knn.hip, msst_probe.hip, msst_kmeans.hip, msst_pca.hip, msst_gauss.hip): rows x [M][96] fp32, or an
 // encode_scene map [Bs][96][plane] read in place, walked in tiles of 64 rows by workgroups of 256 threads = 4 waves, with one score per
 // (row, class) on v_mfma_f32_16x16x4_f32.  Every rule that these files must agree on to keep their bits lives here, once:
 //   zero rows   a row past the end of the walk is loaded as zeros (never as garbage) and masked by index by the caller.
@@ -7,6 +7,8 @@
 //               Map layout: thread = (row tid & 63, channels 4 i + (tid >> 6)), the 64 lanes of a wave on 64 adjacent pixels of one
 //               channel plane; the same 24 registers.  The LDS pitch is the caller's: 98 (= 2 mod 32: the 32 lanes of a one-dword operand
 //               read on 32 banks; rows start on 8 bytes, stored as two float2) or a multiple of 4 (16-byte rows, one f32x4 store).
+//   centre      c = x - centre in fp32 on the registers of a prefetched tile, and the flags of a stored tile (a channel that is not finite;
+//               past the end), four threads per row: msst_pca.hip and msst_gauss.hip.
 //   scores      wave w owns rows 16 w .. 16 w + 15: A = x[16 w + (l & 15)][4 ks + (l >> 4)], B = w[16 jt + (l & 15)][4 ks + (l >> 4)], 24
 //               k-steps ascending, so a score is the fp32 fmaf chain over d = 0 .. 95 in order behind the accumulator's start value;
 //               lane l then holds rows 4 (l >> 4) + r, classes 16 jt + (l & 15).
@@ -72,6 +74,39 @@ __device__ __forceinline__ void feat_map_store(float* xs, const f32x4 (&pre)[6],
     const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
     for (int i = 0; i < 24; ++i) xs[lane * PITCH + 4 * i + wave] = pre[i >> 2][i & 3];
+}
+
+// ---- c = x - centre on the registers of a prefetched tile (scen: [96] in LDS, 16-byte aligned), formed in fp32 before any product
+__device__ __forceinline__ void feat_centre_rows(f32x4 (&pre)[6], const float* scen, int tid) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const int e = tid + FEAT_THREADS * i;
+        const int c4 = e - (e / 24) * 24;
+        pre[i] -= *reinterpret_cast<const f32x4*>(scen + 4 * c4);
+    }
+}
+
+__device__ __forceinline__ void feat_centre_map(f32x4 (&pre)[6], const float* scen, int tid) {
+    const int wave = tid >> 6;
+#pragma unroll
+    for (int i = 0; i < 24; ++i) pre[i >> 2][i & 3] -= scen[4 * i + wave];
+}
+
+// ---- four threads per row of a stored tile: flag 0 = counted, 1 = a channel is not finite, 2 = at or past rend; a flagged row is zeroed
+template <int PITCH>
+__device__ __forceinline__ void feat_flag_rows(float* xs, int* sflag, long r0, long rend, int tid) {
+    float* xr = xs + (tid >> 2) * PITCH + (tid & 3);
+    int bad = 0;
+#pragma unroll
+    for (int i = 0; i < 24; ++i) bad |= !(fabsf(xr[4 * i]) <= 3.4028234e38f) ? 1 : 0;
+    bad |= __shfl_xor(bad, 1);
+    bad |= __shfl_xor(bad, 2);
+    const int flag = r0 + (tid >> 2) >= rend ? 2 : bad;
+    if (flag) {
+#pragma unroll
+        for (int i = 0; i < 24; ++i) xr[4 * i] = 0.f;
+    }
+    if ((tid & 3) == 0) sflag[tid >> 2] = flag;
 }
 
 // ---- scores of the wave's 16 rows x 16 NCT classes, added to c as the caller initialised it

@@ -578,6 +578,13 @@ int launch_feat_moments_finish(const float* slab, long rows, const float* centre
 int launch_feat_project(const float* x, int x_layout, long rows, long plane, const float* mean, const float* components, int r, float* out,
                         int out_layout, float* sumsq, hipStream_t st);
 
+// msst_gauss.hip (msst_gauss_score): class-conditional Gaussian scores of frozen features -- per table the whitening projection on the
+// fp32 MFMA, per class the squared distance to an offset in the whitened coordinates (the class stage on the MFMA too), the argmax
+// under the total order and the distance to it.  class_table is a HOST array [nc] of ids in [0, n_tables), checked by the caller
+int launch_gauss_score(const float* x, int x_layout, long rows, long plane, const float* centres, const float* tables, int n_tables,
+                       const int32_t* class_table, const float* offsets, const float* consts, int nc, float max_d2, int32_t* classes,
+                       float* distance, float* scores, int out_layout, hipStream_t st);
+
 // msst_mask.hip (msst_draw_masks): the SimMIM token mask, gather indices and the gather's token-CSR of global rows row0 .. row0 + rows - 1
 // from a counter hash; one workgroup per row
 struct MaskDrawArgs {

@@ -3,7 +3,7 @@
 // projection of rows or a map onto 1 <= r <= 96 given directions (PCA scores, whitened scores, the squared Mahalanobis distance of the
 // RX detector).  fp32, no atomics; every output has the same bits in every call.
 //
-// The tile loaders of both layouts, the scores loop, the table store and the partition are msst_feat.h's.
+// The tile loaders of both layouts, the centring and the row flags, the scores loop, the table store and the partition are msst_feat.h's.
 // feat_moments  grid = workgroups of whole 64-row tiles (feat_partition), 256 threads = 4 waves, LDS: x tile [64][98] | centre [96] |
 //             row flags [64]: 25 KB, two workgroups per CU.
 //   tile      one tile ahead in registers; c = x - centre (null centre: zeros) is formed in fp32 in the registers on the way to LDS.
@@ -41,38 +41,6 @@ constexpr int PCA_P = 98;                                    // LDS pitch of a f
 constexpr int PCA_PAIRS = 21;                                // channel tile pairs it <= jt
 constexpr int PCA_PPW = (PCA_PAIRS + 3) / 4;                 // 6: wave 0 has six, the others five
 constexpr int PCA_SLAB = 1 + FEAT_D + FEAT_D * FEAT_D;       // floats of a workgroup's slab row
-
-// ---- c = x - centre on the registers of a prefetched tile (scen: [96] in LDS, 16-byte aligned)
-__device__ __forceinline__ void pca_centre_rows(f32x4 (&pre)[6], const float* scen, int tid) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const int e = tid + FEAT_THREADS * i;
-        const int c4 = e - (e / 24) * 24;
-        pre[i] -= *reinterpret_cast<const f32x4*>(scen + 4 * c4);
-    }
-}
-
-__device__ __forceinline__ void pca_centre_map(f32x4 (&pre)[6], const float* scen, int tid) {
-    const int wave = tid >> 6;
-#pragma unroll
-    for (int i = 0; i < 24; ++i) pre[i >> 2][i & 3] -= scen[4 * i + wave];
-}
-
-// ---- four threads per row: flag 0 = counted, 1 = a channel is not finite, 2 = at or past rend; a flagged row is zeroed
-__device__ __forceinline__ void pca_flag_rows(float* xs, int* sflag, long r0, long rend, int tid) {
-    float* xr = xs + (tid >> 2) * PCA_P + (tid & 3);
-    int bad = 0;
-#pragma unroll
-    for (int i = 0; i < 24; ++i) bad |= !(fabsf(xr[4 * i]) <= 3.4028234e38f) ? 1 : 0;
-    bad |= __shfl_xor(bad, 1);
-    bad |= __shfl_xor(bad, 2);
-    const int flag = r0 + (tid >> 2) >= rend ? 2 : bad;
-    if (flag) {
-#pragma unroll
-        for (int i = 0; i < 24; ++i) xr[4 * i] = 0.f;
-    }
-    if ((tid & 3) == 0) sflag[tid >> 2] = flag;
-}
 
 // ---- pair p = wave + 4 i of the 21 (it <= jt), rows of the upper triangle in order; false: the wave has no i-th pair
 __device__ __forceinline__ bool pca_wave_pair(int wave, int i, int& it, int& jt) {
@@ -134,15 +102,15 @@ __global__ __launch_bounds__(256, 2) void feat_moments_kernel(PcaMomArgs a) {
         const long r0 = rbeg + t * 64;
         __syncthreads();   // the previous tile's reads (and, first, the centre) are done
         if (LAYOUT == 0) {
-            pca_centre_rows(pre, scen, tid);
+            feat_centre_rows(pre, scen, tid);
             feat_rows_store<PCA_P>(xs, pre, tid);
         } else {
-            pca_centre_map(pre, scen, tid);
+            feat_centre_map(pre, scen, tid);
             feat_map_store<PCA_P>(xs, pre, tid);
         }
         __syncthreads();
         if (t + 1 < ntiles) load_tile(r0 + 64);
-        pca_flag_rows(xs, sflag, r0, rend, tid);
+        feat_flag_rows<PCA_P>(xs, sflag, r0, rend, tid);
         __syncthreads();
         // ---- s2 += tile^T tile over the 64 rows; the pairs inside, so that a wave's accumulators are independent
 #pragma unroll 2
@@ -288,15 +256,15 @@ __global__ __launch_bounds__(256, NCT <= 2 ? 4 : NCT == 4 ? 2 : 1) void feat_pro
         const long nq = min((long)64, rend - r0);
         __syncthreads();   // the previous tile's reads (and, first, the components and the mean) are done
         if (a.x_layout == 0) {
-            pca_centre_rows(pre, smean, tid);
+            feat_centre_rows(pre, smean, tid);
             feat_rows_store<PCA_P>(xs, pre, tid);
         } else {
-            pca_centre_map(pre, smean, tid);
+            feat_centre_map(pre, smean, tid);
             feat_map_store<PCA_P>(xs, pre, tid);
         }
         __syncthreads();
         if (WALK && t + 1 < ntiles) load_tile(r0 + 64);
-        pca_flag_rows(xs, sflag, r0, rend, tid);
+        feat_flag_rows<PCA_P>(xs, sflag, r0, rend, tid);
         __syncthreads();
         f32x4 c[NCT];
 #pragma unroll

@@ -495,6 +495,22 @@ class ViTSpatialSpectral(nn.Module):
         from .pca import anomaly_scene
         return anomaly_scene(self, scene, pca, stride, max_windows)
 
+    def gaussian_predict_scene(self, scene, clf, stride=None, max_distance=None, max_windows=None):
+        """The maximum-likelihood class map of whole scenes [Bs, channels, Hs, Ws] under a maskedsst_amd.GaussianClassifier (from
+        maskedsst_amd.fit_gaussian on a bank of raw features): encode_scene(normalize=False), then ONE msst_gauss_score launch on the
+        returned map in place, no permuted copy.  Returns GaussianScene(classes, scores, distance, cover):
+          classes   [Bs, Hs, Ws] int64: the argmax of the log joint density score_c(x) = log prior_c - 0.5 (d2_c(x) + logdet_c) - 48
+                    log(2 pi) under the total order (score descending, then class ascending); -1 where no window covers the pixel;
+                    -2 where max_distance is given and the distance exceeds it (the pixel is none of the classes);
+          scores    [Bs, nc, Hs, Ws] fp32, the layout of predict_scene's logits; NaN where uncovered;
+          distance  [Bs, Hs, Ws] fp32: d2 = |A_c (x - mu_c)|^2 of the predicted class, the open-set score; NaN where uncovered;
+          cover     as from encode_scene.
+        The maps have the same bits in every call and equal clf.classify on the permuted map.  stride, max_windows: encode_scene's.
+        No head runs; the module's mode is left unchanged.  ValueError, before any device work, for a clf that is no
+        GaussianClassifier, a max_distance that is negative or no number, or a scene encode_scene refuses."""
+        from .gaussian import gaussian_predict_scene
+        return gaussian_predict_scene(self, scene, clf, stride, max_distance, max_windows)
+
     def attention_maps(self, img, stack="both", reduce="mean", blocks=None):
         """The attention probabilities of the transformer blocks for img [B, channels, image_size, image_size] (fp32, on the device):
         AttentionMaps(spatial, spectral), fp32 on the device; the stack not asked for is None.
