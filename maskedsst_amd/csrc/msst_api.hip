@@ -1572,20 +1572,33 @@ long msst_ce_scratch_bytes(int R0, int n_classes, int M) {
     return (long)ce_workgroups((long)R0 * M) * (5 + 2L * n_classes) * 4;
 }
 
-int msst_ce_stats_fwd(const float* logits, const int64_t* labels, const int64_t* skip, long ignore_index, float* d, float* loss,
-                      int64_t* record, void* scratch, int R0, int n_classes, int M, void* stream) {
-    int rc = ce_shape(R0, n_classes, M);
-    if (rc) return fail(rc, "msst_ce_stats_fwd");
-    if (!logits || !labels || !loss || !record || !scratch) return fail(MSST_ERR_BADARG, "msst_ce_stats_fwd");   // skip and d are optional
+// the forward of both entry points: the arguments, the scratch (partial | [wpartial] | slab | [cslab]) and the two launches.
+// ext: the layout of msst_ce_ext_fwd, which keeps the wpartial region whether or not the call is weighted
+static int ce_forward(const float* logits, const int64_t* labels, const int64_t* skip, long ignore_index, const float* class_weight,
+                      float label_smoothing, float* d, float* loss, int64_t* record, double* sums, int64_t* confusion, void* scratch,
+                      bool ext, int R0, int n_classes, int M, void* stream, const char* what) {
     CeArgs a = {};
     a.logits = logits; a.labels = labels; a.skip = skip; a.d = d; a.loss = loss; a.record = record;
     a.rows = (long)R0 * M; a.ignore_index = ignore_index; a.NC = n_classes; a.M = M;
+    a.w = class_weight; a.eps = label_smoothing; a.confusion = confusion; a.sums = sums;
+    const long G = ce_workgroups(a.rows);
     a.partial = (float*)scratch;
-    a.slab = (int*)scratch + ce_workgroups(a.rows);
+    a.wpartial = ext ? a.partial + G : nullptr;
+    a.slab = (int*)scratch + (ext ? 2 : 1) * G;
+    a.cslab = confusion ? a.slab + G * (4 + 2L * n_classes) : nullptr;
     hipStream_t st = (hipStream_t)stream;
-    rc = launch_ce_fwd(a, st);
+    const int rc = launch_ce_fwd(a, st);
+    if (rc) return fail(rc, what);
+    return fail(launch_ce_finish(a, st), what, "(finish)");
+}
+
+int msst_ce_stats_fwd(const float* logits, const int64_t* labels, const int64_t* skip, long ignore_index, float* d, float* loss,
+                      int64_t* record, void* scratch, int R0, int n_classes, int M, void* stream) {
+    const int rc = ce_shape(R0, n_classes, M);
     if (rc) return fail(rc, "msst_ce_stats_fwd");
-    return fail(launch_ce_finish(a, st), "msst_ce_stats_fwd(finish)");
+    if (!logits || !labels || !loss || !record || !scratch) return fail(MSST_ERR_BADARG, "msst_ce_stats_fwd");   // skip and d are optional
+    return ce_forward(logits, labels, skip, ignore_index, nullptr, 0.f, d, loss, record, nullptr, nullptr, scratch, false, R0, n_classes, M,
+                      stream, "msst_ce_stats_fwd");
 }
 
 int msst_ce_bwd(const float* d, const int64_t* record, const float* gout, float* dlogits, int R0, int n_classes, int M, void* stream) {
@@ -1623,20 +1636,8 @@ int msst_ce_ext_fwd(const float* logits, const int64_t* labels, const int64_t* s
     if (rc) return fail(rc, "msst_ce_ext_fwd (confusion matrix: more than MSST_CE_CONFUSION_MAX_CLASSES classes, or 2^31 scratch words)");
     if (!logits || !labels || !loss || !record || !sums || !scratch)   // skip, class_weight, d and confusion are optional
         return fail(MSST_ERR_BADARG, "msst_ce_ext_fwd");
-    CeExtArgs e = {};
-    CeArgs& a = e.c;
-    a.logits = logits; a.labels = labels; a.skip = skip; a.d = d; a.loss = loss; a.record = record;
-    a.rows = (long)R0 * M; a.ignore_index = ignore_index; a.NC = n_classes; a.M = M;
-    const int G = ce_workgroups(a.rows);
-    a.partial = (float*)scratch;
-    e.wpartial = a.partial + G;
-    a.slab = (int*)scratch + 2L * G;
-    e.cslab = confusion ? a.slab + (long)G * (4 + 2L * n_classes) : nullptr;
-    e.w = class_weight; e.eps = label_smoothing; e.confusion = confusion; e.sums = sums;
-    hipStream_t st = (hipStream_t)stream;
-    rc = launch_ce_ext_fwd(e, st);
-    if (rc) return fail(rc, "msst_ce_ext_fwd");
-    return fail(launch_ce_ext_finish(e, st), "msst_ce_ext_fwd(finish)");
+    return ce_forward(logits, labels, skip, ignore_index, class_weight, label_smoothing, d, loss, record, sums, confusion, scratch, true,
+                      R0, n_classes, M, stream, "msst_ce_ext_fwd");
 }
 
 int msst_ce_ext_bwd(const float* d, const double* sums, const float* gout, float* dlogits, int R0, int n_classes, int M, void* stream) {

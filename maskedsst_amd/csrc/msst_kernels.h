@@ -466,35 +466,31 @@ int launch_layernorm_fwd(const float* x, const float* g, const float* b, float* 
 int layernorm_bwd_grid(long rows, int D);   // workgroups (= slab rows of 2 D floats) the backward launch uses
 int launch_layernorm_bwd(const float* x, const float* g, const float* dy, float* dx, float* slab, int grid, long rows, int D,
                          float eps, hipStream_t st);
-// msst_loss.hip: softmax cross entropy with ignore_index over class-major logits [R0][NC][M], rows = R0 M (one lane per row)
+// msst_loss.hip: softmax cross entropy with ignore_index over class-major logits [R0][NC][M], rows = R0 M (one lane per row),
+// optionally with class weights, label smoothing and a confusion matrix.  One kernel family; w, eps = 0, wpartial, cslab, confusion
+// and sums all null / 0 is the plain call
+constexpr int CE_CONF_MAX_CLASSES = 128;   // include/msst.h: MSST_CE_CONFUSION_MAX_CLASSES (msst_api.hip asserts they agree)
 struct CeArgs {
     const float* logits; const int64_t* labels; const int64_t* skip;   // skip: optional [rows], entries < 0 do not count
-    float* d;            // optional [R0][NC][M]: softmax - onehot (zeros for rows that do not count)
-    float* loss;         // the mean over the rows that count (NaN over none)
-    int64_t* record;     // [5 + 2 NC]: loss sum (a double) | n_valid | n_correct | bad_labels | nonfinite | support[NC] | correct[NC]
-    float* partial;      // [workgroups] loss partials
-    int* slab;           // [workgroups][4 + 2 NC] count partials
+    float* d;             // optional [R0][NC][M]: the loss sum's gradient (unweighted: softmax - onehot; zeros for rows that do not count)
+    float* loss;          // the mean over the rows that count (NaN over none, or over none of positive weight)
+    int64_t* record;      // [5 + 2 NC]: loss sum (a double) | n_valid | n_correct | bad_labels | nonfinite | support[NC] | correct[NC]
+    float* partial;       // [workgroups] loss partials
+    int* slab;            // [workgroups][4 + 2 NC] count partials
     long rows, ignore_index;
     int NC, M;
-};
-int ce_workgroups(long rows);   // workgroups of the forward launch = rows of its two partial arrays
-int launch_ce_fwd(const CeArgs& a, hipStream_t st);
-int launch_ce_finish(const CeArgs& a, hipStream_t st);
-int launch_ce_bwd(const float* d, const int64_t* record, const float* gout, float* dlogits, long n, hipStream_t st);
-// ... with class weights, label smoothing and a confusion matrix (the second forward family of msst_loss.hip)
-constexpr int CE_CONF_MAX_CLASSES = 128;   // include/msst.h: MSST_CE_CONFUSION_MAX_CLASSES (msst_api.hip asserts they agree)
-struct CeExtArgs {
-    CeArgs c;             // as for ce_fwd: c.partial [workgroups], c.slab [workgroups][4 + 2 NC]
     const float* w;       // optional [NC] class weights (null: ones)
     float eps;            // label smoothing, in [0, 1)
-    float* wpartial;      // [workgroups] partials of the counting rows' w[label]
+    float* wpartial;      // [workgroups] partials of the counting rows' w[label]; written and read only with w or eps != 0
     int* cslab;           // [workgroups][NC][NC] confusion partials, null when no confusion matrix is wanted
     int64_t* confusion;   // [NC][NC] (label, argmax) over the counting rows; null with cslab
-    double* sums;         // [2]: the loss sum (= record slot 0) | the sum of w[label] the mean divides by
+    double* sums;         // optional [2]: the loss sum (= record slot 0) | what the mean divides by (the sum of w[label]; n_valid)
 };
-int launch_ce_ext_fwd(const CeExtArgs& e, hipStream_t st);
-int launch_ce_ext_finish(const CeExtArgs& e, hipStream_t st);
-int launch_ce_ext_bwd(const float* d, const double* sums, const float* gout, float* dlogits, long n, hipStream_t st);
+int ce_workgroups(long rows);   // workgroups of the forward launch = rows of its partial arrays
+int launch_ce_fwd(const CeArgs& a, hipStream_t st);
+int launch_ce_finish(const CeArgs& a, hipStream_t st);
+int launch_ce_bwd(const float* d, const int64_t* record, const float* gout, float* dlogits, long n, hipStream_t st);   // over record[1]
+int launch_ce_ext_bwd(const float* d, const double* sums, const float* gout, float* dlogits, long n, hipStream_t st);   // over sums[1]
 // msst_recon.hip: to_pixels over every token into the cube layout, with the per-band |pred - img| sums over the masked pixels
 struct ReconArgs {
     const float* y;        // [B][T][96] encoder output (16-byte aligned)

@@ -134,63 +134,38 @@ class CEStats:
 
 
 class _CrossEntropyFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, labels, skip, ignore_index, shape):
-        lib = _lib.load()
-        R0, nc, M = shape
-        dev = logits.device
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        record = torch.empty(5 + 2 * nc, dtype=torch.int64, device=dev)
-        scratch = torch.empty(max(1, int(lib.msst_ce_scratch_bytes(R0, nc, M)) // 4), dtype=torch.int32, device=dev)
-        d = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
-        _lib.check(lib.msst_ce_stats_fwd(_p(logits), _p(labels), _p(skip), int(ignore_index), _p(d), _p(loss), _p(record), _p(scratch),
-                                         R0, nc, M, _stream()), "msst_ce_stats_fwd")
-        ctx.save_for_backward(d, record)
-        ctx.shape = shape
-        ctx.mark_non_differentiable(record)
-        ctx.set_materialize_grads(False)   # no zeros_like(record) launch in the backward
-        return loss, record
-
-    @staticmethod
-    def backward(ctx, gloss, _grecord):
-        if gloss is None:
-            return None, None, None, None, None
-        lib = _lib.load()
-        d, record = ctx.saved_tensors
-        R0, nc, M = ctx.shape
-        gout = gloss.contiguous().float()
-        dlogits = torch.empty_like(d)
-        _lib.check(lib.msst_ce_bwd(_p(d), _p(record), _p(gout), _p(dlogits), R0, nc, M, _stream()), "msst_ce_bwd")
-        return dlogits, None, None, None, None
-
-
-class _CrossEntropyExtFn(torch.autograd.Function):
-    """msst_ce_ext_fwd / msst_ce_ext_bwd: class weights, label smoothing, confusion matrix.  -> (loss, buf[, confusion]); buf is
-    int64 [5 + 2 nc + 2]: the record, then the two double sums"""
+    """msst_ce_stats_fwd / msst_ce_bwd; with class weights, label smoothing or a confusion matrix msst_ce_ext_fwd / msst_ce_ext_bwd.
+    -> (loss, buf[, confusion]); buf is int64: the record [5 + 2 nc], behind it the two double sums of an extended call"""
 
     @staticmethod
     def forward(ctx, logits, labels, skip, weight, ignore_index, eps, want_confusion, shape):
         lib = _lib.load()
         R0, nc, M = shape
         dev = logits.device
-        nbytes = int(lib.msst_ce_ext_scratch_bytes(R0, nc, M, int(want_confusion)))
+        ext = weight is not None or eps != 0.0 or want_confusion
+        nbytes = int(lib.msst_ce_ext_scratch_bytes(R0, nc, M, int(want_confusion)) if ext else lib.msst_ce_scratch_bytes(R0, nc, M))
         if want_confusion and nc > _lib.CE_CONFUSION_MAX_CLASSES:
             raise _lib.MsstError(f"a confusion matrix needs n_classes <= {_lib.CE_CONFUSION_MAX_CLASSES}, got {nc} "
                                  "(include/msst.h: MSST_CE_CONFUSION_MAX_CLASSES)")
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        buf = torch.empty(5 + 2 * nc + 2, dtype=torch.int64, device=dev)
-        record, sums = buf[:5 + 2 * nc], buf[5 + 2 * nc:]
+        buf = torch.empty(5 + 2 * nc + (2 if ext else 0), dtype=torch.int64, device=dev)
         confusion = torch.empty((nc, nc), dtype=torch.int64, device=dev) if want_confusion else None
         scratch = torch.empty(max(1, nbytes // 4), dtype=torch.int32, device=dev)
         d = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
-        _lib.check(lib.msst_ce_ext_fwd(_p(logits), _p(labels), _p(skip), int(ignore_index), _p(weight), float(eps), _p(d), _p(loss),
-                                       _p(record), _p(sums), _p(confusion), _p(scratch), R0, nc, M, _stream()), "msst_ce_ext_fwd")
-        ctx.save_for_backward(d, sums)
-        ctx.shape = shape
+        if ext:
+            den = buf[5 + 2 * nc:]   # the sums
+            _lib.check(lib.msst_ce_ext_fwd(_p(logits), _p(labels), _p(skip), int(ignore_index), _p(weight), float(eps), _p(d), _p(loss),
+                                           _p(buf), _p(den), _p(confusion), _p(scratch), R0, nc, M, _stream()), "msst_ce_ext_fwd")
+        else:
+            den = buf                # the record
+            _lib.check(lib.msst_ce_stats_fwd(_p(logits), _p(labels), _p(skip), int(ignore_index), _p(d), _p(loss), _p(buf), _p(scratch),
+                                             R0, nc, M, _stream()), "msst_ce_stats_fwd")
+        ctx.save_for_backward(d, den)
+        ctx.shape, ctx.ext = shape, ext
         ctx.mark_non_differentiable(buf)
         if want_confusion:
             ctx.mark_non_differentiable(confusion)
-        ctx.set_materialize_grads(False)
+        ctx.set_materialize_grads(False)   # no zeros_like(buf) launch in the backward
         return (loss, buf, confusion) if want_confusion else (loss, buf)
 
     @staticmethod
@@ -198,11 +173,12 @@ class _CrossEntropyExtFn(torch.autograd.Function):
         if gloss is None:
             return (None,) * 8
         lib = _lib.load()
-        d, sums = ctx.saved_tensors
+        d, den = ctx.saved_tensors
         R0, nc, M = ctx.shape
         gout = gloss.contiguous().float()
         dlogits = torch.empty_like(d)
-        _lib.check(lib.msst_ce_ext_bwd(_p(d), _p(sums), _p(gout), _p(dlogits), R0, nc, M, _stream()), "msst_ce_ext_bwd")
+        name = "msst_ce_ext_bwd" if ctx.ext else "msst_ce_bwd"
+        _lib.check(getattr(lib, name)(_p(d), _p(den), _p(gout), _p(dlogits), R0, nc, M, _stream()), name)
         return (dlogits,) + (None,) * 7
 
 
@@ -249,11 +225,10 @@ def cross_entropy_stats(logits, labels, ignore_index=-1, skip=None, weight=None,
                              f"{getattr(weight, 'dtype', type(weight))} {tuple(getattr(weight, 'shape', ()))}")
         weight = weight.detach().to(device=dev, dtype=torch.float32).contiguous()
     shape = tuple(int(v) for v in shape)
-    if weight is None and eps == 0.0 and not confusion:
-        loss, record = _CrossEntropyFn.apply(logits.contiguous().float(), labels, skip, int(ignore_index), shape)
-        return loss, CEStats(record, nc)
-    out = _CrossEntropyExtFn.apply(logits.contiguous().float(), labels, skip, weight, int(ignore_index), eps, bool(confusion), shape)
+    out = _CrossEntropyFn.apply(logits.contiguous().float(), labels, skip, weight, int(ignore_index), eps, bool(confusion), shape)
     loss, buf = out[0], out[1]
+    if buf.numel() == 5 + 2 * nc:   # none of weight, smoothing and matrix: the record alone
+        return loss, CEStats(buf, nc)
     return loss, CEStats(buf[:5 + 2 * nc], nc, sums=buf[5 + 2 * nc:].view(torch.float64), confusion=out[2] if confusion else None, buf=buf)
 
 

@@ -134,7 +134,7 @@ def compare(got, ref, tag, finite_rows=None):
 
 # ------------------------------------------------------------------------------------------------ 1. kernels against float64
 CASES = [(256, 8, 64), (32, 20, 64), (3, 8, 49), (256, 8, 1), (1, 8, 1), (5, 1, 64), (7, 2, 3), (2, 33, 64), (2, 40, 64), (2, 97, 5),
-         (4, 8, 4096)]
+         (4, 8, 4096), (1, 1025, 3)]   # 1025 classes: a second CE_CHUNK histogram pass
 VARIANTS = ["mixed", "none_ignored", "all_ignored", "bad_labels"]
 
 

@@ -1,5 +1,6 @@
-"""GPU: the cross entropy with class weights, label smoothing and a confusion matrix (msst_loss.hip: ce_ext_fwd / ce_ext_finish /
-ce_ext_bwd; include/msst.h: msst_ce_ext_fwd, msst_ce_ext_bwd; maskedsst_amd.ops.cross_entropy_stats(weight=, label_smoothing=,
+"""GPU: the cross entropy with class weights, label smoothing and a confusion matrix (msst_loss.hip: the weighted instances of ce_fwd,
+ce_finish and ce_bwd, and the unweighted ones behind the extended entry points; include/msst.h: msst_ce_ext_fwd, msst_ce_ext_bwd;
+maskedsst_amd.ops.cross_entropy_stats(weight=, label_smoothing=,
 confusion=), FusedCrossEntropy(weight, label_smoothing), confusion_report; maskedsst_amd.scene.scene_report).
 
 Yardstick: float64 ``torch.nn.functional.cross_entropy(weight=, label_smoothing=, ignore_index=)`` and its autograd on the CPU (labels
@@ -15,7 +16,8 @@ Every shape runs every combination of labels {all valid, about 25 % ignored, all
 in [0.1, 3], one class at 0, all present classes at 0}, eps {0, 0.1} and logit scale {1, 100}, through the C ABI with every output
 and the scratch prefilled with NaN bytes, twice (bit-identical).
 
-Errors are handed to tests/util.py::record (MSST_RECORD=1 writes them out); no MI355X figures are committed for this file yet."""
+Errors are handed to tests/util.py::record (MSST_RECORD=1 writes them out); measured on an MI355X:
+profiles/ce_ext_parity_measured.jsonl."""
 import ctypes
 
 import numpy as np
@@ -27,7 +29,8 @@ from util import record
 pytestmark = pytest.mark.gpu
 
 BAR, SUM_BAR = 1e-4, 1e-6
-SHAPES = [(1, 1, 1), (3, 5, 1), (2, 8, 64), (1, 9, 7), (2, 20, 49), (2, 33, 5), (5, 8, 64), (1, 128, 3)]
+SHAPES = [(1, 1, 1), (3, 5, 1), (2, 8, 64), (1, 9, 7), (2, 20, 49), (2, 33, 5), (5, 8, 64), (1, 128, 3),
+          (2, 16, 5), (2, 17, 5), (2, 32, 5)]   # the full 16 and 32 register buckets, the first class past the 16 bucket
 LABELS = ["valid", "ignored25", "all_ignored", "bad"]
 WEIGHTS = ["none", "random", "one_zero", "present_zero"]
 EPS = [0.0, 0.1]
@@ -131,17 +134,20 @@ def ext_abi(x, lab, w=None, eps=0.0, confusion=True, skip=None, gout=None, want_
     return dict(loss=loss, record=rec, sums=sums, confusion=cm, d=d, dlogits=dl)
 
 
-def old_abi(x, lab, skip=None):
-    """the existing entry points, msst_ce_stats_fwd + msst_ce_bwd -> dict(loss, record, d, dlogits)"""
+def old_abi(x, lab, skip=None, gout=None, want_d=True):
+    """the plain entry points, msst_ce_stats_fwd + msst_ce_bwd -> dict(loss, record, d, dlogits)"""
     from maskedsst_amd import _lib
     lib = _lib.load()
     R0, nc, M = x.shape
     loss = torch.full((), float("nan"), device="cuda")
     rec = torch.full((5 + 2 * nc,), -1, dtype=torch.int64, device="cuda")
     scratch = torch.full((lib.msst_ce_scratch_bytes(R0, nc, M),), 0xFF, dtype=torch.uint8, device="cuda")
-    d, dl = torch.full_like(x, float("nan")), torch.full_like(x, float("nan"))
+    d = torch.full_like(x, float("nan")) if want_d else None
     assert lib.msst_ce_stats_fwd(P(x), P(lab), P(skip), -1, P(d), P(loss), P(rec), P(scratch), R0, nc, M, stream()) == 0
-    assert lib.msst_ce_bwd(P(d), P(rec), None, P(dl), R0, nc, M, stream()) == 0
+    dl = None
+    if want_d:
+        dl = torch.full_like(x, float("nan"))
+        assert lib.msst_ce_bwd(P(d), P(rec), P(gout), P(dl), R0, nc, M, stream()) == 0
     torch.cuda.synchronize()
     return dict(loss=loss, record=rec, d=d, dlogits=dl)
 
@@ -239,8 +245,8 @@ def test_ce_ext_refuses_a_confusion_matrix_past_the_class_limit():
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "R%d-nc%d-M%d" % s)
 def test_ce_ext_without_weights_gives_the_bits_of_the_existing_calls(shape):
     """no weight, eps = 0: loss, record, d and dlogits of msst_ce_ext_* are those of msst_ce_stats_fwd / msst_ce_bwd bit for bit, with
-    and without the confusion matrix; the Python op without the new arguments still goes through the existing calls, and with
-    confusion=True alone it gives the same loss and gradient"""
+    and without the confusion matrix, without d, and with a skip map and an incoming gradient; the Python op without the new
+    arguments still goes through the plain calls, and with confusion=True alone it gives the same loss and gradient"""
     from maskedsst_amd.ops import cross_entropy_stats
     R0, nc, M = shape
     for labels in LABELS:
@@ -267,6 +273,16 @@ def test_ce_ext_without_weights_gives_the_bits_of_the_existing_calls(shape):
                     assert np.array_equal(stats.host().confusion, with_cm["confusion"].cpu().numpy())
                 else:
                     assert stats.confusion is None and stats.sums is None and stats.host().confusion is None
+    # once per shape: without d (loss and record), and with a skip map and an incoming gradient
+    x, lab, _ = make_inputs(shape, "ignored25", "none", 1.0)
+    xc, lc = x.cuda(), lab.cuda()
+    same_bits(ext_abi(xc, lc, confusion=False, want_d=False), old_abi(xc, lc, want_d=False), ("loss", "record"), "R%d nc%d M%d no d" % shape)
+    gen = torch.Generator().manual_seed(79)
+    skip = torch.randint(0, nc, (R0, M), generator=gen)
+    skip[torch.rand(R0, M, generator=gen) < 0.2] = -1
+    sc, gout = skip.cuda(), torch.tensor(0.375, device="cuda")
+    same_bits(ext_abi(xc, lc, skip=sc, gout=gout), old_abi(xc, lc, skip=sc, gout=gout), ("loss", "record", "d", "dlogits"),
+              "R%d nc%d M%d skip gout" % shape)
 
 
 def test_ce_ext_python_op_skip_map_and_incoming_gradient():
