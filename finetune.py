@@ -126,6 +126,12 @@ def build_parser():
                          "full covariances = QDA, a tied one = LDA) on the raw frozen features and the split of --val-knn: the bank is the "
                          "first half of the --val-scenes, scored on the second half, with the mean distance to the predicted class and the "
                          "share of pixels farther than the bank's 0.99 quantile; needs --val-scenes and --val-every")
+    ap.add_argument("--val-crf", type=int, default=0, metavar="ITERS",
+                    help="one more line per validation: the accuracy of the class map before and after ITERS mean-field steps of the "
+                         "feature-guided CRF (maskedsst_amd.crf_affinity / crf_refine at the API defaults) over predict_scene's logits "
+                         "and one encode_scene pass on the --val-scenes, and the pixels whose class changed; needs --val-scenes and "
+                         "--val-every")
+    ap.add_argument("--val-crf-radius", type=int, default=2, metavar="R", help="the neighbourhood radius of --val-crf, 1 .. 3")
     ap.add_argument("--val-saliency", action="store_true",
                     help="one more line per validation: the five bands with the largest mean |gradient x input| attribution "
                          "(maskedsst_amd.band_importance, argmax class) over the windows of the --val-scenes")
@@ -241,6 +247,7 @@ def main():
     check_val_cluster(args)
     check_val_pca(args)
     check_val_gauss(args)
+    check_val_crf(args)
     if not 0.0 <= args.label_smoothing < 1.0:
         raise SystemExit("--label-smoothing must lie in [0, 1)")
     # --class-weights inverse: the weights come from the first step's labels, so the criterion is made there
@@ -302,6 +309,8 @@ def main():
                 validate_pca(model, val, step, args.val_pca)
             if args.val_gauss:
                 validate_gauss(model, val, step, args.val_gauss, config.n_classes, config.ignored_label)
+            if args.val_crf:
+                validate_crf(model, val, step, args.val_crf, args.val_crf_radius, config.ignored_label)
             if args.val_saliency:
                 validate_saliency(model, val, step)
             if args.val_saliency_scene:
@@ -568,6 +577,37 @@ def validate_gauss(model, val, step, covariance, n_classes, ignored_label):
             rejected = float((res.distance > limit).double().mean())
     print(f"val-gauss step {step} cov {covariance} gauss_acc {acc:.3f} mean_d2 {mean_d2:.4g} rejected {rejected:.3f} bank_pixels {len(ltr)} "
           f"test_pixels {len(lte)} scenes {val[0].shape[0]}", flush=True)
+
+
+def check_val_crf(args):
+    if not args.val_crf:
+        return
+    if args.val_crf < 1:
+        raise SystemExit("--val-crf ITERS must be at least 1")
+    if not 1 <= args.val_crf_radius <= 3:
+        raise SystemExit("--val-crf-radius R must lie in [1, 3]")
+    if args.val_scenes < 1 or args.val_every < 1:
+        raise SystemExit("--val-crf refines the validation scenes: it needs --val-scenes and --val-every")
+
+
+def validate_crf(model, val, step, iters, radius, ignored_label):
+    """--val-crf ITERS: the spectral-spatial last stage on the validation scenes.  predict_scene(return_logits=True) gives the logit
+    map, one encode_scene(normalize=True) pass the feature map; maskedsst_amd.crf_affinity (one HIP launch, radius --val-crf-radius,
+    the API defaults otherwise) and crf_refine (ITERS + 1 launches of msst_crf_step) refine it.  acc_before: the accuracy of the
+    argmax of softmax(logits) (step 0) on the labelled live pixels; acc_after: that of the refined map; changed: the pixels whose
+    class differs between the two.  nan when no labelled pixel is live."""
+    from maskedsst_amd import crf_affinity, crf_refine
+    img, lab = val
+    _, logits = model.predict_scene(img, return_logits=True)
+    aff = crf_affinity(model.encode_scene(img, normalize=True), radius=radius)
+    before = crf_refine(logits, aff, iters=0).classes
+    after = crf_refine(logits, aff, iters=iters).classes
+    ok = (lab != ignored_label) & (after >= 0)
+    acc0 = acc1 = float("nan")
+    if bool(ok.any()):
+        acc0, acc1 = float((before[ok] == lab[ok]).double().mean()), float((after[ok] == lab[ok]).double().mean())
+    print(f"val-crf step {step} iters {iters} radius {radius} acc_before {acc0:.3f} acc_after {acc1:.3f} changed {int((before != after).sum())} "
+          f"pixels {int(ok.sum())} scenes {img.shape[0]}", flush=True)
 
 
 def validate_saliency(model, val, step, batch=256, top=5):

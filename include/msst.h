@@ -553,6 +553,38 @@ int msst_gauss_score(const float* x, int x_layout, long rows, long plane, int di
                      const int32_t* class_table, const float* offsets, const float* consts, int nc, float max_d2, int32_t* classes,
                      float* distance, float* scores, int out_layout, void* stream);
 
+/* Feature-guided CRF refinement of class maps (maskedsst_amd/crf.py: crf_affinity, crf_refine, ViTSpatialSpectral.refine_scene): a
+ * local dense CRF (mean field, Potts compatibility) over the score maps the scene classifiers write.  Additive under MSST_VERSION 109:
+ * no struct and no existing signature changes.  dim == 96, 1 <= radius <= 3, 1 <= nc <= 128, fp32, no float atomics.  The
+ * K = (2 radius + 1)^2 - 1 neighbour offsets (dy, dx) are numbered j = 0 .. K-1 with dy ascending, then dx ascending, (0, 0) skipped.
+ *
+ * msst_crf_affinity: feat [Bs][96][Hs][Ws] (an encode_scene map, raw or normalised, read in place), cover [Bs][Hs][Ws] int32 or null
+ * -> k [Bs][K][Hs][Ws] and live [Bs][Hs][Ws] (uint8).  A pixel is live when its 96 features are finite, ss = the fp32 fmaf chain of
+ * their squares over d = 0 .. 95 from zero is positive and finite, and cover is null or > 0 there; rn = 1 / sqrtf(ss).
+ *   k[p, j] = fmaf(a_tab[j], expf(-(d2 g)), s_tab[j]) when p and q = p + o_j are live and q lies inside p's scene, else exactly 0;
+ *   d2 = max(0, 2 (1 - dot(f_p, f_q) (rn_p rn_q))), dot the fp32 fmaf chain over d = 0 .. 95 from zero (on the fp32 MFMA).
+ * a_tab and s_tab are HOST arrays [K], taken as they are.  With tables symmetric under o -> -o, k[p, j] and k[p + o_j, j'] (j' the
+ * opposite offset) have the same bits.
+ *
+ * msst_crf_step: one mean-field step.  scores, q_in (null: step 0), q_out: [Bs][nc][Hs][Ws]; k and live from msst_crf_affinity at the
+ * same radius.  U[c] = unary_scale scores[c] (unary 0) or unary_scale logf(max(scores[c], 1e-30)) (unary 1);
+ *   q_out = softmax_c(U[c] + sum_j k[p, j] q_in[c, p + o_j]), the sum one fmaf chain in j order from zero, the softmax with the maximum
+ *   subtracted and its sum in class order; without q_in: softmax_c(U).  The message is not divided by sum_j k.
+ * A neighbour whose q_in is NaN (a dead pixel) or that lies outside the scene is skipped by a test, not multiplied by zero.  A pixel
+ * that is not live, has a NaN score or no score above -inf gets NaN probabilities and class -1.  classes (int32 [Bs][Hs][Ws], may be
+ * null) is the argmax of q_out under the total order (value descending, then class ascending); with prev_classes (which may be the
+ * classes buffer itself) and changed, *changed (int32, zeroed by the caller) is increased by the number of live pixels whose class
+ * differs from prev_classes: integer atomics, bit-reproducible.
+ *
+ * Both check before any HIP call, in this order: MSST_ERR_BADARG for Bs, dim / nc, Hs or Ws below 1; MSST_ERR_UNSUPPORTED outside
+ * dim == 96, nc <= 128, 1 <= radius <= 3, or for more than 2^31 - 1 tiles; MSST_ERR_BADARG for a g that is negative or not finite, a
+ * unary outside {0, 1}, a unary_scale that is not positive and finite; MSST_ERR_BADARG for a null or misaligned required pointer,
+ * q_in == q_out, or changed without prev_classes. */
+int msst_crf_affinity(const float* feat, const int32_t* cover, int Bs, int dim, int Hs, int Ws, int radius, const float* a_tab,
+                      const float* s_tab, float g, float* k, uint8_t* live, void* stream);
+int msst_crf_step(const float* scores, int unary, float unary_scale, const float* q_in, const float* k, const uint8_t* live, int Bs, int nc,
+                  int Hs, int Ws, int radius, float* q_out, int32_t* classes, const int32_t* prev_classes, int32_t* changed, void* stream);
+
 /* a7-a10: one fused pre-norm transformer block (PreNorm+Attention+FeedForward+residuals,
  * vit_spatial_spectral.py:22-104) over all B*S*N tokens; mode selects the spatial or spectral
  * sequence grouping of vit_spatial_spectral.py:410-431 (no transposes are materialised).

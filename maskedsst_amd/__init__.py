@@ -20,6 +20,7 @@ from .probe import LinearProbe, ProbeScene, fit_linear_probe, probe_bank, probe_
 from .cluster import KMeans, ClusterScene, ClusterMatch, fit_kmeans, cluster_scene, contingency, match_clusters  # noqa: F401
 from .pca import FeaturePCA, PcaScene, AnomalyScene, fit_pca, pca_scene, anomaly_scene  # noqa: F401
 from .gaussian import GaussianClassifier, GaussianResult, GaussianScene, fit_gaussian, gaussian_predict_scene  # noqa: F401
+from .crf import CrfAffinity, CrfResult, RefinedScene, crf_affinity, crf_refine, refine_scene  # noqa: F401
 
 __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "MaskGenerator", "Reconstruction", "recon_report",
            "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows", "SceneEmbedding",
@@ -30,4 +31,5 @@ __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "
            "LinearProbe", "ProbeScene", "fit_linear_probe", "probe_bank", "probe_gradient", "probe_predict_scene",
            "KMeans", "ClusterScene", "ClusterMatch", "fit_kmeans", "cluster_scene", "contingency", "match_clusters",
            "FeaturePCA", "PcaScene", "AnomalyScene", "fit_pca", "pca_scene", "anomaly_scene",
-           "GaussianClassifier", "GaussianResult", "GaussianScene", "fit_gaussian", "gaussian_predict_scene"]
+           "GaussianClassifier", "GaussianResult", "GaussianScene", "fit_gaussian", "gaussian_predict_scene",
+           "CrfAffinity", "CrfResult", "RefinedScene", "crf_affinity", "crf_refine", "refine_scene"]

@@ -764,6 +764,33 @@ int msst_gauss_score(const float* x, int x_layout, long rows, long plane, int di
                                    distance, scores, out_layout, (hipStream_t)stream), "msst_gauss_score");
 }
 
+int msst_crf_affinity(const float* feat, const int32_t* cover, int Bs, int dim, int Hs, int Ws, int radius, const float* a_tab,
+                      const float* s_tab, float g, float* k, uint8_t* live, void* stream) {
+    if (Bs < 1 || dim < 1 || Hs < 1 || Ws < 1) return fail(MSST_ERR_BADARG, "msst_crf_affinity (Bs, dim, Hs or Ws below 1)");
+    if (dim != 96 || radius < 1 || radius > 3 || crf_tiles(Bs, Hs, Ws, 0) > 2147483647L)
+        return fail(MSST_ERR_UNSUPPORTED, "msst_crf_affinity (dim == 96, 1 <= radius <= 3, at most 2^31 - 1 tiles of 8 x 16 pixels)");
+    if (!(g >= 0.f) || !(g <= 3.4028234e38f)) return fail(MSST_ERR_BADARG, "msst_crf_affinity (g negative or not finite)");
+    if (!feat || !a_tab || !s_tab || !k || !live || ((uintptr_t)feat & 3) || ((uintptr_t)cover & 3) || ((uintptr_t)a_tab & 3) ||
+        ((uintptr_t)s_tab & 3) || ((uintptr_t)k & 3))
+        return fail(MSST_ERR_BADARG, "msst_crf_affinity (null or misaligned argument)");
+    return fail(launch_crf_affinity(feat, cover, Bs, Hs, Ws, radius, a_tab, s_tab, g, k, live, (hipStream_t)stream), "msst_crf_affinity");
+}
+
+int msst_crf_step(const float* scores, int unary, float unary_scale, const float* q_in, const float* k, const uint8_t* live, int Bs, int nc,
+                  int Hs, int Ws, int radius, float* q_out, int32_t* classes, const int32_t* prev_classes, int32_t* changed, void* stream) {
+    if (Bs < 1 || nc < 1 || Hs < 1 || Ws < 1) return fail(MSST_ERR_BADARG, "msst_crf_step (Bs, nc, Hs or Ws below 1)");
+    if (nc > 128 || radius < 1 || radius > 3 || crf_tiles(Bs, Hs, Ws, 1) > 2147483647L)
+        return fail(MSST_ERR_UNSUPPORTED, "msst_crf_step (nc <= 128, 1 <= radius <= 3, at most 2^31 - 1 tiles of 8 x 32 pixels)");
+    if (unary < 0 || unary > 1 || !(unary_scale > 0.f) || !(unary_scale <= 3.4028234e38f))
+        return fail(MSST_ERR_BADARG, "msst_crf_step (unary outside {0, 1}, or unary_scale not positive and finite)");
+    if (!scores || !k || !live || !q_out || q_in == q_out || ((uintptr_t)scores & 3) || ((uintptr_t)q_in & 3) || ((uintptr_t)k & 3) ||
+        ((uintptr_t)q_out & 3) || ((uintptr_t)classes & 3) || ((uintptr_t)prev_classes & 3) || ((uintptr_t)changed & 3))
+        return fail(MSST_ERR_BADARG, "msst_crf_step (null or misaligned argument, or q_in == q_out)");
+    if (changed && !prev_classes) return fail(MSST_ERR_BADARG, "msst_crf_step (changed without prev_classes)");
+    return fail(launch_crf_step(scores, unary, unary_scale, q_in, k, live, Bs, nc, Hs, Ws, radius, q_out, classes, prev_classes, changed,
+                                (hipStream_t)stream), "msst_crf_step");
+}
+
 int msst_scene_embed_assemble(const float* win_feat, long win0, int nwin, float* feat, int32_t* cover, int Bs, int D, int Hs, int Ws,
                               int window, int stride, int finalize, int l2norm, void* stream) {
     if (Bs < 1 || D < 1 || Hs < 1 || Ws < 1 || window < 1 || stride < 1 || nwin < 0 || win0 < 0)

@@ -581,6 +581,15 @@ int launch_gauss_score(const float* x, int x_layout, long rows, long plane, cons
                        const int32_t* class_table, const float* offsets, const float* consts, int nc, float max_d2, int32_t* classes,
                        float* distance, float* scores, int out_layout, hipStream_t st);
 
+// msst_crf.hip (msst_crf_affinity, msst_crf_step): the pairwise weights of a local dense CRF from the feature map (a tile with its halo
+// in LDS once, the dots on the fp32 MFMA) and one mean-field step over the score maps.  a_tab and s_tab are HOST arrays [K];
+// crf_tiles is the grid of either launch (which 0: affinity, 1: step), for the caller's range check
+int launch_crf_affinity(const float* feat, const int32_t* cover, int Bs, int Hs, int Ws, int R, const float* a_tab, const float* s_tab, float g,
+                        float* k, uint8_t* live, hipStream_t st);
+int launch_crf_step(const float* scores, int unary, float unary_scale, const float* q_in, const float* k, const uint8_t* live, int Bs, int nc,
+                    int Hs, int Ws, int R, float* q_out, int32_t* classes, const int32_t* prev_classes, int32_t* changed, hipStream_t st);
+long crf_tiles(int Bs, int Hs, int Ws, int which);
+
 // msst_mask.hip (msst_draw_masks): the SimMIM token mask, gather indices and the gather's token-CSR of global rows row0 .. row0 + rows - 1
 // from a counter hash; one workgroup per row
 struct MaskDrawArgs {

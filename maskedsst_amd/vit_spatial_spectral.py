@@ -511,6 +511,25 @@ class ViTSpatialSpectral(nn.Module):
         from .gaussian import gaussian_predict_scene
         return gaussian_predict_scene(self, scene, clf, stride, max_distance, max_windows)
 
+    def refine_scene(self, scene, scores, embedding=None, stride=None, iters=5, unary="logits", unary_scale=1.0, **affinity_kwargs):
+        """The class map of whole scenes [Bs, channels, Hs, Ws] after a feature-guided CRF (mean field, Potts compatibility) over the
+        score maps `scores` [Bs, nc, Hs, Ws] of any scene classifier -- predict_scene's logits, probe_predict_scene's logits,
+        gaussian_predict_scene's scores (unary="logits") or knn_predict_scene's votes (unary="votes"): ONE msst_crf_affinity launch on
+        the feature map in place, then iters + 1 msst_crf_step launches.  Returns RefinedScene(classes, probs, history, cover):
+          classes   [Bs, Hs, Ws] int64: the argmax of the last probabilities under the total order (value descending, then class
+                    ascending); -1 where the pixel is dead (uncovered, features not finite or zero, a NaN score, no score above -inf);
+          probs     [Bs, nc, Hs, Ws] fp32; NaN where dead;
+          history   [iters] int64 on the CPU: the live pixels whose class changed in each step;
+          cover     as from encode_scene.
+        embedding=None runs encode_scene(normalize=True) (stride: encode_scene's); pass the SceneEmbedding a *_predict_scene call was
+        made from to avoid a second encoder pass -- a raw map and a normalised one both work, the kernel forms the norms.
+        affinity_kwargs: radius, w_appearance, theta_feature, theta_position, w_smooth, theta_smooth of maskedsst_amd.crf_affinity; the
+        defaults are API defaults, not tuned on data.  The message is not normalised: border pixels are smoothed less.  The maps have
+        the same bits in every call and equal crf_refine on encode_scene's map.  No head runs; the module's mode is left unchanged.
+        ValueError, before any device work, for wrong shapes, dtypes or ranges, or a scene encode_scene refuses."""
+        from .crf import refine_scene
+        return refine_scene(self, scene, scores, embedding, stride, iters, unary, unary_scale, **affinity_kwargs)
+
     def attention_maps(self, img, stack="both", reduce="mean", blocks=None):
         """The attention probabilities of the transformer blocks for img [B, channels, image_size, image_size] (fp32, on the device):
         AttentionMaps(spatial, spectral), fp32 on the device; the stack not asked for is None.
