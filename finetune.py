@@ -132,6 +132,13 @@ def build_parser():
                          "and one encode_scene pass on the --val-scenes, and the pixels whose class changed; needs --val-scenes and "
                          "--val-every")
     ap.add_argument("--val-crf-radius", type=int, default=2, metavar="R", help="the neighbourhood radius of --val-crf, 1 .. 3")
+    ap.add_argument("--val-superpixel", type=int, default=0, metavar="STEP",
+                    help="one more line per validation: the accuracy of the class map before and after object-based classification -- "
+                         "SLIC superpixels (maskedsst_amd.fit_superpixels, grid step STEP in {4, 8, 16}, the API defaults otherwise) of "
+                         "one encode_scene pass on the --val-scenes, predict_scene's logits pooled per superpixel "
+                         "(superpixel_classify) -- and the pixels whose class changed; needs --val-scenes and --val-every")
+    ap.add_argument("--val-superpixel-compactness", type=float, default=0.2, metavar="M",
+                    help="the compactness of --val-superpixel: the weight of a step's distance against a unit of feature distance")
     ap.add_argument("--val-saliency", action="store_true",
                     help="one more line per validation: the five bands with the largest mean |gradient x input| attribution "
                          "(maskedsst_amd.band_importance, argmax class) over the windows of the --val-scenes")
@@ -248,6 +255,7 @@ def main():
     check_val_pca(args)
     check_val_gauss(args)
     check_val_crf(args)
+    check_val_superpixel(args)
     if not 0.0 <= args.label_smoothing < 1.0:
         raise SystemExit("--label-smoothing must lie in [0, 1)")
     # --class-weights inverse: the weights come from the first step's labels, so the criterion is made there
@@ -311,6 +319,8 @@ def main():
                 validate_gauss(model, val, step, args.val_gauss, config.n_classes, config.ignored_label)
             if args.val_crf:
                 validate_crf(model, val, step, args.val_crf, args.val_crf_radius, config.ignored_label)
+            if args.val_superpixel:
+                validate_superpixel(model, val, step, args.val_superpixel, args.val_superpixel_compactness, config.ignored_label)
             if args.val_saliency:
                 validate_saliency(model, val, step)
             if args.val_saliency_scene:
@@ -608,6 +618,39 @@ def validate_crf(model, val, step, iters, radius, ignored_label):
         acc0, acc1 = float((before[ok] == lab[ok]).double().mean()), float((after[ok] == lab[ok]).double().mean())
     print(f"val-crf step {step} iters {iters} radius {radius} acc_before {acc0:.3f} acc_after {acc1:.3f} changed {int((before != after).sum())} "
           f"pixels {int(ok.sum())} scenes {img.shape[0]}", flush=True)
+
+
+def check_val_superpixel(args):
+    if not args.val_superpixel:
+        return
+    if args.val_superpixel not in (4, 8, 16):
+        raise SystemExit("--val-superpixel STEP must be 4, 8 or 16")
+    c = args.val_superpixel_compactness
+    if not (c >= 0.0 and c < float("inf")):
+        raise SystemExit("--val-superpixel-compactness M must be a finite number >= 0")
+    if args.val_scenes < 1 or args.val_every < 1:
+        raise SystemExit("--val-superpixel segments the validation scenes: it needs --val-scenes and --val-every")
+
+
+def validate_superpixel(model, val, step, sp_step, compactness, ignored_label):
+    """--val-superpixel STEP: object-based classification of the validation scenes.  predict_scene(return_logits=True) gives the
+    logit map, one encode_scene(normalize=True) pass the feature map; maskedsst_amd.fit_superpixels (grid step STEP, compactness
+    --val-superpixel-compactness, the API default of 10 iterations) segments it and superpixel_classify pools the logits per
+    superpixel and gives every pixel its superpixel's class.  acc_before: the accuracy of predict_scene's class map on the labelled
+    live pixels; acc_after: that of the object-based map; changed: the live pixels whose class differs between the two; superpixels:
+    those with at least one pixel.  nan when no labelled pixel is live."""
+    from maskedsst_amd import fit_superpixels, superpixel_classify
+    img, lab = val
+    before, logits = model.predict_scene(img, return_logits=True)
+    sp = fit_superpixels(model.encode_scene(img, normalize=True), step=sp_step, compactness=compactness)
+    after = superpixel_classify(sp, logits).classes
+    live = after >= 0
+    ok = (lab != ignored_label) & live
+    acc0 = acc1 = float("nan")
+    if bool(ok.any()):
+        acc0, acc1 = float((before[ok] == lab[ok]).double().mean()), float((after[ok] == lab[ok]).double().mean())
+    print(f"val-superpixel step {step} sp_step {sp_step} superpixels {int((sp.counts > 0).sum())} acc_before {acc0:.3f} acc_after {acc1:.3f} "
+          f"changed {int(((before != after) & live).sum())} pixels {int(ok.sum())} scenes {img.shape[0]}", flush=True)
 
 
 def validate_saliency(model, val, step, batch=256, top=5):

@@ -585,6 +585,56 @@ int msst_crf_affinity(const float* feat, const int32_t* cover, int Bs, int dim, 
 int msst_crf_step(const float* scores, int unary, float unary_scale, const float* q_in, const float* k, const uint8_t* live, int Bs, int nc,
                   int Hs, int Ws, int radius, float* q_out, int32_t* classes, const int32_t* prev_classes, int32_t* changed, void* stream);
 
+/* SLIC superpixels of an encode_scene feature map and object-based class maps (maskedsst_amd/superpixel.py: fit_superpixels,
+ * superpixel_pool, superpixel_classify, ViTSpatialSpectral.superpixel_scene): the grid form of SLIC (Achanta et al. 2012; gSLICr).
+ * Additive under MSST_VERSION 109: no struct and no existing signature changes.  dim == 96, step S in {4, 8, 16}, C <= 128, Hs, Ws <=
+ * 32768, fp32, no float atomics: the same bits in every call.
+ *
+ * Grid: gy = ceil(Hs / S) by gx = ceil(Ws / S) cells per scene; cell (i, j) owns rows [i S, min((i + 1) S, Hs)) and columns [j S,
+ * min((j + 1) S, Ws)); superpixel id = i gx + j per scene, n_sp = gy gx.  A centre is centroids [Bs][n_sp][96], offsets [Bs][n_sp][2]
+ * (y, x as fp32 offsets from the centre's own cell origin, in [-S, 2 S)), bias [Bs][n_sp], counts [Bs][n_sp] int32.  Labels and classes
+ * are int64 [Bs][Hs][Ws], -1 for a dead pixel.
+ * Live: the 96 features are finite and cover (int32 [Bs][Hs][Ws], may be null) is > 0.  A dead pixel gets label -1 and contributes to no
+ * sum.  Nothing crosses the scene border; nothing passes between the scenes of a batch.
+ *
+ * msst_slic_assign: a live pixel in cell (i, j) competes among the centres of cells (i + di, j + dj), di, dj in {-1, 0, 1}, that lie
+ * inside the grid and have count > 0:
+ *   s_c(p) = fmaf(-hl, fmaf(dy, dy, dx dx), dot(f_p, c) + bias_c), dot the fp32 fmaf chain over d = 0 .. 95 from zero (on the fp32 MFMA),
+ *   dy = (float)(y_p - i_c S) - offset_y (the integer is formed from the cell difference: small and exact), dx alike;
+ * ONE total order: score descending, then superpixel id ascending; no candidate: label -1.  centroids == null is the home mode
+ * (iteration 0): every live pixel takes its own cell, offsets, bias, counts and hl are not read.  With prev_labels (which may be the
+ * labels buffer itself) and moved, *moved (int32, zeroed by the caller) is increased by the number of pixels whose label differs from
+ * prev_labels: integer atomics, bit-reproducible.  best ([Bs][Hs][Ws], may be null) receives the winning score, NaN for label -1 and in
+ * the home mode.  With slab (msst_slic_scratch_floats(Bs, Hs, Ws, S, MSST_SLIC_FIT_CHANNELS) floats)
+ * every block of 8 x 8 pixels writes the sums of its pixels' features, places and the counts per centre of its window.
+ * msst_slic_update: per centre the slab entries that can hold it, added in an order that depends on (Hs, Ws, S) alone; count > 0:
+ * centroid = sum / count, offset = sum / count (one IEEE division each), bias = -0.5 x the fp32 fmaf chain of c[d]^2 from zero; count
+ * == 0: counts becomes 0, centroid, offset and bias are kept, and the centre is never a candidate from then on.  *empty (int32, zeroed
+ * by the caller, may be null) is increased by the number of empty centres.
+ * msst_slic_pool / msst_slic_pool_finish: map [Bs][C][Hs][Ws] and labels -> table [Bs][n_sp][C] = the mean over the pixels of each
+ * superpixel, a fixed-order sum (a selection, never a product with zero: -inf pools to -inf) and one division, NaN for a superpixel
+ * without pixels; region_classes (int64 [Bs][n_sp], may be null) = the first largest entry above -inf, -1 where there is none.  Labels
+ * are those of a fit: a label outside the 3 x 3 cells of its pixel contributes to no sum.
+ * msst_slic_broadcast: classes[p] = region_classes[labels[p]], -1 for a label outside [0, n_sp).
+ * msst_slic_scratch_floats: the floats of a slab for C summed channels; 0 for arguments the calls refuse.
+ *
+ * All check before any HIP call, in this order: MSST_ERR_BADARG for a size below 1; MSST_ERR_UNSUPPORTED outside dim == 96, step in
+ * {4, 8, 16}, C <= 128, Hs, Ws <= 32768 (or more than 2^29 blocks); MSST_ERR_BADARG for an hl that is negative or not finite; then
+ * MSST_ERR_BADARG for a null or misaligned required pointer, centroids without offsets, bias and counts, moved without prev_labels, or
+ * a short slab.  msst_last_error names the call. */
+#define MSST_SLIC_FIT_CHANNELS 98   /* 96 feature sums and 2 place sums per centre; the count is the slab's own column */
+long msst_slic_scratch_floats(int Bs, int Hs, int Ws, int step, int C);
+int msst_slic_assign(const float* feat, const int32_t* cover, int Bs, int dim, int Hs, int Ws, int step, float hl, const float* centroids,
+                     const float* offsets, const float* bias, const int32_t* counts, int64_t* labels, const int64_t* prev_labels, int32_t* moved,
+                     float* best, float* slab, long slab_floats, void* stream);
+int msst_slic_update(const float* slab, long slab_floats, int Bs, int dim, int Hs, int Ws, int step, float* centroids, float* offsets,
+                     float* bias, int32_t* counts, int32_t* empty, void* stream);
+int msst_slic_pool(const float* map, const int64_t* labels, int Bs, int C, int Hs, int Ws, int step, float* slab, long slab_floats,
+                   void* stream);
+int msst_slic_pool_finish(const float* slab, long slab_floats, int Bs, int C, int Hs, int Ws, int step, float* table, int64_t* region_classes,
+                          void* stream);
+int msst_slic_broadcast(const int64_t* labels, const int64_t* region_classes, int Bs, int Hs, int Ws, int step, int64_t* classes, void* stream);
+
 /* a7-a10: one fused pre-norm transformer block (PreNorm+Attention+FeedForward+residuals,
  * vit_spatial_spectral.py:22-104) over all B*S*N tokens; mode selects the spatial or spectral
  * sequence grouping of vit_spatial_spectral.py:410-431 (no transposes are materialised).

@@ -21,6 +21,8 @@ from .cluster import KMeans, ClusterScene, ClusterMatch, fit_kmeans, cluster_sce
 from .pca import FeaturePCA, PcaScene, AnomalyScene, fit_pca, pca_scene, anomaly_scene  # noqa: F401
 from .gaussian import GaussianClassifier, GaussianResult, GaussianScene, fit_gaussian, gaussian_predict_scene  # noqa: F401
 from .crf import CrfAffinity, CrfResult, RefinedScene, crf_affinity, crf_refine, refine_scene  # noqa: F401
+from .superpixel import (Superpixels, ObjectResult, SuperpixelScene, SlicCentres, fit_superpixels, superpixel_pool,  # noqa: F401
+                         superpixel_classify, superpixel_assign, superpixel_update, superpixel_scene)
 
 __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "MaskGenerator", "Reconstruction", "recon_report",
            "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows", "SceneEmbedding",
@@ -32,4 +34,6 @@ __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "
            "KMeans", "ClusterScene", "ClusterMatch", "fit_kmeans", "cluster_scene", "contingency", "match_clusters",
            "FeaturePCA", "PcaScene", "AnomalyScene", "fit_pca", "pca_scene", "anomaly_scene",
            "GaussianClassifier", "GaussianResult", "GaussianScene", "fit_gaussian", "gaussian_predict_scene",
-           "CrfAffinity", "CrfResult", "RefinedScene", "crf_affinity", "crf_refine", "refine_scene"]
+           "CrfAffinity", "CrfResult", "RefinedScene", "crf_affinity", "crf_refine", "refine_scene",
+           "Superpixels", "ObjectResult", "SuperpixelScene", "SlicCentres", "fit_superpixels", "superpixel_pool", "superpixel_classify",
+           "superpixel_assign", "superpixel_update", "superpixel_scene"]

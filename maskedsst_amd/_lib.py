@@ -114,6 +114,12 @@ _SIGS = {
     "msst_gauss_score": (c_int, [_P, c_int, c_long, c_long, c_int, _P, _P, c_int, _P, _P, _P, c_int, c_float, _P, _P, _P, c_int, _P]),
     "msst_crf_affinity": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_float, _P, _P, _P]),
     "msst_crf_step": (c_int, [_P, c_int, c_float, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "msst_slic_scratch_floats": (c_long, [c_int, c_int, c_int, c_int, c_int]),
+    "msst_slic_assign": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_long, _P]),
+    "msst_slic_update": (c_int, [_P, c_long, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "msst_slic_pool": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_long, _P]),
+    "msst_slic_pool_finish": (c_int, [_P, c_long, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "msst_slic_broadcast": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "msst_draw_masks": (c_int, [_P, _P, _P, _P, c_uint32, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "msst_scene_assemble": (c_int, [_P, c_long, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "msst_cls_head_fwd": (c_int, [_P] * 6 + [c_int, c_int, c_int, c_int, _P]),

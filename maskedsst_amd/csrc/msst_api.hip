@@ -791,6 +791,75 @@ int msst_crf_step(const float* scores, int unary, float unary_scale, const float
                                 (hipStream_t)stream), "msst_crf_step");
 }
 
+// the sizes every SLIC call shares: C is 96 where the call has no channel count of its own
+static int slic_shape(const char* what, int Bs, int dim, int Hs, int Ws, int step, int C) {
+    if (Bs < 1 || dim < 1 || Hs < 1 || Ws < 1 || step < 1 || C < 1) return fail(MSST_ERR_BADARG, what, " (Bs, dim, Hs, Ws, step or C below 1)");
+    if (dim != 96 || (step != 4 && step != 8 && step != 16) || C > 128 || Hs > 32768 || Ws > 32768 || slic_blocks(Bs, Hs, Ws) > (1L << 29))
+        return fail(MSST_ERR_UNSUPPORTED, what, " (dim == 96, step in {4, 8, 16}, C <= 128, Hs, Ws <= 32768, blocks <= 2^29)");
+    return 0;
+}
+
+long msst_slic_scratch_floats(int Bs, int Hs, int Ws, int step, int C) {
+    if (Bs < 1 || Hs < 1 || Ws < 1 || C < 1 || C > 128 || (step != 4 && step != 8 && step != 16) || Hs > 32768 || Ws > 32768 ||
+        slic_blocks(Bs, Hs, Ws) > (1L << 29))
+        return 0;
+    return slic_scratch_floats(Bs, Hs, Ws, C);
+}
+
+int msst_slic_assign(const float* feat, const int32_t* cover, int Bs, int dim, int Hs, int Ws, int step, float hl, const float* centroids,
+                     const float* offsets, const float* bias, const int32_t* counts, int64_t* labels, const int64_t* prev_labels, int32_t* moved,
+                     float* best, float* slab, long slab_floats, void* stream) {
+    if (int rc = slic_shape("msst_slic_assign", Bs, dim, Hs, Ws, step, 96)) return rc;
+    if (!(hl >= 0.f) || !(hl <= 3.4028234e38f)) return fail(MSST_ERR_BADARG, "msst_slic_assign (hl negative or not finite)");
+    if (!feat || !labels || ((uintptr_t)feat & 3) || ((uintptr_t)cover & 3) || ((uintptr_t)centroids & 3) || ((uintptr_t)offsets & 3) ||
+        ((uintptr_t)bias & 3) || ((uintptr_t)counts & 3) || ((uintptr_t)labels & 7) || ((uintptr_t)prev_labels & 7) || ((uintptr_t)moved & 3) ||
+        ((uintptr_t)best & 3) || ((uintptr_t)slab & 3))
+        return fail(MSST_ERR_BADARG, "msst_slic_assign (null or misaligned argument)");
+    if (centroids && (!offsets || !bias || !counts)) return fail(MSST_ERR_BADARG, "msst_slic_assign (centroids without offsets, bias and counts)");
+    if (moved && !prev_labels) return fail(MSST_ERR_BADARG, "msst_slic_assign (moved without prev_labels)");
+    if (slab && slab_floats < slic_scratch_floats(Bs, Hs, Ws, MSST_SLIC_FIT_CHANNELS))
+        return fail(MSST_ERR_BADARG, "msst_slic_assign (slab smaller than msst_slic_scratch_floats(.., MSST_SLIC_FIT_CHANNELS))");
+    return fail(launch_slic_assign(feat, cover, Bs, Hs, Ws, step, hl, centroids, offsets, bias, counts, labels, prev_labels, moved, best, slab,
+                                   (hipStream_t)stream), "msst_slic_assign");
+}
+
+int msst_slic_update(const float* slab, long slab_floats, int Bs, int dim, int Hs, int Ws, int step, float* centroids, float* offsets,
+                     float* bias, int32_t* counts, int32_t* empty, void* stream) {
+    if (int rc = slic_shape("msst_slic_update", Bs, dim, Hs, Ws, step, 96)) return rc;
+    if (!slab || !centroids || !offsets || !bias || !counts || ((uintptr_t)slab & 3) || ((uintptr_t)centroids & 3) || ((uintptr_t)offsets & 3) ||
+        ((uintptr_t)bias & 3) || ((uintptr_t)counts & 3) || ((uintptr_t)empty & 3))
+        return fail(MSST_ERR_BADARG, "msst_slic_update (null or misaligned argument)");
+    if (slab_floats < slic_scratch_floats(Bs, Hs, Ws, MSST_SLIC_FIT_CHANNELS))
+        return fail(MSST_ERR_BADARG, "msst_slic_update (slab smaller than msst_slic_scratch_floats(.., MSST_SLIC_FIT_CHANNELS))");
+    return fail(launch_slic_update(slab, Bs, Hs, Ws, step, centroids, offsets, bias, counts, empty, (hipStream_t)stream), "msst_slic_update");
+}
+
+int msst_slic_pool(const float* map, const int64_t* labels, int Bs, int C, int Hs, int Ws, int step, float* slab, long slab_floats,
+                   void* stream) {
+    if (int rc = slic_shape("msst_slic_pool", Bs, 96, Hs, Ws, step, C)) return rc;
+    if (!map || !labels || !slab || ((uintptr_t)map & 3) || ((uintptr_t)labels & 7) || ((uintptr_t)slab & 3))
+        return fail(MSST_ERR_BADARG, "msst_slic_pool (null or misaligned argument)");
+    if (slab_floats < slic_scratch_floats(Bs, Hs, Ws, C)) return fail(MSST_ERR_BADARG, "msst_slic_pool (slab smaller than msst_slic_scratch_floats)");
+    return fail(launch_slic_pool(map, labels, Bs, C, Hs, Ws, step, slab, (hipStream_t)stream), "msst_slic_pool");
+}
+
+int msst_slic_pool_finish(const float* slab, long slab_floats, int Bs, int C, int Hs, int Ws, int step, float* table, int64_t* region_classes,
+                          void* stream) {
+    if (int rc = slic_shape("msst_slic_pool_finish", Bs, 96, Hs, Ws, step, C)) return rc;
+    if (!slab || !table || ((uintptr_t)slab & 3) || ((uintptr_t)table & 3) || ((uintptr_t)region_classes & 7))
+        return fail(MSST_ERR_BADARG, "msst_slic_pool_finish (null or misaligned argument)");
+    if (slab_floats < slic_scratch_floats(Bs, Hs, Ws, C))
+        return fail(MSST_ERR_BADARG, "msst_slic_pool_finish (slab smaller than msst_slic_scratch_floats)");
+    return fail(launch_slic_pool_finish(slab, Bs, C, Hs, Ws, step, table, region_classes, (hipStream_t)stream), "msst_slic_pool_finish");
+}
+
+int msst_slic_broadcast(const int64_t* labels, const int64_t* region_classes, int Bs, int Hs, int Ws, int step, int64_t* classes, void* stream) {
+    if (int rc = slic_shape("msst_slic_broadcast", Bs, 96, Hs, Ws, step, 96)) return rc;
+    if (!labels || !region_classes || !classes || ((uintptr_t)labels & 7) || ((uintptr_t)region_classes & 7) || ((uintptr_t)classes & 7))
+        return fail(MSST_ERR_BADARG, "msst_slic_broadcast (null or misaligned argument)");
+    return fail(launch_slic_broadcast(labels, region_classes, Bs, Hs, Ws, step, classes, (hipStream_t)stream), "msst_slic_broadcast");
+}
+
 int msst_scene_embed_assemble(const float* win_feat, long win0, int nwin, float* feat, int32_t* cover, int Bs, int D, int Hs, int Ws,
                               int window, int stride, int finalize, int l2norm, void* stream) {
     if (Bs < 1 || D < 1 || Hs < 1 || Ws < 1 || window < 1 || stride < 1 || nwin < 0 || win0 < 0)

@@ -590,6 +590,21 @@ int launch_crf_step(const float* scores, int unary, float unary_scale, const flo
                     int Hs, int Ws, int R, float* q_out, int32_t* classes, const int32_t* prev_classes, int32_t* changed, hipStream_t st);
 long crf_tiles(int Bs, int Hs, int Ws, int which);
 
+// msst_slic.hip (msst_slic_assign, msst_slic_update, msst_slic_pool, msst_slic_pool_finish, msst_slic_broadcast): SLIC superpixels of the
+// feature map in the grid form -- an 8 x 8 pixel block against the at most 16 centres of its window on the fp32 MFMA, per-block partial
+// sums without float atomics, the ordered per-centre update -- and the per-superpixel means, region classes and class map of any map.
+// slic_blocks is the grid of the per-block launches, for the caller's range check; a slab holds slic_scratch_floats(.., C) floats
+long slic_blocks(int Bs, int Hs, int Ws);
+long slic_scratch_floats(int Bs, int Hs, int Ws, int C);
+int launch_slic_assign(const float* feat, const int32_t* cover, int Bs, int Hs, int Ws, int step, float hl, const float* centroids,
+                       const float* offsets, const float* bias, const int32_t* counts, int64_t* labels, const int64_t* prev_labels, int32_t* moved,
+                       float* best, float* slab, hipStream_t st);
+int launch_slic_update(const float* slab, int Bs, int Hs, int Ws, int step, float* centroids, float* offsets, float* bias, int32_t* counts,
+                       int32_t* empty, hipStream_t st);
+int launch_slic_pool(const float* map, const int64_t* labels, int Bs, int C, int Hs, int Ws, int step, float* slab, hipStream_t st);
+int launch_slic_pool_finish(const float* slab, int Bs, int C, int Hs, int Ws, int step, float* table, int64_t* region_classes, hipStream_t st);
+int launch_slic_broadcast(const int64_t* labels, const int64_t* region_classes, int Bs, int Hs, int Ws, int step, int64_t* classes, hipStream_t st);
+
 // msst_mask.hip (msst_draw_masks): the SimMIM token mask, gather indices and the gather's token-CSR of global rows row0 .. row0 + rows - 1
 // from a counter hash; one workgroup per row
 struct MaskDrawArgs {

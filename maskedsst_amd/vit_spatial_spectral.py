@@ -530,6 +530,23 @@ class ViTSpatialSpectral(nn.Module):
         from .crf import refine_scene
         return refine_scene(self, scene, scores, embedding, stride, iters, unary, unary_scale, **affinity_kwargs)
 
+    def superpixel_scene(self, scene, scores=None, embedding=None, stride=None, step=8, compactness=0.2, iters=10):
+        """SLIC superpixels of whole scenes [Bs, channels, Hs, Ws] from the encoder's feature map and, with the score maps `scores`
+        [Bs, nc, Hs, Ws] of any scene classifier (predict_scene's logits, probe_predict_scene's logits, gaussian_predict_scene's
+        scores, knn_predict_scene's votes), the object-based class map: the scores pooled per superpixel, every pixel given its
+        superpixel's class.  Returns SuperpixelScene(superpixels, classes, region_scores, cover):
+          superpixels    maskedsst_amd.fit_superpixels' result (labels, centroids, positions, counts, history, step, grid);
+          classes        [Bs, Hs, Ws] int64, -1 where the pixel is dead (uncovered, features not finite); None without scores;
+          region_scores  [Bs, n_sp, nc] fp32, NaN for a superpixel without pixels; None without scores;
+          cover          as from encode_scene.
+        embedding=None runs encode_scene(normalize=True) (stride: encode_scene's); pass the SceneEmbedding a *_predict_scene call was
+        made from to avoid a second encoder pass.  step in {4, 8, 16}; step, compactness and iters are API defaults, not tuned on
+        data.  No connectivity enforcement.  The maps have the same bits in every call and equal fit_superpixels and
+        superpixel_classify on encode_scene's map.  No head runs; the module's mode is left unchanged.  ValueError, before any device
+        work, for wrong shapes, dtypes or ranges, or a scene encode_scene refuses."""
+        from .superpixel import superpixel_scene
+        return superpixel_scene(self, scene, scores, embedding, stride, step, compactness, iters)
+
     def attention_maps(self, img, stack="both", reduce="mean", blocks=None):
         """The attention probabilities of the transformer blocks for img [B, channels, image_size, image_size] (fp32, on the device):
         AttentionMaps(spatial, spectral), fp32 on the device; the stack not asked for is None.
