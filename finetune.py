@@ -139,6 +139,15 @@ def build_parser():
                          "(superpixel_classify) -- and the pixels whose class changed; needs --val-scenes and --val-every")
     ap.add_argument("--val-superpixel-compactness", type=float, default=0.2, metavar="M",
                     help="the compactness of --val-superpixel: the weight of a step's distance against a unit of feature distance")
+    ap.add_argument("--val-superpixel-connect", action="store_true",
+                    help="with --val-superpixel: one more line after it, the superpixels after SLIC's connectivity pass "
+                         "(maskedsst_amd.enforce_connectivity): the orphan pieces before and after, and the accuracy of the object-based "
+                         "map on the connected superpixels")
+    ap.add_argument("--val-sieve", type=int, default=0, metavar="MIN_SIZE",
+                    help="one more line per validation: the sieve (minimum mapping unit, maskedsst_amd.sieve_classes) on predict_scene's "
+                         "class maps of the --val-scenes -- connected patches of fewer than MIN_SIZE pixels merged into their largest "
+                         "neighbour -- with the regions and the accuracy before and after; needs --val-scenes and --val-every")
+    ap.add_argument("--val-sieve-connectivity", type=int, default=4, choices=(4, 8), help="the connectivity of --val-sieve")
     ap.add_argument("--val-saliency", action="store_true",
                     help="one more line per validation: the five bands with the largest mean |gradient x input| attribution "
                          "(maskedsst_amd.band_importance, argmax class) over the windows of the --val-scenes")
@@ -256,6 +265,7 @@ def main():
     check_val_gauss(args)
     check_val_crf(args)
     check_val_superpixel(args)
+    check_val_sieve(args)
     if not 0.0 <= args.label_smoothing < 1.0:
         raise SystemExit("--label-smoothing must lie in [0, 1)")
     # --class-weights inverse: the weights come from the first step's labels, so the criterion is made there
@@ -320,7 +330,10 @@ def main():
             if args.val_crf:
                 validate_crf(model, val, step, args.val_crf, args.val_crf_radius, config.ignored_label)
             if args.val_superpixel:
-                validate_superpixel(model, val, step, args.val_superpixel, args.val_superpixel_compactness, config.ignored_label)
+                validate_superpixel(model, val, step, args.val_superpixel, args.val_superpixel_compactness, config.ignored_label,
+                                    connect=args.val_superpixel_connect)
+            if args.val_sieve:
+                validate_sieve(model, val, step, args.val_sieve, args.val_sieve_connectivity, config.ignored_label)
             if args.val_saliency:
                 validate_saliency(model, val, step)
             if args.val_saliency_scene:
@@ -621,6 +634,8 @@ def validate_crf(model, val, step, iters, radius, ignored_label):
 
 
 def check_val_superpixel(args):
+    if args.val_superpixel_connect and not args.val_superpixel:
+        raise SystemExit("--val-superpixel-connect connects the superpixels of --val-superpixel STEP: it needs that flag")
     if not args.val_superpixel:
         return
     if args.val_superpixel not in (4, 8, 16):
@@ -632,14 +647,17 @@ def check_val_superpixel(args):
         raise SystemExit("--val-superpixel segments the validation scenes: it needs --val-scenes and --val-every")
 
 
-def validate_superpixel(model, val, step, sp_step, compactness, ignored_label):
+def validate_superpixel(model, val, step, sp_step, compactness, ignored_label, connect=False):
     """--val-superpixel STEP: object-based classification of the validation scenes.  predict_scene(return_logits=True) gives the
     logit map, one encode_scene(normalize=True) pass the feature map; maskedsst_amd.fit_superpixels (grid step STEP, compactness
     --val-superpixel-compactness, the API default of 10 iterations) segments it and superpixel_classify pools the logits per
     superpixel and gives every pixel its superpixel's class.  acc_before: the accuracy of predict_scene's class map on the labelled
     live pixels; acc_after: that of the object-based map; changed: the live pixels whose class differs between the two; superpixels:
-    those with at least one pixel.  nan when no labelled pixel is live."""
-    from maskedsst_amd import fit_superpixels, superpixel_classify
+    those with at least one pixel.  nan when no labelled pixel is live.
+    connect (--val-superpixel-connect): one more line, after maskedsst_amd.enforce_connectivity at its defaults on the same
+    superpixels: fragments_before / fragments_after: the pieces beyond one per superpixel; acc_after: the accuracy of the object-based
+    map on the connected superpixels."""
+    from maskedsst_amd import enforce_connectivity, fit_superpixels, superpixel_classify
     img, lab = val
     before, logits = model.predict_scene(img, return_logits=True)
     sp = fit_superpixels(model.encode_scene(img, normalize=True), step=sp_step, compactness=compactness)
@@ -651,6 +669,44 @@ def validate_superpixel(model, val, step, sp_step, compactness, ignored_label):
         acc0, acc1 = float((before[ok] == lab[ok]).double().mean()), float((after[ok] == lab[ok]).double().mean())
     print(f"val-superpixel step {step} sp_step {sp_step} superpixels {int((sp.counts > 0).sum())} acc_before {acc0:.3f} acc_after {acc1:.3f} "
           f"changed {int(((before != after) & live).sum())} pixels {int(ok.sum())} scenes {img.shape[0]}", flush=True)
+    if not connect:
+        return
+    con = enforce_connectivity(sp)
+    joined = superpixel_classify(con.superpixels, logits).classes
+    frag0 = int(con.history[0, 1]) if len(con.history) else 0
+    frag1 = int(con.regions.count.sum()) - int((con.superpixels.counts > 0).sum())
+    acc2 = float((joined[ok] == lab[ok]).double().mean()) if bool(ok.any()) else float("nan")
+    print(f"val-superpixel-connected step {step} fragments_before {frag0} fragments_after {frag1} acc_after {acc2:.3f} "
+          f"pixels {int(ok.sum())} scenes {img.shape[0]}", flush=True)
+
+
+def check_val_sieve(args):
+    if not args.val_sieve:
+        return
+    if args.val_sieve < 1:
+        raise SystemExit("--val-sieve MIN_SIZE must be at least 1")
+    if args.val_scenes < 1 or args.val_every < 1:
+        raise SystemExit("--val-sieve sieves the validation scenes' class maps: it needs --val-scenes and --val-every")
+
+
+def validate_sieve(model, val, step, min_size, connectivity, ignored_label):
+    """--val-sieve MIN_SIZE: the minimum mapping unit on the validation scenes.  predict_scene gives the class maps;
+    maskedsst_amd.sieve_classes (connectivity --val-sieve-connectivity, the API default of 4 rounds) merges every connected patch of
+    fewer than MIN_SIZE pixels into its largest neighbour.  regions_before / regions_after: the connected regions of the maps;
+    acc_before / acc_after: the accuracy on the labelled live pixels; changed: the pixels whose class differs.  nan when no labelled
+    pixel is live."""
+    from maskedsst_amd import sieve_classes
+    img, lab = val
+    before = model.predict_scene(img).contiguous()
+    res = sieve_classes(before, min_size, connectivity=connectivity)
+    after = res.classes
+    ok = (lab != ignored_label) & (after >= 0)
+    acc0 = acc1 = float("nan")
+    if bool(ok.any()):
+        acc0, acc1 = float((before[ok] == lab[ok]).double().mean()), float((after[ok] == lab[ok]).double().mean())
+    print(f"val-sieve step {step} min_size {min_size} regions_before {int(res.history[0, 0])} regions_after {int(res.regions.count.sum())} "
+          f"acc_before {acc0:.3f} acc_after {acc1:.3f} changed {int((before != after).sum())} pixels {int(ok.sum())} scenes {img.shape[0]}",
+          flush=True)
 
 
 def validate_saliency(model, val, step, batch=256, top=5):

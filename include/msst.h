@@ -635,6 +635,49 @@ int msst_slic_pool_finish(const float* slab, long slab_floats, int Bs, int C, in
                           void* stream);
 int msst_slic_broadcast(const int64_t* labels, const int64_t* region_classes, int Bs, int Hs, int Ws, int step, int64_t* classes, void* stream);
 
+/* Connected regions of an integer map (maskedsst_amd/regions.py: label_regions, region_ids, sieve_classes, enforce_connectivity):
+ * connected-component labelling of a class map or a superpixel label map, and one round of merging flagged regions into a neighbour:
+ * the sieve (minimum mapping unit) and SLIC's connectivity pass.  Additive under MSST_VERSION 109: no struct and no existing signature
+ * changes.  Integer arithmetic throughout, integer atomics only: every output has the same bits in every call, and the same bits for a
+ * scene alone or inside a batch.  Limits: Hs, Ws <= 32768, Hs * Ws < 2^31, at most 2^31 - 1 tiles of 16 x 16 pixels in the batch.
+ *
+ * values is int64 [Bs][Hs][Ws]; a value < 0 is dead.  connectivity is 4 (the cross) or 8 (the 3 x 3 square).  A region is a maximal set
+ * of live pixels of one scene with equal value, connected under `connectivity`; nothing crosses the scene border (the last pixel of a
+ * row and the first of the next are no neighbours), nothing passes between the scenes of a batch.
+ *
+ * msst_regions_label: labels[b][y][x] (int64) = y0 Ws + x0 of the region's first pixel in raster order (its smallest linear index: the
+ * ROOT), -1 for a dead pixel; sizes[b][y][x] (int32) = the region's pixel count at the root pixel, 0 everywhere else; count[b] (int32) =
+ * the regions of scene b.  Three launches, whatever the map holds.
+ * msst_regions_merge: one SIMULTANEOUS round -- every decision is taken from the round's input (values with the labels and sizes that
+ * msst_regions_label gave for them under the same connectivity).
+ *   mode 0 (sieve): a region is flagged when size < min_size; step is not read.
+ *   mode 1 (fragments): values are superpixel ids of a step S grid, gy = ceil(Hs / S), gx = ceil(Ws / S), n_sp = gy gx; a value >= n_sp
+ *     is treated as dead.  Per scene and id the kept region is the one of largest size, then lowest root; every other region of the id
+ *     is flagged.  min_size is not read.
+ *   The candidates of a flagged region R: the regions T that are live, unflagged and different from R, with a pixel that is a neighbour
+ *   (under connectivity) of a pixel of R; in mode 1 only those whose id m is eligible: with [i0, i1] x [j0, j1] the box of the cells
+ *   (y / S, x / S) of R's pixels and (im, jm) = (m / gx, m % gx): im - 1 <= i0, i1 <= im + 1, jm - 1 <= j0, j1 <= jm + 1 -- so a label
+ *   stays in the 3 x 3 cells of its pixel, which msst_slic_pool relies on.  The winner is the candidate of largest size, then lowest
+ *   root (one 64-bit integer atomicMax of (size << 32) | (0xFFFFFFFF - root) per boundary pixel).  values_out: every pixel of R takes the
+ *   winner's value; a flagged region without a candidate, an unflagged region and a dead pixel keep their value (-1 stays -1, -2 stays
+ *   -2).  values_out != values.  history (four int32, zeroed by the caller) is increased by the live regions, the flagged regions, the
+ *   merged regions and the changed pixels, each summed over the batch.  Three launches in mode 0, four in mode 1.
+ * scratch: msst_regions_scratch_bytes(Bs, Hs, Ws) bytes (0 for arguments the calls refuse), 16-byte aligned.  Its first int32 is the
+ * ERROR WORD: zeroed by the caller before the first call, never zeroed and only ever raised by the calls; everything behind it is
+ * overwritten by every call.  Every device loop (the finds and unions of the labelling) terminates because it follows strictly
+ * decreasing indices, and still counts its turns against a cap derived from Hs * Ws; a loop that reaches the cap, or meets a parent
+ * above its child, stops and raises the error word (1: find, 2: union, 3: both).  A non-zero error word means the outputs are not to be
+ * used.  No loop waits for another workgroup.
+ *
+ * Both check before any HIP call, in this order: MSST_ERR_BADARG for a size below 1 (Bs, Hs, Ws; min_size in mode 0, step in mode 1);
+ * MSST_ERR_UNSUPPORTED over the limits; MSST_ERR_BADARG for a connectivity outside {4, 8} or a mode outside {0, 1}; MSST_ERR_BADARG for
+ * a null or misaligned pointer, values_out == values, or a short scratch.  msst_last_error names the call. */
+long msst_regions_scratch_bytes(int Bs, int Hs, int Ws);
+int msst_regions_label(const int64_t* values, int Bs, int Hs, int Ws, int connectivity, int64_t* labels, int32_t* sizes, int32_t* count,
+                       void* scratch, long scratch_bytes, void* stream);
+int msst_regions_merge(const int64_t* values, const int64_t* labels, const int32_t* sizes, int Bs, int Hs, int Ws, int connectivity, int mode,
+                       int min_size, int step, int64_t* values_out, int32_t* history, void* scratch, long scratch_bytes, void* stream);
+
 /* a7-a10: one fused pre-norm transformer block (PreNorm+Attention+FeedForward+residuals,
  * vit_spatial_spectral.py:22-104) over all B*S*N tokens; mode selects the spatial or spectral
  * sequence grouping of vit_spatial_spectral.py:410-431 (no transposes are materialised).

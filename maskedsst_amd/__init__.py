@@ -23,6 +23,8 @@ from .gaussian import GaussianClassifier, GaussianResult, GaussianScene, fit_gau
 from .crf import CrfAffinity, CrfResult, RefinedScene, crf_affinity, crf_refine, refine_scene  # noqa: F401
 from .superpixel import (Superpixels, ObjectResult, SuperpixelScene, SlicCentres, fit_superpixels, superpixel_pool,  # noqa: F401
                          superpixel_classify, superpixel_assign, superpixel_update, superpixel_scene)
+from .regions import (Regions, SieveResult, ConnectedSuperpixels, label_regions, region_ids, check_regions, sieve_classes,  # noqa: F401
+                      enforce_connectivity)
 
 __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "MaskGenerator", "Reconstruction", "recon_report",
            "ReconReport", "SceneReconstruction", "window_masks_to_scene", "scene_mask_to_windows", "SceneEmbedding",
@@ -36,4 +38,6 @@ __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "
            "GaussianClassifier", "GaussianResult", "GaussianScene", "fit_gaussian", "gaussian_predict_scene",
            "CrfAffinity", "CrfResult", "RefinedScene", "crf_affinity", "crf_refine", "refine_scene",
            "Superpixels", "ObjectResult", "SuperpixelScene", "SlicCentres", "fit_superpixels", "superpixel_pool", "superpixel_classify",
-           "superpixel_assign", "superpixel_update", "superpixel_scene"]
+           "superpixel_assign", "superpixel_update", "superpixel_scene",
+           "Regions", "SieveResult", "ConnectedSuperpixels", "label_regions", "region_ids", "check_regions", "sieve_classes",
+           "enforce_connectivity"]

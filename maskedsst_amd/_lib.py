@@ -120,6 +120,9 @@ _SIGS = {
     "msst_slic_pool": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_long, _P]),
     "msst_slic_pool_finish": (c_int, [_P, c_long, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "msst_slic_broadcast": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    "msst_regions_scratch_bytes": (c_long, [c_int, c_int, c_int]),
+    "msst_regions_label": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_long, _P]),
+    "msst_regions_merge": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_long, _P]),
     "msst_draw_masks": (c_int, [_P, _P, _P, _P, c_uint32, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "msst_scene_assemble": (c_int, [_P, c_long, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "msst_cls_head_fwd": (c_int, [_P] * 6 + [c_int, c_int, c_int, c_int, _P]),

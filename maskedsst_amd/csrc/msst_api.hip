@@ -860,6 +860,47 @@ int msst_slic_broadcast(const int64_t* labels, const int64_t* region_classes, in
     return fail(launch_slic_broadcast(labels, region_classes, Bs, Hs, Ws, step, classes, (hipStream_t)stream), "msst_slic_broadcast");
 }
 
+// the sizes both region calls share
+static int regions_shape(const char* what, int Bs, int Hs, int Ws, int connectivity) {
+    if (Bs < 1 || Hs < 1 || Ws < 1) return fail(MSST_ERR_BADARG, what, " (Bs, Hs or Ws below 1)");
+    if (Hs > 32768 || Ws > 32768 || (long)Hs * Ws >= (1L << 31) || regions_tiles(Bs, Hs, Ws) > 2147483647L)
+        return fail(MSST_ERR_UNSUPPORTED, what, " (Hs, Ws <= 32768, Hs * Ws < 2^31, at most 2^31 - 1 tiles of 16 x 16 pixels)");
+    if (connectivity != 4 && connectivity != 8) return fail(MSST_ERR_BADARG, what, " (connectivity outside {4, 8})");
+    return 0;
+}
+
+long msst_regions_scratch_bytes(int Bs, int Hs, int Ws) {
+    if (Bs < 1 || Hs < 1 || Ws < 1 || Hs > 32768 || Ws > 32768 || (long)Hs * Ws >= (1L << 31) || regions_tiles(Bs, Hs, Ws) > 2147483647L) return 0;
+    return regions_scratch_bytes(Bs, Hs, Ws);
+}
+
+int msst_regions_label(const int64_t* values, int Bs, int Hs, int Ws, int connectivity, int64_t* labels, int32_t* sizes, int32_t* count,
+                       void* scratch, long scratch_bytes, void* stream) {
+    if (int rc = regions_shape("msst_regions_label", Bs, Hs, Ws, connectivity)) return rc;
+    if (!values || !labels || !sizes || !count || !scratch || ((uintptr_t)values & 7) || ((uintptr_t)labels & 7) || ((uintptr_t)sizes & 3) ||
+        ((uintptr_t)count & 3) || ((uintptr_t)scratch & 15))
+        return fail(MSST_ERR_BADARG, "msst_regions_label (null or misaligned argument)");
+    if (scratch_bytes < regions_scratch_bytes(Bs, Hs, Ws))
+        return fail(MSST_ERR_BADARG, "msst_regions_label (scratch smaller than msst_regions_scratch_bytes)");
+    return fail(launch_regions_label(values, Bs, Hs, Ws, connectivity, labels, sizes, count, scratch, (hipStream_t)stream), "msst_regions_label");
+}
+
+int msst_regions_merge(const int64_t* values, const int64_t* labels, const int32_t* sizes, int Bs, int Hs, int Ws, int connectivity, int mode,
+                       int min_size, int step, int64_t* values_out, int32_t* history, void* scratch, long scratch_bytes, void* stream) {
+    if (Bs >= 1 && Hs >= 1 && Ws >= 1 && ((mode == 0 && min_size < 1) || (mode == 1 && step < 1)))
+        return fail(MSST_ERR_BADARG, "msst_regions_merge (min_size or step below 1)");
+    if (int rc = regions_shape("msst_regions_merge", Bs, Hs, Ws, connectivity)) return rc;
+    if (mode != 0 && mode != 1) return fail(MSST_ERR_BADARG, "msst_regions_merge (mode outside {0, 1})");
+    if (!values || !labels || !sizes || !values_out || !history || !scratch || ((uintptr_t)values & 7) || ((uintptr_t)labels & 7) ||
+        ((uintptr_t)sizes & 3) || ((uintptr_t)values_out & 7) || ((uintptr_t)history & 3) || ((uintptr_t)scratch & 15))
+        return fail(MSST_ERR_BADARG, "msst_regions_merge (null or misaligned argument)");
+    if (values_out == values) return fail(MSST_ERR_BADARG, "msst_regions_merge (values_out == values: the round reads its input throughout)");
+    if (scratch_bytes < regions_scratch_bytes(Bs, Hs, Ws))
+        return fail(MSST_ERR_BADARG, "msst_regions_merge (scratch smaller than msst_regions_scratch_bytes)");
+    return fail(launch_regions_merge(values, labels, sizes, Bs, Hs, Ws, connectivity, mode, min_size, step, values_out, history, scratch,
+                                     (hipStream_t)stream), "msst_regions_merge");
+}
+
 int msst_scene_embed_assemble(const float* win_feat, long win0, int nwin, float* feat, int32_t* cover, int Bs, int D, int Hs, int Ws,
                               int window, int stride, int finalize, int l2norm, void* stream) {
     if (Bs < 1 || D < 1 || Hs < 1 || Ws < 1 || window < 1 || stride < 1 || nwin < 0 || win0 < 0)

@@ -605,6 +605,17 @@ int launch_slic_pool(const float* map, const int64_t* labels, int Bs, int C, int
 int launch_slic_pool_finish(const float* slab, int Bs, int C, int Hs, int Ws, int step, float* table, int64_t* region_classes, hipStream_t st);
 int launch_slic_broadcast(const int64_t* labels, const int64_t* region_classes, int Bs, int Hs, int Ws, int step, int64_t* classes, hipStream_t st);
 
+// msst_regions.hip (msst_regions_label, msst_regions_merge): connected regions of an int64 map -- a union-find per 16 x 16 tile in LDS,
+// unions across the tile borders with integer atomicMin on a parent array, a flatten that counts the sizes at the roots -- and one
+// simultaneous merge round on top of it (the sieve; SLIC's connectivity pass).  regions_tiles is the grid of the per-tile launches, for
+// the caller's range check; the scratch holds regions_scratch_bytes bytes and starts with the error word, which the launches only raise
+long regions_tiles(int Bs, int Hs, int Ws);
+long regions_scratch_bytes(int Bs, int Hs, int Ws);
+int launch_regions_label(const int64_t* values, int Bs, int Hs, int Ws, int connectivity, int64_t* labels, int32_t* sizes, int32_t* count,
+                         void* scratch, hipStream_t st);
+int launch_regions_merge(const int64_t* values, const int64_t* labels, const int32_t* sizes, int Bs, int Hs, int Ws, int connectivity, int mode,
+                         int min_size, int step, int64_t* values_out, int32_t* history, void* scratch, hipStream_t st);
+
 // msst_mask.hip (msst_draw_masks): the SimMIM token mask, gather indices and the gather's token-CSR of global rows row0 .. row0 + rows - 1
 // from a counter hash; one workgroup per row
 struct MaskDrawArgs {

@@ -39,8 +39,8 @@ The contract:
                 classes[p] = region_classes[label[p]], -1 for a dead pixel.
 
 The defaults (step 8, compactness 0.2, 10 iterations) are API defaults like kNN's temperature, not tuned on any data; compactness is in
-feature units per step, 0.2 suits unit-length (normalize=True) maps.  Connectivity enforcement (SLIC's serial relabelling pass) is out
-of scope: a superpixel may consist of several pieces inside its 3 x 3 cells.  Limits: feature width 96, step in {4, 8, 16}, at most
+feature units per step, 0.2 suits unit-length (normalize=True) maps.  The fit does not enforce connectivity: a superpixel may
+consist of several pieces inside its 3 x 3 cells; maskedsst_amd.regions.enforce_connectivity is SLIC's relabelling pass, run afterwards.  Limits: feature width 96, step in {4, 8, 16}, at most
 128 pooled channels, Hs, Ws <= 32768, fp32.  There is no CPU or eager fallback.
 """
 import ctypes
@@ -194,7 +194,7 @@ def fit_superpixels(features, cover=None, step=8, compactness=0.2, iters=10):
     SceneEmbedding, whose cover is then used unless cover is given.  iters = 0 gives the home labels and the cell means.  2 (iters + 1)
     launches and one synchronisation, to read the history.  The defaults are API defaults, not tuned on data.  ValueError before any
     device work for wrong shapes, dtypes or ranges or a step outside {4, 8, 16}; RuntimeError for CPU tensors.  No CPU or eager
-    fallback; no connectivity enforcement."""
+    fallback; connectivity is enforced afterwards, by enforce_connectivity."""
     features, cover = _check_features(features, cover)
     _check_step(step)
     _check_compactness(compactness, step)
