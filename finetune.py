@@ -116,6 +116,12 @@ def build_parser():
                          "(maskedsst_amd.fit_kmeans, K clusters, cosine, k-means++) on the covered pixels of the first half of the "
                          "--val-scenes, the second half assigned and matched to the classes (Hungarian accuracy, purity, NMI); the split "
                          "of --val-embed; needs --val-scenes and --val-every")
+    ap.add_argument("--val-gmm", type=int, default=0, metavar="K",
+                    help="one more line per validation: the clustering score of a Gaussian mixture of the raw frozen features, no label "
+                         "used for the fit: EM (maskedsst_amd.fit_mixture, K components, k-means init) on the covered pixels of the first "
+                         "half of the --val-scenes, the second half assigned and matched to the classes as under --val-cluster, with the "
+                         "mean log-likelihood of the second half; needs --val-scenes and --val-every")
+    ap.add_argument("--val-gmm-cov", default="full", choices=["full", "diag"], help="the covariances of --val-gmm")
     ap.add_argument("--val-pca", type=int, default=0, metavar="R",
                     help="one more line per validation: the spectrum of the frozen features' covariance, no label read: "
                          "maskedsst_amd.fit_pca on the covered pixels of the first half of the --val-scenes (the R leading "
@@ -261,6 +267,7 @@ def main():
     check_val_knn(args)
     check_val_probe(args)
     check_val_cluster(args)
+    check_val_gmm(args)
     check_val_pca(args)
     check_val_gauss(args)
     check_val_crf(args)
@@ -323,6 +330,8 @@ def main():
                 validate_probe(model, val, step, args.val_probe, config.n_classes, config.ignored_label)
             if args.val_cluster:
                 validate_cluster(model, val, step, args.val_cluster, config.n_classes, config.ignored_label)
+            if args.val_gmm:
+                validate_gmm(model, val, step, args.val_gmm, args.val_gmm_cov, config.n_classes, config.ignored_label)
             if args.val_pca:
                 validate_pca(model, val, step, args.val_pca)
             if args.val_gauss:
@@ -531,6 +540,34 @@ def validate_cluster(model, val, step, k, n_classes, ignored_label, iters=50):
         acc, purity, nmi, inertia = m.accuracy, m.purity, m.nmi, km.inertia
     print(f"val-cluster step {step} k {k} cluster_acc {acc:.3f} purity {purity:.3f} nmi {nmi:.3f} inertia {inertia:.4g} "
           f"test_pixels {len(lte)} train_pixels {len(ftr)} scenes {val[0].shape[0]}", flush=True)
+
+
+def check_val_gmm(args):
+    if not args.val_gmm:
+        return
+    if not 1 <= args.val_gmm <= 32:
+        raise SystemExit("--val-gmm K must lie in [1, 32]")
+    if args.val_scenes < 1 or args.val_every < 1:
+        raise SystemExit("--val-gmm scores the validation scenes: it needs --val-scenes and --val-every")
+
+
+def validate_gmm(model, val, step, k, covariance, n_classes, ignored_label, iters=30):
+    """--val-gmm K: the clustering score of a Gaussian mixture of the RAW frozen features, the protocol of --val-cluster: EM
+    (maskedsst_amd.fit_mixture: k-means init with seed 0, three HIP launches per iteration) is fitted on ALL covered pixels of the
+    first half of the scenes -- no label is read -- and the labelled covered pixels of the second half are assigned to their most
+    probable component and matched to the classes (maskedsst_amd.match_clusters).  mean_ll: the mean log-likelihood of those pixels;
+    starved: the components the last iteration left without rows.  nan when a half has no such pixel or fewer than K."""
+    from maskedsst_amd import contingency, fit_mixture, match_clusters
+    ftr, _, fte, lte = frozen_split(model, val, ignored_label, False, all_covered=True)
+    acc = purity = nmi = mean_ll = float("nan")
+    starved = 0
+    if len(ftr) >= k and len(lte):
+        gm = fit_mixture(ftr.contiguous(), k=k, covariance=covariance, iters=iters, seed=0, check_every=5)
+        res = gm.predict(fte.contiguous())
+        m = match_clusters(contingency(res.classes, lte, k, n_classes, ignored_label))
+        acc, purity, nmi, mean_ll, starved = m.accuracy, m.purity, m.nmi, float(res.log_likelihood.double().mean()), int(gm.history[-1, 2])
+    print(f"val-gmm step {step} k {k} cov {covariance} cluster_acc {acc:.3f} purity {purity:.3f} nmi {nmi:.3f} mean_ll {mean_ll:.4g} "
+          f"starved {starved} test_pixels {len(lte)} train_pixels {len(ftr)} scenes {val[0].shape[0]}", flush=True)
 
 
 def check_val_pca(args):

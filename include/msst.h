@@ -553,6 +553,56 @@ int msst_gauss_score(const float* x, int x_layout, long rows, long plane, int di
                      const int32_t* class_table, const float* offsets, const float* consts, int nc, float max_d2, int32_t* classes,
                      float* distance, float* scores, int out_layout, void* stream);
 
+/* Gaussian mixtures of frozen features by EM (maskedsst_amd/mixture.py: fit_mixture, GaussianMixture,
+ * ViTSpatialSpectral.mixture_scene).  Additive under MSST_VERSION 109: no struct and no existing signature changes.  dim == 96, fp32,
+ * no float atomics; every sum runs in an order that depends on (rows, k) alone and the row partition on rows alone.
+ *
+ * The contract.  score_c(x) = log w_c - 0.5 (d2_c(x) + logdet_c) - 48 log(2 pi), d2_c = |A_c (x - mu_c)|^2, Sigma_c = L_c L_c^T,
+ * A_c = L_c^-1 (lower triangular), logdet_c = 2 sum_i log L_c[i][i]: msst_gauss_score's full-covariance table form with zero offsets
+ * (table c for component c, consts[c] = log w_c - 0.5 logdet_c - 48 log(2 pi)), which is the E-step's expensive part and is not
+ * changed.  Posterior of a row: m = max_c score_c, lse = m + logf(sum_c expf(score_c - m)) with c ascending in fp32, r_c =
+ * expf(score_c - lse); a score of -inf contributes exactly 0.  A row with a NaN score has lse NaN and NaN probs.  A row whose scores
+ * are all -inf has lse = -inf and probs 0; in msst_gmm_moments it is skipped and not counted.
+ *
+ * msst_gmm_posterior.  scores as rows [rows][k] (in_layout 0) or as the map [rows / plane][k][plane] that msst_gauss_score writes with
+ * out_layout 1 (in_layout 1); 1 <= k <= 128.  Writes lse [rows] and, when not null, probs in either layout (out_layout).  A row's
+ * outputs have the same bits whatever batch or layout it sits in.
+ *
+ * msst_gmm_moments.  One pass over x (x_layout as in msst_feat_moments) and scores [rows][k], 1 <= k <= 32, centres [k][96].  Per row
+ * lse and r as above; a row with a channel that is not finite, and a row whose lse is not finite, is skipped and not counted, by
+ * selection.  The grid is (workgroups of feat_partition, k): per workgroup and component the slab row [n | s1 96 | s2 96 x 96] about
+ * centres[c] -- n = sum r_c, s1 = sum r_c (x - centre_c), s2 = sum r_c (x - centre_c)(x - centre_c)^T as the product of the rows
+ * scaled by sqrt(r_c) with themselves on v_mfma_f32_16x16x4_f32, the row as the k index: symmetric bit for bit, exact for r in {0, 1}
+ * -- and behind them per workgroup [counted rows (int32 bits) | sum lse of the counted rows].  msst_gmm_scratch_floats(rows, k)
+ * floats in all (0 for arguments the calls refuse).
+ *
+ * msst_gmm_update.  One workgroup per component sums that component's slab rows in workgroup order in double, N_c = sum n (every
+ * workgroup sums all k for itself), and with delta = s1 / N_c writes
+ *   weights[c] = N_c / sum_c N_c (0 when the sum is 0);  centres[c] += delta;
+ *   covs[c] = s2 / N_c - delta delta^T + reg_covar I (cov_kind MSST_GMM_DIAG: the off-diagonal entries 0), symmetric bit for bit;
+ *   tables[c] = A_c and logdet[c] from the Cholesky factorisation and triangular inverse in double, each rounded to fp32 once;
+ *   consts[c] = log w_c - 0.5 logdet_c - 48 log(2 pi);
+ *   raw (null: not wanted) [k][1 + 96 + 96 x 96] = the summed slab rows [N_c | s1 | s2] rounded to fp32.
+ * A component with N_c < min_count (starved), and one whose factorisation meets a pivot that is not finite or not positive (failed),
+ * keeps its centre, table, covariance and logdet; its weight and constant are still written (weight 0: constant -inf).  record [4] =
+ * [mean lse per counted row, float (NaN without rows) | counted rows | starved components | failed factorisations, the three as int32
+ * bits]; the last is ADDED to with an integer atomic, so the caller zeroes the record before the launch.
+ *
+ * Checked before any HIP call, in this order: MSST_ERR_BADARG for rows, dim or k below 1, a cov_kind outside {0, 1}, reg_covar or
+ * min_count negative or NaN; MSST_ERR_UNSUPPORTED outside dim == 96, k <= 32 (msst_gmm_posterior: 128), rows <= 2^31 - 1;
+ * MSST_ERR_BADARG for a layout outside {0, 1}, with a map on either side a plane below 1 or not dividing rows, a null or misaligned
+ * required pointer, a slab smaller than msst_gmm_scratch_floats.  msst_last_error names the call. */
+#define MSST_GMM_FULL 0
+#define MSST_GMM_DIAG 1
+long msst_gmm_scratch_floats(long rows, int k);
+int msst_gmm_posterior(const float* scores, int in_layout, long rows, long plane, int k, float* lse, float* probs, int out_layout,
+                       void* stream);
+int msst_gmm_moments(const float* x, int x_layout, long rows, long plane, int dim, const float* scores, int k, const float* centres,
+                     float* slab, long slab_floats, void* stream);
+int msst_gmm_update(const float* slab, long slab_floats, long rows, int dim, int k, int cov_kind, double reg_covar, double min_count,
+                    float* centres, float* tables, float* covs, float* logdet, float* consts, float* weights, float* raw, float* record,
+                    void* stream);
+
 /* Feature-guided CRF refinement of class maps (maskedsst_amd/crf.py: crf_affinity, crf_refine, ViTSpatialSpectral.refine_scene): a
  * local dense CRF (mean field, Potts compatibility) over the score maps the scene classifiers write.  Additive under MSST_VERSION 109:
  * no struct and no existing signature changes.  dim == 96, 1 <= radius <= 3, 1 <= nc <= 128, fp32, no float atomics.  The

@@ -20,6 +20,7 @@ from .probe import LinearProbe, ProbeScene, fit_linear_probe, probe_bank, probe_
 from .cluster import KMeans, ClusterScene, ClusterMatch, fit_kmeans, cluster_scene, contingency, match_clusters  # noqa: F401
 from .pca import FeaturePCA, PcaScene, AnomalyScene, fit_pca, pca_scene, anomaly_scene  # noqa: F401
 from .gaussian import GaussianClassifier, GaussianResult, GaussianScene, fit_gaussian, gaussian_predict_scene  # noqa: F401
+from .mixture import GaussianMixture, MixtureResult, MixtureScene, fit_mixture, mixture_scene  # noqa: F401
 from .crf import CrfAffinity, CrfResult, RefinedScene, crf_affinity, crf_refine, refine_scene  # noqa: F401
 from .superpixel import (Superpixels, ObjectResult, SuperpixelScene, SlicCentres, fit_superpixels, superpixel_pool,  # noqa: F401
                          superpixel_classify, superpixel_assign, superpixel_update, superpixel_scene)
@@ -36,6 +37,7 @@ __all__ = ["ViTSpatialSpectral", "SimMIMSpatialSpectral", "BlockwiseToPixels", "
            "KMeans", "ClusterScene", "ClusterMatch", "fit_kmeans", "cluster_scene", "contingency", "match_clusters",
            "FeaturePCA", "PcaScene", "AnomalyScene", "fit_pca", "pca_scene", "anomaly_scene",
            "GaussianClassifier", "GaussianResult", "GaussianScene", "fit_gaussian", "gaussian_predict_scene",
+           "GaussianMixture", "MixtureResult", "MixtureScene", "fit_mixture", "mixture_scene",
            "CrfAffinity", "CrfResult", "RefinedScene", "crf_affinity", "crf_refine", "refine_scene",
            "Superpixels", "ObjectResult", "SuperpixelScene", "SlicCentres", "fit_superpixels", "superpixel_pool", "superpixel_classify",
            "superpixel_assign", "superpixel_update", "superpixel_scene",

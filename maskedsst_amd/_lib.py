@@ -112,6 +112,10 @@ _SIGS = {
     "msst_feat_moments_finish": (c_int, [_P, c_long, c_long, c_int, _P, c_int, _P, _P, _P, _P, _P]),
     "msst_feat_project": (c_int, [_P, c_int, c_long, c_long, c_int, _P, _P, c_int, _P, c_int, _P, _P]),
     "msst_gauss_score": (c_int, [_P, c_int, c_long, c_long, c_int, _P, _P, c_int, _P, _P, _P, c_int, c_float, _P, _P, _P, c_int, _P]),
+    "msst_gmm_scratch_floats": (c_long, [c_long, c_int]),
+    "msst_gmm_posterior": (c_int, [_P, c_int, c_long, c_long, c_int, _P, _P, c_int, _P]),
+    "msst_gmm_moments": (c_int, [_P, c_int, c_long, c_long, c_int, _P, c_int, _P, _P, c_long, _P]),
+    "msst_gmm_update": (c_int, [_P, c_long, c_long, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double] + [_P] * 9),
     "msst_crf_affinity": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_float, _P, _P, _P]),
     "msst_crf_step": (c_int, [_P, c_int, c_float, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "msst_slic_scratch_floats": (c_long, [c_int, c_int, c_int, c_int, c_int]),

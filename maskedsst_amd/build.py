@@ -11,8 +11,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmsst.so")
-SOURCES = ["msst_fwd.hip", "msst_fwd3.hip", "msst_bwd.hip", "msst_bwd3.hip", "msst_bwd4.hip", "msst_bwd5.hip", "msst_ln.hip", "msst_opt.hip", "msst_accum.hip", "msst_head.hip", "msst_pixhead.hip", "msst_loss.hip", "msst_recon.hip", "msst_scene_recon.hip", "msst_scene_embed.hip", "msst_input_grad.hip", "msst_attn_maps.hip", "msst_knn.hip", "msst_probe.hip", "msst_kmeans.hip", "msst_pca.hip", "msst_gauss.hip", "msst_crf.hip", "msst_slic.hip", "msst_regions.hip", "msst_mask.hip", "msst_api.hip"]
-HEADERS = ["msst_dev.h", "msst_kernels.h", "msst_feat.h", "msst_regions_core.h", os.path.join("..", "..", "include", "msst.h")]
+SOURCES = ["msst_fwd.hip", "msst_fwd3.hip", "msst_bwd.hip", "msst_bwd3.hip", "msst_bwd4.hip", "msst_bwd5.hip", "msst_ln.hip", "msst_opt.hip", "msst_accum.hip", "msst_head.hip", "msst_pixhead.hip", "msst_loss.hip", "msst_recon.hip", "msst_scene_recon.hip", "msst_scene_embed.hip", "msst_input_grad.hip", "msst_attn_maps.hip", "msst_knn.hip", "msst_probe.hip", "msst_kmeans.hip", "msst_pca.hip", "msst_gauss.hip", "msst_gmm.hip", "msst_crf.hip", "msst_slic.hip", "msst_regions.hip", "msst_mask.hip", "msst_api.hip"]
+HEADERS = ["msst_dev.h", "msst_kernels.h", "msst_feat.h", "msst_regions_core.h", "msst_gmm_core.h", os.path.join("..", "..", "include", "msst.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 
 

@@ -764,6 +764,54 @@ int msst_gauss_score(const float* x, int x_layout, long rows, long plane, int di
                                    distance, scores, out_layout, (hipStream_t)stream), "msst_gauss_score");
 }
 
+long msst_gmm_scratch_floats(long rows, int k) {
+    if (rows < 1 || rows > 2147483647L || k < 1 || k > 32) return 0;
+    return gmm_scratch_floats(rows, k);
+}
+
+// the sizes of the three calls on Gaussian mixtures: kmax is 32, or 128 for the posterior alone
+static int gmm_shape(const char* what, long rows, int dim, int k, int kmax, int cov_kind = MSST_GMM_FULL, double reg_covar = 0.0,
+                     double min_count = 0.0) {
+    if (rows < 1 || dim < 1 || k < 1 || (cov_kind != MSST_GMM_FULL && cov_kind != MSST_GMM_DIAG) || !(reg_covar >= 0.0) || !(min_count >= 0.0))
+        return fail(MSST_ERR_BADARG, what, " (a size below 1, a cov_kind outside {0, 1}, or a negative reg_covar or min_count)");
+    if (dim != 96 || k > kmax || rows > 2147483647L)
+        return fail(MSST_ERR_UNSUPPORTED, what, kmax == 32 ? " (dim == 96, k <= 32, rows <= 2^31 - 1)" : " (k <= 128, rows <= 2^31 - 1)");
+    return 0;
+}
+
+int msst_gmm_posterior(const float* scores, int in_layout, long rows, long plane, int k, float* lse, float* probs, int out_layout,
+                       void* stream) {
+    if (int rc = gmm_shape("msst_gmm_posterior", rows, 96, k, 128)) return rc;
+    if (int rc = feat_layout("msst_gmm_posterior", "layout", "rows", rows, plane, in_layout, out_layout)) return rc;
+    if (!scores || !lse || ((uintptr_t)scores & 3) || ((uintptr_t)lse & 3) || ((uintptr_t)probs & 3))
+        return fail(MSST_ERR_BADARG, "msst_gmm_posterior (null or misaligned argument)");
+    return fail(launch_gmm_posterior(scores, in_layout, rows, plane, k, lse, probs, out_layout, (hipStream_t)stream), "msst_gmm_posterior");
+}
+
+int msst_gmm_moments(const float* x, int x_layout, long rows, long plane, int dim, const float* scores, int k, const float* centres,
+                     float* slab, long slab_floats, void* stream) {
+    if (int rc = gmm_shape("msst_gmm_moments", rows, dim, k, 32)) return rc;
+    if (int rc = feat_layout("msst_gmm_moments", "x_layout", "rows", rows, plane, x_layout)) return rc;
+    if (!x || !scores || !centres || !slab || ((uintptr_t)x & (x_layout == 0 ? 15 : 3)) || ((uintptr_t)scores & 3) || ((uintptr_t)centres & 3) ||
+        ((uintptr_t)slab & 3))
+        return fail(MSST_ERR_BADARG, "msst_gmm_moments (null or misaligned argument)");
+    if (slab_floats < gmm_scratch_floats(rows, k)) return fail(MSST_ERR_BADARG, "msst_gmm_moments (slab smaller than msst_gmm_scratch_floats)");
+    return fail(launch_gmm_moments(x, x_layout, rows, plane, scores, k, centres, slab, (hipStream_t)stream), "msst_gmm_moments");
+}
+
+int msst_gmm_update(const float* slab, long slab_floats, long rows, int dim, int k, int cov_kind, double reg_covar, double min_count,
+                    float* centres, float* tables, float* covs, float* logdet, float* consts, float* weights, float* raw, float* record,
+                    void* stream) {
+    if (int rc = gmm_shape("msst_gmm_update", rows, dim, k, 32, cov_kind, reg_covar, min_count)) return rc;
+    if (!slab || !centres || !tables || !covs || !logdet || !consts || !weights || !record || ((uintptr_t)slab & 3) || ((uintptr_t)centres & 3) ||
+        ((uintptr_t)tables & 3) || ((uintptr_t)covs & 3) || ((uintptr_t)logdet & 3) || ((uintptr_t)consts & 3) || ((uintptr_t)weights & 3) ||
+        ((uintptr_t)raw & 3) || ((uintptr_t)record & 3))
+        return fail(MSST_ERR_BADARG, "msst_gmm_update (null or misaligned argument)");
+    if (slab_floats < gmm_scratch_floats(rows, k)) return fail(MSST_ERR_BADARG, "msst_gmm_update (slab smaller than msst_gmm_scratch_floats)");
+    return fail(launch_gmm_update(slab, rows, k, cov_kind, reg_covar, min_count, centres, tables, covs, logdet, consts, weights, raw, record,
+                                  (hipStream_t)stream), "msst_gmm_update");
+}
+
 int msst_crf_affinity(const float* feat, const int32_t* cover, int Bs, int dim, int Hs, int Ws, int radius, const float* a_tab,
                       const float* s_tab, float g, float* k, uint8_t* live, void* stream) {
     if (Bs < 1 || dim < 1 || Hs < 1 || Ws < 1) return fail(MSST_ERR_BADARG, "msst_crf_affinity (Bs, dim, Hs or Ws below 1)");

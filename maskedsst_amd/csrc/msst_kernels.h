@@ -581,6 +581,17 @@ int launch_gauss_score(const float* x, int x_layout, long rows, long plane, cons
                        const int32_t* class_table, const float* offsets, const float* consts, int nc, float max_d2, int32_t* classes,
                        float* distance, float* scores, int out_layout, hipStream_t st);
 
+// msst_gmm.hip (msst_gmm_posterior, msst_gmm_moments, msst_gmm_update): Gaussian mixtures by EM on top of launch_gauss_score -- the
+// posterior of a scores table, the responsibility-weighted moments about the current means (components across blockIdx.y, per-workgroup
+// partials without atomics) and the per-component M-step with a double Cholesky factorisation and triangular inverse in LDS
+long gmm_scratch_floats(long rows, int k);
+int launch_gmm_posterior(const float* scores, int in_layout, long rows, long plane, int k, float* lse, float* probs, int out_layout,
+                         hipStream_t st);
+int launch_gmm_moments(const float* x, int x_layout, long rows, long plane, const float* scores, int k, const float* centres, float* slab,
+                       hipStream_t st);
+int launch_gmm_update(const float* slab, long rows, int k, int cov_kind, double reg_covar, double min_count, float* centres, float* tables,
+                      float* covs, float* logdet, float* consts, float* weights, float* raw, float* record, hipStream_t st);
+
 // msst_crf.hip (msst_crf_affinity, msst_crf_step): the pairwise weights of a local dense CRF from the feature map (a tile with its halo
 // in LDS once, the dots on the fp32 MFMA) and one mean-field step over the score maps.  a_tab and s_tab are HOST arrays [K];
 // crf_tiles is the grid of either launch (which 0: affinity, 1: step), for the caller's range check

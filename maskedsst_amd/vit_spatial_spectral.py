@@ -511,6 +511,25 @@ class ViTSpatialSpectral(nn.Module):
         from .gaussian import gaussian_predict_scene
         return gaussian_predict_scene(self, scene, clf, stride, max_distance, max_windows)
 
+    def mixture_scene(self, scene, gm, stride=None, probs=False, max_windows=None):
+        """The soft segmentation and the density of whole scenes [Bs, channels, Hs, Ws] under a maskedsst_amd.GaussianMixture (e.g. from
+        maskedsst_amd.fit_mixture on the raw features of other scenes): encode_scene(normalize=False), then msst_gauss_score and
+        msst_gmm_posterior on the returned map in place, no permuted copy.  Returns MixtureScene(classes, log_likelihood, distance,
+        probs, cover):
+          classes         [Bs, Hs, Ws] int64: the component of the largest score log w_c + log N(x; mu_c, Sigma_c) under the total order
+                          (score descending, then index ascending); -1 where no window covers the pixel;
+          log_likelihood  [Bs, Hs, Ws] fp32: log p(x) under the mixture, whose negative is the cluster-based RX anomaly score; NaN
+                          where uncovered;
+          distance        [Bs, Hs, Ws] fp32: d2 = |A_c (x - mu_c)|^2 of the predicted component; NaN where uncovered;
+          probs           probs=True: [Bs, K, Hs, Ws] fp32, the responsibilities in the layout of predict_scene's logits (a score map
+                          for refine_scene and superpixel_classify); NaN where uncovered.  Otherwise None;
+          cover           as from encode_scene.
+        The maps have the same bits in every call and equal gm.predict on the permuted map.  stride, max_windows: encode_scene's.
+        No head runs; the module's mode is left unchanged.  ValueError, before any device work, for a gm that is no GaussianMixture
+        or a scene encode_scene refuses."""
+        from .mixture import mixture_scene
+        return mixture_scene(self, scene, gm, stride, probs, max_windows)
+
     def refine_scene(self, scene, scores, embedding=None, stride=None, iters=5, unary="logits", unary_scale=1.0, **affinity_kwargs):
         """The class map of whole scenes [Bs, channels, Hs, Ws] after a feature-guided CRF (mean field, Potts compatibility) over the
         score maps `scores` [Bs, nc, Hs, Ws] of any scene classifier -- predict_scene's logits, probe_predict_scene's logits,
